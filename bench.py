@@ -10,21 +10,23 @@ SBR / PS side info cycled from reference-captured HE-AACv2 frames (tests/golden/
 per-stream state (IMDCT overlap, SBR, PS, filterbank rings) carried in HBM.  Each rank owns `--sets` x 8192
 independent streams and decodes one frame of 8192 of them per step, round-robin, so the working set streams from
 HBM rather than from the Infinity Cache.  With --gpus N every rank runs this on its own 8192 x sets streams
-(C5: weak scaling, streams sharded by rank, no data-path collective); after the timed region the ranks' PCM is
-gathered once over RCCL (the north star's "final interleaved gather") and that time is reported separately.
+(C5: weak scaling, streams sharded by rank, no data-path collective); with --full, after the timed region the ranks'
+PCM is gathered once over RCCL (the north star's "final interleaved gather") and that time is reported separately.
 
 A "step" = one pass of the hot path over one batch.  Inputs are resident in HBM before the timed region.
 `value` = frames decoded by all ranks / wall time (max over ranks).  `roofline.achieved` = algorithmic bytes per
-step / mean step duration from HIP events recorded on the launch stream.  Every run checks itself
-(outside the timed region): the status words of the last step must all be zero, and one more step of a
-256-stream slice is decoded by the oracle chain on the host from the same device state and compared word for
-word (`bit_exact_vs_oracle`).  `secondary` (N=1 only; `f4_transforms` = the USAC / 960-line / LD / ELD IMDCT kernels) = short runs of C2 (AAC-LC IMDCT, BASELINE configs[1]), C4A (the
-same HE-AACv2 streams through the reference's default float eSBR path) and
-C3 (HE-AACv1, configs[2]) in the same process.  `cpu_baseline` = the same workload on the host cores (the
-compiled reference when oracle/_ref travelled with the repo, else the bit-exact restatement), bounded sample,
-rank 0 at N=1 only.
+step / mean step duration from HIP events recorded on the launch stream.  `refused_frac` = the share of the
+last step's status words that are not zero (must be zero).  A plain run does nothing else: set-up, warm-up, the K timed
+steps, the line (and --dump-outputs DIR: the last step's outputs as .npy files).
 
-  python bench.py --gpus 1 --steps 100 --warmup 10
+--full adds, outside the timed region: one more step of a 256-stream slice decoded by the oracle chain on the host from
+the same device state and compared word for word (`bit_exact_vs_oracle`); at N > 1 the per-rank rates and the PCM
+gather; at N=1 `secondary` (`f4_transforms` = the USAC / 960-line / LD / ELD IMDCT kernels) = short runs of C2 (AAC-LC
+IMDCT, BASELINE configs[1]), C4A (the same HE-AACv2 streams through the reference's default float eSBR path) and
+C3 (HE-AACv1, configs[2]) in the same process, and `cpu_baseline` = the same workload on the host cores (the
+compiled reference when oracle/_ref travelled with the repo, else the bit-exact restatement), bounded sample.
+
+  python bench.py --gpus 1 --steps 100 --warmup 10 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -53,6 +55,7 @@ PMC_FILE_C2 = os.path.join(ROOT, "profiles", "pmc_hbm_latest.json")   # round-1 
 VALU_CYCLES_PER_WAVE_INSTR = 4.4   # measured: tools/ubench/valu_rate.hip, profiles/r01_m_c2_sq_detail.txt (v_mul_hi_i32 = a shift)
 SIMDS, CLOCK_GHZ = 1024, 2.4       # 256 CUs x 4 SIMDs; MI355X_MICROARCH.md peak engine clock
 PREWARM_STEPS = 60                 # untimed steps before the counted warm-up (Workload.run; profiles/r06_a_clock_probe.txt)
+DUMP_STREAMS = 2048                # streams of the last step --dump-outputs writes: PCM of the widest workload 32 MiB in float32
 
 
 def library_build_id():
@@ -1138,6 +1141,28 @@ class Workload:
         return bool(ok)
 
 
+def dump_outputs(job, out_dir):
+    """--dump-outputs: what the last timed step handed its caller -- the PCM of the batch it decoded, that step's status words
+    and the IMDCT overlap it carries into the batch's next frame -- as DIR/<name>.npy.  PCM and overlap are kept for the same
+    DUMP_STREAMS streams of the batch in every run (a seeded sample, in stream order); int16 goes to float32 and int32 to
+    float64, both exact."""
+    torch = job.torch
+    torch.cuda.synchronize()
+    i = job.next_step - 1
+    b = job.batches[i % len(job.batches)]
+    _, _, _, status, imdct_status = job.lanes[i % len(job.lanes)]
+    rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(FRAMES_PER_STEP, DUMP_STREAMS, replace=False))).to(job.dev)
+    per_stream = lambda t: t.reshape(FRAMES_PER_STEP, -1).index_select(0, rows).cpu().numpy()
+    arrays = {"pcm": per_stream(b["pcm"]).astype(np.float32), "overlap": per_stream(b["overlap"]).astype(np.float64),
+              "imdct_status": imdct_status.cpu().numpy().astype(np.float64)}
+    if status is not None:
+        arrays["status"] = status.cpu().numpy().astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def need_gpus(torch, n):
     """the product has no CPU path: say what is missing instead of failing somewhere inside a launch"""
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -1197,8 +1222,15 @@ def main():
     ap.add_argument("--hip-streams", type=int, default=2,
                     help="HIP streams per rank the steps are dealt out over (step i on stream i %% N; must divide --sets): "
                          "neighbouring steps decode different stream sets, so they share nothing")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short C2 / C3 runs of the N=1 report")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle check of one more step (bit_exact_vs_oracle), the per-rank rates "
+                         "and PCM gather of a multi-rank run, the secondary legs and the CPU baseline of the N=1 report")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (status words; PCM and IMDCT overlap of a fixed, "
+                         "seeded sample of %d of the batch's streams) as DIR/<name>.npy in float32 / float64"
+                    % DUMP_STREAMS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs of the N=1 report")
     ap.add_argument("--workload", choices=["c2", "c2l", "c3", "c4"], default="c4",
                     help="c4 (default): HE-AACv2, mono IMDCT + HQ-SBR + parametric stereo -- the configuration the "
                          "metric is quoted on, and C5 with --gpus N; c2: AAC-LC IMDCT+OLA (BASELINE configs[1]); c2l: c2 "
@@ -1260,20 +1292,24 @@ def main():
     elapsed = xdist.max_over_ranks(dist, own_elapsed, cdev)
     refused = job.refused()
     max_band_hint = job.batches[0].get("max_band_hint", 0) if w == "c4" else None
-    try:
-        checked = job.verify()
-    except Exception as e:  # the checker (oracle/) is test infrastructure: its absence must not hide the measurement
-        checked = "unavailable: %r" % (e,)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
+    checked = None
+    if args.full:
+        try:
+            checked = job.verify()
+        except Exception as e:  # the checker (oracle/) is test infrastructure: its absence must not hide the measurement
+            checked = "unavailable: %r" % (e,)
 
     # the ranks' own rates (load balance of a SCALE run) and the final interleaved gather over RCCL/xGMI, once
     per_rank, gather = None, None
-    if dist is not None:
+    if dist is not None and args.full:
         pcm = job.batches[0]["pcm"].view(FRAMES_PER_STEP, -1)
         per_rank, gather = xdist.post_run_report(dist, pcm.cpu() if shared else pcm, FRAMES_PER_STEP * args.steps / own_elapsed, cdev, barrier)
         assert gather["ok"] is not False, "the gathered PCM differs from the ranks' shards"
 
     secondary = None
-    if world == 1 and not args.no_secondary and w == "c4":
+    if world == 1 and args.full and not args.no_secondary and w == "c4":
         secondary = {}
         try:   # what a caller with smaller batches gets: the same launches per step on the first k streams
             sweep = {}
@@ -1370,8 +1406,9 @@ def main():
                          "kernel": KERNELS[w], "kernel_ms": round(kern_ms, 5), "alg_bytes_per_launch": alg_bytes,
                          "valu": valu_roofline(w, kern_ms)},
             "refused_frac": refused,
-            "bit_exact_vs_oracle": checked,
         }
+        if args.full:
+            out["bit_exact_vs_oracle"] = checked
         if per_rank is not None:
             out["per_rank_frames_per_s"] = per_rank
             out["gather"] = gather
@@ -1381,7 +1418,7 @@ def main():
                                     % (world, torch.cuda.device_count()))
         if secondary is not None:
             out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_sbr(w) if w in ("c3", "c4") else cpu_baseline(limiter=(w == "c2l"))
         print(json.dumps(out))
     if dist is not None:

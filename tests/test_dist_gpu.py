@@ -71,7 +71,7 @@ def test_two_ranks_of_the_bench_decode_on_one_gpu():
     ranks' checksums.  (RCCL itself runs at world 1 above; with two ranks on one device it refuses.)"""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "4", "--warmup", "2",
-                        "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900,
+                        "--full", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -31,7 +31,7 @@ chain() { # $1 = c4 | c3: kernel stats of the bench command, HBM and SQ counter 
 }
 
 if has bench; then
-  python $R/bench.py > $O/${TAG}_bench_c4.json 2> $O/${TAG}_bench_c4.err
+  python $R/bench.py --full > $O/${TAG}_bench_c4.json 2> $O/${TAG}_bench_c4.err
   python -c "import json; d=json.load(open('$O/${TAG}_bench_c4.json')); s=d['secondary']; print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['bit_exact_vs_oracle'], d['refused_frac'], {k: (v.get('ms_per_step'), v.get('bit_exact_vs_oracle')) for k, v in s.items()}, s.get('c4_batch_sweep'), {k: v.get('roofline_frac') for k, v in s['f4_transforms'].items() if isinstance(v, dict)}, d['cpu_baseline']['value'])"
 fi
 has c4 && chain c4

@@ -43,7 +43,7 @@ for n in ('driver_args_1', 'long_1', 'driver_args_2', 'long_2'):
     d = json.load(open('$O/${TAG}_bench_c4_%s.json' % n)); print(n, d['steps'], d['warmup'], d['ms_per_step'], d['roofline']['frac'])"
 fi
 if has bench; then
-  python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_c4.json 2> $O/${TAG}_bench_c4.err
+  python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench_c4.json 2> $O/${TAG}_bench_c4.err
   python -c "import json; d=json.load(open('$O/${TAG}_bench_c4.json')); s=d['secondary']; print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['bit_exact_vs_oracle'], d['refused_frac'], {k: (v.get('ms_per_step'), v.get('bit_exact_vs_oracle')) for k, v in s.items()}, s.get('c4_batch_sweep'), {k: v.get('roofline_frac') for k, v in s['f4_transforms'].items() if isinstance(v, dict)}, d['cpu_baseline']['value'])"
 fi
 has c4 && chain c4
