@@ -525,6 +525,20 @@ XAAC_API int32_t xaac_esbr_qmf_synthesis_ds_batch(xaac_ctx *ctx, const xaac_esbr
 /* Low-power SBR channel-frames (QMF analysis -> HF generation + envelope adjustment -> QMF synthesis). */
 XAAC_API uint64_t xaac_sbr_lp_workspace_bytes(int32_t n_ch);
 XAAC_API int32_t xaac_sbr_lp_process_batch(xaac_ctx *ctx, const xaac_sbr_lp_batch *batch);
+/* The same for the 960-sample cores of DAB+ / DRM (ixheaacd_sbr_dec with low_pow_flag = 1 and num_time_slots 15: 15 time slots
+ * of 2, 30 QMF slots a frame -- the reference's num_time_slots == 15 / num_columns == 30 branches: the 36-slot autocorrelation,
+ * ixheaacd_covariance_matrix_calc_dec_960 (lpp_tran.c:169, :903), the envelope adjuster's borders at time slot 15 and 30 QMF
+ * slots (env_calc.c:724, :815, :918), the overlap slots from slot 30 on (sbr_dec.c:1290)).  The same descriptor with 960 for
+ * 1024 and 1920 for 2048: pcm_in holds 960 core samples per channel, pcm_out gets 1920, interleaved as above.
+ *  - Every channel's header must have num_time_slots 15, time_step 2 and num_columns 30, and envelope borders up to 18 (15 + 3);
+ *    a channel whose side info does not (or whose side info is outside the structs' capacity otherwise) is refused before the
+ *    banks run: status -1, its state and its output samples left as they are, its neighbours in the batch decoded as if it
+ *    were not there.  (A frame the reference itself fails, status -1 too, updates the state as the reference does.)
+ *    xaac_sbr_lp_process_batch goes on refusing 15-slot headers as it refuses any bad side info.
+ *  - The state and xaac_sbr_lp_workspace_bytes(n_ch) are those of the 1024-sample entry (the bank rings keep their layout).
+ *  - down_sample != 0 is refused with XAAC_FATAL_BAD_ARG (the down-sampled bank at 30 slots is not covered).
+ * Out of scope: HQ mode / parametric stereo at 30 slots (HE-AAC v2 960), and the eSBR branch (Path A). */
+XAAC_API int32_t xaac_sbr_lp960_process_batch(xaac_ctx *ctx, const xaac_sbr_lp_batch *batch);
 
 /* HQ SBR stream-frames (complex QMF analysis -> LPP transposer + envelope adjustment -> [parametric
  * stereo] -> complex QMF synthesis, once per output channel). */

@@ -350,6 +350,8 @@ def load_library():
     lib.xaac_esbr_qmf_synthesis_ds_batch.restype = ctypes.c_int32
     lib.xaac_sbr_lp_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_SbrLpBatch)]
     lib.xaac_sbr_lp_process_batch.restype = ctypes.c_int32
+    lib.xaac_sbr_lp960_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_SbrLpBatch)]
+    lib.xaac_sbr_lp960_process_batch.restype = ctypes.c_int32
     lib.xaac_sbr_lp_workspace_bytes.argtypes = [ctypes.c_int32]
     lib.xaac_sbr_lp_workspace_bytes.restype = ctypes.c_uint64
     lib.xaac_sbr_hq_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_SbrHqBatch)]
@@ -966,24 +968,40 @@ class XaacContext:
     def sbr_lp_workspace_bytes(self, n_ch):
         return int(self._lib.xaac_sbr_lp_workspace_bytes(int(n_ch)))
 
+    def _sbr_lp_batch(self, pcm_in, header, frame, state, pcm_out, workspace, status, in_ch_fac, out_ch_fac, down_sample,
+                      frame_in):
+        n_ch = state.shape[0]
+        b = _SbrLpBatch()
+        b.n_ch, b.in_ch_fac, b.out_ch_fac = n_ch, int(in_ch_fac), int(out_ch_fac)
+        b.down_sample = int(bool(down_sample))
+        b.pcm_in = _ptr(pcm_in, "int16", n_ch * frame_in, device_ok=True)
+        b.header = _ptr(header, "uint8", n_ch * SBR_HEADER_BYTES, device_ok=True)
+        b.frame = _ptr(frame, "uint8", n_ch * SBR_FRAME_BYTES, device_ok=True)
+        b.state = _ptr(state, "uint8", n_ch * SBR_STATE_BYTES, device_ok=True)
+        b.pcm_out = _ptr(pcm_out, "int16", n_ch * (frame_in if down_sample else 2 * frame_in), device_ok=True)
+        b.status = _ptr(status, "int32", n_ch, allow_none=True, device_ok=True)
+        b.workspace = _ptr(workspace, "uint8", device_ok=True)
+        b.workspace_bytes = workspace.numel()
+        return b
+
     def sbr_lp_process_batch(self, pcm_in, header, frame, state, pcm_out, workspace, status=None, in_ch_fac=1,
                              out_ch_fac=1, down_sample=False):
         """Batched ixheaacd_sbr_dec, low-power mode (HE-AACv1): one frame per channel.
         pcm_in int16[n_ch*1024]; header/frame/state uint8[n_ch, SBR_*_BYTES] (structs of include/xaac_sbr.h,
         state in/out); pcm_out int16[n_ch*2048]; workspace uint8[>= sbr_lp_workspace_bytes(n_ch)];
         status optional int32[n_ch]."""
-        n_ch = state.shape[0]
-        b = _SbrLpBatch()
-        b.n_ch, b.in_ch_fac, b.out_ch_fac = n_ch, int(in_ch_fac), int(out_ch_fac)
-        b.down_sample = int(bool(down_sample))
-        b.pcm_in = _ptr(pcm_in, "int16", n_ch * 1024, device_ok=True)
-        b.header = _ptr(header, "uint8", n_ch * SBR_HEADER_BYTES, device_ok=True)
-        b.frame = _ptr(frame, "uint8", n_ch * SBR_FRAME_BYTES, device_ok=True)
-        b.state = _ptr(state, "uint8", n_ch * SBR_STATE_BYTES, device_ok=True)
-        b.pcm_out = _ptr(pcm_out, "int16", n_ch * (1024 if down_sample else 2048), device_ok=True)
-        b.status = _ptr(status, "int32", n_ch, allow_none=True, device_ok=True)
-        b.workspace = _ptr(workspace, "uint8", device_ok=True)
-        b.workspace_bytes = workspace.numel()
+        b = self._sbr_lp_batch(pcm_in, header, frame, state, pcm_out, workspace, status, in_ch_fac, out_ch_fac, down_sample,
+                               1024)
         rc = self._lib.xaac_sbr_lp_process_batch(self._h, ctypes.byref(b))
         if rc != 0:
             raise XaacError(rc, "xaac_sbr_lp_process_batch")
+
+    def sbr_lp960_process_batch(self, pcm_in, header, frame, state, pcm_out, workspace, status=None, in_ch_fac=1,
+                                out_ch_fac=1, down_sample=False):
+        """The same for 960-sample cores (DAB+ / DRM: 15 time slots, 30 QMF slots a frame): pcm_in int16[n_ch*960],
+        pcm_out int16[n_ch*1920]; the workspace of sbr_lp_workspace_bytes(n_ch).  down_sample is refused (XAAC_FATAL_BAD_ARG)."""
+        b = self._sbr_lp_batch(pcm_in, header, frame, state, pcm_out, workspace, status, in_ch_fac, out_ch_fac, down_sample,
+                               960)
+        rc = self._lib.xaac_sbr_lp960_process_batch(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, "xaac_sbr_lp960_process_batch")

@@ -431,11 +431,15 @@ FX_HD XsLv xs_seg_running_max(const XsCx &cx, const XsLv &seg, const XsLv &e, in
    64-band instantiation (sbr_core_kernel.hip: "narrow rows"). */
 /* LD_: the low-delay SBR of AAC-ELD (sbr_dec.c:706-775: op_delay 0 -- no overlap slots, nothing carried in the matrix --, one QMF
    slot per time slot, 16 or 15 slots a frame): rows -2, -1 the LPC history, rows 0 .. cols - 1 the frame's slots. */
-template <int HQ_, int NB_ = 64, int LD_ = 0>
+/* NS_: QMF slots of a frame outside low-delay SBR -- 32 (1024-sample cores: 16 time slots of 2) or 30 (the 960-sample cores
+   of DAB+ / DRM: 15 time slots of 2; the reference's num_time_slots == 15 branches, MAX_ENV_COLS_960).  The slots the
+   envelope adjuster compares against (MAX_COLS, SBR_TIME_SLOTS of env_calc.c) follow it. */
+template <int HQ_, int NB_ = 64, int LD_ = 0, int NS_ = 32>
 struct XsQmfT {
   static constexpr int HQ = HQ_;
   static constexpr int NB = NB_;
   static constexpr int LD = LD_;
+  static constexpr int NS = NS_;
   static constexpr int OV = LD_ ? 0 : 6; /* op_delay: the overlap slots in front of the frame's own */
   static constexpr int IM = NB_;                    /* offset of a row's imaginary columns */
   static constexpr int ROW = HQ_ ? 2 * NB_ : NB_;
@@ -1970,7 +1974,7 @@ FX_HD void xs_adapt_noise_gain_lp(const XsCx &cx, ST *st, XsEnv &v, const int16_
     const int shl_a = sh_a > 0 ? (sh_a & 31) : 0, shr_a = sh_a > 0 ? 0 : ((-sh_a) & 31);
     const int shl_b = sh_b > 0 ? (sh_b & 31) : 0, shr_b = sh_b > 0 ? 0 : ((-sh_b) & 31);
     for (int l = s0; l < s1; l++) {
-      if (l == 32 && s0 < 32) { /* (uniform) */
+      if (l == Q::NS && s0 < Q::NS) { /* (uniform) */
         const int diff = final_e - ne;
         ne = final_e;
         const int16_t nl2 = xs_noise_rescale(nl, diff);
@@ -1983,7 +1987,7 @@ FX_HD void xs_adapt_noise_gain_lp(const XsCx &cx, ST *st, XsEnv &v, const int16_
       ph = (ph + nsb) & 511;
       harm = (harm + 1) & 3;
       int32_t val = fx_mul32x16(x(l, sb_start + k), gm);
-      val = (int32_t)((uint32_t)val << (l < 32 ? shl_a : shl_b)) >> (l < 32 ? shr_a : shr_b);
+      val = (int32_t)((uint32_t)val << (l < Q::NS ? shl_a : shl_b)) >> (l < Q::NS ? shr_a : shr_b);
       const int32_t noisy = xs_mac16x16_shl_sat(val, rp, nl); /* (every lane: a select below, not a branch per lane) */
       if (!(hi & 1)) {
         const int32_t toned = hi == 0 ? fx_add_sat(val, sine32) : fx_sub_sat(val, sine32);
@@ -2017,7 +2021,7 @@ FX_HD void xs_adapt_noise_gain_lp(const XsCx &cx, ST *st, XsEnv &v, const int16_
   XS_ONE {
     const int n = s1 > s0 ? s1 - s0 : 0;
     int ne = noise_e;
-    if (s0 < 32 && s1 > 32) ne = final_e;
+    if (s0 < Q::NS && s1 > Q::NS) ne = final_e;
     st->start_up = 0;
     st->filt_buf_noise_e = n > 0 ? ne : fb_noise_e0;
     st->ph_index = (int16_t)((ph0 + n * nsb) & 511);
@@ -2070,7 +2074,7 @@ FX_HD void xs_adapt_noise_gain_lp_split(const XsCx &cx, ST *st, const XsEnv &v, 
   int fi0 = !(sb_start & 1); /* freq_inv for harmonic index 1; index 3 negates it */
   fi0 = (fi0 << 1) - 1;
   const int n = s1 > s0 ? s1 - s0 : 0;
-  const bool crosses = s0 < 32 && s1 > 32;
+  const bool crosses = s0 < Q::NS && s1 > Q::NS;
   const int n_half = (((n + 1) >> 1) + 1) & ~1; /* slots of the lower half of the wave: even, at least half of them */
   XsLv nl_out, fbn_out;
   nl_out.fill(0);
@@ -2118,12 +2122,12 @@ FX_HD void xs_adapt_noise_gain_lp_split(const XsCx &cx, ST *st, const XsEnv &v, 
     for (int u = 0; u < n_half; u++) {
       const int sl_i = first + u, j = sl_i - s0;
       if (sl_i >= s1) continue;
-      const bool late = sl_i >= 32 && s0 < 32; /* behind the change of the noise exponent */
+      const bool late = sl_i >= Q::NS && s0 < Q::NS; /* behind the change of the noise exponent */
       const int16_t nl = late ? nl_b : nl_a;
       const int ph = (ph0 + j * nsb) & 511, hi = (harm0 + j) & 3;
       const int16_t rp = rand_hi[ph + 1 + k];
       int32_t val = fx_mul32x16(x(sl_i, sb_start + k), gm);
-      val = (int32_t)((uint32_t)val << (sl_i < 32 ? shl_a : shl_b)) >> (sl_i < 32 ? shr_a : shr_b);
+      val = (int32_t)((uint32_t)val << (sl_i < Q::NS ? shl_a : shl_b)) >> (sl_i < Q::NS ? shr_a : shr_b);
       const int32_t noisy = xs_mac16x16_shl_sat(val, rp, nl);
       if (!((harm0 + u) & 1)) { /* (uniform) */
         const int32_t toned = hi == 0 ? fx_add_sat(val, sine32) : fx_sub_sat(val, sine32);
@@ -2559,11 +2563,11 @@ FX_HD void xs_adapt_noise_gain_hq(const XsCx &cx, XsAdjMem &m, const XsEnv &v, i
     int n_smooth = s1 - s0 < smooth_length ? s1 - s0 : smooth_length;
     for (; n_smooth > 0; n_smooth--, l++) {
       int scale_change;
-      if (l < 32) {
+      if (l < Q::NS) {
         scale_change = adj_e - input_e;
       } else {
         scale_change = final_e - input_e;
-        if (l == 32 && s0 < 32) {
+        if (l == Q::NS && s0 < Q::NS) {
           const int diff = final_e - ne;
           ne = final_e;
           if (k >= 0) nl = xs_noise_rescale(nl, diff);
@@ -2615,7 +2619,7 @@ FX_HD void xs_adapt_noise_gain_hq(const XsCx &cx, XsAdjMem &m, const XsEnv &v, i
         re = xs_mac16x16_shl_sat(re, (int16_t)(rp >> 16), snz);
         im = xs_mac16x16_shl_sat(im, (int16_t)rp, snz);
       }
-      hr |= (g == 0 && l < 32) ? (fx_abs_nrm(re) | fx_abs_nrm(im)) : 0; /* (the half that writes the slot) */
+      hr |= (g == 0 && l < Q::NS) ? (fx_abs_nrm(re) | fx_abs_nrm(im)) : 0; /* (the half that writes the slot) */
       if (g == 0) {
         x(l, col) = re;
         x.im(l, col) = im;
@@ -2626,13 +2630,13 @@ FX_HD void xs_adapt_noise_gain_hq(const XsCx &cx, XsAdjMem &m, const XsEnv &v, i
        but the random phase and the harmonic index is a constant of the band, so the slots go in bursts of eight
        (rows and random phases fetched together, no control flow between the slots) */
     while (l < s1) {
-      const int seg_end = (l < 32 && s1 > 32) ? 32 : s1;
+      const int seg_end = (l < Q::NS && s1 > Q::NS) ? Q::NS : s1;
       int scale_change;
-      if (l < 32) {
+      if (l < Q::NS) {
         scale_change = adj_e - input_e;
       } else {
         scale_change = final_e - input_e;
-        if (l == 32 && s0 < 32) {
+        if (l == Q::NS && s0 < Q::NS) {
           const int diff = final_e - ne;
           ne = final_e;
           if (k >= 0) nl = xs_noise_rescale(nl, diff);
@@ -2662,7 +2666,7 @@ FX_HD void xs_adapt_noise_gain_hq(const XsCx &cx, XsAdjMem &m, const XsEnv &v, i
       a.step = bands;
       a.kk = kk;
       a.hr = 0;
-      a.hr_keep = (k >= 0 && l < 32) ? -1 : 0;
+      a.hr_keep = (k >= 0 && l < Q::NS) ? -1 : 0;
       /* this lane's share of the segment's slots [l, seg_end) */
       const int count = seg_end - l, half = two ? (count + 1) >> 1 : count;
       int lg = g ? l + half : l, phg = g ? (ph + half * bands) & 511 : ph, harmg = g ? (harm + half) & 3 : harm;
@@ -2696,7 +2700,7 @@ FX_HD void xs_adapt_noise_gain_hq(const XsCx &cx, XsAdjMem &m, const XsEnv &v, i
   {
     const int n = s1 > s0 ? s1 - s0 : 0;
     int ne = noise_e;
-    if (s0 < 32 && s1 > 32) ne = final_e;
+    if (s0 < Q::NS && s1 > Q::NS) ne = final_e;
     m.start_up = 0;
     m.filt_buf_noise_e = n > 0 ? ne : fb_noise_e0;
     m.ph_index = (int16_t)((ph0 + n * bands) & 511);
@@ -2887,7 +2891,7 @@ FX_HD void xs_hf_generator_hq(const XsCx &cx, const xaac_sbr_header *h, ST *st, 
   /* covariances over num_columns + 6 = 38 slots (lpp_tran.c:1034).  All eight sums wrap, so the slots are dealt out
      to the 64 / w lane groups of w lanes (lane = group * w + low band) and the groups' parts added up. */
   /* (low-delay SBR: over the frame's own num_columns = 16 or 15 slots, lpp_tran.c:1040-1052) */
-  const int ncov = Q::LD ? cx.uni(h->num_columns) : 38;
+  const int ncov = Q::LD ? cx.uni(h->num_columns) : Q::NS + 6; /* (960-sample cores: 36, lpp_tran.c:1024-1029) */
   const int cw = stop_patch <= 16 ? 16 : (stop_patch <= 32 ? 32 : 64), cper = (ncov * cw + 63) / 64;
   XsLv cv[8];
   for (int i = 0; i < 8; i++) cv[i].fill(0);
@@ -3061,7 +3065,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
   /* the frame's grid: two QMF slots per time slot and rows up to MAX_ENV_COLS = 38, or -- low-delay SBR, env_calc.c:847-849 --
      one, inside the frame's own rows; the time slot at which an envelope counts for the next frame's exponent: env_calc.c:811-837 */
   const int t_step = Q::LD ? 1 : 2, nts_hdr = cx.uni(h->num_time_slots);
-  const int row_limit = Q::LD ? nts_hdr : 38, frame_end_slot = (Q::LD && nts_hdr == 15) ? 15 : 16;
+  const int row_limit = Q::LD ? nts_hdr : 38, frame_end_slot = Q::LD ? (nts_hdr == 15 ? 15 : 16) : Q::NS / 2;
   {
     XS_UNROLL
     for (int i = 0; i < XAAC_SBR_MAX_ENVELOPES; i++) {
@@ -3124,7 +3128,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
       /* envelope i: the reference's checks, in its order */
       s0[0] = 2 * bordv.get(i);
       s1[0] = 2 * bordv.get(i + 1);
-      if (s0[0] >= 38 || s1[0] > 38 || nf_idx >= XAAC_SBR_MAX_NOISE_ENVELOPES) {
+      if (s0[0] >= 38 || s1[0] > 38 || nf_idx >= XAAC_SBR_MAX_NOISE_ENVELOPES) { /* (MAX_ENV_COLS at 30 slots too) */
         if constexpr (Q::HQ) xs_adj_store(cx, st, nsb, adj);
         return -1;
       }
@@ -3137,7 +3141,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
       ps.fr[0] = resv.get(i);
       ps.nf_off[0] = nf_off;
       ps.noise_absc[0] = (i == transient_env || i == tansient_env_prev) ? 1 : 0;
-      ps.noise_e[0] = (int16_t)(s0[0] < 32 ? adj_e : final_e);
+      ps.noise_e[0] = (int16_t)(s0[0] < Q::NS ? adj_e : final_e);
       ps.env[1] = ps.fr[1] = ps.nf_off[1] = ps.noise_absc[1] = ps.noise_e[1] = 0;
       s0[1] = s1[1] = 0;
       /* envelope i + 1 rides along if it is a regular one behind envelope i: it would pass the same checks, and its slots lie
@@ -3158,7 +3162,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
           ps.fr[1] = resv.get(i + 1);
           ps.nf_off[1] = off2;
           ps.noise_absc[1] = (i + 1 == transient_env || i + 1 == tansient_env_prev) ? 1 : 0;
-          ps.noise_e[1] = (int16_t)(t0 < 32 ? adj_e : final_e);
+          ps.noise_e[1] = (int16_t)(t0 < Q::NS ? adj_e : final_e);
           nf_idx = nf2;
           nf_off = off2;
         }
@@ -3235,7 +3239,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
     XS_T(6);
     xs_noiselimiting(cx, h, skip, n_meta, v, w, &XS_TAB_LIMG(2 * cx.uni(h->limiter_gains)), noise_absc, lim_of);
     XS_T(7);
-    const int16_t noise_e = (int16_t)(s0 < 32 ? adj_e : final_e);
+    const int16_t noise_e = (int16_t)(s0 < Q::NS ? adj_e : final_e);
     if constexpr (!Q::HQ) {
       XsLv grp_end;
       grp_end.fill(0);
@@ -3262,12 +3266,12 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
     ov_reserve = xs_headroom(cx, x, max_sb, sb_end, 0, first_start);
     /* the envelopes tile [first_start, 32) (the parser's grids do): every word of the range has been written by the slot
        walks, which kept the OR of the magnitudes (XsAdjMem::hr); else the scan */
-    bool tiled = Q::HQ && num_env > 0 && 2 * cx.uni(border[num_env]) >= 32;
+    bool tiled = Q::HQ && num_env > 0 && 2 * cx.uni(border[num_env]) >= Q::NS;
     for (int i = 0; i < num_env; i++) tiled = tiled && cx.uni(border[i]) < cx.uni(border[i + 1]);
     if (tiled)
       reserve = xs_pnorm32(xs_lv_or(cx, adj.hr) | 1);
     else
-      reserve = xs_headroom(cx, x, max_sb, sb_end, first_start, 32);
+      reserve = xs_headroom(cx, x, max_sb, sb_end, first_start, Q::NS); /* (MAX_COLS, or max_cols = 30: env_calc.c:969-978) */
   }
   const int output_e = (ov_adj_e - ov_reserve) > (adj_e - reserve) ? (ov_adj_e - ov_reserve) : (adj_e - reserve);
   if (pend) {
@@ -3353,7 +3357,9 @@ FX_HD void xs_rescale_x_overlap(const XsCx &cx, const xaac_sbr_header *h, const 
    frame outside these bounds is refused with -1 like the grid checks of sbr_dec.c:733-748 instead of being indexed.
    A frame the reference decodes always passes. */
 template <class ST>
-FX_HD int xs_side_info_bad(const XsCx &cx, const xaac_sbr_header *h, const xaac_sbr_frame *f, const ST *st, int ld = 0) {
+/* nq: QMF slots of the frame grid the caller is laid out for outside low-delay SBR, 32 or 30 (XsQmfT::NS) */
+FX_HD int xs_side_info_bad(const XsCx &cx, const xaac_sbr_header *h, const xaac_sbr_frame *f, const ST *st, int ld = 0,
+                           int nq = 32) {
   int bad = 0;
   /* A frame without SBR processing (apply_processing 0: the decoder has no valid SBR header yet, or lost it) is up-sampled
      by the two banks alone (xs_sbr_core_tail): header and frame side info are whatever the parser last held -- the
@@ -3371,7 +3377,7 @@ FX_HD int xs_side_info_bad(const XsCx &cx, const xaac_sbr_header *h, const xaac_
     /* the frame grid this implementation (and the reference's MAX_ENV_COLS buffers, sbr_dec.c:733-748) is laid out
        for: 16 time slots of 2 QMF slots, 32 columns -- decided here, before xs_rescale_x_overlap turns
        time_step * (prev_end_position - num_time_slots) into a row index */
-    if (!ld) bad |= (h->num_time_slots != 16) | (h->time_step != 2) | (h->num_columns != 32);
+    if (!ld) bad |= (h->num_time_slots != nq / 2) | (h->time_step != 2) | (h->num_columns != nq);
     else bad |= (h->num_time_slots != 16 && h->num_time_slots != 15) | (h->time_step != 1) | (h->num_columns != h->num_time_slots); /* low-delay SBR */
     /* (the state members that become row / band indices are looked at above: a state is the host's to initialise,
        sbrdec_initfuncs.c) */
@@ -3401,7 +3407,7 @@ FX_HD int xs_side_info_bad(const XsCx &cx, const xaac_sbr_header *h, const xaac_
       /* a patch's high bands (low band + dst_end_band, the reference's name for the offset) stay inside the row */
       bad |= pp->src_end_band > pp->src_start_band && pp->src_end_band + pp->dst_end_band > 64;
     }
-    if (i <= n_env && i <= XAAC_SBR_MAX_ENVELOPES) bad |= (unsigned)f->border_vec[i] > (ld ? (unsigned)h->num_time_slots : 19u); /* (low-delay: the matrix holds the frame's own rows) */
+    if (i <= n_env && i <= XAAC_SBR_MAX_ENVELOPES) bad |= (unsigned)f->border_vec[i] > (ld ? (unsigned)h->num_time_slots : (unsigned)(nq / 2 + 3)); /* (low-delay: the matrix holds the frame's own rows) */
     if (i < n_env && i < XAAC_SBR_MAX_ENVELOPES) bad |= (unsigned)f->freq_res[i] > 1u;
     if (i <= n_nenv && i <= XAAC_SBR_MAX_NOISE_ENVELOPES) bad |= (unsigned)f->noise_border_vec[i] > 19u;
   }
@@ -3497,7 +3503,7 @@ FX_HD int xs_sbr_core_tail(const XsCx &cx, const xaac_sbr_header *h, const xaac_
     XS_ONE st->hb_scale = (int16_t)save_lb_scale;
   }
   cx.sync();
-  xs_lpc_save(cx, st, x, cx.uni(st->codec_usb), Q::LD ? cx.uni(h->num_time_slots) * cx.uni(h->time_step) : 32);
+  xs_lpc_save(cx, st, x, cx.uni(st->codec_usb), Q::LD ? cx.uni(h->num_time_slots) * cx.uni(h->time_step) : Q::NS);
   cx.sync();
   XS_T(15);
   return 0;
@@ -3519,7 +3525,7 @@ FX_HD int xs_sbr_core(const XsCx &cx, const xaac_sbr_header *h, const xaac_sbr_f
      out for: 16 time slots of 2 QMF slots; anything else is refused like the reference refuses its own limits */
   const int no_bins = cx.uni(h->num_time_slots) * cx.uni(h->time_step);
   if (Q::LD ? ((no_bins != 16 && no_bins != 15) || cx.uni(h->time_step) != 1 || cx.uni(h->num_columns) != no_bins)
-            : (no_bins != 32 || cx.uni(h->num_columns) != 32))
+            : (no_bins != Q::NS || cx.uni(h->num_columns) != Q::NS))
     return -1;
   /* xs_side_info_bad has been run by the caller, before xs_rescale_x_overlap touched the overlap slots */
   const int usb = cx.uni(st->codec_usb);

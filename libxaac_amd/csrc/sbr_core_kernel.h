@@ -28,6 +28,8 @@ typedef struct XaacSbrCoreParams {
   int32_t *work_counter; /* = defer_count + 1: the persistent waves' next channel-frame */
   int32_t num_cu;        /* compute units of the device (grid of the persistent launch) */
   int32_t counters_zeroed; /* 1: an earlier launch on the stream has cleared defer_count / work_counter */
+  int32_t qmf_slots;       /* QMF slots of the frames: 0 / 32, or 30 (960-sample cores, low-power launch only:
+                              xaac_sbr_lp960_process_batch) */
   int32_t narrow_only;     /* the caller's assertion (xaac_sbr_hq_batch.max_band_hint): no list launch; a stream that needs the 64-band
                               rows is refused */
 } XaacSbrCoreParams;
@@ -36,6 +38,8 @@ typedef struct XaacSbrCoreParams {
 extern "C" {
 #endif
 hipError_t xaac_launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t stream);
+/* qmf_slots 30 only: xs_side_info_bad of every channel up front, the verdict in syn_par[8 ch + 7] (1: refused) */
+hipError_t xaac_launch_sbr_screen(const XaacSbrCoreParams *p, hipStream_t stream);
 /* HQ: x rows are 128 words (64 real | 64 imaginary): [n_ch][2 * XAAC_SBR_X_WORDS] */
 hipError_t xaac_launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStream_t stream);
 #ifdef __cplusplus

@@ -133,11 +133,21 @@ __device__ __forceinline__ void copy_words(int32_t *dst, const int32_t *src, int
     if (i + 64 * j < n) dst[i + 64 * j] = t[j];
 }
 
-/* one channel-frame; returns false when the stream has to go through the 64-band rows (nothing written then) */
-template <int HQ, int NB>
+/* one channel-frame; returns false when the stream has to go through the 64-band rows (nothing written then).
+   NS: QMF slots of the frame, 32 or 30 (960-sample cores): the matrix keeps its 40 rows, of which 2 + 6 + NS are in use. */
+template <int HQ, int NB, int NS = 32>
 __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int ch, XsLds<HQ, NB> &s, const int lane) {
-  typedef XsQmfT<HQ, NB> Q;
+  typedef XsQmfT<HQ, NB, 0, NS> Q;
   constexpr int ROW = Q::ROW, ROWG = HQ ? 128 : 64, XWG = (HQ ? 2 : 1) * XAAC_SBR_X_WORDS;
+  if (NS != 32 && __builtin_amdgcn_readfirstlane((int)p.syn_par[8 * (size_t)ch + 7])) {
+    /* refused by the screen in front of the banks (xaac_launch_sbr_screen): status -1, the state left as it is, the synthesis
+       bank told to leave the channel alone */
+    if (lane == 0) {
+      p.syn_par[8 * (size_t)ch + 6] = 1;
+      if (p.status) p.status[ch] = -1;
+    }
+    return true;
+  }
   xaac_sbr_state *gst = p.state + ch;
   int32_t *gx = p.x + (size_t)ch * XWG;
   const int32_t *gstw = reinterpret_cast<const int32_t *>(gst);
@@ -151,7 +161,8 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
   /* ---- copy-in: every global load of the channel-frame is issued before the first LDS store, so the wave pays one
      memory latency here, not one per piece (the kernel is latency bound: a wave's lifetime is its cost) ---- */
   constexpr int NH = (sizeof(xaac_sbr_header) / 4 + 63) / 64, NF = (kFrameHeadBytes / 4 + 63) / 64;
-  constexpr int NT = (kTailWords + 63) / 64, NOV = 6 * ROWG / 64, NAS = 32 * 32 * (HQ ? 2 : 1) / 64;
+  constexpr int NT = (kTailWords + 63) / 64, NOV = 6 * ROWG / 64, NAS = NS * 32 * (HQ ? 2 : 1) / 64;
+  static_assert(NAS * 64 == NS * 32 * (HQ ? 2 : 1), "whole runs of lanes");
   constexpr int NNF = sizeof(s.noise_floor) / 4;
   static_assert(NOV * 64 == 6 * ROWG && NF == 1, "whole rows of lanes");
   constexpr int NSF = (sizeof(((xaac_sbr_frame *)0)->int_env_sf_arr) / 4 + 63) / 64; /* the envelopes' scale factors: 224 words */
@@ -194,6 +205,8 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
     for (int j = 0; j < NT; j++)
       if (lane + 64 * j < kTailWords) m[2 + lane + 64 * j] = r_t[j];
     for (int i = lane; i < 2 * ROW; i += 64) s.x[i] = 0;
+    if (NS < 32) /* rows behind the frame's: the reference's buffers have them (MAX_ENV_COLS), the LP filter's edge writes reach them */
+      for (int i = lane; i < (32 - NS) * ROW; i += 64) s.x[(8 + NS) * ROW + i] = 0;
     if (!HQ)
       for (int i = lane; i < 128; i += 64) s.x[XAAC_SBR_X_ROWS * ROW + i] = 0;
   }
@@ -218,7 +231,7 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
       s.x[(8 + row) * ROW + col] = r_an[j];
     }
     /* what the analysis bank does not write is 0: bands 32 and up of the analysed slots (sbr_dec.c:1121) */
-    for (int i = lane; i < 32 * (HQ ? 2 : 1) * (NB - 32); i += 64) {
+    for (int i = lane; i < NS * (HQ ? 2 : 1) * (NB - 32); i += 64) {
       const int row = i / ((HQ ? 2 : 1) * (NB - 32)), c = i % ((HQ ? 2 : 1) * (NB - 32));
       s.x[(8 + row) * ROW + (c < NB - 32 ? 32 + c : Q::IM + 32 + (c - (NB - 32)))] = 0;
     }
@@ -231,7 +244,7 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
   const XsCx cx = {lane, 64};
   const Q x = {s.x};
   if (lane == 0) s.st.lb_scale = 0;
-  const int refused = xs_side_info_bad(cx, &s.h, f, &s.st); /* counts / band numbers past the structs' capacity */
+  const int refused = xs_side_info_bad(cx, &s.h, f, &s.st, 0, NS); /* counts / band numbers past the structs' capacity */
   if (NB < 64) {
     /* every band number this frame can turn into a column: the SBR range and its tables, the patches' targets, the
        bank limits xs_rescale_x_overlap walks between (all within 0..64 once xs_side_info_bad has passed) */
@@ -330,9 +343,9 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
 #endif
   }
   xs_wave_sync();
-  /* slots 0..31 for synthesis (+ 32..37 for PS); bands the narrow rows do not hold are 0 */
+  /* slots 0..NS-1 for synthesis (+ NS..NS+5 for PS); bands the narrow rows do not hold are 0 */
   {
-    constexpr int NW = 38 * ROWG / 64; /* runs of 64 words: (slot, part) with band = lane */
+    constexpr int NW = (NS + 6) * ROWG / 64; /* runs of 64 words: (slot, part) with band = lane */
     const bool held = NB == 64 || lane < NB;
     const int lane_h = held ? lane : 0; /* every lane reads (a select, not a predicated region per word) */
     /* env_calc.c:975-1003 on the way: the adjusted bands' slots below 32 take the shift xs_calc_sbrenvelope left pending (a
@@ -354,7 +367,7 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
         if (j0 + j < NW) {
           const int row = HQ ? (j0 + j) >> 1 : j0 + j, part = HQ ? (j0 + j) & 1 : 0;
           int32_t v = s.x[(2 + row) * ROW + part * NB + lane_h];
-          if (row < 32) {
+          if (row < NS) {
             const int sl = row < pend.first_start ? ov_l : mn_l, sr = row < pend.first_start ? ov_r : mn_r; /* (uniform) */
             const int32_t w = (int32_t)((uint32_t)v << sl) >> sr;
             v = adj_band ? w : v;
@@ -373,10 +386,10 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
     for (int j = 0; j < 6; j++) {
       const int row = HQ ? j >> 1 : j, part = HQ ? j & 1 : 0;
       const bool held = NB == 64 || lane < NB;
-      int32_t v = s.x[(2 + 32 + row) * ROW + part * NB + (held ? lane : 0)];
+      int32_t v = s.x[(2 + NS + row) * ROW + part * NB + (held ? lane : 0)];
       /* (a first border behind slot 32 -- no parser's grid has one -- leaves the pending overlap-side shift to these rows too:
          env_calc.c:975 adjusts slots 0 .. first border) */
-      if (32 + row < pend.first_start && lane >= pend.b0 && lane < pend.b1) {
+      if (NS + row < pend.first_start && lane >= pend.b0 && lane < pend.b1) {
         const int sh = pend.sh_ov > 31 ? 31 : (pend.sh_ov < -31 ? -31 : pend.sh_ov);
         v = sh > 0 ? (int32_t)((uint32_t)v << sh) : (v >> -sh);
       }
@@ -444,7 +457,7 @@ __device__ __forceinline__ void stage_tables(int tid) {
 #ifndef XS_LP_MIN_WAVES
 #define XS_LP_MIN_WAVES 3
 #endif
-template <int HQ, int NB, int WAVES>
+template <int HQ, int NB, int WAVES, int NS = 32>
 __global__ __launch_bounds__(64 * WAVES, HQ ? 1 : XS_LP_MIN_WAVES) void xaac_sbr_core_kernel(XaacSbrCoreParams p) {
   __shared__ XsLds<HQ, NB> s[WAVES];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -472,7 +485,7 @@ __global__ __launch_bounds__(64 * WAVES, HQ ? 1 : XS_LP_MIN_WAVES) void xaac_sbr
       ch = first ? (int)blockIdx.x * WAVES + wave : p.n_ch;
     }
     if (ch >= p.n_ch) break;
-    if (!core_one<HQ, NB>(p, ch, s[wave], lane) && lane == 0) {
+    if (!core_one<HQ, NB, NS>(p, ch, s[wave], lane) && lane == 0) {
       if (p.narrow_only) { /* the hint was wrong for this stream: refused, nothing of it written */
         if (p.status) p.status[ch] = XAAC_FATAL_BAD_ARG;
       } else {
@@ -484,7 +497,7 @@ __global__ __launch_bounds__(64 * WAVES, HQ ? 1 : XS_LP_MIN_WAVES) void xaac_sbr
 }
 
 /* the streams of p.defer_list through the 64-band rows: a small grid walks the list (usually empty) */
-template <int HQ>
+template <int HQ, int NS = 32>
 __global__ __launch_bounds__(64) void xaac_sbr_core_list_kernel(XaacSbrCoreParams p) {
   __shared__ XsLds<HQ, 64> s;
   const int lane = threadIdx.x;
@@ -493,11 +506,12 @@ __global__ __launch_bounds__(64) void xaac_sbr_core_list_kernel(XaacSbrCoreParam
   stage_tables<HQ, 64>(lane);
   for (int j = blockIdx.x; j < n; j += gridDim.x) {
     xs_wave_sync();
-    core_one<HQ, 64>(p, p.defer_list[j], s, lane);
+    core_one<HQ, 64, NS>(p, p.defer_list[j], s, lane);
   }
 }
 
-extern "C" hipError_t xaac_launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t stream) {
+template <int NS>
+static hipError_t launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t stream) {
   XaacSbrCoreParams q = *p;
   q.work_counter = nullptr;
 #ifndef XS_LP_WAVES
@@ -514,11 +528,33 @@ extern "C" hipError_t xaac_launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStr
 #define XS_LP_WG_PER_CU 5
 #endif
     const int resident = XS_LP_WG_PER_CU * (p->num_cu > 0 ? p->num_cu : 256), need = (p->n_ch + W - 1) / W;
-    hipLaunchKernelGGL((xaac_sbr_core_kernel<0, 64, W>), dim3(need < resident ? need : resident), dim3(64 * W), 0, stream, *p);
+    hipLaunchKernelGGL((xaac_sbr_core_kernel<0, 64, W, NS>), dim3(need < resident ? need : resident), dim3(64 * W), 0, stream, *p);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL((xaac_sbr_core_kernel<0, 64, W>), dim3((p->n_ch + W - 1) / W), dim3(64 * W), 0, stream, q);
+  hipLaunchKernelGGL((xaac_sbr_core_kernel<0, 64, W, NS>), dim3((p->n_ch + W - 1) / W), dim3(64 * W), 0, stream, q);
   return hipGetLastError();
+}
+
+/* The side-info check of the core (xs_side_info_bad) for every channel, before the analysis bank runs: [7] of a channel's
+   synthesis parameter row becomes 1 where the channel is refused, else 0.  The banks and the core then leave a refused
+   channel's state and output alone (the 960-sample entry; the 1024-sample one keeps its own order). */
+template <int NS>
+__global__ __launch_bounds__(256) void xaac_sbr_screen_kernel(XaacSbrCoreParams p) {
+  const int lane = threadIdx.x & 63, ch = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (ch >= p.n_ch) return;
+  const XsCx cx = {lane, 64};
+  const int bad = xs_side_info_bad(cx, p.header + ch, p.frame + ch, p.state + ch, 0, NS);
+  if (lane == 0) p.syn_par[8 * (size_t)ch + 7] = (int16_t)(bad ? 1 : 0);
+}
+
+extern "C" hipError_t xaac_launch_sbr_screen(const XaacSbrCoreParams *p, hipStream_t stream) {
+  if (p->qmf_slots != 30) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((xaac_sbr_screen_kernel<30>), dim3((p->n_ch + 3) / 4), dim3(256), 0, stream, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t xaac_launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t stream) {
+  return p->qmf_slots == 30 ? launch_sbr_core_lp<30>(p, stream) : launch_sbr_core_lp<32>(p, stream);
 }
 
 extern "C" hipError_t xaac_launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStream_t stream) {

@@ -39,10 +39,11 @@ __device__ __forceinline__ int ana_ring_pos(int wr, int a) {
   return p >= 320 ? p - 320 : p;
 }
 
-/* 32 steps of the window-phase bookkeeping of generic:698-722 (does not influence the samples) */
+/* NS (32, or 30 for 960-sample cores) steps of the window-phase bookkeeping of generic:698-722 (does not influence the samples) */
+template <int NS = 32>
 __device__ __forceinline__ int ana_phase_after_frame(int phase) {
   int f1 = phase, f2 = phase + 64;
-  for (int s = 0; s < 32; s++) {
+  for (int s = 0; s < NS; s++) {
     f1 += 64;
     f2 += 64;
     int t = f1;
@@ -66,7 +67,8 @@ __device__ __forceinline__ int32_t adj_scale(int32_t v, int shift) {
 }  // namespace
 
 /* ===================================================================================== */
-template <bool LP>
+/* NS: slots of a frame -- 32, or 30 for the 960-sample cores (32 NS new samples; the ring of 320 keeps its layout) */
+template <bool LP, int NS = 32>
 __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQmfAnaParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -89,7 +91,8 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
       /* all loads of both channels (5 ring + 16 PCM per lane and channel) in flight before the first LDS store */
       /* (the rings by position, not by age: their loads then do not wait for the write positions, which only say where in the
          time-ordered history a fetched sample belongs; write position and window phase are read here for the state update too) */
-      int16_t hr[2][5], hp[2][16];
+      constexpr int NP = 32 * NS / 64; /* new samples per lane and channel */
+      int16_t hr[2][5], hp[2][NP];
 #pragma unroll
       for (int c = 0; c < 2; c++) {
         const int ch = 2 * pair + c;
@@ -99,11 +102,11 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
           wr_v[c] = st->wr;
           ph_v[c] = st->phase;
           const int cf = p.ch_fac;
-          const int16_t *src = p.pcm + (size_t)(ch / cf) * 1024 * cf + (ch % cf);
+          const int16_t *src = p.pcm + (size_t)(ch / cf) * (32 * NS) * cf + (ch % cf);
 #pragma unroll
           for (int j = 0; j < 5; j++) hr[c][j] = st->ring[lane + 64 * j];
 #pragma unroll
-          for (int j = 0; j < 16; j++) hp[c][j] = src[(size_t)(lane + 64 * j) * cf];
+          for (int j = 0; j < NP; j++) hp[c][j] = src[(size_t)(lane + 64 * j) * cf];
         }
       }
 #pragma unroll
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
             if (a < 288) h[287 - a] = hr[c][j];
           }
 #pragma unroll
-          for (int j = 0; j < 16; j++) h[288 + lane + 64 * j] = hp[c][j];
+          for (int j = 0; j < NP; j++) h[288 + lane + 64 * j] = hp[c][j];
         } else {
           for (int i = lane; i < kHist; i += 64) h[i] = 0;
         }
@@ -132,11 +135,11 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
 #pragma unroll
     for (int c = 0; c < 2; c++) {
       const int16_t *h = hist + c * kHist + 288 + 31 - lane;
-      int32_t u[40]; /* u[8 + k] = x[32 k + 31 - m], k = -8 .. 31 */
+      int32_t u[8 + NS]; /* u[8 + k] = x[32 k + 31 - m], k = -8 .. NS - 1 */
 #pragma unroll
-      for (int k = 0; k < 40; k++) u[k] = h[32 * (k - 8)];
+      for (int k = 0; k < 8 + NS; k++) u[k] = h[32 * (k - 8)];
 #pragma unroll
-      for (int sl = 0; sl < 32; sl++) {
+      for (int sl = 0; sl < NS; sl++) {
         int32_t acc = 0;
 #pragma unroll
         for (int j = 0; j < 5; j++) acc += u[8 + sl - 2 * j] * coef[j]; /* |acc| < 2^30: exact */
@@ -183,26 +186,28 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
         int32_t *row = p.qmf + (size_t)ch * p.qmf_ch_stride + (lane & 31);
         const int32_t *src = z + 65 * 32 * (lane >> 5) + (lane & 31);
 #pragma unroll 8
-        for (int r = 0; r < 32; r++) row[(size_t)r * p.slot_stride] = src[65 * r];
+        for (int r = 0; r < NS; r++) row[(size_t)r * p.slot_stride] = src[65 * r];
       }
     } else {
       for (int r = 0; r < 64; r++) {
         const int ch = 2 * pair + (r >> 5);
         if (ch >= p.n_ch) break;
+        if ((r & 31) >= NS) continue; /* (lanes of slots past the frame's transform what nobody wrote: dropped) */
         int32_t *row = p.qmf + (size_t)ch * p.qmf_ch_stride + (size_t)(r & 31) * p.slot_stride;
         row[(lane & 31) + 64 * (lane >> 5)] = z[65 * r + lane];
       }
     }
-    /* ---- state: the ring as the reference leaves it after 32 slots -------------------------- */
+    /* ---- state: the ring as the reference leaves it after NS slots (32 NS samples further on) -------------------------- */
     for (int c = 0; c < 2; c++) {
       const int ch = 2 * pair + c;
       if (ch >= p.n_ch) break;
+      if (NS != 32 && p.refused && __builtin_amdgcn_readfirstlane((int)p.refused[8 * (size_t)ch + 7])) continue;
       xaac_qmf_ana_state *st =
           reinterpret_cast<xaac_qmf_ana_state *>(reinterpret_cast<char *>(p.state) + (size_t)ch * p.state_stride);
-      const int wr_new = (__builtin_amdgcn_readfirstlane(wr_v[c]) + 256) % 320;
-      const int ph_new = ana_phase_after_frame(__builtin_amdgcn_readfirstlane(ph_v[c]));
+      const int wr_new = (__builtin_amdgcn_readfirstlane(wr_v[c]) + 320 - (32 * NS) % 320) % 320;
+      const int ph_new = ana_phase_after_frame<NS>(__builtin_amdgcn_readfirstlane(ph_v[c]));
       const int16_t *h = hist + c * kHist;
-      for (int a = lane; a < 320; a += 64) st->ring[ana_ring_pos(wr_new, a)] = h[kHist - 1 - a];
+      for (int a = lane; a < 320; a += 64) st->ring[ana_ring_pos(wr_new, a)] = h[288 + 32 * NS - 1 - a];
       if (lane == 0) {
         st->wr = (int16_t)wr_new;
         st->phase = (int16_t)ph_new;
@@ -378,8 +383,9 @@ __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaPar
 #endif
 
 /* ===================================================================================== */
-/* DS: the down-sampled bank -- 32 channels: the same kernel with half-size slot blocks (NC) */
-template <bool LP, bool DS>
+/* DS: the down-sampled bank -- 32 channels: the same kernel with half-size slot blocks (NC).  NS: slots of a frame, 32 or 30
+   (960-sample cores: 1920 samples out; the lanes of slots 30, 31 transform zero rows that nobody reads) */
+template <bool LP, bool DS, int NS = 32>
 __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(XaacQmfSynParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ROW = LP ? 64 : 128;    /* words per slot row */
@@ -450,13 +456,13 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(Xaac
         const int r = r0 + j, ch = 2 * pair + (r >> 5);
         const int32_t *row = p.qmf + (size_t)(ch < p.n_ch ? ch : 0) * p.qmf_ch_stride + (size_t)(r & 31) * p.slot_stride;
 #pragma unroll
-        for (int q = 0; q < ROW / 64; q++) tmp[j][q] = row[lane + 64 * q];
+        for (int q = 0; q < ROW / 64; q++) tmp[j][q] = (r & 31) < NS ? row[lane + 64 * q] : 0;
       }
 #pragma unroll
       for (int j = 0; j < G; j++) {
         const int r = r0 + j, ch = 2 * pair + (r >> 5);
 #pragma unroll
-        for (int q = 0; q < ROW / 64; q++) rows[RS * r + lane + 64 * q] = ch < p.n_ch ? tmp[j][q] : 0;
+        for (int q = 0; q < ROW / 64; q++) rows[RS * r + lane + 64 * q] = ch < p.n_ch && (r & 31) < NS ? tmp[j][q] : 0;
       }
       if (EARLY && r0 == 0) { /* the ring offsets have arrived with the first rows */
         const int d0 = __builtin_amdgcn_readfirstlane(d_v[0]), d1 = __builtin_amdgcn_readfirstlane(d_v[1]);
@@ -567,10 +573,10 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(Xaac
       if (p.per_ch_bands && __builtin_amdgcn_readfirstlane(off_v[c])) continue; /* channel inactive this frame */
       const int cf = p.pcm_sample_stride ? p.pcm_sample_stride : p.ch_fac;
       int16_t *dst = p.pcm_sample_stride ? p.pcm + (size_t)ch * p.pcm_ch_stride
-                                         : p.pcm + (size_t)(ch / cf) * (32 * NC) * cf + (ch % cf);
+                                         : p.pcm + (size_t)(ch / cf) * (NS * NC) * cf + (ch % cf);
       const int shift = LP ? 2 : 1;
       /* a wave covers one slot of 64 samples, or two slots of 32 */
-      for (int s0 = 0; s0 < 32; s0 += 64 / NC) {
+      for (int s0 = 0; s0 < NS; s0 += 64 / NC) {
         const int s = DS ? s0 + (lane >> 5) : s0, k = DS ? (lane & 31) : lane;
         const int16_t *vs = v + (c * VSLOTS + 9 + s) * VROW + k;
         int32_t acc = 0x8000 >> shift;
@@ -587,14 +593,14 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(Xaac
       if (p.per_ch_bands && __builtin_amdgcn_readfirstlane(off_v[c])) continue;
       xaac_qmf_syn_state *st =
           reinterpret_cast<xaac_qmf_syn_state *>(reinterpret_cast<char *>(p.state) + (size_t)ch * p.state_stride);
-      const int d_new = (__builtin_amdgcn_readfirstlane(d_v[c]) + RING - (32 * BLK) % RING) % RING; /* 32 slots of BLK downwards */
-      const int ph_new = (st->phase + 128) % 640;
+      const int d_new = (__builtin_amdgcn_readfirstlane(d_v[c]) + RING - (NS * BLK) % RING) % RING; /* NS slots of BLK downwards */
+      const int ph_new = (st->phase + (64 * NS) % 640) % 640; /* qmf_dec.c:1007-1010: 64 a slot */
       for (int i = lane; i < RING; i += 64) {
         const int A = 1 + i / BLK; /* age relative to the NEXT frame's slot 0: 1..10 */
         int pos = d_new + BLK * A + i % BLK;
         if (pos >= RING) pos -= RING;
         if (pos >= RING) pos -= RING;
-        st->ring[pos] = v[(c * VSLOTS + 9 + 32 - A) * VROW + i % BLK];
+        st->ring[pos] = v[(c * VSLOTS + 9 + NS - A) * VROW + i % BLK];
       }
       if (lane == 0) {
         st->drc_offset = (int16_t)d_new;
@@ -1080,6 +1086,12 @@ extern "C" hipError_t xaac_launch_qmf_analysis_eld(const xaac_qmf_ana_eld_batch 
 }
 
 extern "C" hipError_t xaac_launch_qmf_analysis(const XaacQmfAnaParams *p, int grid, hipStream_t stream) {
+  if (p->n_slots == 30) { /* 960-sample cores: the low-power bank only (xaac_sbr_lp960_process_batch) */
+    if (!p->low_pow) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((xaac_qmf_analysis_kernel<true, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
+                       XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
+    return hipGetLastError();
+  }
   if (p->low_pow)
     hipLaunchKernelGGL(xaac_qmf_analysis_kernel<true>, dim3(grid), dim3(XAAC_QMF_BLOCK),
                        XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
@@ -1089,6 +1101,12 @@ extern "C" hipError_t xaac_launch_qmf_analysis(const XaacQmfAnaParams *p, int gr
 }
 
 extern "C" hipError_t xaac_launch_qmf_synthesis(const XaacQmfSynParams *p, int grid, hipStream_t stream) {
+  if (p->n_slots == 30) { /* 960-sample cores: the low-power 64-channel bank only (xaac_sbr_lp960_process_batch) */
+    if (!p->low_pow || p->down_sample) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, false, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
+                       XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);
+    return hipGetLastError();
+  }
   if (p->low_pow && p->down_sample)
     hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, true>), dim3(grid), dim3(XAAC_QMF_BLOCK),
                        XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);

@@ -646,9 +646,11 @@ uint64_t xaac_sbr_lp_workspace_bytes(int32_t n_ch) {
   return (uint64_t)n_ch * (XAAC_SBR_X_WORDS * 4 + 8 * 2) + 256 + 128; /* matrix, synthesis parameters, the core's counters */
 }
 
-int32_t xaac_sbr_lp_process_batch(xaac_ctx *c, const xaac_sbr_lp_batch *b) {
+/* ns: QMF slots of the frames -- 32 (xaac_sbr_lp_process_batch) or 30 (xaac_sbr_lp960_process_batch: 960 samples in, 1920 out) */
+static int32_t sbr_lp_run(xaac_ctx *c, const xaac_sbr_lp_batch *b, int ns) {
   if (!c || !b) return XAAC_FATAL_NULL_ARG;
   if (b->n_ch < 0) return XAAC_FATAL_BAD_ARG;
+  if (ns == 30 && b->down_sample) return XAAC_FATAL_BAD_ARG; /* see xaac_sbr_lp960_process_batch */
   if ((b->in_ch_fac != 1 && b->in_ch_fac != 2) || (b->out_ch_fac != 1 && b->out_ch_fac != 2)) return XAAC_FATAL_BAD_ARG;
   if (b->n_ch % b->in_ch_fac || b->n_ch % b->out_ch_fac) return XAAC_FATAL_BAD_ARG;
   if (b->n_ch == 0) return XAAC_OK;
@@ -658,9 +660,9 @@ int32_t xaac_sbr_lp_process_batch(xaac_ctx *c, const xaac_sbr_lp_batch *b) {
   int32_t *x = reinterpret_cast<int32_t *>(((uintptr_t)b->workspace + 255) & ~(uintptr_t)255);
   int16_t *par = reinterpret_cast<int16_t *>(x + (size_t)b->n_ch * XAAC_SBR_X_WORDS);
   char *st = reinterpret_cast<char *>(b->state);
-  /* 1. analysis bank: 32 new slots into rows 8..39 of each channel's matrix */
+  /* 1. analysis bank: ns new slots into rows 8..7 + ns of each channel's matrix */
   XaacQmfAnaParams pa = {};
-  pa.n_ch = b->n_ch; pa.ch_fac = b->in_ch_fac; pa.low_pow = 1; pa.usb = 32; pa.slot_stride = 64;
+  pa.n_ch = b->n_ch; pa.ch_fac = b->in_ch_fac; pa.low_pow = 1; pa.usb = 32; pa.slot_stride = 64; pa.n_slots = ns;
   pa.state_stride = (int32_t)sizeof(xaac_sbr_state); pa.qmf_ch_stride = XAAC_SBR_X_WORDS;
   pa.pcm = b->pcm_in;
   pa.state = reinterpret_cast<xaac_qmf_ana_state *>(st + offsetof(xaac_sbr_state, ana_ring));
@@ -668,16 +670,24 @@ int32_t xaac_sbr_lp_process_batch(xaac_ctx *c, const xaac_sbr_lp_batch *b) {
   /* the core's work counter (and its neighbour) behind the synthesis parameters; the analysis launch clears them on its way */
   int32_t *counters = reinterpret_cast<int32_t *>(((uintptr_t)(par + (size_t)b->n_ch * 8) + 63) & ~(uintptr_t)63);
   pa.zero_words = counters;
+  if (ns == 30) {
+    /* 0. the side-info check up front: a refused channel's state and output are left as they are (xaac_sbr_lp960_process_batch) */
+    XaacSbrCoreParams sc = {};
+    sc.n_ch = b->n_ch; sc.header = b->header; sc.frame = b->frame; sc.state = b->state; sc.syn_par = par; sc.qmf_slots = ns;
+    if (!hip_ok(xaac_launch_sbr_screen(&sc, c->stream))) return XAAC_FATAL_HIP;
+    pa.refused = par;
+  }
   if (!hip_ok(xaac_launch_qmf_analysis(&pa, qmf_grid(c, b->n_ch, 0), c->stream))) return XAAC_FATAL_HIP;
   /* 2. everything between the banks */
   XaacSbrCoreParams pc = {};
   pc.n_ch = b->n_ch; pc.header = b->header; pc.frame = b->frame; pc.state = b->state; pc.x = x; pc.syn_par = par;
   pc.status = b->status;
   pc.defer_count = counters; pc.work_counter = counters + 1; pc.num_cu = c->num_cu; pc.counters_zeroed = 1;
+  pc.qmf_slots = ns;
   if (!hip_ok(xaac_launch_sbr_core_lp(&pc, c->stream))) return XAAC_FATAL_HIP;
-  /* 3. synthesis bank over rows 2..33 (the 6 delayed + first 26 new slots) */
+  /* 3. synthesis bank over rows 2..1 + ns (the 6 delayed + first ns - 6 new slots) */
   XaacQmfSynParams ps = {};
-  ps.n_ch = b->n_ch; ps.ch_fac = b->out_ch_fac; ps.low_pow = 1; ps.lsb = 0; ps.usb = 0; ps.split = 6;
+  ps.n_ch = b->n_ch; ps.ch_fac = b->out_ch_fac; ps.low_pow = 1; ps.lsb = 0; ps.usb = 0; ps.split = 6; ps.n_slots = ns;
   ps.down_sample = b->down_sample ? 1 : 0;
   ps.slot_stride = 64; ps.state_stride = (int32_t)sizeof(xaac_sbr_state); ps.qmf_ch_stride = XAAC_SBR_X_WORDS;
   ps.scale_stride = 8; ps.per_ch_bands = 1;
@@ -689,6 +699,9 @@ int32_t xaac_sbr_lp_process_batch(xaac_ctx *c, const xaac_sbr_lp_batch *b) {
   c->last_grid = grid; c->last_block = XAAC_QMF_BLOCK; c->last_lds = XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP;
   return XAAC_OK;
 }
+
+int32_t xaac_sbr_lp_process_batch(xaac_ctx *c, const xaac_sbr_lp_batch *b) { return sbr_lp_run(c, b, 32); }
+int32_t xaac_sbr_lp960_process_batch(xaac_ctx *c, const xaac_sbr_lp_batch *b) { return sbr_lp_run(c, b, 30); }
 
 uint64_t xaac_sbr_hq_workspace_bytes(int32_t n_ch, int32_t with_ps) {
   if (n_ch < 0) return 0;
