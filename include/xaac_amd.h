@@ -537,7 +537,7 @@ XAAC_API int32_t xaac_sbr_lp_process_batch(xaac_ctx *ctx, const xaac_sbr_lp_batc
  *    xaac_sbr_lp_process_batch goes on refusing 15-slot headers as it refuses any bad side info.
  *  - The state and xaac_sbr_lp_workspace_bytes(n_ch) are those of the 1024-sample entry (the bank rings keep their layout).
  *  - down_sample != 0 is refused with XAAC_FATAL_BAD_ARG (the down-sampled bank at 30 slots is not covered).
- * Out of scope: HQ mode / parametric stereo at 30 slots (HE-AAC v2 960), and the eSBR branch (Path A). */
+ * HQ mode / parametric stereo at 30 slots: xaac_sbr_hq960_process_batch below.  Out of scope: the eSBR branch (Path A). */
 XAAC_API int32_t xaac_sbr_lp960_process_batch(xaac_ctx *ctx, const xaac_sbr_lp_batch *batch);
 
 /* HQ SBR stream-frames (complex QMF analysis -> LPP transposer + envelope adjustment -> [parametric
@@ -546,6 +546,22 @@ XAAC_API uint64_t xaac_sbr_eld_workspace_bytes(int32_t n_ch);
 XAAC_API int32_t xaac_sbr_eld_process_batch(xaac_ctx *ctx, const xaac_sbr_eld_batch *batch);
 XAAC_API uint64_t xaac_sbr_hq_workspace_bytes(int32_t n_ch, int32_t with_ps);
 XAAC_API int32_t xaac_sbr_hq_process_batch(xaac_ctx *ctx, const xaac_sbr_hq_batch *batch);
+/* The same for the 960-sample cores of DAB+ / DRM (ixheaacd_sbr_dec with low_pow_flag = 0 and num_time_slots 15: HE-AAC mono
+ * and HE-AACv2 960, 15 time slots of 2, 30 QMF slots a frame -- the reference's num_time_slots == 15 branches of the HQ chain:
+ * the 36-slot covariances, the envelope adjuster's borders at time slot 15 and 30 QMF slots, the LPC history from slots 28-29
+ * and the overlap slots from slot 30 (sbr_dec.c:1221-1290), and the parametric-stereo tool over 30 sub-samples with its delay
+ * shift from slot 24 (qmf_dec.c:1016-1030, thumb_ps_dec.c:77-85)).  The same descriptor with 960 for 1024 and 1920 for 2048:
+ * pcm_in holds 960 core samples per stream, pcm_out gets 1920 samples, or with PS 1920 L,R pairs.
+ *  - Every stream's header must have num_time_slots 15, time_step 2 and num_columns 30, and envelope borders up to 18; a stream
+ *    whose side info does not (or whose side info is outside the structs' capacity otherwise) is refused before the banks run:
+ *    status -1, its SBR state, its PS state and its output samples left as they are, its neighbours in the batch decoded as if it
+ *    were not there.  PS borders are clamped into 0..30 (status -1 if that changed one; the parser ends PS grids at 30).
+ *    xaac_sbr_hq_process_batch goes on refusing 15-slot headers as it refuses any bad side info.
+ *  - The states and xaac_sbr_hq_workspace_bytes(n_ch, with_ps) are those of the 1024-sample entry; max_band_hint keeps its
+ *    meaning.
+ *  - down_sample != 0 is refused with XAAC_FATAL_BAD_ARG (the down-sampled bank at 30 slots is not covered).
+ * Out of scope: the eSBR branch (Path A). */
+XAAC_API int32_t xaac_sbr_hq960_process_batch(xaac_ctx *ctx, const xaac_sbr_hq_batch *batch);
 
 /* Channel-configuration hand-overs (device pointers, asynchronous). */
 XAAC_API int32_t xaac_sbr_state_handover(xaac_ctx *ctx, const xaac_sbr_handover_batch *batch);

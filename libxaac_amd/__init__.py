@@ -356,6 +356,8 @@ def load_library():
     lib.xaac_sbr_lp_workspace_bytes.restype = ctypes.c_uint64
     lib.xaac_sbr_hq_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_SbrHqBatch)]
     lib.xaac_sbr_hq_process_batch.restype = ctypes.c_int32
+    lib.xaac_sbr_hq960_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_SbrHqBatch)]
+    lib.xaac_sbr_hq960_process_batch.restype = ctypes.c_int32
     lib.xaac_sbr_eld_workspace_bytes.argtypes = [ctypes.c_int32]
     lib.xaac_sbr_eld_workspace_bytes.restype = ctypes.c_uint64
     lib.xaac_sbr_eld_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_SbrEldBatch)]
@@ -913,30 +915,47 @@ class XaacContext:
     def sbr_hq_workspace_bytes(self, n_ch, with_ps=True):
         return int(self._lib.xaac_sbr_hq_workspace_bytes(int(n_ch), int(bool(with_ps))))
 
-    def sbr_hq_process_batch(self, pcm_in, header, frame, state, pcm_out, workspace, ps_frame=None, ps_state=None,
-                             status=None, in_ch_fac=1, out_ch_fac=1, down_sample=False, max_band_hint=0):
-        """Batched ixheaacd_sbr_dec, HQ mode: one frame per stream.  With ps_frame / ps_state (uint8[n, PS_*_BYTES])
-        the parametric-stereo tool runs too (HE-AACv2) and pcm_out is int16[n*2048*2] of L,R pairs; without them
-        pcm_out is int16[n*2048] (HE-AAC mono, HQ)."""
+    def _sbr_hq_batch(self, pcm_in, header, frame, state, pcm_out, workspace, ps_frame, ps_state, status, in_ch_fac, out_ch_fac,
+                      down_sample, max_band_hint, frame_in):
         n_ch = state.shape[0]
         with_ps = ps_frame is not None
         b = _SbrHqBatch()
         b.n_ch, b.in_ch_fac, b.out_ch_fac = n_ch, int(in_ch_fac), int(out_ch_fac)
         b.down_sample = int(bool(down_sample))
-        b.pcm_in = _ptr(pcm_in, "int16", n_ch * 1024, device_ok=True)
+        b.pcm_in = _ptr(pcm_in, "int16", n_ch * frame_in, device_ok=True)
         b.header = _ptr(header, "uint8", n_ch * SBR_HEADER_BYTES, device_ok=True)
         b.frame = _ptr(frame, "uint8", n_ch * SBR_FRAME_BYTES, device_ok=True)
         b.state = _ptr(state, "uint8", n_ch * SBR_STATE_BYTES, device_ok=True)
         b.ps_frame = _ptr(ps_frame, "uint8", n_ch * PS_FRAME_BYTES, allow_none=True, device_ok=True)
         b.ps_state = _ptr(ps_state, "uint8", n_ch * PS_STATE_BYTES, allow_none=True, device_ok=True)
-        b.pcm_out = _ptr(pcm_out, "int16", n_ch * (1024 if down_sample else 2048) * (2 if with_ps else 1), device_ok=True)
+        b.pcm_out = _ptr(pcm_out, "int16", n_ch * (frame_in if down_sample else 2 * frame_in) * (2 if with_ps else 1), device_ok=True)
         b.status = _ptr(status, "int32", n_ch, allow_none=True, device_ok=True)
         b.workspace = _ptr(workspace, "uint8", device_ok=True)
         b.workspace_bytes = workspace.numel()
         b.max_band_hint = int(max_band_hint)   # 48: no stream of the batch reaches above QMF band 48 (xaac_amd.h); 0: no assertion
+        return b
+
+    def sbr_hq_process_batch(self, pcm_in, header, frame, state, pcm_out, workspace, ps_frame=None, ps_state=None,
+                             status=None, in_ch_fac=1, out_ch_fac=1, down_sample=False, max_band_hint=0):
+        """Batched ixheaacd_sbr_dec, HQ mode: one frame per stream.  With ps_frame / ps_state (uint8[n, PS_*_BYTES])
+        the parametric-stereo tool runs too (HE-AACv2) and pcm_out is int16[n*2048*2] of L,R pairs; without them
+        pcm_out is int16[n*2048] (HE-AAC mono, HQ)."""
+        b = self._sbr_hq_batch(pcm_in, header, frame, state, pcm_out, workspace, ps_frame, ps_state, status, in_ch_fac,
+                               out_ch_fac, down_sample, max_band_hint, 1024)
         rc = self._lib.xaac_sbr_hq_process_batch(self._h, ctypes.byref(b))
         if rc != 0:
             raise XaacError(rc, "xaac_sbr_hq_process_batch")
+
+    def sbr_hq960_process_batch(self, pcm_in, header, frame, state, pcm_out, workspace, ps_frame=None, ps_state=None,
+                                status=None, in_ch_fac=1, out_ch_fac=1, down_sample=False, max_band_hint=0):
+        """The same for 960-sample cores (DAB+ / DRM HE-AAC mono and HE-AACv2: 15 time slots, 30 QMF slots a frame):
+        pcm_in int16[n*960], pcm_out int16[n*1920] (x 2 with PS); the workspace of sbr_hq_workspace_bytes.  down_sample is
+        refused (XAAC_FATAL_BAD_ARG)."""
+        b = self._sbr_hq_batch(pcm_in, header, frame, state, pcm_out, workspace, ps_frame, ps_state, status, in_ch_fac,
+                               out_ch_fac, down_sample, max_band_hint, 960)
+        rc = self._lib.xaac_sbr_hq960_process_batch(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, "xaac_sbr_hq960_process_batch")
 
     def peak_limiter_workspace_bytes(self, n_streams):
         return int(self._lib.xaac_peak_limiter_workspace_bytes(int(n_streams)))

@@ -28,8 +28,8 @@ typedef struct XaacSbrCoreParams {
   int32_t *work_counter; /* = defer_count + 1: the persistent waves' next channel-frame */
   int32_t num_cu;        /* compute units of the device (grid of the persistent launch) */
   int32_t counters_zeroed; /* 1: an earlier launch on the stream has cleared defer_count / work_counter */
-  int32_t qmf_slots;       /* QMF slots of the frames: 0 / 32, or 30 (960-sample cores, low-power launch only:
-                              xaac_sbr_lp960_process_batch) */
+  int32_t qmf_slots;       /* QMF slots of the frames: 0 / 32, or 30 (960-sample cores: xaac_sbr_lp960_process_batch,
+                              xaac_sbr_hq960_process_batch) */
   int32_t narrow_only;     /* the caller's assertion (xaac_sbr_hq_batch.max_band_hint): no list launch; a stream that needs the 64-band
                               rows is refused */
 } XaacSbrCoreParams;

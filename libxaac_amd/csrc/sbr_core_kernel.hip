@@ -536,8 +536,9 @@ static hipError_t launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t str
 }
 
 /* The side-info check of the core (xs_side_info_bad) for every channel, before the analysis bank runs: [7] of a channel's
-   synthesis parameter row becomes 1 where the channel is refused, else 0.  The banks and the core then leave a refused
-   channel's state and output alone (the 960-sample entry; the 1024-sample one keeps its own order). */
+   synthesis parameter row becomes 1 where the channel is refused, else 0.  The banks, the core and the parametric-stereo tool
+   then leave a refused channel's state and output alone (the 960-sample entries; the 1024-sample ones keep their own order).
+   The check is the same in both modes. */
 template <int NS>
 __global__ __launch_bounds__(256) void xaac_sbr_screen_kernel(XaacSbrCoreParams p) {
   const int lane = threadIdx.x & 63, ch = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -557,11 +558,12 @@ extern "C" hipError_t xaac_launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStr
   return p->qmf_slots == 30 ? launch_sbr_core_lp<30>(p, stream) : launch_sbr_core_lp<32>(p, stream);
 }
 
-extern "C" hipError_t xaac_launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStream_t stream) {
+template <int NS>
+static hipError_t launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStream_t stream) {
   if (!p->defer_list || !p->defer_count || !p->work_counter) {
     XaacSbrCoreParams q = *p;
     q.work_counter = nullptr;
-    hipLaunchKernelGGL((xaac_sbr_core_kernel<1, 64, 1>), dim3(p->n_ch), dim3(64), 0, stream, q);
+    hipLaunchKernelGGL((xaac_sbr_core_kernel<1, 64, 1, NS>), dim3(p->n_ch), dim3(64), 0, stream, q);
     return hipGetLastError();
   }
   /* defer_count and work_counter are neighbours */
@@ -576,16 +578,20 @@ extern "C" hipError_t xaac_launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStr
     per_cu = e && atoi(e) > 0 ? atoi(e) : 2;
   }
   const int resident = per_cu * (p->num_cu > 0 ? p->num_cu : 256), need = (p->n_ch + W - 1) / W;
-  hipLaunchKernelGGL((xaac_sbr_core_kernel<1, XAAC_SBR_NARROW_BANDS, W>), dim3(need < resident ? need : resident), dim3(64 * W), 0,
+  hipLaunchKernelGGL((xaac_sbr_core_kernel<1, XAAC_SBR_NARROW_BANDS, W, NS>), dim3(need < resident ? need : resident), dim3(64 * W), 0,
                      stream, *p);
   if (p->narrow_only) return hipGetLastError(); /* the caller knows the list stays empty (xaac_sbr_hq_batch.max_band_hint) */
   const int grid = p->n_ch < 64 ? p->n_ch : 64;
-  hipLaunchKernelGGL((xaac_sbr_core_list_kernel<1>), dim3(grid), dim3(64), 0, stream, *p);
+  hipLaunchKernelGGL((xaac_sbr_core_list_kernel<1, NS>), dim3(grid), dim3(64), 0, stream, *p);
   return hipGetLastError();
+}
+
+extern "C" hipError_t xaac_launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStream_t stream) {
+  return p->qmf_slots == 30 ? launch_sbr_core_hq<30>(p, stream) : launch_sbr_core_hq<32>(p, stream);
 }
 
 /* xaac_warm_up (xaac_abi.cpp): asking for a kernel's attributes puts this translation unit's code object on the device */
 extern "C" hipError_t xaac_warm_sbr_core(void) {
   hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&xaac_sbr_core_kernel<1, XAAC_SBR_NARROW_BANDS, XAAC_SBR_CORE_HQ_WAVES>));
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&xaac_sbr_core_kernel<1, XAAC_SBR_NARROW_BANDS, XAAC_SBR_CORE_HQ_WAVES, 32>));
 }

@@ -1,6 +1,6 @@
 /*
- * sbr_ps_frame.h -- one whole frame (32 QMF slots) of the fixed-point parametric-stereo tool, arranged for a
- * 64-lane wave instead of for a slot loop.
+ * sbr_ps_frame.h -- one whole frame (32 QMF slots, or 30 for the 960-sample cores of DAB+ / DRM) of the fixed-point
+ * parametric-stereo tool, arranged for a 64-lane wave instead of for a slot loop.
  *
  * The reference runs the tool slot by slot inside the left channel's synthesis loop (decoder/ixheaacd_qmf_dec.c:
  * 1015-1031 -> ixheaacd_apply_ps, thumb_ps_dec.c:69).  Of everything it does per slot only three things are
@@ -12,7 +12,7 @@
  * 1-slot delays, the interpolated 2x2 rotation (H advances by a constant per slot: H_l = H_0 + n * delta mod 2^16),
  * the hybrid synthesis sums, the scale shifts -- depends on its slot only.  So the frame runs in phases:
  *
- *   P1 hybrid analysis of all 32 slots            lane = slot / (band, slot)
+ *   P1 hybrid analysis of all NS slots            lane = slot / (band, slot)
  *   P2 envelope walk: segments of constant delta  scalar; coefficients of each border: lane = parameter group
  *   P3 band powers, all-pass / delay inputs       lane = QMF band, loop over slots (coalesced row reads)
  *      group sums of the upper bins               lane = (slot, group): the addends are >= 0, so the saturating
@@ -27,6 +27,9 @@
  * lane count 1 is checked against that slot loop on the reference's captured frames and on fuzzed side info
  * (tests/test_ps_frame_cpu.py) before the GPU sees it.
  *
+ * The slot count NS is a template parameter: the reference's synthesis loop passes num_time_slots as no_col
+ * (qmf_dec.c:1016-1030), so at 30 slots the tool runs over 30 sub-samples, the hybrid look-ahead's delay shift switches
+ * at slot NS - 6 = 24 (thumb_ps_dec.c:77-85) and the parser ends the PS grid at border 30 (ps_bitdec.c:106, :243-249).
  * Borders no parser produces are handled as the slot loop would: the envelope counter only ever looks at its
  * current border (a border that lies behind the current slot is never reached), and if the first border is not
  * slot 0 the band limit `usb` (and the clearing of newly active all-pass delay lines, ps_dec.c:733-757) switches
@@ -54,7 +57,7 @@
 
 struct XpFrameWork {
   union {                    /* scratch areas that are never live together */
-    int32_t hyb_u[3][2][44]; /* P1: hybrid filter input of QMF bands 0..2: 12 slots of history + this frame's 32 */
+    int32_t hyb_u[3][2][44]; /* P1: hybrid filter input of QMF bands 0..2: 12 slots of history + this frame's NS */
     int32_t gsum[8][56];     /* P3: addends of the group sums, bands 9..63 of eight slots */
     int32_t peak[32][20];    /* P4: transient peak difference */
     uint32_t dl[32][13];     /* P5/P7: rounded samples of QMF bands 23..34 (the 14-slot delay looks 14 slots back); column
@@ -143,16 +146,18 @@ FX_HD int32_t xp_bin_power_hyb(const XpTables *T, int bin, const int32_t *re, co
   return xp_power(re[sb], im[sb]);
 }
 
-/* One frame.  xl: the stream's QMF matrix, slot 0 at xl (rows of 64 re | 64 im; rows 0..37 are read, rows 0..31
-   are rewritten with the left channel in the scale the synthesis bank expects); xr: 32 rows out, the right channel.
-   lb/ov_lb/hb_scale, st_syn, lsb, usb: what the SBR core left for the synthesis bank.  Returns ps_scale. */
-template <class PS>
+/* One frame of NS slots (32, or 30).  xl: the stream's QMF matrix, slot 0 at xl (rows of 64 re | 64 im; rows 0..NS + 5
+   are read, rows 0..NS - 1 are rewritten with the left channel in the scale the synthesis bank expects); xr: NS rows out,
+   the right channel.  lb/ov_lb/hb_scale, st_syn, lsb, usb: what the SBR core left for the synthesis bank.  Returns
+   ps_scale. */
+template <int NS = 32, class PS>
 FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_frame *pf, XpFrameWork *w, int32_t *xl,
                       int32_t *xr, int lb_scale, int ov_lb_scale, int hb_scale, int st_syn, int lsb, int usb,
                       int ps_scale_done = XP_NO_PS_SCALE) {
+  static_assert(NS == 32 || NS == 30, "frames of 32 or 30 QMF slots");
 #if defined(__HIP_DEVICE_COMPILE__)
   /* The matrix rows this frame reads before anything rewrites them, fetched now: P1's look-ahead words of QMF bands
-     0..2 (lane = slot) and P3's 32 slots of the lane's band.  Issued ahead of the state rescale and the hybrid
+     0..2 (lane = slot) and P3's NS slots of the lane's band (slots NS..31 of a shorter frame: zero powers, not used).  Issued ahead of the state rescale and the hybrid
      filters, their memory latency is covered instead of being paid once per phase and per group of eight slots. */
   int32_t p1v[3][2], p3re[32], p3im[32];
   {
@@ -164,8 +169,8 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     }
     XP_UNROLL
     for (int l = 0; l < 32; l++) {
-      p3re[l] = xl[l * 128 + cx.lane];
-      p3im[l] = xl[l * 128 + 64 + cx.lane];
+      p3re[l] = NS == 32 || l < NS ? xl[l * 128 + cx.lane] : 0;
+      p3im[l] = NS == 32 || l < NS ? xl[l * 128 + 64 + cx.lane] : 0;
     }
   }
 #endif
@@ -178,11 +183,11 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
 
   /* ---- P1: hybrid analysis (hybrid.c:214: a 13-tap FIR on QMF bands 0..2 looking six slots ahead).  Input of step
      l: row l + 6 as adjust_scale leaves it (qmf_dec.c:937: slots of the next frame are not rescaled), then the
-     delay-buffer shift of thumb_ps_dec.c:77. */
-  XS_PAR(l, 0, 32) {
-    const int shiftdelay = l < 32 - 6 ? 0 : (int16_t)(lb_scale - ps_scale);
+     delay-buffer shift of thumb_ps_dec.c:77 (from slot NS - MAX_OV_COLS on). */
+  XS_PAR(l, 0, NS) {
+    const int shiftdelay = l < NS - 6 ? 0 : (int16_t)(lb_scale - ps_scale);
     for (int b = 0; b < 3; b++) {
-      const int sha = l + 6 < 32 ? (b < lsb ? lb_shift : (b < usb ? hb_shift : 0)) : 0;
+      const int sha = l + 6 < NS ? (b < lsb ? lb_shift : (b < usb ? hb_shift : 0)) : 0;
       for (int c = 0; c < 2; c++) {
 #if defined(__HIP_DEVICE_COMPILE__)
         int32_t v = xp_adj_word(p1v[b][c], sha); /* lane = slot l */
@@ -200,7 +205,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
       w->hyb_u[b][1][i] = ps->hyb_buf[b][1][i];
     }
   cx.sync();
-  XS_PAR(l, 0, 32) { /* QMF band 0: eight-channel filter, six sub-bands */
+  XS_PAR(l, 0, NS) { /* QMF band 0: eight-channel filter, six sub-bands */
     int32_t re[8], im[8];
     xp_filt_8ch(T, &w->hyb_u[0][0][l], &w->hyb_u[0][1][l], re, im);
     for (int k = 0; k < 6; k++) {
@@ -210,6 +215,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   }
   XS_PAR(i, 0, 64) { /* QMF bands 1 and 2: two sub-bands each */
     const int b = 1 + (i >> 5), l = i & 31;
+    if (NS != 32 && l >= NS) continue;
     int32_t re[2], im[2];
     xp_filt_2ch(T, &w->hyb_u[b][0][l], &w->hyb_u[b][1][l], re, im);
     w->hyb_l[l][4 + 2 * b] = re[0];
@@ -219,8 +225,8 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   }
   XS_PAR(i, 0, 12)
     for (int b = 0; b < 3; b++) {
-      ps->hyb_buf[b][0][i] = w->hyb_u[b][0][32 + i];
-      ps->hyb_buf[b][1][i] = w->hyb_u[b][1][32 + i];
+      ps->hyb_buf[b][0][i] = w->hyb_u[b][0][NS + i];
+      ps->hyb_buf[b][1][i] = w->hyb_u[b][1][NS + i];
     }
   cx.sync();
   XP_T(2);
@@ -239,11 +245,11 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   }
   const int usb_prev = cx.uni(ps->usb);
   uint32_t seg_mask = 0; /* bit l: a border was reached at slot l -- segment popcount(bits 0..l) starts there (a scalar) */
-  int clear_slot = 32; /* first slot that runs with the new usb: the slot of border 0, if it is reached at all */
+  int clear_slot = NS; /* first slot that runs with the new usb: the slot of border 0, if it is reached at all */
   {
     int env = 0, nseg = 1;
     int next = cx.uni(pf->border_position[0]); /* the border the counter is waiting for; 64 = none left */
-    for (int l = 0; l < 32; l++) {
+    for (int l = 0; l < NS; l++) {
       if (l == next) {
         if (env == 0) clear_slot = l;
         cx.sync();
@@ -325,7 +331,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
       cx.sync();
     }
   }
-  XS_PAR(i, 0, 256) {
+  XS_PAR(i, 0, 8 * NS) {
     const int l = i >> 3, bin = i & 7;
     w->binpw[l][bin] = xp_bin_power_hyb(T, bin, &w->hyb_l[l][0], &w->hyb_l[l][10]);
   }
@@ -335,11 +341,11 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   /* ---- P4: transient detector (ps_dec.c:547-590): peak decay against smoothed energy, per bin */
   XS_PAR(bin, 0, 20) {
     int32_t pd = ps->peak_decay_diff[bin], pdp = ps->peak_decay_diff_prev[bin], nrg = ps->energy_prev[bin];
-    int32_t pin[32]; /* the bin's 32 powers first: the recursion below then waits for no LDS load */
+    int32_t pin[NS]; /* the bin's NS powers first: the recursion below then waits for no LDS load */
     XP_UNROLL
-    for (int l = 0; l < 32; l++) pin[l] = w->binpw[l][bin];
+    for (int l = 0; l < NS; l++) pin[l] = w->binpw[l][bin];
     XP_UNROLL
-    for (int l = 0; l < 32; l++) {
+    for (int l = 0; l < NS; l++) {
       int32_t pw = fx_shl(pin[l], 1);
       if (pw < 0) pw = 0;
       pd = fx_mul32x16_shl(pd, 0x620a);
@@ -354,9 +360,9 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     ps->energy_prev[bin] = nrg;
   }
   cx.sync();
-  for (int i0 = 0; i0 < 640; i0 += 64) { /* every lane reads its (energy, peak) pair before any lane stores a ratio */
+  for (int i0 = 0; i0 < 20 * NS; i0 += 64) { /* every lane reads its (energy, peak) pair before any lane stores a ratio */
     int16_t q = 0;
-    XS_PAR(i, i0, i0 + 64) {
+    XS_PAR(i, i0, (20 * NS) % 64 == 0 || i0 + 64 < 20 * NS ? i0 + 64 : 20 * NS) {
       const int32_t pk = (&w->peak[0][0])[i], nrg = (&w->binpw[0][0])[i];
       q = pk <= nrg ? (int16_t)0x7fff : (int16_t)xp_divide16_pos(nrg, pk);
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -455,14 +461,14 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         nim[j] = xl[j * 128 + 64 + sb];
       }
       XP_NOUNROLL
-      for (int l0 = 0; l0 < 32; l0 += 4) {
+      for (int l0 = 0; l0 < NS; l0 += 4) {
         int32_t cre[4], cim[4];
         XP_UNROLL
         for (int j = 0; j < 4; j++) {
           cre[j] = nre[j];
           cim[j] = nim[j];
         }
-        if (l0 + 4 < 32) {
+        if (l0 + 4 < NS) {
           XP_UNROLL
           for (int j = 0; j < 4; j++) {
             nre[j] = xl[(l0 + 4 + j) * 128 + sb];
@@ -472,12 +478,13 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         XP_UNROLL
         for (int j = 0; j < 4; j++) {
           const int l = l0 + j;
+          if (NS % 4 != 0 && l >= NS) break; /* (30 slots: the last pass has two) */
           const int usb_l = l >= clear_slot ? usb : usb_prev;
           const int16_t tr = tr_nx;
           const int32_t hre = hre_nx, him = him_nx;
           const uint32_t ld_cur = ld_nx;
           {
-            const int ln = l + 1 < 32 ? l + 1 : 31, pn = (idx_long0 + ln) % 14;
+            const int ln = l + 1 < NS ? l + 1 : NS - 1, pn = (idx_long0 + ln) % 14;
             tr_nx = w->ratio[ln][bin_sb];
             hre_nx = w->hyb_l[ln][csb];
             him_nx = w->hyb_l[ln][10 + csb];
@@ -562,25 +569,25 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
       if (chain) {
         XP_UNROLL
         for (int j = 0; j < 2; j++) {
-          int16_t *q = hyb_chain ? &ps->sub[(idx0 + j) % 2][2 * csb] : &ps->ap[(idx0 + j) % 2][2 * csb]; /* 32 slots: same phase */
+          int16_t *q = hyb_chain ? &ps->sub[(idx0 + j) % 2][2 * csb] : &ps->ap[(idx0 + j) % 2][2 * csb]; /* an even NS: same phase */
           q[0] = xp_lo16(d0[j]);
           q[1] = xp_hi16(d0[j]);
         }
         XP_UNROLL
         for (int j = 0; j < 3; j++) {
-          int16_t *q = hyb_chain ? &ps->sub_ser[(is0 + 32 + j) % 3][0][2 * csb] : &ps->ser[(is0 + 32 + j) % 3][0][2 * csb];
+          int16_t *q = hyb_chain ? &ps->sub_ser[(is0 + NS + j) % 3][0][2 * csb] : &ps->ser[(is0 + NS + j) % 3][0][2 * csb];
           q[0] = xp_lo16(r0[j]);
           q[1] = xp_hi16(r0[j]);
         }
         XP_UNROLL
         for (int j = 0; j < 4; j++) {
-          int16_t *q = hyb_chain ? &ps->sub_ser[(is1 + 32 + j) % 4][1][2 * csb] : &ps->ser[(is1 + 32 + j) % 4][1][2 * csb];
+          int16_t *q = hyb_chain ? &ps->sub_ser[(is1 + NS + j) % 4][1][2 * csb] : &ps->ser[(is1 + NS + j) % 4][1][2 * csb];
           q[0] = xp_lo16(r1[j]);
           q[1] = xp_hi16(r1[j]);
         }
         XP_UNROLL
         for (int j = 0; j < 5; j++) {
-          int16_t *q = hyb_chain ? &ps->sub_ser[(is2 + 32 + j) % 5][2][2 * csb] : &ps->ser[(is2 + 32 + j) % 5][2][2 * csb];
+          int16_t *q = hyb_chain ? &ps->sub_ser[(is2 + NS + j) % 5][2][2 * csb] : &ps->ser[(is2 + NS + j) % 5][2][2 * csb];
           q[0] = xp_lo16(r2[j]);
           q[1] = xp_hi16(r2[j]);
         }
@@ -590,7 +597,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         ps->sd[2 * (sb - 35) + 1] = xp_hi16(prev);
       }
       if (is_d14) { /* each position of the 14-slot ring ends up with the input of the last slot that wrote it */
-        for (int l = (clear_slot == 0 || usb == usb_prev) ? 18 : 0; l < 32; l++) {
+        for (int l = (clear_slot == 0 || usb == usb_prev) ? NS - 14 : 0; l < NS; l++) {
           const int pos = (idx_long0 + l) % 14;
           if (sb < (l >= clear_slot ? usb : usb_prev)) {
             ps->ld[pos][ldj] = xp_lo16(w->dl[l][dlj]);
@@ -601,12 +608,12 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     }
     cx.sync();
     XS_ONE {
-      ps->idx = (int16_t)idx0; /* 32 slots later the 2-slot line is in the same phase */
-      ps->idx_ser[0] = (int16_t)((is0 + 32) % 3);
-      ps->idx_ser[1] = (int16_t)((is1 + 32) % 4);
-      ps->idx_ser[2] = (int16_t)((is2 + 32) % 5);
-      ps->idx_long = (int16_t)((idx_long0 + 32) % 14);
-      if (clear_slot < 32) ps->usb = (int16_t)usb;
+      ps->idx = (int16_t)idx0; /* NS (even) slots later the 2-slot line is in the same phase */
+      ps->idx_ser[0] = (int16_t)((is0 + NS) % 3);
+      ps->idx_ser[1] = (int16_t)((is1 + NS) % 4);
+      ps->idx_ser[2] = (int16_t)((is2 + NS) % 5);
+      ps->idx_long = (int16_t)((idx_long0 + NS) % 14);
+      if (clear_slot < NS) ps->usb = (int16_t)usb;
     }
   }
   cx.sync();
@@ -614,7 +621,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
 
   /* ---- P6: rotation of the hybrid sub-bands (ps_dec.c:856, groups 0..9) and hybrid synthesis of QMF bands 0..2
      (the saturating sums of ps_dec.c:899-925, in sub-band order), one (slot, band, re | im) per lane */
-  XS_PAR(i, 0, 192) {
+  XS_PAR(i, 0, 6 * NS) {
     const int l = i / 6, b = (i % 6) >> 1, c = i & 1;
     const int p = b == 0 ? 0 : 4 + 2 * b, n = b == 0 ? 6 : 2;
     const uint32_t below = seg_mask & (0xffffffffu >> (31 - l));     /* borders at or before slot l */
@@ -642,7 +649,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     xr[l * 128 + 64 * c + b] = acc_r;
   }
   {
-    const int s = xp_popc(seg_mask), n = 32 - (seg_mask ? 31 - xp_clz(seg_mask) : 0);
+    const int s = xp_popc(seg_mask), n = NS - (seg_mask ? 31 - xp_clz(seg_mask) : 0);
     XS_PAR(g, 0, XAAC_PS_GROUPS) {
       ps->H11_H12[2 * g] = (int16_t)(w->seg_h[s][0][g] + n * w->seg_d[s][0][g]);
       ps->H11_H12[2 * g + 1] = (int16_t)(w->seg_h[s][1][g] + n * w->seg_d[s][1][g]);

@@ -11,8 +11,8 @@
 typedef struct XaacPsParams {
   int32_t n;                  /* streams */
   int32_t *x;                 /* [n][40 * 128]: the HQ QMF matrix the core kernel left (slot 0 at row 2);
-                                 rows 2..33 become the LEFT channel, in the scale the synthesis bank wants */
-  int32_t *xr;                /* [n][32 * 128]: out, the RIGHT channel's 32 slots */
+                                 rows 2..1 + n_slots become the LEFT channel, in the scale the synthesis bank wants */
+  int32_t *xr;                /* [n][32 * 128]: out, the RIGHT channel's n_slots slots */
   const xaac_sbr_header *header;   /* [n]: channel_mode */
   const xaac_sbr_frame *sbr_frame; /* [n]: apply_processing */
   const xaac_ps_frame *frame; /* [n] */
@@ -24,6 +24,7 @@ typedef struct XaacPsParams {
                                  [6] = 1 where the stream has no PS this frame (bank and output left alone) */
   int32_t *status;            /* optional [n]: -1 where PS side info had to be clamped into its tables */
   int32_t *dbg;               /* profiling builds (-DXS_PROFILE) only: 32 cycle counters, else unused */
+  int32_t n_slots;            /* 0 / 32, or 30 (960-sample cores: par_l[8 i + 7] != 0 marks a stream refused up front) */
 } XaacPsParams;
 
 #ifdef __cplusplus

@@ -156,9 +156,10 @@ __device__ __forceinline__ int xp_init_ps_scale_regs(const XsCx &cx, int32_t (&r
   return ps_scale;
 }
 
-/* xp_frame_sanitize (sbr_ps.h) the same way, on the side info's words in registers: borders into 0..32, IID indices into
+/* xp_frame_sanitize (sbr_ps.h) the same way, on the side info's words in registers: borders into 0..NSL (32, or 30 for the
+   960-sample cores, whose PS grids the parser ends at max_num_columns = 30: ps_bitdec.c:106, :243-249), IID indices into
    +-7 (+-15 fine), ICC indices into 0..7; returns whether anything had to be changed */
-template <int NF>
+template <int NF, int NSL = 32>
 __device__ __forceinline__ int xp_frame_sanitize_regs(const XsCx &cx, int32_t (&rf)[NF]) {
   constexpr int E_BORDER = offsetof(xaac_ps_frame, border_position) / 2, E_IID = offsetof(xaac_ps_frame, iid_par_table) / 2;
   constexpr int E_ICC = offsetof(xaac_ps_frame, icc_par_table) / 2, E_END = sizeof(xaac_ps_frame) / 2;
@@ -174,7 +175,7 @@ __device__ __forceinline__ int xp_frame_sanitize_regs(const XsCx &cx, int32_t (&
     for (int c = 0; c < 2; c++) {
       const int e = 2 * w + c; /* element number */
       const bool border = e >= E_BORDER && e < E_BORDER + XAAC_PS_MAX_ENV + 2, iid = e >= E_IID && e < E_ICC, icc = e >= E_ICC && e < E_END;
-      const int lo = border ? 0 : (iid ? -steps : (icc ? 0 : -32768)), hi = border ? 32 : (iid ? steps : (icc ? 7 : 32767));
+      const int lo = border ? 0 : (iid ? -steps : (icc ? 0 : -32768)), hi = border ? NSL : (iid ? steps : (icc ? 7 : 32767));
       const int t = h[c] < lo ? lo : (h[c] > hi ? hi : h[c]);
       bad |= t != h[c];
       h[c] = t;
@@ -186,6 +187,10 @@ __device__ __forceinline__ int xp_frame_sanitize_regs(const XsCx &cx, int32_t (&
 
 }  // namespace
 
+/* NSL: QMF slots of a frame, 32 or 30 (the 960-sample cores: xaac_sbr_hq960_process_batch).  At 30 a stream the screen in front
+   of the banks refused (its synthesis parameter row's [7], sbr_core_kernel.hip: xaac_sbr_screen_kernel) is left alone: PS state,
+   parameter rows (the core has flagged the left bank already) and status as they are, the right bank told to skip it. */
+template <int NSL = 32>
 __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel(XaacPsParams p) {
   __shared__ XpLds sw[kPsWaves];
   __shared__ int32_t s_tabs[(kTabBytes + 3) / 4];
@@ -207,7 +212,7 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
   for (int n = blockIdx.x * kPsWaves + wave; n < p.n; n += gridDim.x * kPsWaves) {
     xaac_ps_state *gps = p.state + n;
     int32_t *gx = p.x + (size_t)n * (40 * 128) + 2 * 128; /* slot 0 */
-    int32_t *gr = p.xr + (size_t)n * (32 * 128);
+    int32_t *gr = p.xr + (size_t)n * (32 * 128); /* (30-slot frames use the first 30 rows) */
     int16_t *par = p.par_l + 8 * (size_t)n;
     /* Everything the stream's set-up reads from global memory in flight together: the two words that say whether this is a PS
        frame at all, state, side info and the six scale parameters the core left (as a chain -- flags, then state, then
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     int32_t rs[NS], rf[NF];
     const int32_t *gs = reinterpret_cast<const int32_t *>(gps), *gf = reinterpret_cast<const int32_t *>(p.frame + n);
     const int apply_v = p.sbr_frame[n].apply_processing, mode_v = p.header[n].channel_mode;
-    const int par_v = lane < 6 ? par[lane] : 0;
+    const int par_v = lane < (NSL != 32 ? 8 : 6) ? par[lane] : 0;
     /* the right bank's scale and band limits, for the parameter row written at the end: read here with the rest -- read there,
        by one lane, they came back behind every store of the stream (a wave's memory operations retire in order) and the row,
        and the next stream's loads behind it, waited for that */
@@ -226,6 +231,10 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     for (int j = 0; j < NS; j++) rs[j] = lane + 64 * j < kHeadWords ? gs[lane + 64 * j] : 0;
 #pragma unroll
     for (int j = 0; j < NF; j++) rf[j] = lane + 64 * j < (int)(sizeof(xaac_ps_frame) / 4) ? gf[lane + 64 * j] : 0;
+    if (NSL != 32 && __builtin_amdgcn_readlane(par_v, 7)) { /* refused up front */
+      if (lane == 0) p.par_r[8 * (size_t)n + 6] = 1;
+      continue;
+    }
     if (!(__builtin_amdgcn_readfirstlane(apply_v) && __builtin_amdgcn_readfirstlane(mode_v) == 3)) { /* sbr_dec.c:1246: mono this frame */
       if (lane == 0) {
         p.par_l[8 * (size_t)n + 6] = 0;
@@ -237,7 +246,7 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     const int hb_scale = __builtin_amdgcn_readlane(par_v, 2), st_syn = __builtin_amdgcn_readlane(par_v, 3);
     const int lsb = __builtin_amdgcn_readlane(par_v, 4), usb = __builtin_amdgcn_readlane(par_v, 5);
     const int ps_scale_done = xp_init_ps_scale_regs<NS>(cx, rs, lb_scale, ov_lb_scale, hb_scale);
-    const int ps_clamped = xp_frame_sanitize_regs<NF>(cx, rf); /* indices a parser cannot produce: contained, reported */
+    const int ps_clamped = xp_frame_sanitize_regs<NF, NSL>(cx, rf); /* indices a parser cannot produce: contained, reported */
     xp_wave_sync(); /* the previous stream's state has left the LDS copy */
 #pragma unroll
     for (int j = 0; j < NS; j++)
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     if (threadIdx.x == 0) xp_prof_last = clock64();
 #endif
     const int ps_scale =
-        xp_ps_frame(cx, tabs, &s.ps, &s.pf, &s.w, gx, gr, lb_scale, ov_lb_scale, hb_scale, st_syn, lsb, usb, ps_scale_done);
+        xp_ps_frame<NSL>(cx, tabs, &s.ps, &s.pf, &s.w, gx, gr, lb_scale, ov_lb_scale, hb_scale, st_syn, lsb, usb, ps_scale_done);
     /* ---- state and the two synthesis launches' parameters ---- */
     xp_wave_sync();
     {
@@ -354,23 +363,26 @@ extern "C" hipError_t xaac_launch_sbr_handover(const xaac_sbr_handover_batch *b,
 }
 
 extern "C" hipError_t xaac_launch_ps(const XaacPsParams *p, hipStream_t stream) {
-  static int resident = 0; /* workgroups the chip holds at once (LDS-bound) */
+  static int resident = 0; /* workgroups the chip holds at once (LDS-bound; the same for both slot counts) */
   if (!resident) {
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xaac_ps_kernel, 64 * kPsWaves, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xaac_ps_kernel<32>, 64 * kPsWaves, 0) != hipSuccess || per_cu < 1) per_cu = 2;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) prop.multiProcessorCount = 256;
     const char *e = getenv("XAAC_PS_WG_PER_CU"); /* developer override */
     if (e && atoi(e) > 0) per_cu = atoi(e);
     resident = per_cu * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
   }
   const int need = (p->n + kPsWaves - 1) / kPsWaves, grid = need < resident ? need : resident;
-  hipLaunchKernelGGL(xaac_ps_kernel, dim3(grid), dim3(64 * kPsWaves), 0, stream, *p);
+  if (p->n_slots == 30)
+    hipLaunchKernelGGL(xaac_ps_kernel<30>, dim3(grid), dim3(64 * kPsWaves), 0, stream, *p);
+  else
+    hipLaunchKernelGGL(xaac_ps_kernel<32>, dim3(grid), dim3(64 * kPsWaves), 0, stream, *p);
   return hipGetLastError();
 }
 
 /* xaac_warm_up (xaac_abi.cpp): asking for a kernel's attributes puts this translation unit's code object on the device */
 extern "C" hipError_t xaac_warm_sbr_ps(void) {
   hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&xaac_ps_kernel));
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&xaac_ps_kernel<32>));
 }

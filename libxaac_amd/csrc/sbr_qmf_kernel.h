@@ -37,7 +37,7 @@ typedef struct XaacQmfAnaParams {
      points into xaac_sbr_state).  NULL: use `usb` for every channel. */
   const xaac_sbr_frame *frame;
   int32_t *zero_words; /* optional: two words the HQ kernel clears for the launch behind it (the SBR core's counters) */
-  int32_t n_slots;     /* 0 / 32, or 30: 960 samples in per channel (low-power only) */
+  int32_t n_slots;     /* 0 / 32, or 30: 960 samples in per channel */
   const int16_t *refused; /* optional [n_ch][8], [7] != 0: the channel's state is left alone (xaac_launch_sbr_screen) */
 } XaacQmfAnaParams;
 
@@ -55,7 +55,7 @@ typedef struct XaacQmfSynParams {
      pcm[c * pcm_ch_stride + n * pcm_sample_stride] (one launch per output channel of a PS stream) */
   int32_t pcm_ch_stride, pcm_sample_stride;
   int32_t *dbg; /* profiling builds (-DXS_PROFILE) only: cycle counters at dbg[64..], else unused */
-  int32_t n_slots; /* 0 / 32, or 30: 1920 samples out per channel (low-power, 64 channels only) */
+  int32_t n_slots; /* 0 / 32, or 30: 1920 samples out per channel (64 channels only) */
 } XaacQmfSynParams;
 
 /* HE-AACv2: both complex synthesis banks of a stream in one wave (channel 0 = left, state in xaac_sbr_state; channel
@@ -70,8 +70,9 @@ typedef struct XaacQmfSynPairParams {
   const int16_t *scale[2];
   xaac_qmf_syn_state *state[2];
   int32_t state_stride[2];  /* bytes */
-  int16_t *pcm;             /* [n][2048][2] */
+  int16_t *pcm;             /* [n][32 n_slots][2] */
   int32_t *status;          /* [n] or NULL: -1 where a stream's ring state is refused (see the kernel) */
+  int32_t n_slots;          /* 0 / 32, or 30: 1920 L,R pairs out per stream (960-sample cores) */
 } XaacQmfSynPairParams;
 
 #ifdef __cplusplus

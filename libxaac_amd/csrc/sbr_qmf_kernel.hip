@@ -225,7 +225,10 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
      slot) on both: wave 0 takes the difference terms (real parts), wave 1 the sums (imaginary parts), 32 words per
      lane instead of the 64 + 128 + 128 of the whole transform; they meet through two 64 x 33-word tiles for the final
      rotation (wave 0 forms the real outputs, wave 1 the imaginary ones) and for the way out (lane = band);
-   - 22 KB of LDS per workgroup: seven workgroups (14 waves) per CU where the one-wave-per-pair kernel had six waves. */
+   - 22 KB of LDS per workgroup: seven workgroups (14 waves) per CU where the one-wave-per-pair kernel had six waves.
+   NS: slots of a frame, 32 or 30 (960-sample cores: 32 NS new samples into rows 8..7 + NS; the lanes of slots 30, 31
+   transform zero rows that nobody reads, and a channel refused by the screen in front keeps its ring). */
+template <int NS = 32>
 __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaParams p) {
   __shared__ int16_t hist[2][kHist];
   __shared__ int32_t tile[2 * 64 * 33]; /* the 64 x 65 window-add tile, then the two 64 x 33 half tiles */
@@ -258,12 +261,13 @@ __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaPar
       const int wr_v = st->wr;
       phase_old = st->phase;
       const int cf = p.ch_fac;
-      const int16_t *src = p.pcm + (size_t)(chw / cf) * 1024 * cf + (chw % cf);
-      int16_t hr[5], hp[16];
+      constexpr int NP = 32 * NS / 64; /* new samples per lane */
+      const int16_t *src = p.pcm + (size_t)(chw / cf) * (32 * NS) * cf + (chw % cf);
+      int16_t hr[5], hp[NP];
 #pragma unroll
       for (int j = 0; j < 5; j++) hr[j] = st->ring[lane + 64 * j];
 #pragma unroll
-      for (int j = 0; j < 16; j++) hp[j] = src[(size_t)(lane + 64 * j) * cf];
+      for (int j = 0; j < NP; j++) hp[j] = src[(size_t)(lane + 64 * j) * cf];
       wr = __builtin_amdgcn_readfirstlane(wr_v);
 #pragma unroll
       for (int j = 0; j < 5; j++) {
@@ -273,7 +277,7 @@ __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaPar
         if (a < 288) h[287 - a] = hr[j];
       }
 #pragma unroll
-      for (int j = 0; j < 16; j++) h[288 + lane + 64 * j] = hp[j];
+      for (int j = 0; j < NP; j++) h[288 + lane + 64 * j] = hp[j];
     } else {
       for (int i = lane; i < kHist; i += 64) h[i] = 0;
     }
@@ -285,16 +289,18 @@ __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaPar
 #pragma unroll
     for (int j = 0; j < 5; j++) coef[j] = xaac_qmf_qmf_c[2 * lane + 128 * j];
     const int16_t *h = hist[w] + 288 + 31 - lane;
-    int32_t u[40]; /* u[8 + k] = x[32 k + 31 - m], k = -8 .. 31 */
+    int32_t u[8 + NS]; /* u[8 + k] = x[32 k + 31 - m], k = -8 .. NS - 1 */
 #pragma unroll
-    for (int k = 0; k < 40; k++) u[k] = h[32 * (k - 8)];
+    for (int k = 0; k < 8 + NS; k++) u[k] = h[32 * (k - 8)];
 #pragma unroll
-    for (int sl = 0; sl < 32; sl++) {
+    for (int sl = 0; sl < NS; sl++) {
       int32_t acc = 0;
 #pragma unroll
       for (int j = 0; j < 5; j++) acc += u[8 + sl - 2 * j] * coef[j]; /* |acc| < 2^30: exact */
       tile[65 * (32 * w + sl) + lane] = acc;
     }
+#pragma unroll
+    for (int sl = NS; sl < 32; sl++) tile[65 * (32 * w + sl) + lane] = 0;
   }
   __syncthreads();
   /* ---- the halves: lane = (channel, slot) ---- */
@@ -347,17 +353,18 @@ __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaPar
     int32_t *row = p.qmf + (size_t)chw * p.qmf_ch_stride + (lane & 31) + 64 * (lane >> 5);
     const int32_t *src = tile + (lane >> 5) * (64 * 33) + 33 * (32 * w) + (lane & 31);
 #pragma unroll 8
-    for (int r = 0; r < 32; r++) row[(size_t)r * p.slot_stride] = src[33 * r];
+    for (int r = 0; r < NS; r++) row[(size_t)r * p.slot_stride] = src[33 * r];
   }
-  /* ---- state: the ring as the reference leaves it after 32 slots ---- */
+  if (NS != 32 && p.refused && __builtin_amdgcn_readfirstlane((int)p.refused[8 * (size_t)chw + 7])) return;
+  /* ---- state: the ring as the reference leaves it after NS slots (32 NS samples further on) ---- */
   {
-    const int wr_new = (wr + 256) % 320;
-    const int ph_new = ana_phase_after_frame(phase_old);
+    const int wr_new = (wr + 320 - (32 * NS) % 320) % 320;
+    const int ph_new = ana_phase_after_frame<NS>(phase_old);
     const int16_t *h = hist[w];
 #pragma unroll
     for (int j = 0; j < 5; j++) {
       const int a = lane + 64 * j;
-      st->ring[ana_ring_pos(wr_new, a)] = h[kHist - 1 - a];
+      st->ring[ana_ring_pos(wr_new, a)] = h[288 + 32 * NS - 1 - a];
     }
     if (lane == 0) {
       st->wr = (int16_t)wr_new;
@@ -632,7 +639,9 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(Xaac
      wave window-adds 16 slots of both channels, lane = sample, and stores interleaved L,R words;
    - the ring state keeps the reference's layout (2-byte accesses in and out).
    A state whose drc_offset is not one of the reference's (a multiple of 128 below 1280) is refused: status -1, nothing
-   written for that stream. */
+   written for that stream.
+   NS: slots of a frame, 32 or 30 (960-sample cores: 1920 L,R pairs out, each wave window-adds NS / 2 = 15 slots; the lanes of
+   slots 30, 31 transform zero rows whose ring samples nobody reads). */
 namespace {
 __device__ __forceinline__ int32_t pair_rescale(int32_t v, int shl, int shr) { return (int32_t)((uint32_t)v << shl) >> shr; }
 /* clamp(a, lo, hi) with lo <= hi as ONE v_med3_i32 (the compiler, which cannot know lo <= hi, spends a max, a compare
@@ -652,7 +661,9 @@ typedef short xq_short2 __attribute__((ext_vector_type(2)));
 #ifndef XQ_STAGGER_FIRST
 #define XQ_STAGGER_FIRST 1536 /* six workgroups per CU: the ones that start together */
 #endif
+template <int NS = 32>
 __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSynPairParams p) {
+  constexpr int NH = NS / 2; /* slots a wave window-adds */
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int RS = 65;          /* padded LDS row stride (dwords) of tiles and pair rows */
   constexpr int EROWS = 9 + 32 + 1; /* pair rows of a channel: slots -9 .. 32 */
@@ -687,7 +698,7 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
 #pragma unroll
   for (int r = 0; r < 64; r++) {
     const int c = r >> 5;
-    tmp[r] = (p.qmf[c] + (size_t)i * p.qmf_stride[c] + (size_t)(r & 31) * 128 + 64 * w)[lane];
+    tmp[r] = (r & 31) < NS ? (p.qmf[c] + (size_t)i * p.qmf_stride[c] + (size_t)(r & 31) * 128 + 64 * w)[lane] : 0;
   }
   const auto lo16 = [](int v) { return (int)(int16_t)v; };
   const auto hi16 = [](int v) { return v >> 16; };
@@ -796,7 +807,7 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
     }
   }
   __syncthreads();
-  /* ---- phase C: window-add, wave w = slots 16 w .. 16 w + 15 of both channels, lane = sample k ----------------- */
+  /* ---- phase C: window-add, wave w = slots NH w .. NH w + NH - 1 of both channels, lane = sample k ------------- */
   {
     xq_short2 cp[5];
 #pragma unroll
@@ -804,14 +815,14 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
       cp[j].x = xaac_qmf_qmf_c[128 * j + lane];
       cp[j].y = xaac_qmf_qmf_c[128 * j + 64 + lane];
     }
-    int32_t e[2][24]; /* E[16 w - 8 .. 16 w + 15][lane] */
+    int32_t e[2][8 + NH]; /* E[NH w - 8 .. NH w + NH - 1][lane] */
 #pragma unroll
     for (int c = 0; c < 2; c++)
 #pragma unroll
-      for (int q = 0; q < 24; q++) e[c][q] = E[(c * EROWS + 9 + 16 * w - 8 + q) * RS + lane];
-    int32_t *out = reinterpret_cast<int32_t *>(p.pcm) + (size_t)i * 2048 + 1024 * w + lane; /* one word per L,R pair */
+      for (int q = 0; q < 8 + NH; q++) e[c][q] = E[(c * EROWS + 9 + NH * w - 8 + q) * RS + lane];
+    int32_t *out = reinterpret_cast<int32_t *>(p.pcm) + (size_t)i * (64 * NS) + (64 * NH) * w + lane; /* one word per L,R pair */
 #pragma unroll
-    for (int s = 0; s < 16; s++) {
+    for (int s = 0; s < NH; s++) {
       int32_t acc[2] = {0x4000, 0x4000};
 #pragma unroll
       for (int c = 0; c < 2; c++)
@@ -830,14 +841,14 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
   /* ---- state of channel w: ring blocks of the last 10 slots, drc offset, window phase --------------------------- */
   if (w == 0 ? inactive0 : inactive1) return;
   {
-    const int d_new = (d_old + RING - (32 * 128) % RING) % RING; /* 32 slots of 128 downwards */
-    const int ph_new = (st_w->phase + 128) % 640;
+    const int d_new = (d_old + RING - (NS * 128) % RING) % RING; /* NS slots of 128 downwards */
+    const int ph_new = (st_w->phase + (64 * NS) % 640) % 640;   /* 64 a slot */
     const int16_t *hrow = reinterpret_cast<const int16_t *>(E + (w * EROWS) * RS);
     int16_t v_lo[10], v_hi[10];
 #pragma unroll
-    for (int A = 1; A <= 10; A++) { /* age relative to the NEXT frame's slot 0: slot 32 - A */
-      v_lo[A - 1] = hrow[(9 + 32 - A) * 2 * RS + 2 * lane];
-      v_hi[A - 1] = hrow[(10 + 32 - A) * 2 * RS + 2 * lane + 1];
+    for (int A = 1; A <= 10; A++) { /* age relative to the NEXT frame's slot 0: slot NS - A */
+      v_lo[A - 1] = hrow[(9 + NS - A) * 2 * RS + 2 * lane];
+      v_hi[A - 1] = hrow[(10 + NS - A) * 2 * RS + 2 * lane + 1];
     }
 #pragma unroll
     for (int A = 1; A <= 10; A++) {
@@ -855,7 +866,10 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
 }
 
 extern "C" hipError_t xaac_launch_qmf_synthesis_pair(const XaacQmfSynPairParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel, dim3(p->n), dim3(128), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
+  if (p->n_slots == 30) /* 960-sample cores (xaac_sbr_hq960_process_batch) */
+    hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel<30>, dim3(p->n), dim3(128), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
+  else
+    hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel<32>, dim3(p->n), dim3(128), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
   return hipGetLastError();
 }
 
@@ -1086,25 +1100,31 @@ extern "C" hipError_t xaac_launch_qmf_analysis_eld(const xaac_qmf_ana_eld_batch 
 }
 
 extern "C" hipError_t xaac_launch_qmf_analysis(const XaacQmfAnaParams *p, int grid, hipStream_t stream) {
-  if (p->n_slots == 30) { /* 960-sample cores: the low-power bank only (xaac_sbr_lp960_process_batch) */
-    if (!p->low_pow) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((xaac_qmf_analysis_kernel<true, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
+  if (p->n_slots == 30) { /* 960-sample cores (xaac_sbr_lp960_process_batch, xaac_sbr_hq960_process_batch) */
+    if (p->low_pow)
+      hipLaunchKernelGGL((xaac_qmf_analysis_kernel<true, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
+                         XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
+    else
+      hipLaunchKernelGGL(xaac_qmf_analysis_hq_kernel<30>, dim3((p->n_ch + 1) / 2), dim3(128), 0, stream, *p);
     return hipGetLastError();
   }
   if (p->low_pow)
     hipLaunchKernelGGL(xaac_qmf_analysis_kernel<true>, dim3(grid), dim3(XAAC_QMF_BLOCK),
                        XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
   else /* two channels per workgroup, not persistent: `grid` (sized for the low-power kernel) does not apply */
-    hipLaunchKernelGGL(xaac_qmf_analysis_hq_kernel, dim3((p->n_ch + 1) / 2), dim3(128), 0, stream, *p);
+    hipLaunchKernelGGL(xaac_qmf_analysis_hq_kernel<32>, dim3((p->n_ch + 1) / 2), dim3(128), 0, stream, *p);
   return hipGetLastError();
 }
 
 extern "C" hipError_t xaac_launch_qmf_synthesis(const XaacQmfSynParams *p, int grid, hipStream_t stream) {
-  if (p->n_slots == 30) { /* 960-sample cores: the low-power 64-channel bank only (xaac_sbr_lp960_process_batch) */
-    if (!p->low_pow || p->down_sample) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, false, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);
+  if (p->n_slots == 30) { /* 960-sample cores, 64 channels only (xaac_sbr_lp960_process_batch, xaac_sbr_hq960_process_batch) */
+    if (p->down_sample) return hipErrorInvalidValue;
+    if (p->low_pow)
+      hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, false, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
+                         XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);
+    else
+      hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<false, false, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
+                         XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ, stream, *p);
     return hipGetLastError();
   }
   if (p->low_pow && p->down_sample)
@@ -1138,5 +1158,5 @@ extern "C" int xaac_qmf_blocks_per_cu(int which) {
 /* xaac_warm_up (xaac_abi.cpp): asking for a kernel's attributes puts this translation unit's code object on the device */
 extern "C" hipError_t xaac_warm_sbr_qmf(void) {
   hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&xaac_qmf_synthesis_pair_kernel));
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&xaac_qmf_synthesis_pair_kernel<32>));
 }

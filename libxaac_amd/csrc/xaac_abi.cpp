@@ -751,11 +751,13 @@ int32_t xaac_sbr_eld_process_batch(xaac_ctx *c, const xaac_sbr_eld_batch *b) {
   return XAAC_OK;
 }
 
-int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) {
+/* ns: QMF slots of the frames -- 32 (xaac_sbr_hq_process_batch) or 30 (xaac_sbr_hq960_process_batch: 960 samples in, 1920 out) */
+static int32_t sbr_hq_run(xaac_ctx *c, const xaac_sbr_hq_batch *b, int ns) {
   if (!c || !b) return XAAC_FATAL_NULL_ARG;
   if (b->n_ch < 0) return XAAC_FATAL_BAD_ARG;
   const bool with_ps = b->ps_frame != nullptr;
   if ((b->ps_frame == nullptr) != (b->ps_state == nullptr)) return XAAC_FATAL_BAD_ARG;
+  if (ns == 30 && b->down_sample) return XAAC_FATAL_BAD_ARG; /* see xaac_sbr_hq960_process_batch */
   if (b->in_ch_fac != 1 && b->in_ch_fac != 2) return XAAC_FATAL_BAD_ARG;
   if (!with_ps && b->out_ch_fac != 1 && b->out_ch_fac != 2) return XAAC_FATAL_BAD_ARG;
   if (with_ps && b->down_sample) return XAAC_FATAL_BAD_ARG; /* see xaac_sbr_hq_batch.down_sample */
@@ -771,9 +773,9 @@ int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) {
   int16_t *par_l = reinterpret_cast<int16_t *>(xr + (with_ps ? n * 32 * 128 : 0));
   int16_t *par_r = par_l + n * 8;
   char *st = reinterpret_cast<char *>(b->state);
-  /* 1. complex analysis bank: 32 new slots into rows 8..39 of each stream's matrix */
+  /* 1. complex analysis bank: ns new slots into rows 8..7 + ns of each stream's matrix */
   XaacQmfAnaParams pa = {};
-  pa.n_ch = b->n_ch; pa.ch_fac = b->in_ch_fac; pa.low_pow = 0; pa.usb = 32; pa.slot_stride = 128;
+  pa.n_ch = b->n_ch; pa.ch_fac = b->in_ch_fac; pa.low_pow = 0; pa.usb = 32; pa.slot_stride = 128; pa.n_slots = ns;
   pa.state_stride = (int32_t)sizeof(xaac_sbr_state); pa.qmf_ch_stride = xw;
   pa.pcm = b->pcm_in;
   pa.state = reinterpret_cast<xaac_qmf_ana_state *>(st + offsetof(xaac_sbr_state, ana_ring));
@@ -783,6 +785,14 @@ int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) {
      synthesis parameters; the analysis launch clears them on its way */
   int32_t *counters = reinterpret_cast<int32_t *>(((uintptr_t)(par_l + n * 8 * (with_ps ? 2 : 1)) + 63) & ~(uintptr_t)63);
   pa.zero_words = counters;
+  if (ns == 30) {
+    /* 0. the side-info check up front: a refused stream's SBR state, PS state and output are left as they are
+       (xaac_sbr_hq960_process_batch) */
+    XaacSbrCoreParams sc = {};
+    sc.n_ch = b->n_ch; sc.header = b->header; sc.frame = b->frame; sc.state = b->state; sc.syn_par = par_l; sc.qmf_slots = ns;
+    if (!hip_ok(xaac_launch_sbr_screen(&sc, c->stream))) return XAAC_FATAL_HIP;
+    pa.refused = par_l;
+  }
   if (!hip_ok(xaac_launch_qmf_analysis(&pa, qmf_grid(c, b->n_ch, 1), c->stream))) return XAAC_FATAL_HIP;
   /* 2. everything between the banks */
   XaacSbrCoreParams pc = {};
@@ -791,18 +801,20 @@ int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) {
   pc.defer_count = counters; pc.work_counter = counters + 1; pc.defer_list = counters + 2; pc.num_cu = c->num_cu;
   pc.counters_zeroed = 1;
   pc.narrow_only = b->max_band_hint == XAAC_SBR_NARROW_BANDS ? 1 : 0;
+  pc.qmf_slots = ns;
   if (!hip_ok(xaac_launch_sbr_core_hq(&pc, c->stream))) return XAAC_FATAL_HIP;
-  /* 3. parametric stereo: rows 2..33 become the left channel, xr the right one */
+  /* 3. parametric stereo: rows 2..1 + ns become the left channel, xr the right one */
   if (with_ps) {
-    XaacPsParams pp;
+    XaacPsParams pp = {};
+    pp.n_slots = ns;
     pp.n = b->n_ch; pp.x = x; pp.xr = xr; pp.header = b->header; pp.sbr_frame = b->frame; pp.frame = b->ps_frame;
     pp.state = b->ps_state; pp.sbr_state = b->state; pp.par_l = par_l; pp.par_r = par_r; pp.status = b->status; pp.dbg = XAAC_DBG_BUF(b->status, b->n_ch);
     if (!hip_ok(xaac_launch_ps(&pp, c->stream))) return XAAC_FATAL_HIP;
   }
-  /* 4. synthesis bank(s) over the 6 delayed + first 26 new slots */
+  /* 4. synthesis bank(s) over the 6 delayed + first ns - 6 new slots */
   if (with_ps) { /* both banks of a stream in one wave, interleaved L,R out */
     XaacQmfSynPairParams pq = {};
-    pq.n = b->n_ch; pq.split = 6;
+    pq.n = b->n_ch; pq.split = 6; pq.n_slots = ns;
     pq.qmf[0] = x + 2 * 128; pq.qmf_stride[0] = xw; pq.scale[0] = par_l;
     pq.state[0] = reinterpret_cast<xaac_qmf_syn_state *>(st + offsetof(xaac_sbr_state, syn_ring));
     pq.state_stride[0] = (int32_t)sizeof(xaac_sbr_state);
@@ -816,7 +828,7 @@ int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) {
     return XAAC_OK;
   }
   XaacQmfSynParams ps = {};
-  ps.n_ch = b->n_ch; ps.ch_fac = b->out_ch_fac; ps.low_pow = 0; ps.split = 6;
+  ps.n_ch = b->n_ch; ps.ch_fac = b->out_ch_fac; ps.low_pow = 0; ps.split = 6; ps.n_slots = ns;
   ps.down_sample = b->down_sample ? 1 : 0;
   ps.slot_stride = 128; ps.state_stride = (int32_t)sizeof(xaac_sbr_state); ps.qmf_ch_stride = xw;
   ps.scale_stride = 8; ps.per_ch_bands = 1;
@@ -828,6 +840,9 @@ int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) {
   c->last_grid = grid; c->last_block = XAAC_QMF_BLOCK; c->last_lds = XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ;
   return XAAC_OK;
 }
+
+int32_t xaac_sbr_hq_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) { return sbr_hq_run(c, b, 32); }
+int32_t xaac_sbr_hq960_process_batch(xaac_ctx *c, const xaac_sbr_hq_batch *b) { return sbr_hq_run(c, b, 30); }
 
 /* ixheaacd_peak_limiter_init, decoder/ixheaacd_peak_limiter.c:46-77 (host side: a stream's state is made once) */
 int32_t xaac_peak_limiter_init(xaac_limiter_state *s, uint32_t num_channels, uint32_t sample_rate) {
