@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "xaac_sbr.h"
+#include "xaac_tools.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -476,6 +477,30 @@ typedef struct xaac_usac_imdct_batch {
 } xaac_usac_imdct_batch;
 
 typedef struct xaac_ctx xaac_ctx;
+
+/* ---- AAC spectral tools ----------------------------------------------------------------------
+ * xaac_aac_tools_process_batch <-> the tool half of ixheaacd_channel_pair_process (decoder/ixheaacd_channel.c:602-725):
+ * M/S stereo and intensity stereo (ixheaacd_stereo.c:54-243), perceptual noise substitution (ixheaacd_pns_js_thumb.c:74-199)
+ * and temporal noise shaping (ixheaacd_pns_js_thumb.c:248-514, ixheaacd_aac_tns.c) on n channel elements at once, in front
+ * of xaac_imdct_process_batch.  In: the spectra as they stand at the entry of ixheaacd_channel_pair_process (what the host
+ * parser's stage 1 delivers), the side info of xaac_tools.h (xaac_parse_core_tools_side) and the stream's noise generator
+ * state.  Out: the spectra ixheaacd_imdct_process receives, in place, and the state moved on.  1024-line frames, at most
+ * two channels, no LTP / prediction.  The CPU twin with the same arithmetic is xaac_core_tools_apply_host (xaac_parse.h). */
+typedef struct xaac_aac_tools_batch {
+  int32_t n;                        /* channel elements, >= 0 */
+  int32_t spec_stride;              /* int32 words from one element's spectra to the next one's: a multiple of 4, >= 1024; an
+                                       element whose side row has n_ch = 2 needs >= 2048 and is refused (status -1) below that */
+  int32_t *spec;                    /* in / out, 16-byte aligned: element i's channel c at spec + i * spec_stride + 1024 * c */
+  const xaac_core_tools_side *side; /* [n] */
+  xaac_core_tools_state *state;     /* [n] in / out: zero for a new stream */
+  int32_t *status;                  /* optional [n]: 0, or -1 for side info outside the struct's capacity or the syntax (channel
+                                       count, sampling frequency index, max_sfb beyond the band table, window grouping, code
+                                       book 12 or > 15, TNS filter count / order > 12 / coefficient index) or a pair behind a stride
+                                       of fewer than 2048 words: that element's
+                                       spectra and state are left as they are, its neighbours are processed */
+} xaac_aac_tools_batch;
+XAAC_API int32_t xaac_aac_tools_process_batch(xaac_ctx *c, const xaac_aac_tools_batch *b);
+
 
 /* Create a context bound to HIP device `device`.  `hip_stream` is a
  * hipStream_t to launch on (NULL: the context creates and owns one). */

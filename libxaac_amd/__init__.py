@@ -279,6 +279,15 @@ QMF_SYN_STATE_WORDS = 1282   # int16 words of struct xaac_qmf_syn_state: ring[12
 _lib = None
 
 
+class _AacToolsBatch(ctypes.Structure):
+    # struct xaac_aac_tools_batch
+    _fields_ = [("n", ctypes.c_int32), ("spec_stride", ctypes.c_int32), ("spec", ctypes.c_void_p), ("side", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES = 1652, 516   # include/xaac_tools.h
+
+
 def load_library():
     """dlopen the product library; loud failure when it has not been built."""
     global _lib
@@ -307,6 +316,8 @@ def load_library():
     lib.xaac_imdct_process_batch_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ImdctBatch)]
     lib.xaac_imdct960_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ImdctBatch)]
     lib.xaac_imdct960_process_batch.restype = ctypes.c_int32
+    lib.xaac_aac_tools_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_AacToolsBatch)]
+    lib.xaac_aac_tools_process_batch.restype = ctypes.c_int32
     lib.xaac_imdct_ld_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ImdctLdBatch)]
     lib.xaac_imdct_ld_process_batch.restype = ctypes.c_int32
     lib.xaac_last_launch.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int32)] * 3
@@ -489,6 +500,24 @@ class XaacContext:
         rc = self._lib.xaac_imdct_process_batch(self._h, ctypes.byref(b))
         if rc != 0:
             raise XaacError(rc, "xaac_imdct_process_batch")
+
+    def aac_tools_process_batch(self, spec, side, state, status=None, spec_stride=None):
+        """The AAC spectral tools (M/S, intensity, PNS, TNS: the tool half of ixheaacd_channel_pair_process) on device tensors
+        (asynchronous), in front of imdct_process_batch: spec int32[N, 2, 1024] (or [N, 1024] for mono elements) as the host
+        parser's stage 1 delivers it, in / out; side uint8[N, CORE_TOOLS_SIDE_BYTES] (xaac_parse_core_tools_side); state
+        uint8[N, CORE_TOOLS_STATE_BYTES] in / out (zero for a new stream); optional status int32[N]: 0, or -1 for side info
+        the tools refuse (that element is left untouched)."""
+        n = side.shape[0]
+        stride = int(spec_stride) if spec_stride is not None else spec.numel() // max(n, 1)
+        b = _AacToolsBatch()
+        b.n, b.spec_stride = n, stride
+        b.spec = _ptr(spec, "int32", n * stride, device_ok=True)
+        b.side = _ptr(side, "uint8", n * CORE_TOOLS_SIDE_BYTES, device_ok=True)
+        b.state = _ptr(state, "uint8", n * CORE_TOOLS_STATE_BYTES, device_ok=True)
+        b.status = _ptr(status, "int32", n, allow_none=True, device_ok=True)
+        rc = self._lib.xaac_aac_tools_process_batch(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, "xaac_aac_tools_process_batch")
 
     def imdct960_process_batch(self, spec, ics, overlap, state, out32=None, pcm16=None, qshift_adj=None, ch_fac=1,
                                pcm_mode=PCM_LC, status=None):

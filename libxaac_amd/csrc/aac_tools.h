@@ -1,0 +1,461 @@
+/*
+ * aac_tools.h -- the arithmetic of the AAC spectral tools, for g++ (the host parser and its CPU twin,
+ * libxaac_amd/host/aac_core.cpp) and hipcc (aac_tools_kernel.hip) alike: the tool half of ixheaacd_channel_pair_process
+ * (decoder/ixheaacd_channel.c:602-725) on the side info of include/xaac_tools.h.
+ *   M/S stereo                     ixheaacd_stereo.c:54-116
+ *   intensity stereo               ixheaacd_stereo.c:129-243
+ *   perceptual noise substitution  ixheaacd_pns_js_thumb.c:74-199, ixheaacd_basic_funcs.c:155-196 (square roots)
+ *   temporal noise shaping         ixheaacd_pns_js_thumb.c:248-514, ixheaacd_aac_tns.c:147-202 (parcor -> LPC), :371-420
+ * Functions every compiler takes are FX_HD; the serial forms the host runs (xt_apply_host and what it calls) are host only:
+ * the kernel spreads the same steps over a wave.
+ */
+#ifndef XAAC_AAC_TOOLS_H
+#define XAAC_AAC_TOOLS_H
+
+#include <stddef.h>
+
+#include "fx.h"
+#include "../../include/xaac_tools.h"
+
+#ifndef XT_TABLES_DECLARED
+#define XT_TABLES_DECLARED
+#if defined(__HIPCC__)
+#define XAAC_TAB_QUAL static __device__ const
+#include "tables_aac_tools.inc"
+#undef XAAC_TAB_QUAL
+#else
+#include "tables_aac_tools.inc"
+#endif
+#endif
+
+#define XT_EIGHT_SHORT 2
+#define XT_NOISE_HCB 13
+#define XT_INTENSITY_HCB2 14
+#define XT_SLACK 16 /* the TNS filter runs its order (rounded up to four) lines even over a shorter region */
+
+/* ---- side info ------------------------------------------------------------------------------------------------------ */
+FX_HD bool xt_is_short(const xaac_core_tools_channel &c) { return c.window_sequence == XT_EIGHT_SHORT; }
+
+/* Whether the tools can run on this side info: the items item, item + stride, ... of it (a wave checks it with one item per
+   lane; the host with item 0, stride 1).  Non-zero: outside what the struct, the band tables or the syntax allow. */
+FX_HD int xt_side_check(const xaac_core_tools_side *s, int item, int stride) {
+  if (s->n_ch < 1 || s->n_ch > 2 || s->sr_index > 11 || s->common_window > 1 || (s->n_ch == 1 && s->common_window)) return 1;
+  int bad = 0;
+  for (int c = 0; c < s->n_ch; c++) {
+    const xaac_core_tools_channel &ch = s->ch[c];
+    if (ch.window_sequence > 3) return 1;
+    const bool is_short = xt_is_short(ch);
+    const int num_swb = is_short ? xt_num_swb_short[s->sr_index] : xt_num_swb_long[s->sr_index];
+    if (ch.max_sfb > num_swb) return 1;
+    if (is_short) {
+      if (ch.num_groups < 1 || ch.num_groups > 8) return 1;
+      int windows = 0;
+      for (int g = 0; g < ch.num_groups; g++) {
+        if (ch.group_len[g] < 1) return 1;
+        windows += ch.group_len[g];
+      }
+      if (windows != 8) return 1;
+    } else if (ch.num_groups != 1 || ch.group_len[0] != 1) {
+      return 1;
+    }
+    if (c == 1 && s->common_window) {
+      const xaac_core_tools_channel &l = s->ch[0];
+      if (l.window_sequence != ch.window_sequence || l.max_sfb != ch.max_sfb || l.num_groups != ch.num_groups) return 1;
+      for (int g = 0; g < ch.num_groups; g++)
+        if (l.group_len[g] != ch.group_len[g]) return 1;
+    }
+    if (ch.tns_present) {
+      const int windows = is_short ? 8 : 1;
+      for (int w = 0; w < windows; w++) {
+        if (ch.n_filt[w] > (is_short ? 1 : 3)) return 1;
+        for (int f = 0; f < ch.n_filt[w]; f++) {
+          const xaac_tns_filter_side &flt = ch.tns[is_short ? w : f];
+          if (flt.order < 0 || flt.order > XAAC_TOOLS_TNS_MAX_ORDER) return 1;
+          if (flt.order == 0) continue;
+          if ((flt.direction != 1 && flt.direction != -1) || flt.resolution > 1) return 1;
+          const int half = flt.resolution ? 8 : 4;
+          for (int i = 0; i < flt.order; i++)
+            if (flt.coef[i] < -half || flt.coef[i] >= half) return 1;
+        }
+      }
+    }
+    const int bands = ch.num_groups * 16; /* long windows: 16 .. 63 are looked at only below max_sfb */
+    for (int b = item; b < (is_short ? bands : ch.max_sfb); b += stride) {
+      if (is_short && (b & 15) >= ch.max_sfb) continue;
+      if (ch.cb[b] > 15 || ch.cb[b] == 12) bad = 1;
+    }
+  }
+  return bad;
+}
+
+/* ---- the reference's reciprocal square root, square root and division (basic_funcs.c:155-196, basic_ops.h:74-98) ---- */
+FX_HD int32_t xt_mul32_shl_sat(int32_t a, int32_t b) { /* basic_ops40.h: mult32_shl_sat */
+  if (a == FX_MIN32 && b == FX_MIN32) return FX_MAX32;
+  return fx_mul32_shl(a, b);
+}
+FX_HD int32_t xt_mul32x16_shl_sat(int32_t a, int16_t b) {
+  if (a == FX_MIN32 && b == (int16_t)-32768) return FX_MAX32;
+  return fx_mul32x16_shl(a, b);
+}
+FX_HD int32_t xt_mul32x16h_shl_sat(int32_t a, int32_t b) { /* basic_ops.h:62: the clamp looks at all of b */
+  if (a == FX_MIN32 && b == -32768) return FX_MAX32;
+  return fx_mul32x16_shl(a, (int16_t)(b >> 16));
+}
+
+FX_HD int32_t xt_one_by_sqrt(int32_t op) {
+  int32_t a = fx_add_sat((int32_t)0x900ebee0, xt_mul32x16_shl_sat(op, 0x39d9));
+  int32_t iy = fx_add_sat(0x573b645a, xt_mul32x16h_shl_sat(op, a));
+  iy = fx_shl_dir_sat_limit(iy, 1);
+  for (int it = 0; it < 3; it++) {
+    a = xt_mul32_shl_sat(op, iy);
+    a = fx_sub_sat(0x40000000, fx_shl_dir_sat_limit(xt_mul32_shl_sat(a, iy), 1));
+    iy = fx_add_sat(iy, xt_mul32_shl_sat(a, iy));
+  }
+  return iy;
+}
+
+FX_HD int32_t xt_sqrt(int32_t op) {
+  if (op == 0) return 0;
+  int shift = fx_norm32(op) & ~1;
+  op = fx_shl_dir_sat_limit(op, shift);
+  shift = fx_shl_dir_sat_limit(shift, -1);
+  op = xt_mul32_shl_sat(xt_one_by_sqrt(op), op);
+  return fx_shl_dir_sat_limit(op, -(int)fx_sat16(shift - 1));
+}
+
+FX_HD int32_t xt_div32_pos_normb(int32_t a, int32_t b) { /* a / b in Q31 by 32 compare-subtract-shift steps */
+  if (a == b) return FX_MAX32;
+  uint32_t nr = (uint32_t)a, q = 0;
+  const uint32_t dr = (uint32_t)b;
+  for (int i = 0; i < 32; i++) {
+    q <<= 1;
+    if (nr >= dr) {
+      nr -= dr;
+      q += 1;
+    }
+    nr <<= 1;
+  }
+  return (int32_t)q;
+}
+
+/* ---- stereo tools, one line ------------------------------------------------------------------------------------------ */
+/* the gain of an intensity band (stereo.c:170-190): the mantissa of the position, its sign from the code book and ms_used */
+FX_HD int32_t xt_intensity_scale(int sf, int cb, int ms_used) {
+  const int32_t scale = xt_scale_tab[sf & 3];
+  return (ms_used ^ (cb & 1)) ? scale : fx_neg_sat(scale);
+}
+FX_HD int32_t xt_intensity_line(int32_t l, int32_t scale, int sf) {
+  const int scf_exp = -((sf >> 2) + 2);
+  int sh = fx_norm32(l);
+  int32_t t = fx_shl(l, sh);
+  t = (int32_t)(((int64_t)t * (int64_t)scale) >> 16);
+  sh += scf_exp;
+  if (sh < 0) return fx_shl_sat(t, sh < -31 ? 31 : -sh);
+  return fx_shr(t, sh > 31 ? 31 : sh);
+}
+
+/* ---- perceptual noise substitution ------------------------------------------------------------------------------------- */
+#define XT_LCG_A 1664525u
+#define XT_LCG_C 1013904223u
+FX_HD int32_t xt_lcg_next(int32_t seed) { return (int32_t)(XT_LCG_A * (uint32_t)seed + XT_LCG_C); }
+/* k steps of the generator at once: seed -> A * seed + C with A = a^k, C = c (a^k - 1) / (a - 1) mod 2^32, by squaring */
+FX_HD int32_t xt_lcg_jump(int32_t seed, uint32_t k) {
+  uint32_t A = 1, C = 0, a = XT_LCG_A, c = XT_LCG_C;
+  for (; k; k >>= 1) {
+    if (k & 1) {
+      A *= a;
+      C = C * a + c;
+    }
+    c *= a + 1;
+    a *= a;
+  }
+  return (int32_t)(A * (uint32_t)seed + C);
+}
+
+/* the noise of one band: last + 1 lines at x of energy scale * 2^-shift, the generator run on from *seed
+   (pns_js_thumb.c:74-112) */
+FX_HD void xt_gen_rand_vec(int32_t scale, int shift, int32_t *x, int last, int32_t *seed) {
+  int32_t nrg = 0, s = *seed;
+  for (int i = 0; i <= last; i++) {
+    s = xt_lcg_next(s);
+    x[i] = s >> 3;
+    nrg = fx_add_sat(nrg, xt_mul32_shl_sat(x[i], x[i]));
+  }
+  *seed = s;
+  int nrg_scale = fx_norm32(nrg);
+  if (nrg_scale > 0) {
+    nrg_scale &= ~1;
+    nrg = fx_shl_sat(nrg, nrg_scale);
+    shift -= nrg_scale >> 1;
+  }
+  nrg = xt_sqrt(nrg);
+  scale = xt_div32_pos_normb(scale, nrg);
+  if (shift < -31) shift = -31;
+  for (int i = 0; i <= last; i++) x[i] = fx_shl_dir_sat_limit(xt_mul32_shl_sat(x[i], scale), -shift);
+}
+FX_HD int32_t xt_pns_mant(int sf) { return xt_scale_mant_tab[sf & 3]; }
+FX_HD int xt_pns_exp(int sf) { return 31 - (sf >> 2) - 4; } /* PNS_SCALE_MANT_TAB_SCALING -4 */
+
+/* ---- temporal noise shaping, the 16-bit variant every stream of at most two channels takes ----------------------------- */
+/* aac_tns.c:147-202; t1 / t2: work arrays of order + 1 words */
+FX_HD void xt_parcor_to_lpc(const int16_t *parcor, int16_t *lpc, int *scale_out, int order, int16_t *t1, int16_t *t2) {
+  int status = 1, scale = 0;
+  while (status) {
+    status = 0;
+    for (int j = 0; j <= order; j++) t1[j] = 0, t2[j] = 0;
+    int32_t accu1 = 0x7fffffff >> scale;
+    for (int i = 0; i <= order; i++) {
+      const int32_t accu = accu1;
+      for (int j = 0; j < order; j++) {
+        t2[j] = fx_round16(accu1);
+        const int32_t prod = ((int32_t)parcor[j] * t1[j] == 0x40000000) ? FX_MAX32 : fx_shlw((int32_t)parcor[j] * t1[j], 1);
+        accu1 = fx_add_sat(accu1, prod);
+        if (fx_abs_sat(accu1) == 0x7fffffff) status = 1;
+      }
+      for (int j = order - 1; j >= 0; j--) {
+        int32_t accu2 = fx_shlw((int32_t)t1[j], 16);
+        const int32_t prod = ((int32_t)parcor[j] * t2[j] == 0x40000000) ? FX_MAX32 : fx_shlw((int32_t)parcor[j] * t2[j], 1);
+        accu2 = fx_add_sat(accu2, prod);
+        t1[j + 1] = fx_round16(accu2);
+        if (fx_abs_sat(accu2) == 0x7fffffff) status = 1;
+      }
+      t1[0] = fx_round16(accu);
+      lpc[i] = fx_round16(accu1);
+      accu1 = 0;
+    }
+    if (status) scale = (int16_t)(scale + 1);
+  }
+  *scale_out = scale;
+}
+FX_HD int16_t xt_tns_parcor(const xaac_tns_filter_side &flt, int i) {
+  return flt.resolution ? xt_tns_coef4[flt.coef[i] + 8] : xt_tns_coef3[flt.coef[i] + 4];
+}
+
+/* where one filter of window `win` works (pns_js_thumb.c:300-340, :420-450) */
+struct XtTnsPlan {
+  int start, size; /* the region: lines start .. start + size - 1 of the window */
+  int first;       /* the line of the CHANNEL the recursion starts at, and its step */
+  int inc;
+  int lines;       /* how many lines it filters: the order rounded up to four where the region is shorter (aac_tns.c:371) */
+};
+/* false: the filter does nothing */
+FX_HD bool xt_tns_plan(const xaac_core_tools_side *s, const xaac_core_tools_channel &ch, int win, const xaac_tns_filter_side &flt,
+                       XtTnsPlan *p) {
+  if (flt.order <= 0) return false;
+  const bool is_short = xt_is_short(ch);
+  const int max_bands = xt_tns_max_bands[2 * s->sr_index + (is_short ? 1 : 0)];
+  const int16_t *swb = is_short ? xt_swb_short[s->sr_index] : xt_swb_long[s->sr_index];
+  int lo = flt.start_band < max_bands ? flt.start_band : max_bands;
+  if (lo > ch.max_sfb) lo = ch.max_sfb;
+  int hi = flt.stop_band < max_bands ? flt.stop_band : max_bands;
+  if (hi > ch.max_sfb) hi = ch.max_sfb;
+  const int start = swb[lo], stop = swb[hi];
+  p->start = start, p->size = stop - start;
+  if (p->size <= 0) return false;
+  if (flt.direction == -1) {
+    p->first = (win << 7) + stop - 1, p->inc = -1;
+    if (p->first < flt.order) return false;
+  } else {
+    p->first = (win << 7) + start, p->inc = 1;
+    if (p->first + flt.order > 1024) return false;
+  }
+  const int padded = (flt.order + 3) & ~3;
+  p->lines = p->size > padded ? p->size : padded;
+  return true;
+}
+/* the headroom the region's lines leave, from the OR of their xt_tns_mag_bits, less the four bits and the LPC scale */
+FX_HD int32_t xt_tns_mag_bits(int32_t v) { return fx_abs_nrm(v); }
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+/* ======== the serial forms: the host parser's stage 2 and the CPU twin of the kernel ================================= */
+/* One output of the all-pole filter: acc = sum over j = m .. 1 of mul32x16(s[i - j], lpc[j]), added up with saturation in
+   that order (aac_tns.c:371-420).  If the magnitudes of the products add up to less than 2^31 no partial sum can leave
+   the 32-bit range, the saturating chain is the plain sum and the order does not matter.  With L = sum |lpc[j]| and
+   every state so far at most `quiet` = (2^31 - 1 - order) * 2^16 / L in magnitude that holds for sure
+   (|floor(s * l / 2^16)| <= |s| |l| / 2^16 + 1): the case for every stream with the headroom the reference's scaling
+   leaves (four bits), and it turns a chain of `order` dependent clamped adds per line into independent multiply-adds.
+   From the first state beyond `quiet` on the chain is run as written. */
+static inline int32_t xt_tns_acc_chain(const int32_t *h, const int16_t *lpc, int m) {
+  int32_t acc = 0;
+  for (int j = m; j > 0; j--) acc = fx_add_sat(acc, fx_mul32x16(h[-j], lpc[j]));
+  return acc;
+}
+template <int M>
+static inline int32_t xt_tns_acc_plain(const int32_t *h, const int16_t *lpc, int m_runtime) {
+  const int m = M ? M : m_runtime;
+  int64_t sum = 0;
+  for (int j = 1; j <= m; j++) sum += ((int64_t)h[-j] * lpc[j]) >> 16; /* = fx_mul32x16, exactly */
+  return (int32_t)sum;
+}
+static inline uint32_t xt_tns_mag(int32_t v) { return v < 0 ? 0u - (uint32_t)v : (uint32_t)v; }
+
+/* lines from .. n-1; returns the first line it did not do (n, or where a state left the quiet range) */
+template <int M>
+static inline int xt_tns_ar_run(int32_t *x, int from, int n, int inc, const int16_t *lpc, int order, int shift_value, int scale_spec,
+                                int32_t *hist, uint32_t quiet, uint32_t *loudest) {
+  x += (ptrdiff_t)from * inc;
+  uint32_t top = *loudest;
+  int i = from;
+  for (; i < n && top <= quiet; i++) {
+    const int32_t y0 = fx_shl_sat(*x, scale_spec);
+    const int32_t acc = xt_tns_acc_plain<M>(hist + i, lpc, i < order ? i : order);
+    /* y = sub_sat(y0, shl_sat(acc, 1)), state = shl_sat(y, shift_value): line i + 1 waits for this state, so the three
+       clamps are first assumed idle (plain 64-bit arithmetic, checked beside the chain) and only redone if one was not */
+    const int64_t t64 = 2 * (int64_t)acc, y64 = (int64_t)y0 - t64, s64 = (int64_t)((uint64_t)y64 << shift_value);
+    int32_t y = (int32_t)y64, s = (int32_t)s64; /* the reference's state[0]: state[j] of step i is hist[i - 1 - j] */
+    if (__builtin_expect(t64 != (int32_t)t64 || y64 != (int32_t)y64 || s64 != (int32_t)s64, 0)) {
+      y = fx_sub_sat(y0, fx_shl_sat(acc, 1));
+      s = fx_shl_sat(y, shift_value);
+    }
+    hist[i] = s;
+    const uint32_t a = xt_tns_mag(s);
+    top = a > top ? a : top;
+    *x = y >> scale_spec;
+    x += inc;
+  }
+  *loudest = top;
+  return i;
+}
+
+static inline void xt_tns_ar_filter(int32_t *x, int size, int inc, int16_t *lpc, int order, int shift_value, int scale_spec) {
+  /* aac_tns.c:371-420: the order is rounded up to a multiple of four with zero coefficients, and the first `order`
+     lines are filtered whether the region has that many or not */
+  int32_t hist[1024 + 64];
+  if (order & 3) {
+    int i;
+    for (i = order + 1; i < (order & ~3) + 4; i++) lpc[i] = 0;
+    if (i < 32) {
+      lpc[i] = 0;
+      order = (order & ~3) + 4;
+    } else {
+      order = 31;
+    }
+  }
+  const int n = size > order ? size : order;
+  int64_t l1 = 0;
+  for (int j = 1; j <= order; j++) l1 += lpc[j] < 0 ? -(int64_t)lpc[j] : lpc[j];
+  const int64_t q = l1 ? (((int64_t)FX_MAX32 - order) << 16) / l1 : (int64_t)0xffffffff;
+  const uint32_t quiet = q > (int64_t)0xffffffff ? 0xffffffffu : (uint32_t)q;
+  uint32_t loudest = 0;
+  const int lead = order < n ? order : n;
+  int i = xt_tns_ar_run<0>(x, 0, lead, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); /* fewer than `order` states yet */
+  if (i == lead) {
+    switch (order) {
+      case 4: i = xt_tns_ar_run<4>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
+      case 8: i = xt_tns_ar_run<8>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
+      case 12: i = xt_tns_ar_run<12>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
+      default: i = xt_tns_ar_run<0>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
+    }
+  }
+  x += (ptrdiff_t)i * inc;
+  for (; i < n; i++) { /* a state beyond the quiet range: the chain as the reference runs it */
+    int32_t y = fx_shl_sat(*x, scale_spec);
+    const int32_t acc = xt_tns_acc_chain(hist + i, lpc, i < order ? i : order);
+    y = fx_sub_sat(y, fx_shl_sat(acc, 1));
+    hist[i] = fx_shl_sat(y, shift_value);
+    *x = y >> scale_spec;
+    x += inc;
+  }
+}
+
+/* spec: the channel's 1024 lines with XT_SLACK words of the caller's on either side */
+static inline void xt_tns_host(const xaac_core_tools_side *s, const xaac_core_tools_channel &ch, int32_t *spec) {
+  const bool is_short = xt_is_short(ch);
+  for (int win = 0; win < (is_short ? 8 : 1); win++)
+    for (int f = 0; f < ch.n_filt[win]; f++) {
+      const xaac_tns_filter_side &flt = ch.tns[is_short ? win : f];
+      XtTnsPlan pl;
+      if (flt.order <= 0) continue;
+      const bool run = xt_tns_plan(s, ch, win, flt, &pl);
+      if (pl.size <= 0 || !run) continue;
+      /* sized by XAAC_TOOLS_TNS_MAX_ORDER: callers come through xt_side_check, or are the parser, whose read_tns refuses
+         an order above 12 (aac_core.cpp, channel.c:1021) */
+      int16_t parcor[XAAC_TOOLS_TNS_MAX_ORDER + 1], lpc[XAAC_TOOLS_TNS_MAX_ORDER + 4 + 1], t1[XAAC_TOOLS_TNS_MAX_ORDER + 1],
+          t2[XAAC_TOOLS_TNS_MAX_ORDER + 1];
+      for (int i = 0; i < flt.order; i++) parcor[i] = xt_tns_parcor(flt, i);
+      int scale_lpc;
+      xt_parcor_to_lpc(parcor, lpc, &scale_lpc, flt.order, t1, t2);
+      int32_t *region = spec + (win << 7) + pl.start;
+      int32_t m = 0;
+      for (int i = 0; i < pl.size; i++) m |= xt_tns_mag_bits(region[i]);
+      int scale_spec = fx_norm32(m) - 4 - scale_lpc;
+      int32_t *at = spec + pl.first;
+      if (scale_spec > 0) {
+        if (scale_spec > 31) scale_spec = 31;
+        xt_tns_ar_filter(at, pl.size, pl.inc, lpc, flt.order, scale_lpc, scale_spec);
+      } else {
+        /* not enough headroom: lines down, filter, lines up again.  The reference takes the lines it shifts down
+           from window 0 whatever the window is (`win >> 7`, pns_js_thumb.c:455) and shifts the filtered window up */
+        int32_t *down = spec + pl.start;
+        scale_spec = -scale_spec;
+        if (scale_spec > 31) scale_spec = 31;
+        for (int i = 0; i < pl.size; i++) down[i] >>= scale_spec;
+        xt_tns_ar_filter(at, pl.size, pl.inc, lpc, flt.order, scale_lpc, 0);
+        for (int i = 0; i < pl.size; i++) region[i] = fx_shlw(region[i], scale_spec);
+      }
+    }
+}
+
+static inline void xt_stereo_host(const xaac_core_tools_side *s, int32_t *l, int32_t *r) { /* stereo.c:54-243 */
+  const xaac_core_tools_channel &rc = s->ch[1];
+  const bool is_short = xt_is_short(rc);
+  const int16_t *swb = is_short ? xt_swb_short[s->sr_index] : xt_swb_long[s->sr_index];
+  for (int pass = 0; pass < 2; pass++) { /* M/S over the whole frame first (the pair's common window), then intensity */
+    if (pass == 0 && !s->common_window) continue;
+    int win = 0;
+    for (int g = 0; g < rc.num_groups; g++)
+      for (int w = 0; w < rc.group_len[g]; w++, win++)
+        for (int sfb = 0; sfb < rc.max_sfb; sfb++) {
+          const int band = 16 * g + sfb, at = 128 * win + swb[sfb], width = swb[sfb + 1] - swb[sfb];
+          if (pass == 0) {
+            if (s->ms_used[band])
+              for (int k = at; k < at + width; k++) {
+                const int32_t a = l[k], b = r[k];
+                l[k] = fx_add_sat(a, b);
+                r[k] = fx_sub_sat(a, b);
+              }
+          } else if (rc.cb[band] >= XT_INTENSITY_HCB2) {
+            const int32_t scale = xt_intensity_scale(rc.sf[band], rc.cb[band], s->ms_used[band]);
+            for (int k = at; k < at + width; k++) r[k] = xt_intensity_line(l[k], scale, rc.sf[band]);
+          }
+        }
+  }
+}
+
+static inline void xt_pns_host(const xaac_core_tools_side *s, int c, int32_t *spec, xaac_core_tools_state *st) { /* pns_js_thumb.c:114-199 */
+  const xaac_core_tools_channel &ch = s->ch[c];
+  if (!ch.pns_active) return;
+  const int16_t *swb = xt_is_short(ch) ? xt_swb_short[s->sr_index] : xt_swb_long[s->sr_index];
+  for (int g = 0; g < ch.num_groups; g++)
+    for (int w = 0; w < ch.group_len[g]; w++, spec += 128)
+      for (int sfb = 0; sfb < ch.max_sfb; sfb++) {
+        const int band = (g << 4) + sfb;
+        if (!ch.pns_used[band]) continue;
+        const int last = swb[sfb + 1] - swb[sfb] - 1;
+        int32_t *x = spec + swb[sfb];
+        if (s->pns_correlated[band]) {
+          if (c == 0) {
+            st->pns_corr_seed[band] = st->pns_seed;
+            xt_gen_rand_vec(xt_pns_mant(ch.sf[band]), xt_pns_exp(ch.sf[band]), x, last, &st->pns_seed);
+          } else {
+            xt_gen_rand_vec(xt_pns_mant(ch.sf[band]), xt_pns_exp(ch.sf[band]), x, last, &st->pns_corr_seed[band]);
+          }
+        } else {
+          xt_gen_rand_vec(xt_pns_mant(ch.sf[band]), xt_pns_exp(ch.sf[band]), x, last, &st->pns_seed);
+        }
+      }
+}
+
+/* the tools on one element (channel.c:602-692); spec0 / spec1: the channels' lines, each with XT_SLACK words of the
+   caller's on either side; the side info has passed xt_side_check */
+static inline void xt_apply_host(const xaac_core_tools_side *s, xaac_core_tools_state *st, int32_t *spec0, int32_t *spec1) {
+  if (s->n_ch == 2) xt_stereo_host(s, spec0, spec1);
+  for (int c = 0; c < s->n_ch; c++) {
+    int32_t *spec = c ? spec1 : spec0;
+    xt_pns_host(s, c, spec, st);
+    if (s->ch[c].tns_present) xt_tns_host(s, s->ch[c], spec);
+  }
+}
+#endif /* !__HIP_DEVICE_COMPILE__ */
+
+#endif /* XAAC_AAC_TOOLS_H */

@@ -26,6 +26,7 @@
 #include "esbr_core_kernel.h"
 #include "hbe_kernel.h"
 #include "pvc_kernel.h"
+#include "aac_tools_kernel.h"
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -130,7 +131,7 @@ int32_t xaac_set_stream(xaac_ctx *c, void *hip_stream) {
 extern "C" {
 hipError_t xaac_warm_imdct(void), xaac_warm_sbr_qmf(void), xaac_warm_sbr_core(void), xaac_warm_sbr_ps(void), xaac_warm_limiter(void),
     xaac_warm_esbr_qmf(void), xaac_warm_esbr_core(void), xaac_warm_esbr_ps(void), xaac_warm_hbe(void), xaac_warm_usac_imdct(void),
-    xaac_warm_imdct960(void), xaac_warm_imdct_ld(void), xaac_warm_pvc(void), xaac_warm_sbr_ld_core(void);
+    xaac_warm_imdct960(void), xaac_warm_imdct_ld(void), xaac_warm_pvc(void), xaac_warm_sbr_ld_core(void), xaac_warm_aac_tools(void);
 }
 
 int32_t xaac_warm_up(xaac_ctx *c) {
@@ -138,7 +139,8 @@ int32_t xaac_warm_up(xaac_ctx *c) {
   if (!hip_ok(hipSetDevice(c->device))) return XAAC_FATAL_HIP;
   hipError_t (*const hooks[])(void) = {xaac_warm_imdct,     xaac_warm_sbr_qmf,   xaac_warm_sbr_core, xaac_warm_sbr_ps,     xaac_warm_limiter,
                                        xaac_warm_esbr_qmf,  xaac_warm_esbr_core, xaac_warm_esbr_ps,  xaac_warm_hbe,        xaac_warm_usac_imdct,
-                                       xaac_warm_imdct960,  xaac_warm_imdct_ld,  xaac_warm_pvc,      xaac_warm_sbr_ld_core};
+                                       xaac_warm_imdct960,  xaac_warm_imdct_ld,  xaac_warm_pvc,      xaac_warm_sbr_ld_core,
+                                       xaac_warm_aac_tools};
   for (auto h : hooks)
     if (!hip_ok(h())) return XAAC_FATAL_HIP;
   return XAAC_OK;
@@ -172,6 +174,28 @@ int32_t xaac_imdct_process_batch(xaac_ctx *c, const xaac_imdct_batch *b) {
   c->last_grid = grid;
   c->last_block = XAAC_IMDCT_BLOCK;
   c->last_lds = XAAC_IMDCT_LDS_BYTES;
+  return XAAC_OK;
+}
+
+int32_t xaac_aac_tools_process_batch(xaac_ctx *c, const xaac_aac_tools_batch *b) {
+  if (!c || !b) return XAAC_FATAL_NULL_ARG;
+  if (b->n < 0) return XAAC_FATAL_BAD_ARG;
+  if (b->n == 0) return XAAC_OK;
+  if (!b->spec || !b->side || !b->state) return XAAC_FATAL_NULL_ARG;
+  /* the rows are moved 16 bytes at a time */
+  if (b->spec_stride < 1024 || (b->spec_stride & 3) || (reinterpret_cast<uintptr_t>(b->spec) & 15)) return XAAC_FATAL_BAD_ARG;
+  XaacAacToolsParams p;
+  p.n = b->n;
+  p.spec_stride = b->spec_stride;
+  p.spec = b->spec;
+  p.side = b->side;
+  p.state = b->state;
+  p.status = b->status;
+  if (!hip_ok(hipSetDevice(c->device))) return XAAC_FATAL_HIP;
+  if (!hip_ok(xaac_launch_aac_tools(&p, c->stream))) return XAAC_FATAL_HIP;
+  c->last_grid = b->n;
+  c->last_block = XAAC_AAC_TOOLS_BLOCK;
+  c->last_lds = xaac_aac_tools_lds_bytes();
   return XAAC_OK;
 }
 

@@ -46,6 +46,36 @@ class SbrSide(ctypes.Structure):
                 ("ps_frame", ctypes.c_uint8 * PS_FRAME_BYTES)]
 
 
+class TnsFilterSide(ctypes.Structure):
+    # struct xaac_tns_filter_side (include/xaac_tools.h)
+    _fields_ = [("start_band", ctypes.c_uint8), ("stop_band", ctypes.c_uint8), ("order", ctypes.c_int8),
+                ("direction", ctypes.c_int8), ("resolution", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3),
+                ("coef", ctypes.c_int8 * 12)]
+
+
+class CoreToolsChannel(ctypes.Structure):
+    # struct xaac_core_tools_channel
+    _fields_ = [("window_sequence", ctypes.c_uint8), ("max_sfb", ctypes.c_uint8), ("num_groups", ctypes.c_uint8),
+                ("pns_active", ctypes.c_uint8), ("tns_present", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3),
+                ("group_len", ctypes.c_uint8 * 8), ("n_filt", ctypes.c_uint8 * 8), ("cb", ctypes.c_uint8 * 128),
+                ("sf", ctypes.c_int16 * 128), ("pns_used", ctypes.c_uint8 * 128), ("tns", TnsFilterSide * 8)]
+
+
+class CoreToolsSide(ctypes.Structure):
+    # struct xaac_core_tools_side: what the M/S, intensity, PNS and TNS tools read of one channel element
+    _fields_ = [("element_id", ctypes.c_uint8), ("n_ch", ctypes.c_uint8), ("common_window", ctypes.c_uint8),
+                ("sr_index", ctypes.c_uint8), ("ms_used", ctypes.c_uint8 * 128), ("pns_correlated", ctypes.c_uint8 * 128),
+                ("ch", CoreToolsChannel * 2)]
+
+
+class CoreToolsState(ctypes.Structure):
+    # struct xaac_core_tools_state: the noise generator of one stream (zero for a new one)
+    _fields_ = [("pns_seed", ctypes.c_int32), ("pns_corr_seed", ctypes.c_int32 * 128)]
+
+
+from . import CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES  # noqa: E402  (tests/test_aac_tools_cpu.py pins them to the header)
+
+
 def host_library_path():
     return os.environ.get("XAAC_HOST_LIBRARY") or os.path.join(_HERE, "libxaac_host.so")
 
@@ -70,6 +100,10 @@ def load_host_library():
             getattr(lib, fn).argtypes = [ctypes.c_void_p]
             getattr(lib, fn).restype = None
         lib.xaac_parser_set_esbr.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        lib.xaac_parse_core_tools_side.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.xaac_parse_core_tools_side.restype = ctypes.c_int32
+        lib.xaac_core_tools_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.xaac_core_tools_apply_host.restype = ctypes.c_int32
         lib.xaac_parse_esbr_side.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
         lib.xaac_hbe_state_reinit.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xaac_hbe_state_reinit_tails.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
@@ -184,7 +218,7 @@ class _ParseBatch(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n_streams", "n_ch", "with_sbr", "ps_enable", "stage", "threads")] + \
                [(n, ctypes.c_void_p) for n in ("parser", "data", "bytes", "spec", "ics", "header", "frame", "ps_frame", "flags",
                                                "tools", "consumed", "status", "esbr_side", "reset_pitch", "pos")] + \
-               [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p)]
+               [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p), ("tools_side", ctypes.c_void_p)]
 
 
 F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(8)
@@ -333,7 +367,8 @@ class BatchParser:
                 self.lib.xaac_parser_destroy(self.parsers[i])
                 self.parsers[i] = None
 
-    def _descriptor(self, spec, ics, hdr, frm, psf, flags, with_sbr, eside=None, status=None, reset_pitch=None, frames=1, lines=None):
+    def _descriptor(self, spec, ics, hdr, frm, psf, flags, with_sbr, eside=None, status=None, reset_pitch=None, frames=1, lines=None,
+                    tools_side=None):
         # data / bytes are the whole streams and stay as they are; the library moves self.pos (xaac_parse_batch::pos), so a
         # call costs this thread the filling of the descriptor and nothing per stream
         b = _ParseBatch()
@@ -348,6 +383,7 @@ class BatchParser:
         b.pos = self.pos.ctypes.data
         b.frames = int(frames)
         b.lines = None if lines is None else lines.ctypes.data
+        b.tools_side = ptr(tools_side)   # uint8[frames, n, CORE_TOOLS_SIDE_BYTES]: the tools' side info of a stage-1 parse
         return b
 
     def _advance(self, ok, status=None):
@@ -364,14 +400,14 @@ class BatchParser:
                 raise ParseError(int(status[i]), int(self.frames[i]))
         return good
 
-    def step(self, spec, ics, hdr=None, frm=None, psf=None, flags=None, eside=None):
+    def step(self, spec, ics, hdr=None, frm=None, psf=None, flags=None, eside=None, tools_side=None):
         """parses the next frame of every stream into the staging arrays; -> bool[n]: which streams delivered a frame
         (the others are at their end: their rows are left as they were)"""
-        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside)
+        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, tools_side=tools_side)
         return self._advance(self.lib.xaac_parse_batch_run_sized(ctypes.byref(b), ctypes.sizeof(b)))
 
     def start_step(self, spec, ics, hdr=None, frm=None, psf=None, flags=None, eside=None, status=None, reset_pitch=None, frames=1,
-                   lines=None):
+                   lines=None, tools_side=None):
         """step() in two halves (xaac_parse_batch_start / _wait): the library's worker team parses while the caller does
         something else; the staging arrays are the team's until wait_step() returns.  status / reset_pitch: the caller's own
         int32[n] arrays for this step's results (a caller that starts the next step before it has looked at this one's).
@@ -379,7 +415,7 @@ class BatchParser:
         a leading dimension T (status / reset_pitch int32[T, n]); finish_step is then called per step t with status[t].
         lines: int32[T, n] out, xaac_parse_batch::lines."""
         self._status_in_flight = status
-        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, status, reset_pitch, frames, lines)
+        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, status, reset_pitch, frames, lines, tools_side)
         rc = self.lib.xaac_parse_batch_start_sized(ctypes.byref(b), ctypes.sizeof(b))
         if rc:
             raise RuntimeError("xaac_parse_batch_start: %d" % rc)
@@ -413,7 +449,7 @@ _ES_QMF_RE, _ES_QMF_IM, _ES_PH_RE, _ES_PH_IM = 1604, 4164, 8479, 8991
 
 
 def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True, timing=None, overlap=True, esbr=False,
-                   _trace=None, frames_per_parse=4):
+                   _trace=None, frames_per_parse=4, gpu_tools=False):
     """Decodes N ADTS streams of the same kind (all AAC-LC stereo, all HE-AAC stereo, or all HE-AAC / HE-AACv2 mono) in
     lock step: per step one frame of every stream is parsed on CPU threads into pinned staging arrays, copied to the GPU
     (spectra + window info, SBR / PS side info: nothing else crosses the bus on the way in), run through the GPU entry
@@ -431,12 +467,15 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     test/decoder/ixheaacd_main.c:2181-2186) instead of -esbr:0.  AAC-LC streams decode
     the same either way.  SBR header changes in the middle of a stream are followed as the reference follows them (the
     reset-time transposer runs, sbrdecoder.c:196-236, read 24 rows of the QMF history of the frame before: kept beside the
-    state)."""
+    state).
+    gpu_tools: the M/S, intensity, PNS and TNS tools run on the GPU (xaac_aac_tools_process_batch in front of the IMDCT) instead of
+    in the parser: the streams are parsed at stage 1, the tools' side rows go up beside the spectra and every stream's noise
+    generator lives on the device.  Off by default; the PCM is the same either way."""
     with _TorchCpuThreads():
-        return _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, esbr, _trace, frames_per_parse)
+        return _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, esbr, _trace, frames_per_parse, gpu_tools)
 
 
-def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, esbr, _trace, frames_per_parse):
+def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, esbr, _trace, frames_per_parse, gpu_tools=False):
     import time
     import torch
     lib = load_host_library()
@@ -444,7 +483,8 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
     own = ctx is None
     if own:   # the context launches on torch's current stream, so that its kernels and torch's copies stay in order
         ctx = XaacContext(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
-    bp = BatchParser(streams, threads=threads, esbr=esbr)
+    gpu_tools = bool(gpu_tools)
+    bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2)
     n, n_ch, sbr, rate = bp.n, bp.n_ch, bp.sbr, bp.core_rate
     esbr = bool(esbr) and sbr
     nc = n * n_ch
@@ -465,7 +505,11 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
     ovl, ovl_state = dz(nc, 512, dtype=torch.int32), dz(nc, 2)
     # two sets of device input arrays: step k + 1 is copied up (its own stream) while step k's kernels read theirs
     spec_d2, ics_d2 = [dz(nc, 1024, dtype=torch.int32) for _ in range(2)], [dz(nc, 2) for _ in range(2)]
-    hdr_d2 = frm_d2 = eside_d2 = psf_d2 = flags_d2 = None
+    hdr_d2 = frm_d2 = eside_d2 = psf_d2 = flags_d2 = tside_d2 = tstatus2 = tstatus_h2 = None
+    if gpu_tools:   # the tools' side rows (two device sets like the spectra), the streams' noise generators, the kernel's status words
+        tside_d2 = [dz(n, CORE_TOOLS_SIDE_BYTES) for _ in range(2)]
+        tools_state = dz(n, CORE_TOOLS_STATE_BYTES)
+        tstatus2 = [dz(n, dtype=torch.int32) for _ in range(2)]
     out = [[] for _ in range(n)]
 
     T = max(1, int(frames_per_parse))
@@ -474,6 +518,7 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
         def __init__(self):
             self.spec, self.ics = pinned(T, nc, 1024, dtype=torch.int32), pinned(T, nc, 2)
             self.hdr = self.frm = self.psf = self.flags = self.eside = self.flags_pin = None
+            self.tside = pinned(T, n, CORE_TOOLS_SIDE_BYTES) if gpu_tools else None
             if esbr:
                 self.eside = pinned(T, nc, ESBR_SIDE_BYTES)
             if sbr:
@@ -492,7 +537,7 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
             if self.sent_once:
                 self.sent[T - 1].synchronize()   # (the set's last copies up: long over when its turn comes again)
             bp.start_step(self.spec, self.ics, self.hdr, self.frm, self.psf, self.flags, self.eside, status=self.status,
-                          reset_pitch=self.reset_pitch, frames=T, lines=self.lines)
+                          reset_pitch=self.reset_pitch, frames=T, lines=self.lines, tools_side=self.tside)
             return self
 
         def end(self):      # back from the team; the results are looked at in finish(), once the next set is on its way
@@ -511,6 +556,7 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
             v.flags, v.flags_pin, v.reset_pitch, v.got, v.sent, v.owner = (pick(self.flags), pick(self.flags_pin),
                                                                          self.reset_pitch[t], self.got[t], self.sent[t], self)
             v.lines = self.lines[t]
+            v.tside = pick(self.tside)
             return v
 
     class _Step:
@@ -568,6 +614,8 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
             psf_d2 = [dz(n, PS_FRAME_BYTES) for _ in range(2)]
             ws = dz(ctx.sbr_hq_workspace_bytes(n, True))
             pcm_mono = dz(n * 2048, dtype=torch.int16)
+    if gpu_tools:
+        tstatus_h2 = [pinned(n, dtype=torch.int32) for _ in range(2)]
     first = True
     cur_set, t_in_set, pending = None, 0, None
     if overlap:
@@ -600,6 +648,8 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
         # what they say about those is not looked at)
         if status_h2 is not None and int(status_h2[slot_].numpy().reshape(n, -1)[got_].min(initial=0)) < 0:
             raise RuntimeError("the SBR kernels refused a frame")
+        if tstatus_h2 is not None and int(tstatus_h2[slot_].numpy()[got_].min(initial=0)) < 0:
+            raise RuntimeError("the AAC tools kernel refused a frame")
         if keep_pcm and not drop_:
             block = pcm_h2[slot_].numpy().reshape(shape_)
             for i in np.nonzero(got_)[0]:
@@ -614,6 +664,8 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
             pcm_h2[slot_].copy_(pcm2[slot_], non_blocking=True)
             if status2 is not None:
                 status_h2[slot_].copy_(status2[slot_], non_blocking=True)
+            if tstatus2 is not None:
+                tstatus_h2[slot_].copy_(tstatus2[slot_], non_blocking=True)
             done[slot_].record(down)
         consume()
         waiting = (slot_, got_, shape_, cut_, drop_)
@@ -673,6 +725,8 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
                     if rc != 0:
                         raise RuntimeError("hipMemcpy2DAsync: %d" % rc)
                 ics_d.copy_(ics_h, non_blocking=True)
+                if gpu_tools:
+                    tside_d2[slot].copy_(cur.tside, non_blocking=True)
                 if sbr:
                     hdr_d.copy_(hdr_h, non_blocking=True)
                     frm_d.copy_(frm_h, non_blocking=True)
@@ -685,6 +739,8 @@ def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, es
                 cur.sent.record(up)
             cur.owner.sent_once = True
             main_stream.wait_event(cur.sent)
+            if gpu_tools:   # stage-1 spectra -> the spectra the IMDCT takes, in place (ended streams' rows run idle, unlooked at)
+                ctx.aac_tools_process_batch(spec_d, tside_d2[slot], tools_state, tstatus2[slot])
             if not sbr:
                 # a stream that ended with the step before: its limiter state as its last frame left it (the rows of ended
                 # streams go on running idle through the kernels; the delay line flushed behind a stream is the one it ended on)

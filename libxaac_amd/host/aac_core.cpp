@@ -5,13 +5,15 @@
  * ixheaacd_longblock.c (sections :62, scale factors :155), ixheaacd_block.c (Huffman + inverse quantisation :129-1130,
  * scale factor gains :1242), ixheaacd_stereo.c (M/S :54, intensity :129), ixheaacd_pns_js_thumb.c (PNS :74-200,
  * TNS :202-514), ixheaacd_aac_tns.c (:147 parcor -> LPC, :371 filter, :422 headroom), ixheaacd_aacpluscheck.c:59 (FIL).
- * Tables: tables_aac.inc (generated from the compiled reference's ROM).
+ * Tables: tables_aac.inc (generated from the compiled reference's ROM).  The arithmetic of the four tools lives in
+ * ../csrc/aac_tools.h, shared with the GPU kernel (aac_tools_kernel.hip); this file hands it the element's side info.
  */
 #include "aac_core.h"
 
 #include <stddef.h>
 #include <string.h>
 
+#include "../csrc/aac_tools.h"
 #include "../csrc/fx.h"
 #include "tables_aac.inc"
 
@@ -527,326 +529,27 @@ int read_channel_stream(const XhCoreState *st, XhBits *br, XhElement *el, int ch
   return read_spectrum(st, br, c);
 }
 
-/* ---- tools ---------------------------------------------------------------------------------------------------------- */
-void ms_stereo(const XhCoreState *st, XhElement *el) { /* stereo.c:54-116 */
+/* ---- tools ----------------------------------------------------------------------------------------------------------
+   The arithmetic is in ../csrc/aac_tools.h, which the GPU kernel compiles too; here: the element's side info for it. */
+/* channel.c:702-725: in a common_window pair with noise substitution the M/S flag of a band marks its noise as correlated,
+   and stops being an M/S flag where both channels substitute noise */
+void derive_pns_correlation(XhElement *el) {
+  if (el->tools_derived) return;
+  el->tools_derived = 1;
+  if (el->n_ch != 2 || !el->common_window || !(el->ch[0].pns_active || el->ch[1].pns_active)) return;
   const XhIcs &ics = el->ch[0].ics;
-  const int8_t *width = el->ch[1].ics.window_sequence == XH_EIGHT_SHORT ? st->width_short : st->width_long;
-  int32_t *l = el->ch[0].spec(), *r = el->ch[1].spec();
   for (int g = 0; g < ics.num_groups; g++)
-    for (int w = 0; w < ics.group_len[g]; w++) {
-      int off = 0;
-      for (int sfb = 0; sfb < ics.max_sfb; sfb++) {
-        if (el->ms_used[g][sfb])
-          for (int k = 0; k < width[sfb]; k++) {
-            const int32_t a = l[off + k], b = r[off + k];
-            l[off + k] = fx_add_sat(a, b);
-            r[off + k] = fx_sub_sat(a, b);
-          }
-        off += width[sfb];
-      }
-      l += 128, r += 128;
-    }
-}
-
-void intensity_stereo(const XhCoreState *st, XhElement *el) { /* stereo.c:129-243 */
-  const XhChannel &rc = el->ch[1];
-  const XhIcs &ics = rc.ics;
-  const int8_t *width = ics.window_sequence == XH_EIGHT_SHORT ? st->width_short : st->width_long;
-  int32_t *l = el->ch[0].spec(), *r = el->ch[1].spec();
-  for (int g = 0; g < ics.num_groups; g++)
-    for (int w = 0; w < ics.group_len[g]; w++) {
-      int off = 0;
-      for (int sfb = 0; sfb < ics.max_sfb; sfb++) {
-        const int cb = rc.cb[16 * g + sfb];
-        if (cb >= XH_INTENSITY_HCB2) {
-          const int sf = rc.sf[16 * g + sfb];
-          int32_t scale = xh_scale_tab[sf & 3];
-          if (!(el->ms_used[g][sfb] ^ (cb & 1))) scale = fx_neg_sat(scale);
-          const int scf_exp = -((sf >> 2) + 2);
-          for (int k = 0; k < width[sfb]; k++) {
-            int32_t t = l[off + k];
-            int sh = fx_norm32(t);
-            t = fx_shl(t, sh);
-            t = (int32_t)(((int64_t)t * (int64_t)scale) >> 16);
-            sh += scf_exp;
-            if (sh < 0) t = fx_shl_sat(t, sh < -31 ? 31 : -sh);
-            else t = fx_shr(t, sh > 31 ? 31 : sh);
-            r[off + k] = t;
-          }
-        }
-        off += width[sfb];
-      }
-      l += 128, r += 128;
-    }
-}
-
-/* the reference's reciprocal square root and square root (basic_funcs.c:155-196) */
-inline int32_t mul32_shl_sat(int32_t a, int32_t b) { /* basic_ops40.h: mult32_shl_sat */
-  if (a == FX_MIN32 && b == FX_MIN32) return FX_MAX32;
-  return fx_mul32_shl(a, b);
-}
-inline int32_t mul32x16_shl_sat(int32_t a, int16_t b) {
-  if (a == FX_MIN32 && b == (int16_t)-32768) return FX_MAX32;
-  return fx_mul32x16_shl(a, b);
-}
-inline int32_t mul32x16h_shl_sat(int32_t a, int32_t b) { /* basic_ops.h:62: the clamp looks at all of b */
-  if (a == FX_MIN32 && b == -32768) return FX_MAX32;
-  return fx_mul32x16_shl(a, (int16_t)(b >> 16));
-}
-
-int32_t one_by_sqrt(int32_t op) {
-  int32_t a = fx_add_sat((int32_t)0x900ebee0, mul32x16_shl_sat(op, 0x39d9));
-  int32_t iy = fx_add_sat(0x573b645a, mul32x16h_shl_sat(op, a));
-  iy = fx_shl_dir_sat_limit(iy, 1);
-  for (int it = 0; it < 3; it++) {
-    a = mul32_shl_sat(op, iy);
-    a = fx_sub_sat(0x40000000, fx_shl_dir_sat_limit(mul32_shl_sat(a, iy), 1));
-    iy = fx_add_sat(iy, mul32_shl_sat(a, iy));
-  }
-  return iy;
-}
-
-int32_t fx_sqrt(int32_t op) {
-  if (op == 0) return 0;
-  int shift = fx_norm32(op) & ~1;
-  op = fx_shl_dir_sat_limit(op, shift);
-  shift = fx_shl_dir_sat_limit(shift, -1);
-  op = mul32_shl_sat(one_by_sqrt(op), op);
-  return fx_shl_dir_sat_limit(op, -(int)fx_sat16(shift - 1));
-}
-
-int32_t div32_pos_normb(int32_t a, int32_t b) { /* basic_ops.h:74-98: a / b in Q31 by 32 compare-subtract-shift steps */
-  if (a == b) return FX_MAX32;
-  uint32_t nr = (uint32_t)a, q = 0;
-  const uint32_t dr = (uint32_t)b;
-  for (int i = 0; i < 32; i++) {
-    q <<= 1;
-    if (nr >= dr) {
-      nr -= dr;
-      q += 1;
-    }
-    nr <<= 1;
-  }
-  return (int32_t)q;
-}
-
-void gen_rand_vec(int32_t scale, int shift, int32_t *x, int last, int32_t *seed) { /* pns_js_thumb.c:74-112 */
-  int32_t nrg = 0;
-  for (int i = 0; i <= last; i++) {
-    *seed = (int32_t)((int64_t)1664525 * (int64_t)*seed + (int64_t)1013904223);
-    x[i] = *seed >> 3;
-    nrg = fx_add_sat(nrg, mul32_shl_sat(x[i], x[i]));
-  }
-  int nrg_scale = fx_norm32(nrg);
-  if (nrg_scale > 0) {
-    nrg_scale &= ~1;
-    nrg = fx_shl_sat(nrg, nrg_scale);
-    shift -= nrg_scale >> 1;
-  }
-  nrg = fx_sqrt(nrg);
-  scale = div32_pos_normb(scale, nrg);
-  if (shift < -31) shift = -31;
-  for (int i = 0; i <= last; i++) x[i] = fx_shl_dir_sat_limit(mul32_shl_sat(x[i], scale), -shift);
-}
-
-void pns(XhCoreState *st, XhElement *el, int ch, int32_t *corr_seed) { /* pns_js_thumb.c:114-199 */
-  XhChannel *c = &el->ch[ch];
-  if (!c->pns_active) return;
-  const XhIcs &ics = c->ics;
-  const int16_t *swb = ics.window_sequence == XH_EIGHT_SHORT ? st->swb_short : st->swb_long;
-  int32_t *spec = c->spec();
-  for (int g = 0; g < ics.num_groups; g++)
-    for (int w = 0; w < ics.group_len[g]; w++, spec += 128)
-      for (int sfb = 0; sfb < ics.max_sfb; sfb++) {
+    for (int sfb = 0; sfb < ics.max_sfb; sfb++)
+      if (el->ms_used[g][sfb]) {
         const int band = (g << 4) + sfb;
-        if (!c->pns_used[band]) continue;
-        const int last = swb[sfb + 1] - swb[sfb] - 1;
-        const int32_t mant = xh_scale_mant_tab[c->sf[band] & 3];
-        const int exp = 31 - (c->sf[band] >> 2) - 4; /* PNS_SCALE_MANT_TAB_SCALING -4 */
-        int32_t *x = spec + swb[sfb];
-        if (el->pns_correlated[band]) {
-          if (ch == 0) {
-            corr_seed[band] = st->pns_seed;
-            gen_rand_vec(mant, exp, x, last, &st->pns_seed);
-          } else {
-            gen_rand_vec(mant, exp, x, last, &corr_seed[band]);
-          }
-        } else {
-          gen_rand_vec(mant, exp, x, last, &st->pns_seed);
-        }
+        el->pns_correlated[band] = 1;
+        if (el->ch[0].pns_used[band] && el->ch[1].pns_used[band]) el->ms_used[g][sfb] ^= 1;
       }
 }
 
-/* TNS, the 16-bit variant every stream of at most two channels takes (pns_js_thumb.c:248-514) */
-void parcor_to_lpc(const int16_t *parcor, int16_t *lpc, int16_t *scale, int order) { /* aac_tns.c:147-202 */
-  int status = 1;
-  *scale = 0;
-  while (status) {
-    status = 0;
-    int16_t t1[32 + 1] = {0}, t2[32 + 1] = {0};
-    int32_t accu1 = 0x7fffffff >> *scale;
-    for (int i = 0; i <= order; i++) {
-      const int32_t accu = accu1;
-      for (int j = 0; j < order; j++) {
-        t2[j] = fx_round16(accu1);
-        const int32_t prod = ((int32_t)parcor[j] * t1[j] == 0x40000000) ? FX_MAX32 : fx_shlw((int32_t)parcor[j] * t1[j], 1);
-        accu1 = fx_add_sat(accu1, prod);
-        if (fx_abs_sat(accu1) == 0x7fffffff) status = 1;
-      }
-      for (int j = order - 1; j >= 0; j--) {
-        int32_t accu2 = fx_shlw((int32_t)t1[j], 16);
-        const int32_t prod = ((int32_t)parcor[j] * t2[j] == 0x40000000) ? FX_MAX32 : fx_shlw((int32_t)parcor[j] * t2[j], 1);
-        accu2 = fx_add_sat(accu2, prod);
-        t1[j + 1] = fx_round16(accu2);
-        if (fx_abs_sat(accu2) == 0x7fffffff) status = 1;
-      }
-      t1[0] = fx_round16(accu);
-      lpc[i] = fx_round16(accu1);
-      accu1 = 0;
-    }
-    if (status) *scale = (int16_t)(*scale + 1);
-  }
-}
-
-/* One output of the all-pole filter: acc = sum over j = m .. 1 of mul32x16(s[i - j], lpc[j]), added up with saturation in
-   that order (aac_tns.c:371-420).  If the magnitudes of the products add up to less than 2^31 no partial sum can leave
-   the 32-bit range, the saturating chain is the plain sum and the order does not matter.  With L = sum |lpc[j]| and
-   every state so far at most `quiet` = (2^31 - 1 - order) * 2^16 / L in magnitude that holds for sure
-   (|floor(s * l / 2^16)| <= |s| |l| / 2^16 + 1): the case for every stream with the headroom the reference's scaling
-   leaves (four bits), and it turns a chain of `order` dependent clamped adds per line into independent multiply-adds.
-   From the first state beyond `quiet` on the chain is run as written. */
-inline int32_t tns_acc_chain(const int32_t *h, const int16_t *lpc, int m) {
-  int32_t acc = 0;
-  for (int j = m; j > 0; j--) acc = fx_add_sat(acc, fx_mul32x16(h[-j], lpc[j]));
-  return acc;
-}
-template <int M>
-inline int32_t tns_acc_plain(const int32_t *h, const int16_t *lpc, int m_runtime) {
-  const int m = M ? M : m_runtime;
-  int64_t sum = 0;
-  for (int j = 1; j <= m; j++) sum += ((int64_t)h[-j] * lpc[j]) >> 16; /* = fx_mul32x16, exactly */
-  return (int32_t)sum;
-}
-inline uint32_t tns_mag(int32_t v) { return v < 0 ? 0u - (uint32_t)v : (uint32_t)v; }
-
-/* lines from .. n-1; returns the first line it did not do (n, or where a state left the quiet range) */
-template <int M>
-inline int tns_ar_run(int32_t *x, int from, int n, int inc, const int16_t *lpc, int order, int shift_value, int scale_spec,
-                      int32_t *hist, uint32_t quiet, uint32_t *loudest) {
-  x += (ptrdiff_t)from * inc;
-  uint32_t top = *loudest;
-  int i = from;
-  for (; i < n && top <= quiet; i++) {
-    const int32_t y0 = fx_shl_sat(*x, scale_spec);
-    const int32_t acc = tns_acc_plain<M>(hist + i, lpc, i < order ? i : order);
-    /* y = sub_sat(y0, shl_sat(acc, 1)), state = shl_sat(y, shift_value): line i + 1 waits for this state, so the three
-       clamps are first assumed idle (plain 64-bit arithmetic, checked beside the chain) and only redone if one was not */
-    const int64_t t64 = 2 * (int64_t)acc, y64 = (int64_t)y0 - t64, s64 = (int64_t)((uint64_t)y64 << shift_value);
-    int32_t y = (int32_t)y64, s = (int32_t)s64; /* the reference's state[0]: state[j] of step i is hist[i - 1 - j] */
-    if (__builtin_expect(t64 != (int32_t)t64 || y64 != (int32_t)y64 || s64 != (int32_t)s64, 0)) {
-      y = fx_sub_sat(y0, fx_shl_sat(acc, 1));
-      s = fx_shl_sat(y, shift_value);
-    }
-    hist[i] = s;
-    const uint32_t a = tns_mag(s);
-    top = a > top ? a : top;
-    *x = y >> scale_spec;
-    x += inc;
-  }
-  *loudest = top;
-  return i;
-}
-
-void tns_ar_filter(int32_t *x, int size, int inc, int16_t *lpc, int order, int shift_value, int scale_spec) {
-  /* aac_tns.c:371-420: the order is rounded up to a multiple of four with zero coefficients, and the first `order`
-     lines are filtered whether the region has that many or not */
-  int32_t hist[1024 + 64];
-  if (order & 3) {
-    int i;
-    for (i = order + 1; i < (order & ~3) + 4; i++) lpc[i] = 0;
-    if (i < 32) {
-      lpc[i] = 0;
-      order = (order & ~3) + 4;
-    } else {
-      order = 31;
-    }
-  }
-  const int n = size > order ? size : order;
-  int64_t l1 = 0;
-  for (int j = 1; j <= order; j++) l1 += lpc[j] < 0 ? -(int64_t)lpc[j] : lpc[j];
-  const int64_t q = l1 ? (((int64_t)FX_MAX32 - order) << 16) / l1 : (int64_t)0xffffffff;
-  const uint32_t quiet = q > (int64_t)0xffffffff ? 0xffffffffu : (uint32_t)q;
-  uint32_t loudest = 0;
-  const int lead = order < n ? order : n;
-  int i = tns_ar_run<0>(x, 0, lead, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); /* fewer than `order` states yet */
-  if (i == lead) {
-    switch (order) {
-      case 4: i = tns_ar_run<4>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
-      case 8: i = tns_ar_run<8>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
-      case 12: i = tns_ar_run<12>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
-      default: i = tns_ar_run<0>(x, lead, n, inc, lpc, order, shift_value, scale_spec, hist, quiet, &loudest); break;
-    }
-  }
-  x += (ptrdiff_t)i * inc;
-  for (; i < n; i++) { /* a state beyond the quiet range: the chain as the reference runs it */
-    int32_t y = fx_shl_sat(*x, scale_spec);
-    const int32_t acc = tns_acc_chain(hist + i, lpc, i < order ? i : order);
-    y = fx_sub_sat(y, fx_shl_sat(acc, 1));
-    hist[i] = fx_shl_sat(y, shift_value);
-    *x = y >> scale_spec;
-    x += inc;
-  }
-}
-
-void tns(const XhCoreState *st, XhChannel *c) {
-  const XhIcs &ics = c->ics;
-  const bool is_short = ics.window_sequence == XH_EIGHT_SHORT;
-  const int max_bands = xh_tns_max_bands[2 * st->sr_index + (is_short ? 1 : 0)];
-  const int16_t *swb = is_short ? st->swb_short : st->swb_long;
-  int32_t *spec = c->spec();
-  for (int win = 0; win < (is_short ? 8 : 1); win++)
-    for (int f = 0; f < c->tns.n_filt[win]; f++) {
-      const XhTnsFilter &flt = c->tns.f[win][f];
-      if (flt.order <= 0) continue;
-      int16_t parcor[32 + 1], lpc[32 + 4 + 1];
-      const int16_t *tab = flt.resolution ? xh_tns_coef4 : xh_tns_coef3;
-      for (int i = 0; i < flt.order; i++) parcor[i] = tab[flt.coef[i] + (flt.resolution ? 8 : 4)];
-      int lo = flt.start_band < max_bands ? flt.start_band : max_bands;
-      if (lo > ics.max_sfb) lo = ics.max_sfb;
-      int hi = flt.stop_band < max_bands ? flt.stop_band : max_bands;
-      if (hi > ics.max_sfb) hi = ics.max_sfb;
-      const int start = swb[lo], stop = swb[hi], size = stop - start;
-      if (size <= 0) continue;
-      int16_t scale_lpc;
-      parcor_to_lpc(parcor, lpc, &scale_lpc, flt.order);
-      int32_t *region = spec + (win << 7) + start;
-      int32_t m = 0;
-      for (int i = 0; i < size; i++) m |= fx_abs_nrm(region[i]);
-      int scale_spec = fx_norm32(m);
-      int position;
-      if (flt.direction == -1) {
-        position = stop - 1;
-        if ((win << 7) + position < flt.order) continue;
-      } else {
-        position = start;
-        if ((win << 7) + position + flt.order > 1024) continue;
-      }
-      scale_spec = scale_spec - 4 - scale_lpc;
-      int32_t *at = spec + (win << 7) + position;
-      if (scale_spec > 0) {
-        if (scale_spec > 31) scale_spec = 31;
-        tns_ar_filter(at, size, flt.direction, lpc, flt.order, scale_lpc, scale_spec);
-      } else {
-        /* not enough headroom: lines down, filter, lines up again.  The reference takes the lines it shifts down
-           from window 0 whatever the window is (`win >> 7`, pns_js_thumb.c:455) and shifts the filtered window up */
-        int32_t *down = spec + start;
-        scale_spec = -scale_spec;
-        if (scale_spec > 31) scale_spec = 31;
-        for (int i = 0; i < size; i++) down[i] >>= scale_spec;
-        tns_ar_filter(at, size, flt.direction, lpc, flt.order, scale_lpc, 0);
-        for (int i = 0; i < size; i++) region[i] = fx_shlw(region[i], scale_spec);
-      }
-    }
+/* the all-pole filter of the TNS tool under the name it had here (tests/fuzz/tns_filter_check.cpp pins it to the plain chain) */
+inline void tns_ar_filter(int32_t *x, int size, int inc, int16_t *lpc, int order, int shift_value, int scale_spec) {
+  xt_tns_ar_filter(x, size, inc, lpc, order, shift_value, scale_spec);
 }
 
 int skip_pce(XhBits *br) { /* program_config_element: read over it (ISO/IEC 14496-3 4.4.1.1) */
@@ -866,6 +569,52 @@ int skip_pce(XhBits *br) { /* program_config_element: read over it (ISO/IEC 1449
 }
 
 }  // namespace
+
+void xh_export_tools_side(const XhCoreState *st, XhElement *el, xaac_core_tools_side *side) {
+  derive_pns_correlation(el);
+  side->element_id = (uint8_t)el->id;
+  side->n_ch = (uint8_t)el->n_ch;
+  side->common_window = (uint8_t)el->common_window;
+  side->sr_index = (uint8_t)st->sr_index;
+  for (int c = 0; c < el->n_ch; c++) {
+    const XhChannel &ch = el->ch[c];
+    xaac_core_tools_channel &o = side->ch[c];
+    const bool is_short = ch.ics.window_sequence == XH_EIGHT_SHORT;
+    o.window_sequence = (uint8_t)ch.ics.window_sequence;
+    o.max_sfb = (uint8_t)ch.ics.max_sfb;
+    o.num_groups = (uint8_t)ch.ics.num_groups;
+    o.pns_active = (uint8_t)ch.pns_active;
+    o.tns_present = (uint8_t)ch.tns.present;
+    memcpy(o.group_len, ch.ics.group_len, 8);
+    for (int g = 0; g < ch.ics.num_groups; g++) {
+      const int at = 16 * g, n = ch.ics.max_sfb;
+      memcpy(o.cb + at, ch.cb + at, (size_t)n);
+      memcpy(o.sf + at, ch.sf + at, (size_t)n * sizeof(int16_t));
+      memcpy(o.pns_used + at, ch.pns_used + at, (size_t)n);
+      /* (for the bands of either channel: a pair without common_window has no flags -- they are cleared per element --
+         and its channels may differ in max_sfb and grouping) */
+      memcpy(side->ms_used + at, el->ms_used[g], (size_t)n);
+      memcpy(side->pns_correlated + at, el->pns_correlated + at, (size_t)n);
+    }
+    for (int w = 0; w < 8; w++) o.n_filt[w] = 0;
+    if (ch.tns.present)
+      for (int w = 0; w < (is_short ? 8 : 1); w++) {
+        const int n_filt = ch.tns.n_filt[w];
+        o.n_filt[w] = (uint8_t)n_filt;
+        for (int f = 0; f < n_filt && f < (is_short ? 1 : 3); f++) {
+          const XhTnsFilter &flt = ch.tns.f[w][f];
+          xaac_tns_filter_side &d = o.tns[is_short ? w : f];
+          d.start_band = (uint8_t)flt.start_band;
+          d.stop_band = (uint8_t)flt.stop_band;
+          d.order = (int8_t)flt.order;
+          d.direction = (int8_t)(flt.order > 0 ? flt.direction : 1);
+          d.resolution = (uint8_t)(flt.order > 0 ? flt.resolution : 0);
+          d.reserved[0] = d.reserved[1] = d.reserved[2] = 0;
+          for (int i = 0; i < XAAC_TOOLS_TNS_MAX_ORDER; i++) d.coef[i] = i < flt.order ? flt.coef[i] : 0;
+        }
+      }
+  }
+}
 
 int32_t xh_inverse_quant(int32_t magnitude, int *err) { return pow43(magnitude, err); }
 
@@ -913,6 +662,7 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stag
         el->n_ch = id == XH_ID_CPE ? 2 : 1;
         el->tag = (int)br->get(4);
         el->common_window = 0;
+        el->tools_derived = 0;
         memset(el->ms_used, 0, sizeof(el->ms_used));
         memset(el->pns_correlated, 0, sizeof(el->pns_correlated));
         for (int c = 0; c < el->n_ch; c++) {
@@ -940,25 +690,11 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stag
           if (e) return e;
         }
         if (stage >= 2) { /* channel.c:602-692 */
-          if (el->n_ch == 2) {
-            if (el->common_window) {
-              if (el->ch[0].pns_active || el->ch[1].pns_active) { /* channel.c:702-725 */
-                const XhIcs &ics = el->ch[0].ics;
-                for (int g = 0; g < ics.num_groups; g++)
-                  for (int sfb = 0; sfb < ics.max_sfb; sfb++)
-                    if (el->ms_used[g][sfb]) {
-                      const int band = (g << 4) + sfb;
-                      el->pns_correlated[band] = 1;
-                      if (el->ch[0].pns_used[band] && el->ch[1].pns_used[band]) el->ms_used[g][sfb] ^= 1;
-                    }
-              }
-              ms_stereo(st, el);
-            }
-            intensity_stereo(st, el);
-          }
-          for (int c = 0; c < el->n_ch; c++) {
-            pns(st, el, c, st->pns_corr_seed);
-            if (el->ch[c].tns.present) tns(st, &el->ch[c]);
+          static thread_local xaac_core_tools_side side; /* only the bands below max_sfb are written and read */
+          /* (a single channel without noise substitution and TNS has no tool to run: most frames of a mono stream) */
+          if (el->n_ch == 2 || el->ch[0].pns_active || el->ch[0].tns.present) {
+            xh_export_tools_side(st, el, &side);
+            xt_apply_host(&side, &st->tools, el->ch[0].spec(), el->ch[1].spec());
           }
         }
         break;

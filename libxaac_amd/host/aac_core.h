@@ -12,6 +12,7 @@
 
 #include <stdint.h>
 
+#include "../../include/xaac_tools.h"
 #include "bits.h"
 
 enum { XH_ONLY_LONG = 0, XH_LONG_START = 1, XH_EIGHT_SHORT = 2, XH_LONG_STOP = 3 };
@@ -72,11 +73,13 @@ struct XhCoreState {
   int16_t swb_long[52], swb_short[16];
   const int8_t *width_long, *width_short;
   int num_swb_long, num_swb_short;
-  int32_t pns_seed;        /* pstr_pns_rand_vec_data->current_seed: starts at 0, runs on from frame to frame */
-  int32_t pns_corr_seed[8 * 16]; /* pstr_pns_corr_info->random_vector: the left channel's seed of a band whose noise the M/S
-                                    flag correlates; a right channel that substitutes noise in such a band where the left one
-                                    does not finds the value an earlier frame left (the reference keeps it in scratch memory
-                                    that AAC-LC decoding does not reuse in between) */
+  xaac_core_tools_state tools; /* the noise generator: pns_seed = pstr_pns_rand_vec_data->current_seed (starts at 0, runs on
+                                  from frame to frame); pns_corr_seed = pstr_pns_corr_info->random_vector: the left channel's
+                                  seed of a band whose noise the M/S flag correlates; a right channel that substitutes noise
+                                  in such a band where the left one does not finds the value an earlier frame left (the
+                                  reference keeps it in scratch memory that AAC-LC decoding does not reuse in between).
+                                  Only stage-2 parsing advances it: behind a stage-1 parse the tools' caller keeps the state
+                                  (xaac_core_tools_apply_host, or the GPU's xaac_aac_tools_process_batch) */
 };
 
 struct XhElement {
@@ -84,6 +87,7 @@ struct XhElement {
   int n_ch, tag, common_window;
   uint8_t ms_used[8][64];
   uint8_t pns_correlated[8 * 16];
+  int tools_derived;        /* pns_correlated / ms_used have been through channel.c:702-725 */
   XhChannel ch[2];
   /* SBR extension payload of the FIL element behind the channel element (aacpluscheck.c:59): extension type 13 / 14,
      then the payload bytes with the first byte holding the 4 bits that follow the extension type */
@@ -104,5 +108,10 @@ int xh_core_init(XhCoreState *st, int sr_index);
    `stage`: 2 = everything; 1 = stop before the tools (spectra as at the entry of ixheaacd_channel_pair_process).
    Returns 0 or a negative XH_ERR_*. */
 int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stage);
+
+/* What the tools read of the element parsed last, as the boundary struct of include/xaac_tools.h (ms_used and
+   pns_correlated as the tools apply them).  Writes the bands below max_sfb, the filters n_filt counts and the scalar
+   members; a caller that hands the struct out clears it first. */
+void xh_export_tools_side(const XhCoreState *st, XhElement *el, xaac_core_tools_side *side);
 
 #endif /* XAAC_HOST_AAC_CORE_H */

@@ -23,6 +23,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include "../csrc/aac_tools.h"
 #include "aac_core.h"
 #include "sbr_side.h"
 
@@ -44,6 +45,7 @@ struct xaac_parser {
      decoder) for the unprotected layout only. */
   int blocks_left, block_crc;
   size_t frame_left;
+  int frame_ok; /* the last parse_frame delivered an element: p->el is whole (xaac_parse_core_tools_side) */
 };
 
 /* A small persistent team for xaac_parse_batch_run.  Workers wait for the next call on a generation counter: a short spin
@@ -255,7 +257,14 @@ static int32_t tools_of(const XhElement &el) {
 }
 
 /* the frame at data[0 .. n) into p->el */
+static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed);
 static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed) {
+  p->frame_ok = 0;
+  const int32_t r = parse_frame_inner(p, data, n, stage, consumed);
+  p->frame_ok = r == 0;
+  return r;
+}
+static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed) {
   /* the frame's lines live in a buffer of the calling thread until the caller has copied them out (both entry points do,
      before they return): nothing of a stream outlives the frame there */
   static thread_local int32_t lines[2][XH_SPEC_WORDS];
@@ -288,8 +297,7 @@ static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_
     const XhCoreState keep = p->core;
     if (xh_core_init(&p->core, h.sr_index)) return XAAC_PARSE_ERR_HEADER;
     if (p->sr_index >= 0) { /* a change of sampling rate in mid-stream: the noise generator runs on */
-      p->core.pns_seed = keep.pns_seed;
-      memcpy(p->core.pns_corr_seed, keep.pns_corr_seed, sizeof(keep.pns_corr_seed));
+      p->core.tools = keep.tools;
     }
     p->sr_index = h.sr_index;
     p->sampling_rate = h.sampling_rate;
@@ -343,6 +351,26 @@ int32_t xaac_parse_sbr_side(xaac_parser *p, int32_t ps_enable, xaac_sbr_side *si
   xs_frame_done(&p->sbr, &r); /* what the frame's ixheaacd_sbr_dec leaves for the next frame's delta decoding */
   side->apply = r.apply, side->reset = r.reset, side->reset_channels = r.reset_channels, side->upsampling = r.upsampling;
   side->stereo = r.stereo, side->ps = r.ps, side->ps_start = r.ps_start, side->frame_ok = r.frame_ok;
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side) {
+  if (!p || !side || p->sr_index < 0 || p->el.n_ch < 1 || !p->frame_ok) return XAAC_PARSE_ERR_SYNTAX;
+  memset(side, 0, sizeof(*side));
+  xh_export_tools_side(&p->core, &p->el, side);
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_tools_state *state, int32_t *spec) {
+  if (!side || !state || !spec) return XAAC_PARSE_ERR_SYNTAX;
+  if (xt_side_check(side, 0, 1)) return XAAC_TOOLS_REFUSED;
+  static thread_local int32_t lines[2][1024 + 2 * XT_SLACK];
+  for (int c = 0; c < side->n_ch; c++) {
+    memset(lines[c], 0, sizeof(lines[c]));
+    memcpy(lines[c] + XT_SLACK, spec + 1024 * c, 1024 * sizeof(int32_t));
+  }
+  xt_apply_host(side, state, lines[0] + XT_SLACK, lines[1] + XT_SLACK);
+  for (int c = 0; c < side->n_ch; c++) memcpy(spec + 1024 * c, lines[c] + XT_SLACK, 1024 * sizeof(int32_t));
   return XAAC_PARSE_OK;
 }
 
@@ -434,7 +462,22 @@ int32_t parse_one(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok)
       }
       top = blk > top ? blk : top;
     }
+    if (b->tools_side) { /* noise and intensity bands are zero until the tools have run; a TNS filter runs its order (rounded up
+                            to four) lines even where that leaves the region */
+      for (int c = 0; c < n_ch; c++) {
+        const XhIcs &ics = p->el.ch[c].ics;
+        const bool is_short = ics.window_sequence == XH_EIGHT_SHORT;
+        const int reach = (is_short ? 7 * 128 + p->core.swb_short[ics.max_sfb] : p->core.swb_long[ics.max_sfb]) + XT_SLACK;
+        const int blk = reach >= 1024 ? 64 : (reach + 15) / 16;
+        top = blk > top ? blk : top;
+      }
+    }
     b->lines[S + i] = 16 * top;
+  }
+  if (b->tools_side) {
+    xaac_core_tools_side *side = b->tools_side + S + i;
+    memset(side, 0, sizeof(*side));
+    xh_export_tools_side(&p->core, &p->el, side);
   }
   if (side && b->reset_pitch && side->reset) b->reset_pitch[S + i] = p->sbr.reset_pitch;
   if (side && b->esbr_side && p->esbr)

@@ -7,7 +7,11 @@
  *
  *   xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:<0|1>] [-copies:<N>] [-verify] [-threads:<T>] [-quiet]
  *   xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-esbr:<0|1>] [-threads:<T>] [-quiet]
- *   ... [-gpus:<G>] [-device:<k>] [-plan]
+ *   ... [-gpus:<G>] [-device:<k>] [-plan] [-gputools:<0|1>]
+ *
+ * -gputools:1 (default 0) runs the M/S, intensity, PNS and TNS tools on the GPU: the streams are parsed up to the entry of
+ * ixheaacd_channel_pair_process (stage 1), the tools' side rows go up beside the spectra and xaac_aac_tools_process_batch runs in
+ * front of the IMDCT.  The output is the same; without the flag nothing of that path is allocated or launched.
  *
  * -gpus:G shards the batch's streams over G devices of this node (k, k + 1, ... from -device:k, default 0): contiguous ranges
  * whose sizes differ by at most one -- libxaac_amd/dist.py: shard_range, the split bench.py --gpus N makes over ranks -- one host
@@ -143,6 +147,7 @@ struct Staging { /* what one step's parse leaves for the GPU */
   xaac_sbr_frame *frame;
   xaac_ps_frame *ps;
   xaac_esbr_side *eside;
+  xaac_core_tools_side *tside; /* -gputools:1: the side info of the M/S, intensity, PNS and TNS tools */
   std::vector<int32_t> flags, status, reset_pitch;
   int delivered;
   int lines; /* leading spectral lines that may be non-zero in a delivered row (xaac_parse_batch::lines, rounded up to 64) */
@@ -175,6 +180,7 @@ struct Job {
   int n_ch, sbr, esbr, out_ch, rate, out_rate, per;
   int hq; /* -esbr_hq:1: the DFT harmonic transposer in the QMF one's place (Path A only) */
   int threads, verify, profile;
+  int gputools; /* -gputools:1: parse at stage 1, the spectral tools run on the GPU in front of the IMDCT */
   bool list_mode;
 };
 /* one device's share of the batch: streams [lo, lo + n) on HIP device `device`, decoded by one host thread */
@@ -195,7 +201,7 @@ void shard_range(int n, int r, int g, int *lo, int *hi) {
 void decode_shard(const Job &J, Shard &S) {
   const int device = S.device, N = S.n, n_ch = J.n_ch, sbr = J.sbr, esbr = J.esbr, out_ch = J.out_ch, rate = J.rate, per = J.per;
   const int threads = J.threads, verify = J.verify, profile = J.profile, hq = J.esbr && J.hq;
-  const bool list_mode = J.list_mode;
+  const bool list_mode = J.list_mode, gputools = J.gputools != 0;
   const int NC = N * n_ch, NCD = NC;
   S.first_frames = N;
   xaac_ctx *ctx = nullptr;
@@ -229,6 +235,15 @@ void decode_shard(const Job &J, Shard &S) {
     d_status2[k] = dev<int32_t>((size_t)NC), h_status2[k] = pinned<int32_t>((size_t)NC, device);
     HIP(hipEventCreateWithFlags(&ev_kernels[k], hipEventDisableTiming));
     HIP(hipEventCreateWithFlags(&ev_down[k], hipEventDisableTiming));
+  }
+  /* -gputools:1: the tools' side rows, the streams' noise generators (zero for a new stream), the kernel's status words */
+  xaac_core_tools_side *d_tside = nullptr;
+  xaac_core_tools_state *d_tstate = nullptr;
+  int32_t *d_tstatus2[2] = {nullptr, nullptr}, *h_tstatus2[2] = {nullptr, nullptr};
+  if (gputools) {
+    d_tside = dev<xaac_core_tools_side>((size_t)N), d_tstate = dev<xaac_core_tools_state>((size_t)N);
+    HIP(hipMemset(d_tstate, 0, (size_t)N * sizeof(xaac_core_tools_state)));
+    for (int k = 0; k < 2; k++) d_tstatus2[k] = dev<int32_t>((size_t)N), h_tstatus2[k] = pinned<int32_t>((size_t)N, device);
   }
   /* AAC-LC */
   int32_t *d_out32 = nullptr;
@@ -352,6 +367,7 @@ void decode_shard(const Job &J, Shard &S) {
     xaac_sbr_frame *frame = sbr ? pinned<xaac_sbr_frame>((size_t)T * NC, device) : nullptr;
     xaac_ps_frame *psf = (sbr && n_ch == 1) ? pinned<xaac_ps_frame>((size_t)T * N, device) : nullptr;
     xaac_esbr_side *eside = esbr ? pinned<xaac_esbr_side>((size_t)T * NC, device) : nullptr;
+    xaac_core_tools_side *tside = gputools ? pinned<xaac_core_tools_side>((size_t)T * N, device) : nullptr;
     grp[g].flags.assign((size_t)T * N * 8, 0), grp[g].status.assign((size_t)T * N, 0), grp[g].reset_pitch.assign((size_t)T * N, 0);
     grp[g].lines.assign((size_t)T * N, 0), grp[g].consumed.assign((size_t)N, 0);
     for (int t = 0; t < T; t++) {
@@ -359,6 +375,7 @@ void decode_shard(const Job &J, Shard &S) {
       s.spec = spec + (size_t)t * NC * 1024, s.ics = ics + (size_t)t * NC * 2;
       s.header = header ? header + (size_t)t * NC : nullptr, s.frame = frame ? frame + (size_t)t * NC : nullptr;
       s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
+      s.tside = tside ? tside + (size_t)t * N : nullptr;
       s.flags.assign((size_t)N * 8, 0), s.status.assign((size_t)N, 0), s.reset_pitch.assign((size_t)N, 0);
       s.delivered = 0, s.lines = 1024;
     }
@@ -375,12 +392,12 @@ void decode_shard(const Job &J, Shard &S) {
       if (broken[(size_t)i]) left[(size_t)i] = 0;
     xaac_parse_batch b;
     memset(&b, 0, sizeof(b));
-    b.n_streams = N, b.n_ch = n_ch, b.with_sbr = sbr, b.ps_enable = 1, b.stage = 2, b.threads = threads;
+    b.n_streams = N, b.n_ch = n_ch, b.with_sbr = sbr, b.ps_enable = 1, b.stage = gputools ? 1 : 2, b.threads = threads;
     b.parser = parser.data(), b.data = ptr.data(), b.bytes = left.data(), b.pos = pos.data(), b.frames = T;
     Staging &s0 = st[g * T];
     b.spec = s0.spec, b.ics = s0.ics, b.header = s0.header, b.frame = s0.frame, b.ps_frame = s0.ps;
     b.flags = G.flags.data(), b.consumed = G.consumed.data(), b.status = G.status.data(), b.esbr_side = s0.eside;
-    b.reset_pitch = G.reset_pitch.data(), b.lines = G.lines.data();
+    b.reset_pitch = G.reset_pitch.data(), b.lines = G.lines.data(), b.tools_side = s0.tside;
     const int ok = xaac_parse_batch_run(&b);
     if (ok < 0) die("xaac_parse_batch_run", ok);
     for (int t = 0; t < T; t++) {
@@ -470,6 +487,15 @@ void decode_shard(const Job &J, Shard &S) {
     int16_t *h_pcm = h_pcm2[pending.slot];
     const int32_t *h_status = h_status2[pending.slot];
     const std::vector<int32_t> &alive = st[pending.which].status; /* 0: the stream delivered a frame in that step */
+    if (gputools) {
+      const int32_t *h_tstatus = h_tstatus2[pending.slot];
+      for (int i = 0; i < N; i++)
+        if (h_tstatus[i] < 0 && alive[(size_t)i] == 0 && !refused[(size_t)i]) { /* as for the SBR kernels' refusals below */
+          if (!list_mode) die("the AAC tools kernel refused a frame", i);
+          fprintf(stderr, "xaacdec_amd: stream %d: the AAC tools kernel refused a frame: the stream ends here\n", S.lo + i);
+          refused[(size_t)i] = 1;
+        }
+    }
     if (sbr) { /* (rows of streams that are over re-run their last staging rows: what the kernels say about those is not looked at) */
       const int rows = (pending.mono_twice || (n_ch == 1 && !esbr)) ? N : NC;
       for (int i = 0; i < rows; i++) {
@@ -534,7 +560,14 @@ void decode_shard(const Job &J, Shard &S) {
       else if (width > 0) HIP(hipMemcpy2DAsync(d_spec, 4096, s.spec, 4096, (size_t)width * 4, (size_t)NC, hipMemcpyHostToDevice, stream));
     }
     HIP(hipMemcpyAsync(d_ics, s.ics, (size_t)NC * 2, hipMemcpyHostToDevice, stream));
+    if (gputools) HIP(hipMemcpyAsync(d_tside, s.tside, (size_t)N * sizeof(xaac_core_tools_side), hipMemcpyHostToDevice, stream));
     lap(0);
+    if (gputools) { /* stage-1 spectra -> the spectra the IMDCT takes, in place (xaac_parse_batch::lines covers what they reach) */
+      xaac_aac_tools_batch tb;
+      memset(&tb, 0, sizeof(tb));
+      tb.n = N, tb.spec_stride = 1024 * n_ch, tb.spec = d_spec, tb.side = d_tside, tb.state = d_tstate, tb.status = d_tstatus2[slot];
+      XA(xaac_aac_tools_process_batch(ctx, &tb));
+    }
     xaac_imdct_batch ib;
     memset(&ib, 0, sizeof(ib));
     ib.n_ch = NCD, ib.ch_fac = n_ch, ib.spec = d_spec, ib.ics = d_ics, ib.overlap = d_overlap, ib.state = d_ovl;
@@ -847,6 +880,7 @@ void decode_shard(const Job &J, Shard &S) {
     if (mono_twice) HIP(hipMemcpyAsync(h_pcm2[slot], d_mono, (size_t)N * 2048 * 2, hipMemcpyDeviceToHost, down));
     else HIP(hipMemcpyAsync(h_pcm2[slot], d_pcm, (size_t)N * per * out_ch * 2, hipMemcpyDeviceToHost, down));
     if (sbr) HIP(hipMemcpyAsync(h_status2[slot], d_status, (size_t)NC * 4, hipMemcpyDeviceToHost, down));
+    if (gputools) HIP(hipMemcpyAsync(h_tstatus2[slot], d_tstatus2[slot], (size_t)N * 4, hipMemcpyDeviceToHost, down));
     HIP(hipEventRecord(ev_down[slot], down));
     consume(); /* the step before this one: its PCM has been on its way while this step's work was queued */
     pending = {true, mono_twice, first, slot, which, some_mono};
@@ -885,7 +919,7 @@ void decode_shard(const Job &J, Shard &S) {
 
 int main(int argc, char **argv) {
   std::string in, out, ilist, odir;
-  int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0;
+  int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0, gputools = 0;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     if (a.rfind("-ifile:", 0) == 0) in = a.substr(7);
@@ -901,6 +935,8 @@ int main(int argc, char **argv) {
     else if (a == "-quiet") quiet = 1;
     else if (a == "-verify") verify = 1;
     else if (a == "-profile") profile = 1; /* synchronise behind every phase of a step and report the seconds spent in each */
+    else if (a == "-gputools:0") gputools = 0;
+    else if (a == "-gputools:1") gputools = 1;
     else if (a == "-esbr:0") esbr = 0;
     else if (a == "-esbr:1") esbr = 1;
     else if (a == "-esbr_hq:1") hq = 1;
@@ -924,7 +960,7 @@ int main(int argc, char **argv) {
     inputs.push_back(in);
   }
   if (inputs.empty() || (ilist.empty() && out.empty() && !plan) || copies < 1 || gpus < 1 || device0 < 0) {
-    fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-quiet]\n");
+    fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-gputools:0|1] [-quiet]\n");
     return 1;
   }
   std::vector<std::vector<uint8_t>> datas(inputs.size());
@@ -1002,7 +1038,7 @@ int main(int argc, char **argv) {
   J.hdr = hdr;
   J.hq = hq;
   J.n_ch = n_ch, J.sbr = sbr, J.esbr = esbr, J.out_ch = out_ch, J.rate = rate, J.out_rate = out_rate, J.per = per;
-  J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode;
+  J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode, J.gputools = gputools;
   const auto t_run = std::chrono::steady_clock::now();
   if (gpus == 1) {
     decode_shard(J, shards[0]);
