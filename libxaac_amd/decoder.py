@@ -9,20 +9,22 @@ stereo :3639-3660), so the PCM equals the reference's byte for byte (tests/test_
 `parse_stream` is the CPU half alone (used by the CPU tests and the parser-rate measurement); `decode_streams` decodes
 N streams in lock step, one batch of frames per GPU call.  There is no CPU fallback for the GPU half.
 """
+import collections
 import ctypes
 import os
+import time
 
 import numpy as np
 
-from . import (ESBR_PS_STATE_BYTES, ESBR_SIDE_BYTES, ESBR_STATE_BYTES, HBE_STATE_BYTES, LIMITER_STATE_BYTES, PCM_LC, PCM_SBR,
-               PS_FRAME_BYTES, PS_STATE_BYTES, SBR_FRAME_BYTES, SBR_HEADER_BYTES, SBR_STATE_BYTES, LimiterState, XaacContext,
-               peak_limiter_init)
+from . import (ESBR_PS_STATE_BYTES, ESBR_SIDE_BYTES, ESBR_STATE_BYTES, HANDOVER_PS_START, HBE_STATE_BYTES, LIMITER_STATE_BYTES,
+               PCM_LC, PCM_SBR, PS_FRAME_BYTES, PS_STATE_BYTES, SBR_FRAME_BYTES, SBR_HEADER_BYTES, SBR_STATE_BYTES, LimiterState,
+               XaacContext, peak_limiter_init)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _host = None
+torch = None    # imported by the first decode_streams call: the parser half of this module works without it
 
 TOOL_MS, TOOL_INTENSITY, TOOL_PNS, TOOL_TNS, TOOL_PULSE, TOOL_SHORT, TOOL_ESCAPE = 1, 2, 4, 8, 16, 32, 64
-HANDOVER_PS_START = 1
 
 
 class AdtsHeader(ctypes.Structure):
@@ -443,9 +445,512 @@ def _struct_bytes(fn, size):
     return np.frombuffer(raw, np.uint8).copy()
 
 
+_hip = None
+
+
+def _hip_runtime():
+    """the HIP runtime itself, for the one copy torch has no call for: hipMemcpy2DAsync (the leading columns of a matrix)"""
+    global _hip
+    if _hip is None:
+        _hip = ctypes.CDLL("libamdhip64.so")
+        _hip.hipMemcpy2DAsync.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                          ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    return _hip
+
+
+# what the pipeline and the chains see of one step of a staging set: which streams delivered a frame, and that step's rows
+_Step = collections.namedtuple("_Step", "sent got spec ics hdr frm psf eside flags flags_pin tside reset_pitch lines")
+
+
+class _Alloc:
+    """zeroed device tensors (dz) and zeroed pinned host tensors (pinned) of one decode"""
+
+    def __init__(self, dev):
+        self.dev, self.near_gpu = dev, _NearGpu(dev.index or 0)
+
+    def dz(self, *shape, dtype=None):
+        return torch.zeros(*shape, dtype=dtype or torch.uint8, device=self.dev)
+
+    def pinned(self, *shape, dtype=None):
+        with self.near_gpu:    # allocated and first touched on the GPU's NUMA node
+            t = torch.empty(*shape, dtype=dtype or torch.uint8, pin_memory=True)
+            t.numpy().fill(0)  # (numpy: one thread; torch.zeros would wake the whole intra-op pool for it)
+        return t
+
+
+class Staging:
+    """what one parser call leaves for the GPU: pinned host arrays of T steps (one frame of every stream each).  arrays: the
+    side info the chain wants beside the spectra and window info (of "hdr", "frm", "psf", "flags", "eside"); tools: the spectral
+    tools' side rows too"""
+
+    def __init__(self, bp, pinned, T, arrays=(), tools=False):
+        n, nc = bp.n, bp.n * bp.n_ch
+        want = lambda name, *shape: pinned(T, *shape) if name in arrays else None
+        self.bp, self.T = bp, T
+        self.spec, self.ics = pinned(T, nc, 1024, dtype=torch.int32), pinned(T, nc, 2)
+        self.tside = pinned(T, n, CORE_TOOLS_SIDE_BYTES) if tools else None
+        self.hdr, self.frm = want("hdr", nc, SBR_HEADER_BYTES), want("frm", nc, SBR_FRAME_BYTES)
+        self.psf, self.eside = want("psf", n, PS_FRAME_BYTES), want("eside", nc, ESBR_SIDE_BYTES)
+        self.flags = self.flags_pin = None
+        if "flags" in arrays:
+            self.flags = np.zeros((T, n, 8), np.int32)
+            self.flags_pin = pinned(T, n, 8, dtype=torch.int32)   # the rows as they go up for xaac_sbr_state_apply_side_batch
+        self.seconds = 0.0
+        self.sent = [torch.cuda.Event() for _ in range(T)]   # step t's copies up are over (sent[T - 1]: the parser may write the set again)
+        self.sent_once = False
+        self.status, self.reset_pitch = np.zeros((T, n), np.int32), np.zeros((T, n), np.int32)   # this set's own
+        self.lines = np.zeros((T, n), np.int32)   # leading spectral lines that may be non-zero, per step and stream
+        self.steps = None
+
+    def begin(self):    # the library's team parses into this set while the caller queues the steps before on the GPU
+        if self.sent_once:
+            self.sent[self.T - 1].synchronize()   # (the set's last copies up: long over when its turn comes again)
+        self.bp.start_step(self.spec, self.ics, self.hdr, self.frm, self.psf, self.flags, self.eside, status=self.status,
+                           reset_pitch=self.reset_pitch, frames=self.T, lines=self.lines, tools_side=self.tside)
+        return self
+
+    def end(self):      # back from the team; the results are looked at in finish(), once the next set is on its way
+        self.ok, self.seconds = self.bp.wait_step(check=False)
+        return self
+
+    def finish(self):
+        rows = (self.spec, self.ics, self.hdr, self.frm, self.psf, self.eside, self.flags, self.flags_pin, self.tside,
+                self.reset_pitch, self.lines)
+        self.steps = [_Step(self.sent[t], self.bp.finish_step(None, self.status[t]), *(a if a is None else a[t] for a in rows))
+                      for t in range(self.T)]
+        return self
+
+
+class _ToolsStage:
+    """gpu_tools: the M/S, intensity, PNS and TNS tools in front of whichever chain's IMDCT -- the tools' side rows (two device
+    sets like the spectra), the streams' noise generators, the kernel's status words"""
+
+    def __init__(self, ctx, n, dz, pinned):
+        self.ctx = ctx
+        self.side_d2 = [dz(n, CORE_TOOLS_SIDE_BYTES) for _ in range(2)]
+        self.state = dz(n, CORE_TOOLS_STATE_BYTES)
+        self.status2 = [dz(n, dtype=torch.int32) for _ in range(2)]
+        self.status_h2 = [pinned(n, dtype=torch.int32) for _ in range(2)]
+
+    def send_up(self, step, slot):
+        self.side_d2[slot].copy_(step.tside, non_blocking=True)
+
+    def run(self, spec_d, slot):   # stage-1 spectra -> the spectra the IMDCT takes, in place (ended streams' rows run idle, unlooked at)
+        self.ctx.aac_tools_process_batch(spec_d, self.side_d2[slot], self.state, self.status2[slot])
+
+
+class _Chain:
+    """What _Pipeline knows of a decode chain: host_arrays (the side info a staging set must carry for it), pcm2 / pcm_h2 and
+    status2 / status_h2 (two sets on the device and in pinned memory; the status sets or None), out_ch / out_rate, and
+    send_up(step, slot, got) -- inside the `up` stream: the chain's own side info into device set `slot`;
+    run(step, slot, got, first, spec_d, ics_d) -- on the main stream: the chain's kernels -> (PCM block shape, samples to cut
+    from the front of the block, drop the block);
+    finish(out, keep_pcm) -- behind the last step.
+    A chain owns the device-resident state of its streams and every buffer its kernels use: allocate(dz, pinned) makes them."""
+    host_arrays = ()
+    status2 = status_h2 = None
+
+    def __init__(self, ctx, lib, dev, n, n_ch, rate, alloc, trace=None):
+        self.ctx, self.lib, self.dev, self.dz, self.trace = ctx, lib, dev, alloc.dz, trace
+        self.n, self.n_ch, self.nc, self.rate = n, n_ch, n * n_ch, rate
+        self.ovl, self.ovl_state = alloc.dz(self.nc, 512, dtype=torch.int32), alloc.dz(self.nc, 2)   # the IMDCT's overlap halves, window state
+        self.allocate(alloc.dz, alloc.pinned)
+
+    def _states(self, init, size, rows):   # `rows` structs as the host library initialises them, on the device
+        return torch.from_numpy(np.tile(_struct_bytes(init, size), (rows, 1)).copy()).to(self.dev)
+
+    def send_up(self, step, slot, got):
+        pass
+
+    def finish(self, out, keep_pcm):
+        pass
+
+
+class _LcChain(_Chain):
+    """AAC-LC: IMDCT -> WORD32 + qshift_adj -> peak limiter -> round16 (api.c:3662-3692), then the limiter's delay line
+    behind each stream"""
+
+    def allocate(self, dz, pinned):
+        ctx, dev, n, n_ch, rate = self.ctx, self.dev, self.n, self.n_ch, self.rate
+        self.out_ch, self.out_rate = n_ch, rate     # as coded
+        self.out32, self.qadj = dz(n * 1024 * n_ch, dtype=torch.int32), dz(n * n_ch, dtype=torch.int8)
+        lim0, self.delay = peak_limiter_init(n_ch, rate)
+        self.lim = torch.from_numpy(np.tile(np.frombuffer(bytes(lim0), np.uint8), (n, 1)).copy()).to(dev)
+        self.lim_at_end, self.lim_taken = {}, np.zeros(n, bool)
+        self.ws = dz(max(ctx.peak_limiter_workspace_bytes(n), 16))
+        self.pcm2 = [dz(n * 1024 * n_ch, dtype=torch.int16) for _ in range(2)]
+        self.pcm_h2 = [pinned(n * 1024 * n_ch, dtype=torch.int16) for _ in range(2)]
+
+    def run(self, step, slot, got, first, spec_d, ics_d):
+        # a stream that ended with the step before: its limiter state as its last frame left it (the rows of ended
+        # streams go on running idle through the kernels; the delay line flushed behind a stream is the one it ended on)
+        for i in np.nonzero(~got & ~self.lim_taken)[0]:
+            self.lim_at_end[int(i)] = self.lim[int(i)].cpu().numpy()     # (waits for the kernels of the step before)
+            self.lim_taken[i] = True
+        self.ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, out32=self.out32, qshift_adj=self.qadj, ch_fac=self.n_ch)
+        self.ctx.peak_limiter_process_batch(self.out32, self.qadj, self.lim, self.n_ch, self.ws, pcm16=self.pcm2[slot])
+        return (self.n, 1024, self.n_ch), (self.delay if first else 0), False   # the limiter's delay is cut from the first frame
+
+    def finish(self, out, keep_pcm):
+        if not keep_pcm:
+            return
+        # the limiter's delay line holds the last attack_time_samples samples: api.c:2824-2866
+        self.ctx.sync()
+        lim_h, n_ch = self.lim.cpu().numpy(), self.n_ch
+        for i in range(self.n):
+            st = LimiterState.from_buffer_copy((self.lim_at_end[i] if i in self.lim_at_end else lim_h[i]).tobytes())
+            att, idx = st.attack_time_samples, st.delayed_input_index
+            d = np.ctypeslib.as_array(st.delayed_input)[:att * n_ch].reshape(att, n_ch)
+            tail = np.concatenate([d[idx:], d[:idx]]).astype(np.float64)
+            inside = (tail > -2147483649.0) & (tail < 2147483648.0)      # (WORD32) of a float as x86 converts it: what does
+            v = np.where(inside, np.trunc(np.where(inside, tail, 0.0)), -2147483648.0).astype(np.int64)   # not fit is INT_MIN
+            v = np.clip(v + 0x8000, -(1 << 31), (1 << 31) - 1) >> 16   # round16
+            out[i].append(v.astype(np.int16))
+
+
+class _SbrBase(_Chain):
+    """what both SBR chains hold: the core's 16-bit PCM, two device sets of header / frame (and PS frame) rows, status words,
+    stereo PCM at twice the core's rate (PS, or the mono column twice)"""
+
+    def allocate(self, dz, pinned):
+        n, nc = self.n, self.nc
+        self.out_ch, self.out_rate = 2, 2 * self.rate
+        self.host_arrays = ("hdr", "frm", "flags") + (("psf",) if self.n_ch == 1 else ())
+        self.core16 = dz(nc * 1024, dtype=torch.int16)
+        self.hdr_d2, self.frm_d2 = [dz(nc, SBR_HEADER_BYTES) for _ in range(2)], [dz(nc, SBR_FRAME_BYTES) for _ in range(2)]
+        self.psf_d2 = [dz(n, PS_FRAME_BYTES) for _ in range(2)] if self.n_ch == 1 else None
+        self.status2 = [dz(nc, dtype=torch.int32) for _ in range(2)]
+        self.status_h2 = [pinned(nc, dtype=torch.int32) for _ in range(2)]
+        self.pcm2 = [dz(n * 2048 * 2, dtype=torch.int16) for _ in range(2)]
+        self.pcm_h2 = [pinned(n * 2048 * 2, dtype=torch.int16) for _ in range(2)]
+        self.ps_state = None
+
+    def send_up(self, step, slot, got, eside_d=None):
+        self.hdr_d2[slot].copy_(step.hdr, non_blocking=True)
+        self.frm_d2[slot].copy_(step.frm, non_blocking=True)
+        if eside_d is not None:
+            eside_d.copy_(step.eside, non_blocking=True)
+        if self.n_ch == 1 and (step.flags[got, F_PS] != 0).all():   # the PS frames, when every delivered frame has one
+            self.psf_d2[slot].copy_(step.psf, non_blocking=True)
+
+
+class _SbrChain(_SbrBase):
+    """The fixed-point SBR tools (-esbr:0) behind the IMDCT's 16-bit PCM: low power for a channel pair; HQ for mono streams,
+    with parametric stereo where the frames carry it, else the mono column twice"""
+
+    def allocate(self, dz, pinned):
+        _SbrBase.allocate(self, dz, pinned)
+        ctx, lib, n, n_ch = self.ctx, self.lib, self.n, self.n_ch
+        self.state = self._states(lib.xaac_sbr_state_init, SBR_STATE_BYTES, self.nc)
+        self.flags_d2 = [dz(n, 8, dtype=torch.int32) for _ in range(2)]
+        self.side_words = False
+        if n_ch == 2:
+            self.ws = dz(ctx.sbr_lp_workspace_bytes(self.nc))
+        else:
+            self.ps_state = self._states(lib.xaac_ps_state_init, PS_STATE_BYTES, n)
+            self.ws = dz(ctx.sbr_hq_workspace_bytes(n, True))
+            self.pcm_mono = dz(n * 2048, dtype=torch.int16)
+
+    def send_up(self, step, slot, got):
+        _SbrBase.send_up(self, step, slot, got)
+        # frames that reset the SBR decoder or fall back to plain up-sampling change a few words of the resident state: on the
+        # device, from xaac_sbr_state_apply_side_batch's flag rows (streams without a frame: zero rows)
+        flags = step.flags
+        self.side_words = bool((got & ((flags[:, F_RESET] != 0) | (flags[:, F_UPSAMPLING] != 0))).any())
+        if self.side_words:
+            step.flags_pin.numpy()[:] = flags * got[:, None].astype(np.int32)
+            self.flags_d2[slot].copy_(step.flags_pin, non_blocking=True)
+
+    def run(self, step, slot, got, first, spec_d, ics_d):
+        ctx, n, n_ch, flags, state = self.ctx, self.n, self.n_ch, step.flags, self.state
+        hdr_d, frm_d, pcm, status = self.hdr_d2[slot], self.frm_d2[slot], self.pcm2[slot], self.status2[slot]
+        ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, pcm16=self.core16, ch_fac=n_ch, pcm_mode=PCM_SBR)
+        if self.side_words:
+            ctx.sbr_state_apply_side_batch(hdr_d, self.flags_d2[slot], state, n_ch, ps_state=self.ps_state)
+        if n_ch == 2:
+            ctx.sbr_lp_process_batch(self.core16, hdr_d, frm_d, state, pcm, self.ws, status=status, in_ch_fac=2, out_ch_fac=2)
+        else:
+            with_ps = flags[got, F_PS] != 0
+            if with_ps.any() != with_ps.all():
+                raise NotImplementedError("a batch mixing PS and non-PS frames")
+            if with_ps.all():
+                starts = np.nonzero(got & (flags[:, F_PS_START] != 0))[0]
+                if starts.size:
+                    idx = torch.from_numpy(starts.astype(np.int32)).to(self.dev)
+                    ctx.sbr_state_handover(HANDOVER_PS_START, idx, idx, state, self.ps_state)
+                ctx.sbr_hq_process_batch(self.core16, hdr_d, frm_d, state, pcm, self.ws, ps_frame=self.psf_d2[slot],
+                                         ps_state=self.ps_state, status=status)
+            else:
+                ctx.sbr_hq_process_batch(self.core16, hdr_d, frm_d, state, self.pcm_mono, self.ws, status=status)
+                # mono duplicated to stereo (api.c:3639-3660)
+                pcm.view(n, 2048, 2).copy_(self.pcm_mono.view(n, 2048, 1).expand(n, 2048, 2))
+        return (n, 2048, 2), 0, False
+
+
 # float offsets of members of struct xaac_esbr_state (include/xaac_esbr.h; tests/test_parser_esbr.py checks them against the
 # ctypes mirror of the header): qmf_re / qmf_im rows, and the transposer's last rows ph_re / ph_im
 _ES_QMF_RE, _ES_QMF_IM, _ES_PH_RE, _ES_PH_IM = 1604, 4164, 8479, 8991
+
+
+class _EsbrChain(_SbrBase):
+    """Path A (-esbr:1): IMDCT (16-bit core PCM) -> xaac_esbr_core_from_pcm16_batch -> the eSBR chain -> xaac_esbr_pcm16_from_float_batch
+    (saturate / truncate to 16 bit: ixheaacd_samples_sat, decode_main.c:82-107); every state member stays on the device"""
+
+    def allocate(self, dz, pinned):
+        _SbrBase.allocate(self, dz, pinned)
+        ctx, lib, n, n_ch, nc = self.ctx, self.lib, self.n, self.n_ch, self.nc
+        self.host_arrays += ("eside",)
+        self.state = self._states(lib.xaac_esbr_state_init, ESBR_STATE_BYTES, nc)
+        self.hbe = dz(nc, HBE_STATE_BYTES)
+        self.eside_d2 = [dz(nc, ESBR_SIDE_BYTES) for _ in range(2)]
+        self.ws = dz(ctx.esbr_workspace_bytes(nc))
+        self.out_l, self.out_r = dz(nc, 2048, dtype=torch.float32), None
+        self.core = dz(nc, 1024, dtype=torch.float32)
+        if n_ch == 1:
+            self.ps_state = self._states(lib.xaac_esbr_ps_state_init, ESBR_PS_STATE_BYTES, n)
+            self.out_r = dz(n, 2048, dtype=torch.float32)
+            self.plain = (self.out_l, 2048)              # without PS: mono twice (api.c:3639-3660)
+        else:
+            self.plain = (self.out_l[1:], 4096)          # a pair's channels are neighbouring rows
+        self.older = dz(nc, 2, 24 * 64, dtype=torch.float32)   # rows 8..31 of the QMF history as the frame before found them
+        self.hbe_tail = np.zeros((nc, 48), np.uint8)            # the transposers' integers (struct xaac_hbe_state from synth_size on)
+
+    def hbe_hint(self):   # the largest transposer bank of the batch, as the ABI's LDS hint takes it (8, or 0 = any)
+        return 8 if int(self.hbe_tail.view(np.int32)[:, 0].max()) <= 8 else 0
+
+    def send_up(self, step, slot, got):
+        _SbrBase.send_up(self, step, slot, got, self.eside_d2[slot])
+
+    def reset_transposers(self, step, touched):
+        """ixheaacd_sbr_dec_reset for Path A (sbrdecoder.c:175-236) on the streams `touched`: new transposer parameters from the
+        header's band tables (its two delay lines cleared), then two transposer runs over rows 8..39 and 40..71 of the QMF buffer
+        as the frame before left it: rows 8..31 are what that frame found as rows 8..31 of its history (`older`), rows 32..71 are
+        the state's history (the codec bank's num_time_slots is 32 here).  The second run's last eight output rows become the
+        state's ph rows (bands outside the transposer's range keep what they held)."""
+        ctx, dev, n_ch, dz = self.ctx, self.dev, self.n_ch, self.dz
+        k = touched.size * n_ch
+        rows_h = (touched[:, None] * n_ch + np.arange(n_ch)[None, :]).ravel()
+        rows = torch.from_numpy(rows_h).to(dev)
+        hb = self.hbe.index_select(0, rows)
+        tail_off = HBE_STATE_BYTES - 48
+        tails = np.ascontiguousarray(self.hbe_tail[rows_h])            # (one call for all of them: every stream's first
+        heads = np.ascontiguousarray(step.hdr.numpy()[rows_h])         #  frame is a reset frame)
+        bad = self.lib.xaac_hbe_state_reinit_tails(tails.ctypes.data, heads.ctypes.data, len(rows_h))
+        if bad >= 0:
+            raise RuntimeError("the QMF transposer refused the SBR band tables of stream %d" % (rows_h[bad] // n_ch))
+        self.hbe_tail[rows_h] = tails
+        hb[:, tail_off:] = torch.from_numpy(tails).to(dev)
+        hb32 = hb.view(torch.float32)
+        hb32[:, 1088:1088 + 1280 + 640] = 0.0          # synth_buf, analy_buf (behind input_buf[1024 + 64])
+        pitch = torch.from_numpy(np.repeat(step.reset_pitch[touched], n_ch).astype(np.int32)).to(dev)
+        st32 = self.state.view(torch.float32)
+        hist, old = st32.index_select(0, rows), self.older.index_select(0, rows)
+        q_re, q_im = dz(k, 32, 64, dtype=torch.float32), dz(k, 32, 64, dtype=torch.float32)
+        pv_re, pv_im = dz(k, 32, 64, dtype=torch.float32), dz(k, 32, 64, dtype=torch.float32)
+        rst = dz(k, dtype=torch.int32)
+        q_re[:, :24] = old[:, 0].view(k, 24, 64)
+        q_im[:, :24] = old[:, 1].view(k, 24, 64)
+        q_re[:, 24:] = hist[:, _ES_QMF_RE:_ES_QMF_RE + 8 * 64].view(k, 8, 64)
+        q_im[:, 24:] = hist[:, _ES_QMF_IM:_ES_QMF_IM + 8 * 64].view(k, 8, 64)
+        ctx.hbe_apply_batch(q_re, q_im, hb, pv_re, pv_im, status=rst, pitch_in_bins=pitch, max_synth_size=self.hbe_hint())
+        q_re[:] = hist[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 40 * 64].view(k, 32, 64)
+        q_im[:] = hist[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 40 * 64].view(k, 32, 64)
+        pv_re[:, 24:] = hist[:, _ES_PH_RE:_ES_PH_RE + 512].view(k, 8, 64)
+        pv_im[:, 24:] = hist[:, _ES_PH_IM:_ES_PH_IM + 512].view(k, 8, 64)
+        ctx.hbe_apply_batch(q_re, q_im, hb, pv_re, pv_im, status=rst, pitch_in_bins=pitch, max_synth_size=self.hbe_hint())
+        hist[:, _ES_PH_RE:_ES_PH_RE + 512] = pv_re[:, 24:].reshape(k, 512)
+        hist[:, _ES_PH_IM:_ES_PH_IM + 512] = pv_im[:, 24:].reshape(k, 512)
+        st32.index_copy_(0, rows, hist)
+        self.hbe.index_copy_(0, rows, hb)
+
+    def run(self, step, slot, got, first, spec_d, ics_d):
+        ctx, n_ch, flags, state, out_l = self.ctx, self.n_ch, step.flags, self.state, self.out_l
+        hdr_d, frm_d, eside_d = self.hdr_d2[slot], self.frm_d2[slot], self.eside_d2[slot]
+        # (interleaved as the reference holds it: its in-place 32 -> 16 bit conversion of a pair leaves traces of channel
+        # 0 in channel 1, api.c:353-366, which the IMDCT's PCM_SBR hand-off restates for ch_fac 2)
+        ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, pcm16=self.core16, ch_fac=n_ch, pcm_mode=PCM_SBR)
+        touched = np.nonzero(got & (flags[:, F_RESET] != 0))[0]
+        if touched.size:
+            self.reset_transposers(step, touched)
+        st32 = state.view(torch.float32)
+        self.older[:, 0] = st32[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 32 * 64]   # for the reset a later frame may bring
+        self.older[:, 1] = st32[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 32 * 64]
+        ctx.esbr_core_from_pcm16(self.core16, self.core, ch_fac=n_ch)
+        if self.trace is not None:   # debugging: the device states in front of the chain call
+            self.trace(dict(state=state, hbe=self.hbe, ps_state=self.ps_state, core=self.core, side=eside_d, header=hdr_d, frame=frm_d))
+        with_ps = (flags[got, F_PS] != 0) if n_ch == 1 else np.zeros(1, bool)
+        if with_ps.any() != with_ps.all():
+            raise NotImplementedError("a batch mixing PS and non-PS frames")
+        ps = with_ps.all()      # float parametric stereo: the chain writes both channels
+        psf_d, ps_state, out_r = (self.psf_d2[slot], self.ps_state, self.out_r) if ps else (None, None, None)
+        right, stride = (out_r, 2048) if ps else self.plain
+        ctx.esbr_sbr_process_batch(self.core, hdr_d, frm_d, eside_d, state, out_l, self.ws, status=self.status2[slot], ps_frame=psf_d,
+                                   ps_state=ps_state, out_r=out_r, hbe_state=self.hbe, hbe_max_synth_size=self.hbe_hint())
+        ctx.esbr_pcm16_from_float(out_l, right, self.pcm2[slot], stride=stride)
+        return (self.n, 2048, 2), 0, first      # the first frame's output is not written in this mode
+
+
+class _Pipeline:
+    """The lock-step driver behind decode_streams.  Three staging sets go round: the parse of step k + 1 | the copies up and
+    kernels of step k | the copy down of step k - 1.  Copies up have a stream of their own (`up`) into two sets of device
+    input arrays, so step k + 1 goes up while step k's kernels read theirs; the copy down of step k runs on a second stream
+    (`down`) beside the copies up and kernels of step k + 1 (two PCM / status sets), and the host takes a step's PCM one step
+    later.  What runs between the two is the chain's business (_LcChain, _SbrChain or _EsbrChain, picked once in here), with
+    the spectral tools in front of it when gpu_tools says so."""
+
+    def __init__(self, streams, ctx, device, threads, keep_pcm, overlap, esbr, trace, frames_per_parse, gpu_tools):
+        self.dev = dev = torch.device(device)
+        alloc, lib = _Alloc(dev), load_host_library()
+        self.own = ctx is None
+        if self.own:   # the context launches on torch's current stream, so that its kernels and torch's copies stay in order
+            ctx = XaacContext(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
+        self.ctx = ctx
+        self.bp = bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2)
+        self.n, self.nc, self.keep_pcm, self.overlap = bp.n, bp.n * bp.n_ch, keep_pcm, overlap
+        self.T = T = max(1, int(frames_per_parse))
+        kind = _LcChain if not bp.sbr else _EsbrChain if esbr else _SbrChain
+        self.chain = chain = kind(ctx, lib, dev, bp.n, bp.n_ch, bp.core_rate, alloc, trace)
+        self.tools = _ToolsStage(ctx, bp.n, alloc.dz, alloc.pinned) if gpu_tools else None
+        # two sets of device input arrays: step k + 1 is copied up (its own stream) while step k's kernels read theirs
+        self.spec_d2 = [alloc.dz(self.nc, 1024, dtype=torch.int32) for _ in range(2)]
+        self.ics_d2 = [alloc.dz(self.nc, 2) for _ in range(2)]
+        self.lines_held = [0, 0]   # per device input set: the leading spectral lines that may be non-zero there
+        self.sets = [Staging(bp, alloc.pinned, T, chain.host_arrays, bool(gpu_tools)) for _ in range(3 if overlap else 1)]
+        self.main_stream, self.down, self.up = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+        self.done = [torch.cuda.Event(), torch.cuda.Event()]
+        self.computed = [torch.cuda.Event(), torch.cuda.Event()]
+        self.hip = _hip_runtime()
+        self.out = [[] for _ in range(bp.n)]
+        self.waiting = None    # (slot, got, shape, cut, drop) of the step whose PCM is on its way
+        self.t_parse = self.t_gpu = self.t_wait_parse = self.t_wait_down = 0.0
+
+    def consume(self):
+        """the host's half of the step whose PCM is on its way, if there is one: wait, look at the status words, keep the PCM"""
+        if self.waiting is None:
+            return
+        slot, got, shape, cut, drop = self.waiting
+        self.waiting = None
+        t_c = time.perf_counter()
+        self.done[slot].synchronize()
+        self.t_wait_down += time.perf_counter() - t_c
+        # (rows of streams that are over run idle on whatever their staging rows hold -- possibly nothing the kernels accept:
+        # what they say about those is not looked at)
+        chain, tools = self.chain, self.tools
+        if chain.status_h2 is not None and int(chain.status_h2[slot].numpy().reshape(self.n, -1)[got].min(initial=0)) < 0:
+            raise RuntimeError("the SBR kernels refused a frame")
+        if tools is not None and int(tools.status_h2[slot].numpy()[got].min(initial=0)) < 0:
+            raise RuntimeError("the AAC tools kernel refused a frame")
+        if self.keep_pcm and not drop:
+            block = chain.pcm_h2[slot].numpy().reshape(shape)
+            for i in np.nonzero(got)[0]:
+                self.out[i].append(block[i, cut:].copy())
+
+    def hand_down(self, slot, got, shape, cut, drop):
+        chain, tools, down = self.chain, self.tools, self.down
+        ev = self.computed[slot]
+        ev.record(self.main_stream)   # this step's kernels are queued: its input set may be refilled, its PCM may go down
+        with torch.cuda.stream(down):
+            down.wait_event(ev)
+            chain.pcm_h2[slot].copy_(chain.pcm2[slot], non_blocking=True)
+            if chain.status2 is not None:
+                chain.status_h2[slot].copy_(chain.status2[slot], non_blocking=True)
+            if tools is not None:
+                tools.status_h2[slot].copy_(tools.status2[slot], non_blocking=True)
+            self.done[slot].record(down)
+        self.consume()
+        self.waiting = (slot, got, shape, cut, drop)
+        if not self.overlap:   # one staging set: its copies up must be over before the next parse writes it
+            self.consume()
+
+    def send_up(self, cur, slot, got, step_no):
+        """everything this step sends up, on the `up` stream beside the kernels of the step before"""
+        up, spec_d = self.up, self.spec_d2[slot]
+        with torch.cuda.stream(up):
+            if step_no > 2:
+                up.wait_event(self.computed[slot])   # (the kernels that read this input set two steps ago)
+            # the spectra: only the leading lines that are not zero in every delivered row (AAC + SBR streams code the lower
+            # half of the spectrum or less; 16 of the 26 MB a step of 4096 HE-AACv2 streams sends up are spectra), and
+            # what this device set still holds beyond them from two steps ago (the host rows are zero there)
+            lines_now = min(1024, (int(cur.lines[got].max()) + 63) & ~63)
+            width = max(lines_now, self.lines_held[slot])
+            self.lines_held[slot] = lines_now
+            if width >= 1024:
+                spec_d.copy_(cur.spec, non_blocking=True)
+            elif width > 0:
+                rc = self.hip.hipMemcpy2DAsync(spec_d.data_ptr(), 4096, cur.spec.data_ptr(), 4096, 4 * width, self.nc, 1, up.cuda_stream)
+                if rc != 0:
+                    raise RuntimeError("hipMemcpy2DAsync: %d" % rc)
+            self.ics_d2[slot].copy_(cur.ics, non_blocking=True)
+            if self.tools is not None:
+                self.tools.send_up(cur, slot)
+            self.chain.send_up(cur, slot, got)
+            cur.sent.record(up)
+
+    def steps(self):
+        """the step loop: until every stream is over"""
+        T, overlap, sets, chain, tools, main_stream = self.T, self.overlap, self.sets, self.chain, self.tools, self.main_stream
+        cur_set, t_in_set, pending, which, step_no, first = None, 0, None, 0, 0, True
+        if overlap:
+            # (the parse of the next steps runs on the parser library's own threads, xaac_parse_batch_start / _wait: a Python helper
+            # thread would have to win the interpreter lock from this one, which gives it up only for microseconds at a time
+            # while it queues copies and launches -- measured, its parse began when this thread blocked on the result)
+            pending = sets[0].begin()
+        while True:
+            if t_in_set == T or cur_set is None:   # the next parser call's frames
+                t_w = time.perf_counter()
+                if not overlap:
+                    pending = sets[0].begin()
+                cur_set = pending.end()
+                self.t_wait_parse += time.perf_counter() - t_w
+                if overlap:    # the next T steps' frames are parsed while this thread looks at these and queues them on the GPU
+                    which = (which + 1) % 3
+                    pending = sets[which].begin()
+                cur_set.finish()
+                self.t_parse += cur_set.seconds
+                t_in_set = 0
+            cur = cur_set.steps[t_in_set]
+            t_in_set += 1
+            got = cur.got
+            if not got.any():
+                if overlap:
+                    pending.end()   # (every stream is over: that call found nothing to parse)
+                break
+            slot = step_no & 1
+            step_no += 1
+            t0 = time.perf_counter()
+            self.send_up(cur, slot, got, step_no)
+            cur_set.sent_once = True
+            main_stream.wait_event(cur.sent)
+            spec_d = self.spec_d2[slot]
+            if tools is not None:
+                tools.run(spec_d, slot)
+            shape, cut, drop = chain.run(cur, slot, got, first, spec_d, self.ics_d2[slot])
+            self.hand_down(slot, got, shape, cut, drop)
+            self.t_gpu += time.perf_counter() - t0
+            first = False
+
+    def run(self, timing):
+        """-> decode_streams' return value.  However the steps end, the parser team is taken back (a batch it still holds
+        included) and a context of the pipeline's own closed: xaac_destroy frees the host-side handle alone -- the stream is
+        torch's, the buffers are this decode's tensors -- so work still queued behind an error is not disturbed"""
+        bp, chain = self.bp, self.chain
+        try:
+            t_steps = time.perf_counter()
+            self.steps()
+            self.consume()
+            t_steps = time.perf_counter() - t_steps
+            chain.finish(self.out, self.keep_pcm)
+            frames = int(bp.frames.sum())
+        finally:
+            bp.close()
+            if self.own:
+                self.ctx.close()
+        if timing is not None:
+            # parse_s: inside the parser calls; wait_parse_s: what the loop waited for them; gpu_s: the loop's GPU section (enqueue
+            # + wait_down_s, the wait for the previous step's PCM)
+            timing.update(parse_s=self.t_parse, gpu_s=self.t_gpu, steps_s=t_steps, frames=frames, wait_parse_s=self.t_wait_parse,
+                          wait_down_s=self.t_wait_down)
+        return [np.concatenate(o) if o else np.zeros((0, chain.out_ch), np.int16) for o in self.out], chain.out_rate
 
 
 def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True, timing=None, overlap=True, esbr=False,
@@ -471,400 +976,7 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     gpu_tools: the M/S, intensity, PNS and TNS tools run on the GPU (xaac_aac_tools_process_batch in front of the IMDCT) instead of
     in the parser: the streams are parsed at stage 1, the tools' side rows go up beside the spectra and every stream's noise
     generator lives on the device.  Off by default; the PCM is the same either way."""
-    with _TorchCpuThreads():
-        return _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, esbr, _trace, frames_per_parse, gpu_tools)
-
-
-def _decode_streams(streams, ctx, device, threads, keep_pcm, timing, overlap, esbr, _trace, frames_per_parse, gpu_tools=False):
-    import time
+    global torch
     import torch
-    lib = load_host_library()
-    dev = torch.device(device)
-    own = ctx is None
-    if own:   # the context launches on torch's current stream, so that its kernels and torch's copies stay in order
-        ctx = XaacContext(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
-    gpu_tools = bool(gpu_tools)
-    bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2)
-    n, n_ch, sbr, rate = bp.n, bp.n_ch, bp.sbr, bp.core_rate
-    esbr = bool(esbr) and sbr
-    nc = n * n_ch
-    t_parse = t_gpu = t_wait_parse = t_wait_down = 0.0
-
-    def dz(*shape, dtype=torch.uint8):
-        return torch.zeros(*shape, dtype=dtype, device=dev)
-
-    near_gpu = _NearGpu(dev.index or 0)
-
-    def pinned(*shape, dtype=torch.uint8):
-        with near_gpu:         # allocated and first touched on the GPU's NUMA node
-            t = torch.empty(*shape, dtype=dtype, pin_memory=True)
-            t.numpy().fill(0)  # (numpy: one thread; torch.zeros would wake the whole intra-op pool for it)
-        return t
-
-    out_ch = 2 if sbr else n_ch     # SBR streams come out in stereo (PS, or the mono column twice); AAC-LC as coded
-    ovl, ovl_state = dz(nc, 512, dtype=torch.int32), dz(nc, 2)
-    # two sets of device input arrays: step k + 1 is copied up (its own stream) while step k's kernels read theirs
-    spec_d2, ics_d2 = [dz(nc, 1024, dtype=torch.int32) for _ in range(2)], [dz(nc, 2) for _ in range(2)]
-    hdr_d2 = frm_d2 = eside_d2 = psf_d2 = flags_d2 = tside_d2 = tstatus2 = tstatus_h2 = None
-    if gpu_tools:   # the tools' side rows (two device sets like the spectra), the streams' noise generators, the kernel's status words
-        tside_d2 = [dz(n, CORE_TOOLS_SIDE_BYTES) for _ in range(2)]
-        tools_state = dz(n, CORE_TOOLS_STATE_BYTES)
-        tstatus2 = [dz(n, dtype=torch.int32) for _ in range(2)]
-    out = [[] for _ in range(n)]
-
-    T = max(1, int(frames_per_parse))
-
-    class Staging:    # what one parser call leaves for the GPU: pinned host arrays of T steps (one frame of every stream each)
-        def __init__(self):
-            self.spec, self.ics = pinned(T, nc, 1024, dtype=torch.int32), pinned(T, nc, 2)
-            self.hdr = self.frm = self.psf = self.flags = self.eside = self.flags_pin = None
-            self.tside = pinned(T, n, CORE_TOOLS_SIDE_BYTES) if gpu_tools else None
-            if esbr:
-                self.eside = pinned(T, nc, ESBR_SIDE_BYTES)
-            if sbr:
-                self.hdr, self.frm = pinned(T, nc, SBR_HEADER_BYTES), pinned(T, nc, SBR_FRAME_BYTES)
-                self.flags = np.zeros((T, n, 8), np.int32)
-                self.flags_pin = pinned(T, n, 8, dtype=torch.int32)   # the rows as they go up for xaac_sbr_state_apply_side_batch
-                if n_ch == 1:
-                    self.psf = pinned(T, n, PS_FRAME_BYTES)
-            self.got, self.seconds = None, 0.0
-            self.sent = [torch.cuda.Event() for _ in range(T)]   # step t's copies up are over (sent[T - 1]: the parser may write the set again)
-            self.sent_once = False
-            self.status, self.reset_pitch = np.zeros((T, n), np.int32), np.zeros((T, n), np.int32)   # this set's own
-            self.lines = np.zeros((T, n), np.int32)   # leading spectral lines that may be non-zero, per step and stream
-
-        def begin(self):    # the library's team parses into this set while the caller queues the steps before on the GPU
-            if self.sent_once:
-                self.sent[T - 1].synchronize()   # (the set's last copies up: long over when its turn comes again)
-            bp.start_step(self.spec, self.ics, self.hdr, self.frm, self.psf, self.flags, self.eside, status=self.status,
-                          reset_pitch=self.reset_pitch, frames=T, lines=self.lines, tools_side=self.tside)
-            return self
-
-        def end(self):      # back from the team; the results are looked at in finish(), once the next set is on its way
-            self.ok, self.seconds = bp.wait_step(check=False)
-            return self
-
-        def finish(self):
-            self.got = [bp.finish_step(None, self.status[t]) for t in range(T)]
-            return self
-
-        def step(self, t):  # what the loop below sees of step t
-            pick = lambda a: None if a is None else a[t]
-            v = _Step()
-            v.spec, v.ics, v.hdr, v.frm, v.psf, v.eside = (pick(self.spec), pick(self.ics), pick(self.hdr), pick(self.frm),
-                                                            pick(self.psf), pick(self.eside))
-            v.flags, v.flags_pin, v.reset_pitch, v.got, v.sent, v.owner = (pick(self.flags), pick(self.flags_pin),
-                                                                         self.reset_pitch[t], self.got[t], self.sent[t], self)
-            v.lines = self.lines[t]
-            v.tside = pick(self.tside)
-            return v
-
-    class _Step:
-        pass
-
-    # three staging sets: the parse of step k + 1 | the copies up and kernels of step k | the copy down of step k - 1
-    sets = [Staging(), Staging(), Staging()] if overlap else [Staging()]
-    if not sbr:
-        # AAC-LC: IMDCT -> WORD32 + qshift_adj -> peak limiter -> round16 (api.c:3662-3692)
-        out32, qadj = dz(n * 1024 * n_ch, dtype=torch.int32), dz(n * n_ch, dtype=torch.int8)
-        lim0, delay = peak_limiter_init(n_ch, rate)
-        lim = torch.from_numpy(np.tile(np.frombuffer(bytes(lim0), np.uint8), (n, 1)).copy()).to(dev)
-        lim_at_end, lim_taken = {}, np.zeros(n, bool)
-        ws = dz(max(ctx.peak_limiter_workspace_bytes(n), 16))
-        pcm2 = [dz(n * 1024 * n_ch, dtype=torch.int16) for _ in range(2)]
-        pcm_h2 = [pinned(n * 1024 * n_ch, dtype=torch.int16) for _ in range(2)]
-        status2 = status_h2 = None
-    elif esbr:
-        # Path A: IMDCT (16-bit core PCM) -> xaac_esbr_core_from_pcm16_batch -> the eSBR chain -> xaac_esbr_pcm16_from_float_batch
-        # (saturate / truncate to 16 bit: ixheaacd_samples_sat, decode_main.c:82-107); every state member stays on the device
-        state = torch.from_numpy(np.tile(_struct_bytes(lib.xaac_esbr_state_init, ESBR_STATE_BYTES), (nc, 1)).copy()).to(dev)
-        hbe = dz(nc, HBE_STATE_BYTES)
-        core16 = dz(nc * 1024, dtype=torch.int16)
-        hdr_d2, frm_d2 = [dz(nc, SBR_HEADER_BYTES) for _ in range(2)], [dz(nc, SBR_FRAME_BYTES) for _ in range(2)]
-        eside_d2 = [dz(nc, ESBR_SIDE_BYTES) for _ in range(2)]
-        status2 = [dz(nc, dtype=torch.int32) for _ in range(2)]
-        status_h2 = [pinned(nc, dtype=torch.int32) for _ in range(2)]
-        ws = dz(ctx.esbr_workspace_bytes(nc))
-        out_l, out_r = dz(nc, 2048, dtype=torch.float32), None
-        core = dz(nc, 1024, dtype=torch.float32)
-        pcm2 = [dz(n * 2048 * 2, dtype=torch.int16) for _ in range(2)]
-        pcm_h2 = [pinned(n * 2048 * 2, dtype=torch.int16) for _ in range(2)]
-        if n_ch == 1:
-            ps_state = torch.from_numpy(np.tile(_struct_bytes(lib.xaac_esbr_ps_state_init, ESBR_PS_STATE_BYTES), (n, 1)).copy()).to(dev)
-            psf_d2 = [dz(n, PS_FRAME_BYTES) for _ in range(2)]
-            out_r = dz(n, 2048, dtype=torch.float32)
-        older = dz(nc, 2, 24 * 64, dtype=torch.float32)   # rows 8..31 of the QMF history as the frame before found them
-        hbe_tail = np.zeros((nc, 48), np.uint8)            # the transposers' integers (struct xaac_hbe_state from synth_size on)
-
-        def hbe_hint():   # the largest transposer bank of the batch, as the ABI's LDS hint takes it (8, or 0 = any)
-            return 8 if int(hbe_tail.view(np.int32)[:, 0].max()) <= 8 else 0
-    else:
-        state = torch.from_numpy(np.tile(_struct_bytes(lib.xaac_sbr_state_init, SBR_STATE_BYTES), (nc, 1)).copy()).to(dev)
-        core16 = dz(nc * 1024, dtype=torch.int16)
-        hdr_d2, frm_d2 = [dz(nc, SBR_HEADER_BYTES) for _ in range(2)], [dz(nc, SBR_FRAME_BYTES) for _ in range(2)]
-        flags_d2 = [dz(n, 8, dtype=torch.int32) for _ in range(2)]
-        status2 = [dz(nc, dtype=torch.int32) for _ in range(2)]
-        status_h2 = [pinned(nc, dtype=torch.int32) for _ in range(2)]
-        pcm_h2 = [pinned(n * 2048 * 2, dtype=torch.int16) for _ in range(2)]
-        pcm2 = [dz(n * 2048 * 2, dtype=torch.int16) for _ in range(2)]
-        if n_ch == 2:
-            ws = dz(ctx.sbr_lp_workspace_bytes(nc))
-        else:
-            ps_state = torch.from_numpy(np.tile(_struct_bytes(lib.xaac_ps_state_init, PS_STATE_BYTES), (n, 1)).copy()).to(dev)
-            psf_d2 = [dz(n, PS_FRAME_BYTES) for _ in range(2)]
-            ws = dz(ctx.sbr_hq_workspace_bytes(n, True))
-            pcm_mono = dz(n * 2048, dtype=torch.int16)
-    if gpu_tools:
-        tstatus_h2 = [pinned(n, dtype=torch.int32) for _ in range(2)]
-    first = True
-    cur_set, t_in_set, pending = None, 0, None
-    if overlap:
-        # (the parse of the next steps runs on the parser library's own threads, xaac_parse_batch_start / _wait: a Python helper
-        # thread would have to win the interpreter lock from this one, which gives it up only for microseconds at a time
-        # while it queues copies and launches -- measured, its parse began when this thread blocked on the result)
-        pending = sets[0].begin()
-    which = 0
-    # The copy down of step k runs on a second stream beside the copies up and kernels of step k + 1 (two PCM / status sets);
-    # the host takes a step's PCM one step later.
-    main_stream, down, up = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-    done = [torch.cuda.Event(), torch.cuda.Event()]
-    computed = [torch.cuda.Event(), torch.cuda.Event()]
-    lines_held = [0, 0]   # per device input set: the leading spectral lines that may be non-zero there
-    hip_rt = ctypes.CDLL("libamdhip64.so")
-    hip_rt.hipMemcpy2DAsync.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
-                                        ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-    waiting = None    # (slot, got, shape, cut, drop) of the step whose PCM is on its way
-
-    def consume():
-        nonlocal waiting, t_wait_down
-        if waiting is None:
-            return
-        slot_, got_, shape_, cut_, drop_ = waiting
-        waiting = None
-        t_c = time.perf_counter()
-        done[slot_].synchronize()
-        t_wait_down += time.perf_counter() - t_c
-        # (rows of streams that are over run idle on whatever their staging rows hold -- possibly nothing the kernels accept:
-        # what they say about those is not looked at)
-        if status_h2 is not None and int(status_h2[slot_].numpy().reshape(n, -1)[got_].min(initial=0)) < 0:
-            raise RuntimeError("the SBR kernels refused a frame")
-        if tstatus_h2 is not None and int(tstatus_h2[slot_].numpy()[got_].min(initial=0)) < 0:
-            raise RuntimeError("the AAC tools kernel refused a frame")
-        if keep_pcm and not drop_:
-            block = pcm_h2[slot_].numpy().reshape(shape_)
-            for i in np.nonzero(got_)[0]:
-                out[i].append(block[i, cut_:].copy())
-
-    def hand_down(slot_, got_, shape_, cut_=0, drop_=False):
-        nonlocal waiting
-        ev = computed[slot_]
-        ev.record(main_stream)   # this step's kernels are queued: its input set may be refilled, its PCM may go down
-        with torch.cuda.stream(down):
-            down.wait_event(ev)
-            pcm_h2[slot_].copy_(pcm2[slot_], non_blocking=True)
-            if status2 is not None:
-                status_h2[slot_].copy_(status2[slot_], non_blocking=True)
-            if tstatus2 is not None:
-                tstatus_h2[slot_].copy_(tstatus2[slot_], non_blocking=True)
-            done[slot_].record(down)
-        consume()
-        waiting = (slot_, got_, shape_, cut_, drop_)
-        if not overlap:   # one staging set: its copies up must be over before the next parse writes it
-            consume()
-
-    step_no = 0
-    t_steps = time.perf_counter()
-    try:
-        while True:
-            if t_in_set == T or cur_set is None:   # the next parser call's frames
-                t_w = time.perf_counter()
-                if not overlap:
-                    pending = sets[0].begin()
-                cur_set = pending.end()
-                t_wait_parse += time.perf_counter() - t_w
-                if overlap:    # the next T steps' frames are parsed while this thread looks at these and queues them on the GPU
-                    which = (which + 1) % 3
-                    pending = sets[which].begin()
-                cur_set.finish()
-                t_parse += cur_set.seconds
-                t_in_set = 0
-            cur = cur_set.step(t_in_set)
-            t_in_set += 1
-            got = cur.got
-            if not got.any():
-                if overlap:
-                    pending.end()   # (every stream is over: that call found nothing to parse)
-                break
-            slot = step_no & 1
-            step_no += 1
-            pcm = pcm2[slot]
-            status = status2[slot] if status2 is not None else None
-            spec_h, ics_h, hdr_h, frm_h, psf_h, flags = cur.spec, cur.ics, cur.hdr, cur.frm, cur.psf, cur.flags
-            overlap_buf = ovl
-            t0 = time.perf_counter()
-            pick = lambda two: None if two is None else two[slot]
-            spec_d, ics_d, hdr_d, frm_d, eside_d, psf_d, flags_d = (pick(spec_d2), pick(ics_d2), pick(hdr_d2), pick(frm_d2),
-                                                                    pick(eside_d2), pick(psf_d2), pick(flags_d2))
-            ps_frames = bool(sbr and n_ch == 1 and (flags[got, F_PS] != 0).all())
-            side_words = bool(sbr and not esbr and (got & ((flags[:, F_RESET] != 0) | (flags[:, F_UPSAMPLING] != 0))).any())
-            if side_words:   # xaac_sbr_state_apply_side_batch's flag rows (streams without a frame: zero rows)
-                cur.flags_pin.numpy()[:] = flags * got[:, None].astype(np.int32)
-            with torch.cuda.stream(up):   # everything this step sends up, beside the kernels of the step before
-                if step_no > 2:
-                    up.wait_event(computed[slot])   # (the kernels that read this input set two steps ago)
-                # the spectra: only the leading lines that are not zero in every delivered row (AAC + SBR streams code the lower
-                # half of the spectrum or less; 16 of the 26 MB a step of 4096 HE-AACv2 streams sends up are spectra), and
-                # what this device set still holds beyond them from two steps ago (the host rows are zero there)
-                lines_now = min(1024, (int(cur.lines[got].max()) + 63) & ~63)
-                width = max(lines_now, lines_held[slot])
-                lines_held[slot] = lines_now
-                if width >= 1024:
-                    spec_d.copy_(spec_h, non_blocking=True)
-                elif width > 0:
-                    rc = hip_rt.hipMemcpy2DAsync(spec_d.data_ptr(), 4096, spec_h.data_ptr(), 4096, 4 * width, nc, 1, up.cuda_stream)
-                    if rc != 0:
-                        raise RuntimeError("hipMemcpy2DAsync: %d" % rc)
-                ics_d.copy_(ics_h, non_blocking=True)
-                if gpu_tools:
-                    tside_d2[slot].copy_(cur.tside, non_blocking=True)
-                if sbr:
-                    hdr_d.copy_(hdr_h, non_blocking=True)
-                    frm_d.copy_(frm_h, non_blocking=True)
-                    if esbr:
-                        eside_d.copy_(cur.eside, non_blocking=True)
-                    if ps_frames:
-                        psf_d.copy_(psf_h, non_blocking=True)
-                    if side_words:
-                        flags_d.copy_(cur.flags_pin, non_blocking=True)
-                cur.sent.record(up)
-            cur.owner.sent_once = True
-            main_stream.wait_event(cur.sent)
-            if gpu_tools:   # stage-1 spectra -> the spectra the IMDCT takes, in place (ended streams' rows run idle, unlooked at)
-                ctx.aac_tools_process_batch(spec_d, tside_d2[slot], tools_state, tstatus2[slot])
-            if not sbr:
-                # a stream that ended with the step before: its limiter state as its last frame left it (the rows of ended
-                # streams go on running idle through the kernels; the delay line flushed behind a stream is the one it ended on)
-                for i in np.nonzero(~got & ~lim_taken)[0]:
-                    lim_at_end[int(i)] = lim[int(i)].cpu().numpy()     # (waits for the kernels of the step before)
-                    lim_taken[i] = True
-                ctx.imdct_process_batch(spec_d, ics_d, overlap_buf, ovl_state, out32=out32, qshift_adj=qadj, ch_fac=n_ch)
-                ctx.peak_limiter_process_batch(out32, qadj, lim, n_ch, ws, pcm16=pcm)
-                hand_down(slot, got, (n, 1024, n_ch), cut_=delay if first else 0)   # the limiter's delay is cut from the first frame
-            elif esbr:
-                # (interleaved as the reference holds it: its in-place 32 -> 16 bit conversion of a pair leaves traces of channel
-                # 0 in channel 1, api.c:353-366, which the IMDCT's PCM_SBR hand-off restates for ch_fac 2)
-                ctx.imdct_process_batch(spec_d, ics_d, overlap_buf, ovl_state, pcm16=core16, ch_fac=n_ch, pcm_mode=PCM_SBR)
-                touched = np.nonzero(got & (flags[:, F_RESET] != 0))[0]
-                if touched.size:
-                    # ixheaacd_sbr_dec_reset for Path A (sbrdecoder.c:175-236): new transposer parameters from the header's band
-                    # tables (its two delay lines cleared), then two transposer runs over rows 8..39 and 40..71 of the QMF buffer
-                    # as the frame before left it: rows 8..31 are what that frame found as rows 8..31 of its history (`older`),
-                    # rows 32..71 are the state's history (the codec bank's num_time_slots is 32 here).  The second run's last eight output rows become the
-                    # state's ph rows (bands outside the transposer's range keep what they held).
-                    k = touched.size * n_ch
-                    rows_h = (touched[:, None] * n_ch + np.arange(n_ch)[None, :]).ravel()
-                    rows = torch.from_numpy(rows_h).to(dev)
-                    hb = hbe.index_select(0, rows)
-                    tail_off = HBE_STATE_BYTES - 48
-                    tails = np.ascontiguousarray(hbe_tail[rows_h])            # (one call for all of them: every stream's first
-                    heads = np.ascontiguousarray(hdr_h.numpy()[rows_h])       #  frame is a reset frame)
-                    bad = lib.xaac_hbe_state_reinit_tails(tails.ctypes.data, heads.ctypes.data, len(rows_h))
-                    if bad >= 0:
-                        raise RuntimeError("the QMF transposer refused the SBR band tables of stream %d" % (rows_h[bad] // n_ch))
-                    hbe_tail[rows_h] = tails
-                    hb[:, tail_off:] = torch.from_numpy(tails).to(dev)
-                    hb32 = hb.view(torch.float32)
-                    hb32[:, 1088:1088 + 1280 + 640] = 0.0          # synth_buf, analy_buf (behind input_buf[1024 + 64])
-                    pitch = torch.from_numpy(np.repeat(cur.reset_pitch[touched], n_ch).astype(np.int32)).to(dev)
-                    st32 = state.view(torch.float32)
-                    hist, old = st32.index_select(0, rows), older.index_select(0, rows)
-                    q_re, q_im = dz(k, 32, 64, dtype=torch.float32), dz(k, 32, 64, dtype=torch.float32)
-                    pv_re, pv_im = dz(k, 32, 64, dtype=torch.float32), dz(k, 32, 64, dtype=torch.float32)
-                    rst = dz(k, dtype=torch.int32)
-                    q_re[:, :24] = old[:, 0].view(k, 24, 64)
-                    q_im[:, :24] = old[:, 1].view(k, 24, 64)
-                    q_re[:, 24:] = hist[:, _ES_QMF_RE:_ES_QMF_RE + 8 * 64].view(k, 8, 64)
-                    q_im[:, 24:] = hist[:, _ES_QMF_IM:_ES_QMF_IM + 8 * 64].view(k, 8, 64)
-                    ctx.hbe_apply_batch(q_re, q_im, hb, pv_re, pv_im, status=rst, pitch_in_bins=pitch, max_synth_size=hbe_hint())
-                    q_re[:] = hist[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 40 * 64].view(k, 32, 64)
-                    q_im[:] = hist[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 40 * 64].view(k, 32, 64)
-                    pv_re[:, 24:] = hist[:, _ES_PH_RE:_ES_PH_RE + 512].view(k, 8, 64)
-                    pv_im[:, 24:] = hist[:, _ES_PH_IM:_ES_PH_IM + 512].view(k, 8, 64)
-                    ctx.hbe_apply_batch(q_re, q_im, hb, pv_re, pv_im, status=rst, pitch_in_bins=pitch, max_synth_size=hbe_hint())
-                    hist[:, _ES_PH_RE:_ES_PH_RE + 512] = pv_re[:, 24:].reshape(k, 512)
-                    hist[:, _ES_PH_IM:_ES_PH_IM + 512] = pv_im[:, 24:].reshape(k, 512)
-                    st32.index_copy_(0, rows, hist)
-                    hbe.index_copy_(0, rows, hb)
-                st32 = state.view(torch.float32)
-                older[:, 0] = st32[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 32 * 64]   # for the reset a later frame may bring
-                older[:, 1] = st32[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 32 * 64]
-                ctx.esbr_core_from_pcm16(core16, core, ch_fac=n_ch)
-                if _trace is not None:   # debugging: the device states in front of the chain call
-                    _trace(dict(state=state, hbe=hbe, ps_state=ps_state if n_ch == 1 else None, core=core, side=eside_d, header=hdr_d,
-                                frame=frm_d))
-                with_ps = (flags[got, F_PS] != 0) if n_ch == 1 else np.zeros(1, bool)
-                if with_ps.any() != with_ps.all():
-                    raise NotImplementedError("a batch mixing PS and non-PS frames")
-                if with_ps.all():
-                    ctx.esbr_sbr_process_batch(core, hdr_d, frm_d, eside_d, state, out_l, ws, status=status, ps_frame=psf_d,
-                                               ps_state=ps_state, out_r=out_r, hbe_state=hbe, hbe_max_synth_size=hbe_hint())
-                    ctx.esbr_pcm16_from_float(out_l, out_r, pcm)
-                elif n_ch == 1:
-                    ctx.esbr_sbr_process_batch(core, hdr_d, frm_d, eside_d, state, out_l, ws, status=status, hbe_state=hbe, hbe_max_synth_size=hbe_hint())
-                    ctx.esbr_pcm16_from_float(out_l, out_l, pcm)                                # mono twice (api.c:3639-3660)
-                else:
-                    ctx.esbr_sbr_process_batch(core, hdr_d, frm_d, eside_d, state, out_l, ws, status=status, hbe_state=hbe, hbe_max_synth_size=hbe_hint())
-                    ctx.esbr_pcm16_from_float(out_l, out_l[1:], pcm, stride=4096)
-                hand_down(slot, got, (n, 2048, 2), drop_=first)      # the first frame's output is not written in this mode
-            else:
-                ctx.imdct_process_batch(spec_d, ics_d, overlap_buf, ovl_state, pcm16=core16, ch_fac=n_ch, pcm_mode=PCM_SBR)
-                # frames that reset the SBR decoder or fall back to plain up-sampling change a few words of the resident state:
-                # on the device, from the flag rows
-                if side_words:
-                    ctx.sbr_state_apply_side_batch(hdr_d, flags_d, state, n_ch, ps_state=ps_state if n_ch == 1 else None)
-                if n_ch == 2:
-                    ctx.sbr_lp_process_batch(core16, hdr_d, frm_d, state, pcm, ws, status=status, in_ch_fac=2, out_ch_fac=2)
-                else:
-                    with_ps = flags[got, F_PS] != 0
-                    if with_ps.any() != with_ps.all():
-                        raise NotImplementedError("a batch mixing PS and non-PS frames")
-                    if with_ps.all():
-                        starts = np.nonzero(got & (flags[:, F_PS_START] != 0))[0]
-                        if starts.size:
-                            idx = torch.from_numpy(starts.astype(np.int32)).to(dev)
-                            ctx.sbr_state_handover(HANDOVER_PS_START, idx, idx, state, ps_state)
-                        ctx.sbr_hq_process_batch(core16, hdr_d, frm_d, state, pcm, ws, ps_frame=psf_d, ps_state=ps_state, status=status)
-                    else:
-                        ctx.sbr_hq_process_batch(core16, hdr_d, frm_d, state, pcm_mono, ws, status=status)
-                        # mono duplicated to stereo (api.c:3639-3660)
-                        pcm.view(n, 2048, 2).copy_(pcm_mono.view(n, 2048, 1).expand(n, 2048, 2))
-                hand_down(slot, got, (n, 2048, 2))
-            t_gpu += time.perf_counter() - t0
-            first = False
-    except BaseException:
-        bp.close()   # (also takes back a batch the parser team still holds)
-        raise
-    consume()
-    t_steps = time.perf_counter() - t_steps
-    if not sbr and keep_pcm:
-        # the limiter's delay line holds the last attack_time_samples samples: api.c:2824-2866
-        ctx.sync()
-        lim_h = lim.cpu().numpy()
-        for i in range(n):
-            st = LimiterState.from_buffer_copy((lim_at_end[i] if i in lim_at_end else lim_h[i]).tobytes())
-            att, idx = st.attack_time_samples, st.delayed_input_index
-            d = np.ctypeslib.as_array(st.delayed_input)[:att * n_ch].reshape(att, n_ch)
-            tail = np.concatenate([d[idx:], d[:idx]]).astype(np.float64)
-            inside = (tail > -2147483649.0) & (tail < 2147483648.0)      # (WORD32) of a float as x86 converts it: what does
-            v = np.where(inside, np.trunc(np.where(inside, tail, 0.0)), -2147483648.0).astype(np.int64)   # not fit is INT_MIN
-            v = np.clip(v + 0x8000, -(1 << 31), (1 << 31) - 1) >> 16   # round16
-            out[i].append(v.astype(np.int16))
-    frames = int(bp.frames.sum())
-    bp.close()
-    if own:
-        ctx.close()
-    if timing is not None:
-        # parse_s: inside the parser calls; wait_parse_s: what the loop waited for them; gpu_s: the loop's GPU section (enqueue
-        # + wait_down_s, the wait for the previous step's PCM)
-        timing.update(parse_s=t_parse, gpu_s=t_gpu, steps_s=t_steps, frames=frames, wait_parse_s=t_wait_parse, wait_down_s=t_wait_down)
-    return [np.concatenate(o) if o else np.zeros((0, out_ch), np.int16) for o in out], rate * (2 if sbr else 1)
+    with _TorchCpuThreads():
+        return _Pipeline(streams, ctx, device, threads, keep_pcm, overlap, esbr, _trace, frames_per_parse, bool(gpu_tools)).run(timing)

@@ -153,3 +153,43 @@ def test_adts_frames_with_several_raw_data_blocks_decode_like_the_plain_stream()
             got, _ = decoder.decode_streams([remux, data, prot], esbr=esbr)
             for g in got:
                 assert zlib.crc32(np.ascontiguousarray(g).tobytes()) & 0xffffffff == int(gold[key][k]), (name, esbr)
+
+
+@pytest.mark.parametrize("name,kw", [("mix_aot2_64k", {}), ("mix_aot5_48k", {}), ("mix_aot29_32k", dict(esbr=True, gpu_tools=True))])
+def test_a_decode_leaves_no_buffers_to_the_cyclic_collector(name, kw, monkeypatch):
+    """the driver, its chain, its staging sets and every tensor they allocate are gone when decode_streams returns, with the
+    cyclic collector off: nothing of a decode sits in a reference cycle (pinned staging and device state go back to torch's
+    caching allocators at once)"""
+    import gc
+    import weakref
+    from libxaac_amd import decoder
+    data = open(os.path.join(STREAMS, name + ".aac"), "rb").read()
+    decoder.decode_streams([data])     # (torch loaded, decoder.torch set)
+    seen = []
+
+    def tracked(cls):
+        init = cls.__init__
+
+        def wrapper(self, *a, **k):
+            init(self, *a, **k)
+            seen.append(weakref.ref(self))
+        monkeypatch.setattr(cls, "__init__", wrapper)
+
+    for cls in (decoder._Pipeline, decoder._Chain, decoder.Staging, decoder._Alloc):
+        tracked(cls)
+    for fn in ("dz", "pinned"):
+        alloc = getattr(decoder._Alloc, fn)
+
+        def wrapper(self, *a, _alloc=alloc, **k):
+            t = _alloc(self, *a, **k)
+            seen.append(weakref.ref(t))
+            return t
+        monkeypatch.setattr(decoder._Alloc, fn, wrapper)
+    gc.collect()
+    gc.disable()
+    try:
+        decoder.decode_streams([data, data], **kw)
+        alive = [type(r()).__name__ for r in seen if r() is not None]
+    finally:
+        gc.enable()
+    assert len(seen) > 20 and not alive, alive
