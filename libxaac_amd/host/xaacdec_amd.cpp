@@ -24,7 +24,12 @@
  * compared with it word for word) and prints the end-to-end rate: the shape a serving host has, with one input here for brevity.
  * -ilist decodes different streams of one kind (sampling rate, channels, SBR / PS or not) in one batch, each to <odir>/<name>.wav;
  * a stream that ends drops out of the steps, the others go on.
- * libxaac_amd/decoder.py is the same loop in Python (used by the tests for its ease of inspection).
+ *
+ * The shape of a shard (decode_shard), the same as libxaac_amd/decoder.py has in Python (used by the tests for its ease of
+ * inspection): ShardOwner hands out and releases what the shard allocates; ParseSide owns the parsers, the staging groups and
+ * the helper thread; ShardDriver owns what every kind of stream shares and runs the step loop; ToolsStage is -gputools:1; the
+ * chain picked once -- LcChain, SbrChain (-esbr:0) or EsbrChain (Path A, over a QmfTransposer or a DftTransposer) -- owns its
+ * streams' device-resident states.  A new kind of stream is a new Chain.
  */
 #include <hip/hip_runtime_api.h>
 #include <ctype.h>
@@ -39,7 +44,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -65,13 +72,6 @@ namespace {
     if (e_ != 0) die(#x, e_); \
   } while (0)
 
-template <class T>
-T *dev(size_t n) {
-  void *p = nullptr;
-  HIP(hipMalloc(&p, n * sizeof(T) ? n * sizeof(T) : 16));
-  HIP(hipMemset(p, 0, n * sizeof(T) ? n * sizeof(T) : 16));
-  return static_cast<T *>(p);
-}
 /* CPUs of the NUMA node the GPU hangs off (hipDeviceGetPCIBusId -> /sys/bus/pci/devices/<id>/numa_node -> the node's
    cpulist); an empty set where that cannot be read.  Pinned staging memory is allocated and first touched from there:
    with the staging on the other socket the bus carries one direction at full rate but both at once -- spectra going up
@@ -121,24 +121,87 @@ cpu_set_t near_cpus(int device, bool *known) { /* (by value: the table may grow 
   *known = k;
   return seen.back().second.second;
 }
-template <class T>
-T *pinned(size_t n, int device) {
-  bool known = false;
-  const cpu_set_t near = near_cpus(device, &known);
-  cpu_set_t before, both;
-  /* first touch on the GPU's NUMA node: only CPUs this thread may run on anyway (a cpuset that does not meet the node leaves the
-     thread where it is) */
-  bool moved = false;
-  if (known && sched_getaffinity(0, sizeof(before), &before) == 0) {
-    CPU_AND(&both, &before, &near);
-    moved = CPU_COUNT(&both) > 0 && sched_setaffinity(0, sizeof(both), &both) == 0;
+
+/* What one shard allocates and makes, and the one place where all of it goes again: zeroed device arrays, pinned arrays near
+   the GPU, the HIP streams and events, the xaac_ctx and the parsers.  The destructor waits for the streams and then releases
+   everything, so a shard's share of a -gpus run does not stay behind until the process ends.  (die() exits the process
+   without unwinding: nothing is released on that path, and nothing has to be.) */
+class ShardOwner {
+ public:
+  explicit ShardOwner(int device) : device_(device) { HIP(hipSetDevice(device)); }
+  ShardOwner(const ShardOwner &) = delete;
+  ~ShardOwner() {
+    (void)hipSetDevice(device_); /* (main's thread releases the shards) */
+    for (hipStream_t s : streams_) (void)hipStreamSynchronize(s);
+    for (void *p : dev_) (void)hipFree(p);
+    for (void *p : host_) (void)hipHostFree(p);
+    for (xaac_parser *p : parsers_) xaac_parser_destroy(p);
+    if (ctx_) (void)xaac_destroy(ctx_);
+    for (hipEvent_t e : events_) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams_) (void)hipStreamDestroy(s);
   }
-  void *p = nullptr;
-  HIP(hipHostMalloc(&p, n * sizeof(T) ? n * sizeof(T) : 16, hipHostMallocDefault));
-  memset(p, 0, n * sizeof(T) ? n * sizeof(T) : 16);
-  if (moved) sched_setaffinity(0, sizeof(before), &before);
-  return static_cast<T *>(p);
-}
+  hipStream_t stream() {
+    hipStream_t s;
+    HIP(hipStreamCreate(&s));
+    streams_.push_back(s);
+    return s;
+  }
+  hipEvent_t event() {
+    hipEvent_t e;
+    HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    events_.push_back(e);
+    return e;
+  }
+  xaac_ctx *context(hipStream_t s) {
+    XA(xaac_create(&ctx_, device_, s));
+    return ctx_;
+  }
+  xaac_parser *parser() {
+    xaac_parser *p = nullptr;
+    XA(xaac_parser_create(&p));
+    parsers_.push_back(p);
+    return p;
+  }
+  void *workspace(uint64_t bytes) { /* device bytes as they come: the kernels that take a workspace write it before they read it */
+    void *p = nullptr;
+    HIP(hipMalloc(&p, bytes ? bytes : 16));
+    dev_.push_back(p);
+    return p;
+  }
+  template <class T>
+  T *dev(size_t n) {
+    void *p = workspace(n * sizeof(T));
+    HIP(hipMemset(p, 0, n * sizeof(T) ? n * sizeof(T) : 16));
+    return static_cast<T *>(p);
+  }
+  template <class T>
+  T *pinned(size_t n) {
+    bool known = false;
+    const cpu_set_t near = near_cpus(device_, &known);
+    cpu_set_t before, both;
+    /* first touch on the GPU's NUMA node: only CPUs this thread may run on anyway (a cpuset that does not meet the node leaves the
+       thread where it is) */
+    bool moved = false;
+    if (known && sched_getaffinity(0, sizeof(before), &before) == 0) {
+      CPU_AND(&both, &before, &near);
+      moved = CPU_COUNT(&both) > 0 && sched_setaffinity(0, sizeof(both), &both) == 0;
+    }
+    void *p = nullptr;
+    HIP(hipHostMalloc(&p, n * sizeof(T) ? n * sizeof(T) : 16, hipHostMallocDefault));
+    host_.push_back(p);
+    memset(p, 0, n * sizeof(T) ? n * sizeof(T) : 16);
+    if (moved) sched_setaffinity(0, sizeof(before), &before);
+    return static_cast<T *>(p);
+  }
+
+ private:
+  const int device_;
+  std::vector<void *> dev_, host_;
+  std::vector<hipStream_t> streams_;
+  std::vector<hipEvent_t> events_;
+  std::vector<xaac_parser *> parsers_;
+  xaac_ctx *ctx_ = nullptr;
+};
 
 struct Staging { /* what one step's parse leaves for the GPU */
   int32_t *spec;
@@ -148,7 +211,7 @@ struct Staging { /* what one step's parse leaves for the GPU */
   xaac_ps_frame *ps;
   xaac_esbr_side *eside;
   xaac_core_tools_side *tside; /* -gputools:1: the side info of the M/S, intensity, PNS and TNS tools */
-  std::vector<int32_t> flags, status, reset_pitch;
+  const int32_t *flags, *status, *reset_pitch; /* the step's rows of its group's vectors: [N][8], [N], [N] */
   int delivered;
   int lines; /* leading spectral lines that may be non-zero in a delivered row (xaac_parse_batch::lines, rounded up to 64) */
 };
@@ -176,8 +239,7 @@ void write_wav(const std::string &path, const std::vector<int16_t> &pcm, int cha
 /* what the command line fixes for every shard */
 struct Job {
   std::vector<std::vector<uint8_t>> datas; /* -ilist: one per stream; else the one input */
-  xaac_adts_header hdr;
-  int n_ch, sbr, esbr, out_ch, rate, out_rate, per;
+  int n_ch, sbr, esbr, out_ch, rate, per;
   int hq; /* -esbr_hq:1: the DFT harmonic transposer in the QMF one's place (Path A only) */
   int threads, verify, profile;
   int gputools; /* -gputools:1: parse at stage 1, the spectral tools run on the GPU in front of the IMDCT */
@@ -189,6 +251,7 @@ struct Shard {
   std::vector<std::vector<int16_t>> pcms; /* every stream's output (-ilist), or the shard's first stream's */
   long frames = 0, mismatched = 0, first_frames = 0;
   double parse_s = 0, wall = 0, steady = 0, phase_s[4] = {0, 0, 0, 0};
+  std::unique_ptr<ShardOwner> mem; /* what the shard allocated, until main lets go of it */
 };
 
 /* libxaac_amd/dist.py: shard_range -- contiguous [lo, hi) of n items owned by shard r of g; sizes differ by at most one */
@@ -198,226 +261,122 @@ void shard_range(int n, int r, int g, int *lo, int *hi) {
   *hi = *lo + base + (r < rem ? 1 : 0);
 }
 
-void decode_shard(const Job &J, Shard &S) {
-  const int device = S.device, N = S.n, n_ch = J.n_ch, sbr = J.sbr, esbr = J.esbr, out_ch = J.out_ch, rate = J.rate, per = J.per;
-  const int threads = J.threads, verify = J.verify, profile = J.profile, hq = J.esbr && J.hq;
-  const bool list_mode = J.list_mode, gputools = J.gputools != 0;
-  const int NC = N * n_ch, NCD = NC;
-  S.first_frames = N;
-  xaac_ctx *ctx = nullptr;
-  hipStream_t stream;
-  HIP(hipSetDevice(device));
-  HIP(hipStreamCreate(&stream));
-  XA(xaac_create(&ctx, device, stream));
-  XA(xaac_warm_up(ctx)); /* the kernels' code objects are on the device before the first batch (and the run's clock) */
-  std::vector<xaac_parser *> parser((size_t)N);
-  for (auto &p : parser) {
-    XA(xaac_parser_create(&p));
-    if (esbr) XA(xaac_parser_set_esbr(p, 1));
-  }
-  std::vector<const uint8_t *> ptr((size_t)N);
-  std::vector<uint64_t> left((size_t)N), pos((size_t)N, 0);
-  std::vector<char> broken((size_t)N, 0); /* -ilist: a stream whose frame did not parse is treated as over from there on */
+/* what a chain wants staged beside the spectra and the window info */
+struct Wants {
+  bool sbr, ps, esbr; /* SBR headers and frames; PS frames; the eSBR side rows (and parsers that read them) */
+};
 
-  /* device-resident state and per-step device buffers */
-  int32_t *d_overlap = dev<int32_t>((size_t)NCD * 512), *d_spec = dev<int32_t>((size_t)NCD * 1024);
-  xaac_ovl_state *d_ovl = dev<xaac_ovl_state>((size_t)NCD);
-  xaac_ics_info *d_ics = dev<xaac_ics_info>((size_t)NCD);
-  /* PCM and status of a step in two sets: the copy down of step k (a second stream) runs beside the copies up and the kernels
-     of step k + 1 */
-  int16_t *d_pcm2[2], *h_pcm2[2], *d_mono2[2] = {nullptr, nullptr};
-  int32_t *d_status2[2], *h_status2[2];
-  hipStream_t down;
-  hipEvent_t ev_kernels[2], ev_down[2];
-  HIP(hipStreamCreate(&down));
-  for (int k = 0; k < 2; k++) {
-    d_pcm2[k] = dev<int16_t>((size_t)N * per * out_ch), h_pcm2[k] = pinned<int16_t>((size_t)N * per * 2, device);
-    d_status2[k] = dev<int32_t>((size_t)NC), h_status2[k] = pinned<int32_t>((size_t)NC, device);
-    HIP(hipEventCreateWithFlags(&ev_kernels[k], hipEventDisableTiming));
-    HIP(hipEventCreateWithFlags(&ev_down[k], hipEventDisableTiming));
-  }
-  /* -gputools:1: the tools' side rows, the streams' noise generators (zero for a new stream), the kernel's status words */
-  xaac_core_tools_side *d_tside = nullptr;
-  xaac_core_tools_state *d_tstate = nullptr;
-  int32_t *d_tstatus2[2] = {nullptr, nullptr}, *h_tstatus2[2] = {nullptr, nullptr};
-  if (gputools) {
-    d_tside = dev<xaac_core_tools_side>((size_t)N), d_tstate = dev<xaac_core_tools_state>((size_t)N);
-    HIP(hipMemset(d_tstate, 0, (size_t)N * sizeof(xaac_core_tools_state)));
-    for (int k = 0; k < 2; k++) d_tstatus2[k] = dev<int32_t>((size_t)N), h_tstatus2[k] = pinned<int32_t>((size_t)N, device);
-  }
-  /* AAC-LC */
-  int32_t *d_out32 = nullptr;
-  int8_t *d_qadj = nullptr;
-  xaac_limiter_state *d_lim = nullptr;
-  int delay = 0;
-  /* SBR */
-  int16_t *d_core = nullptr;
-  xaac_sbr_header *d_header = nullptr;
-  xaac_sbr_frame *d_frame = nullptr;
-  xaac_sbr_state *d_state = nullptr;
-  xaac_ps_frame *d_psf = nullptr;
-  xaac_ps_state *d_ps_state = nullptr;
-  int32_t *d_idx = nullptr;
-  int32_t *d_flags = nullptr, *h_flags = nullptr; /* the parser's flag rows as xaac_sbr_state_apply_side_batch takes them */
-  /* Path A (-esbr:1) */
-  xaac_esbr_side *d_eside = nullptr;
-  xaac_esbr_state *d_estate = nullptr;
-  xaac_hbe_state *d_hbe = nullptr, *d_hbe_tmp = nullptr; /* d_hbe_tmp: the resetting channels of a step gathered (partial resets) */
-  xaac_esbr_ps_state *d_eps = nullptr;
-  float *d_fcore = nullptr, *d_out_l = nullptr, *d_out_r = nullptr, *d_q = nullptr, *d_pv = nullptr;
-  std::vector<uint8_t> hbe_tail; /* every channel's transposer integers, kept between resets: some survive one (max_stretch, fft_ready) */
-  const auto hbe_hint = [&]() { /* the largest bank of the batch, as the ABI's LDS hint takes it: 8, or 0 = any */
-    int32_t smax = 0, v;
-    constexpr size_t kTail = sizeof(xaac_hbe_state) - offsetof(xaac_hbe_state, synth_size);
-    for (size_t i = 0; i * kTail < hbe_tail.size(); i++) memcpy(&v, &hbe_tail[i * kTail], 4), smax = v > smax ? v : smax;
-    return smax <= 8 ? 8 : 0;
-  };
-  /* -esbr_hq:1: every channel's DFT transposer, the configurations their headers' band tables gave (shared by channels with the
-     same tables), and what the host keeps between resets: max_stretch (the re-initialisation leaves it alone when four patches
-     fit), the last processed frame's over_sampling_flag (the reset-time runs use the transposer's: sbr_dec.c:884 sets it) */
-  xaac_hbe_dft_state *d_dft = nullptr, *d_dft_tmp = nullptr;
-  xaac_hbe_dft_cfg *d_dcfg = nullptr;
-  float *d_dcoef = nullptr;       /* [2][NC][64][128]: real matrices of the configurations, then the imaginary ones */
-  int32_t *d_dslot = nullptr, *d_dslot_tmp = nullptr, *d_dovs = nullptr; /* [NC] configuration of a channel; of the gathered channels; their flags */
-  std::vector<int32_t> dft_ms, dft_ovs, dft_slot;
-  std::map<std::string, int> dft_cfgs;
-  float *d_older = nullptr; /* [2][NC][24][64]: rows 8..31 of the QMF history as the frame before found them (see the reset) */
-  void *d_ws = nullptr;
-  uint64_t ws_bytes = 0;
-  if (!sbr) {
-    d_out32 = dev<int32_t>((size_t)N * 1024 * n_ch);
-    d_qadj = dev<int8_t>((size_t)N * n_ch);
-    d_lim = dev<xaac_limiter_state>((size_t)N);
-    xaac_limiter_state l0;
-    delay = xaac_peak_limiter_init(&l0, (uint32_t)n_ch, (uint32_t)rate);
-    if (delay < 0) die("xaac_peak_limiter_init", delay);
-    for (int i = 0; i < N; i++) HIP(hipMemcpy(d_lim + i, &l0, sizeof(l0), hipMemcpyHostToDevice));
-    ws_bytes = xaac_peak_limiter_workspace_bytes(N);
-  } else if (esbr) {
-    d_core = dev<int16_t>((size_t)NC * 1024);
-    d_header = dev<xaac_sbr_header>((size_t)NC);
-    d_frame = dev<xaac_sbr_frame>((size_t)NC);
-    d_eside = dev<xaac_esbr_side>((size_t)NC);
-    d_estate = dev<xaac_esbr_state>((size_t)NC);
-    if (hq) {
-      d_dft = dev<xaac_hbe_dft_state>((size_t)NC); /* all zero for a new stream: refused (last_status -1) until a header sets it up */
-      d_dft_tmp = dev<xaac_hbe_dft_state>((size_t)NC);
-      d_dcfg = dev<xaac_hbe_dft_cfg>((size_t)NC);
-      d_dcoef = dev<float>((size_t)2 * NC * 64 * 128);
-      d_dslot = dev<int32_t>((size_t)NC), d_dslot_tmp = dev<int32_t>((size_t)NC), d_dovs = dev<int32_t>((size_t)NC);
-      dft_ms.assign((size_t)NC, 0), dft_ovs.assign((size_t)NC, 0), dft_slot.assign((size_t)NC, 0);
-    } else {
-      d_hbe = dev<xaac_hbe_state>((size_t)NC); /* all zero for a new stream */
+/* The parse side of a shard: the streams' parsers and read positions, three groups of kFramesPerParse staging sets and the
+   helper thread that fills them.  It knows nothing of what runs on the GPU.
+   Three groups of kFramesPerParse steps: the parse of group g + 1 | the copies up and kernels of group g's steps | the copy
+   down of the step before.  A stream's parser state and bytes are fetched once per call for kFramesPerParse frames (on the
+   2 x 64-core box 32 threads parse 3.9-4.6 x 10^6 frames/s one frame per call, 4.9-5.6 x 10^6 with 2..8).  A step's flag,
+   status and pitch rows are its group's: they stay as parsed until the group is parsed again, two groups of steps later, and
+   the step's PCM is consumed one step late. */
+class ParseSide {
+ public:
+  static constexpr int T = kFramesPerParse;
+  ParseSide(const Job &J, Shard &S, ShardOwner &mem, Wants w)
+      : J_(J), N_(S.n), lo_(S.lo), parse_s_(S.parse_s), parser_((size_t)S.n), ptr_((size_t)S.n), left_((size_t)S.n), pos_((size_t)S.n, 0),
+        broken_((size_t)S.n, 0) {
+    const int N = N_, NC = N * J.n_ch;
+    for (auto &p : parser_) {
+      p = mem.parser();
+      if (w.esbr) XA(xaac_parser_set_esbr(p, 1));
     }
-    d_fcore = dev<float>((size_t)NC * 1024);
-    d_out_l = dev<float>((size_t)NC * 2048);
-    d_older = dev<float>((size_t)2 * NC * 24 * 64);
-    static thread_local xaac_esbr_state e0; /* (thread_local: one decode_shard per device thread) */
-    xaac_esbr_state_init(&e0);
-    for (int i = 0; i < NC; i++) HIP(hipMemcpy(d_estate + i, &e0, sizeof(e0), hipMemcpyHostToDevice));
-    if (n_ch == 1) {
-      d_psf = dev<xaac_ps_frame>((size_t)N);
-      d_eps = dev<xaac_esbr_ps_state>((size_t)N);
-      d_out_r = dev<float>((size_t)N * 2048);
-      static thread_local xaac_esbr_ps_state p0;
-      xaac_esbr_ps_state_init(&p0);
-      for (int i = 0; i < N; i++) HIP(hipMemcpy(d_eps + i, &p0, sizeof(p0), hipMemcpyHostToDevice));
-    }
-    ws_bytes = xaac_esbr_workspace_bytes(NC);
-  } else {
-    d_core = dev<int16_t>((size_t)NC * 1024);
-    d_header = dev<xaac_sbr_header>((size_t)NC);
-    d_frame = dev<xaac_sbr_frame>((size_t)NC);
-    d_state = dev<xaac_sbr_state>((size_t)NC);
-    xaac_sbr_state s0;
-    xaac_sbr_state_init(&s0);
-    {
-      std::vector<xaac_sbr_state> all((size_t)NC, s0);
-      HIP(hipMemcpy(d_state, all.data(), all.size() * sizeof(s0), hipMemcpyHostToDevice));
-    }
-    d_flags = dev<int32_t>((size_t)N * 8), h_flags = pinned<int32_t>((size_t)N * 8, device);
-    if (n_ch == 1) {
-      d_psf = dev<xaac_ps_frame>((size_t)N);
-      d_ps_state = dev<xaac_ps_state>((size_t)N);
-      d_mono2[0] = dev<int16_t>((size_t)N * 2048), d_mono2[1] = dev<int16_t>((size_t)N * 2048);
-      d_idx = dev<int32_t>((size_t)N);
-      xaac_ps_state p0;
-      xaac_ps_state_init(&p0);
-      {
-        std::vector<xaac_ps_state> all((size_t)N, p0);
-        HIP(hipMemcpy(d_ps_state, all.data(), all.size() * sizeof(p0), hipMemcpyHostToDevice));
+    for (int g = 0; g < 3; g++) {
+      int32_t *spec = mem.pinned<int32_t>((size_t)T * NC * 1024);
+      uint8_t *ics = mem.pinned<uint8_t>((size_t)T * NC * 2);
+      xaac_sbr_header *header = w.sbr ? mem.pinned<xaac_sbr_header>((size_t)T * NC) : nullptr;
+      xaac_sbr_frame *frame = w.sbr ? mem.pinned<xaac_sbr_frame>((size_t)T * NC) : nullptr;
+      xaac_ps_frame *psf = w.ps ? mem.pinned<xaac_ps_frame>((size_t)T * N) : nullptr;
+      xaac_esbr_side *eside = w.esbr ? mem.pinned<xaac_esbr_side>((size_t)T * NC) : nullptr;
+      xaac_core_tools_side *tside = J.gputools ? mem.pinned<xaac_core_tools_side>((size_t)T * N) : nullptr;
+      StagingGroup &G = grp_[g];
+      G.flags.assign((size_t)T * N * 8, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N, 0);
+      G.lines.assign((size_t)T * N, 0), G.consumed.assign((size_t)N, 0);
+      for (int t = 0; t < T; t++) {
+        Staging &s = st_[g * T + t];
+        s.spec = spec + (size_t)t * NC * 1024, s.ics = ics + (size_t)t * NC * 2;
+        s.header = header ? header + (size_t)t * NC : nullptr, s.frame = frame ? frame + (size_t)t * NC : nullptr;
+        s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
+        s.tside = tside ? tside + (size_t)t * N : nullptr;
+        s.flags = &G.flags[(size_t)t * N * 8], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N];
+        s.delivered = 0, s.lines = 1024;
       }
-      ws_bytes = xaac_sbr_hq_workspace_bytes(N, 1);
-    } else {
-      ws_bytes = xaac_sbr_lp_workspace_bytes(NC);
     }
+    for (int i = 0; i < N; i++) {
+      const std::vector<uint8_t> &d = J.datas[J.list_mode ? (size_t)(lo_ + i) : 0];
+      ptr_[(size_t)i] = d.data(), left_[(size_t)i] = d.size(); /* the whole streams: the library keeps the read positions (pos) */
+    }
+    /* one helper thread for the whole run: it parses the next staging set when told to, the main thread waits for `done` */
+    worker_ = std::thread([this] { work(); });
   }
-  HIP(hipMalloc(&d_ws, ws_bytes ? ws_bytes : 16));
+  ~ParseSide() { stop(); }
+  void start() { /* the next group's frames are parsed from here on */
+    std::lock_guard<std::mutex> lk(mu_);
+    job_++;
+    cv_.notify_all();
+  }
+  void wait(int group) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return done_ >= group; });
+  }
+  void stop() {
+    if (!worker_.joinable()) return;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      quit_ = true;
+      cv_.notify_all();
+    }
+    worker_.join();
+  }
+  const Staging &step(int which) const { return st_[which]; }
 
-  /* three groups of kFramesPerParse steps: the parse of group g + 1 | the copies up and kernels of group g's steps | the copy
-     down of the step before.  A stream's parser state and bytes are fetched once per call for kFramesPerParse frames (on the
-     2 x 64-core box 32 threads parse 3.9-4.6 x 10^6 frames/s one frame per call, 4.9-5.6 x 10^6 with 2..8). */
-  constexpr int T = kFramesPerParse;
-  Staging st[3 * T];
-  StagingGroup grp[3];
-  for (int g = 0; g < 3; g++) {
-    int32_t *spec = pinned<int32_t>((size_t)T * NC * 1024, device);
-    uint8_t *ics = pinned<uint8_t>((size_t)T * NC * 2, device);
-    xaac_sbr_header *header = sbr ? pinned<xaac_sbr_header>((size_t)T * NC, device) : nullptr;
-    xaac_sbr_frame *frame = sbr ? pinned<xaac_sbr_frame>((size_t)T * NC, device) : nullptr;
-    xaac_ps_frame *psf = (sbr && n_ch == 1) ? pinned<xaac_ps_frame>((size_t)T * N, device) : nullptr;
-    xaac_esbr_side *eside = esbr ? pinned<xaac_esbr_side>((size_t)T * NC, device) : nullptr;
-    xaac_core_tools_side *tside = gputools ? pinned<xaac_core_tools_side>((size_t)T * N, device) : nullptr;
-    grp[g].flags.assign((size_t)T * N * 8, 0), grp[g].status.assign((size_t)T * N, 0), grp[g].reset_pitch.assign((size_t)T * N, 0);
-    grp[g].lines.assign((size_t)T * N, 0), grp[g].consumed.assign((size_t)N, 0);
-    for (int t = 0; t < T; t++) {
-      Staging &s = st[g * T + t];
-      s.spec = spec + (size_t)t * NC * 1024, s.ics = ics + (size_t)t * NC * 2;
-      s.header = header ? header + (size_t)t * NC : nullptr, s.frame = frame ? frame + (size_t)t * NC : nullptr;
-      s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
-      s.tside = tside ? tside + (size_t)t * N : nullptr;
-      s.flags.assign((size_t)N * 8, 0), s.status.assign((size_t)N, 0), s.reset_pitch.assign((size_t)N, 0);
-      s.delivered = 0, s.lines = 1024;
+ private:
+  void work() {
+    for (int expect = 0;; expect++) {
+      std::unique_lock<std::mutex> lk(mu_);
+      cv_.wait(lk, [&] { return quit_ || job_ > expect; });
+      if (quit_) return;
+      lk.unlock();
+      parse(expect % 3);
+      lk.lock();
+      done_ = expect;
+      cv_.notify_all();
     }
   }
-  for (int i = 0; i < N; i++) {
-    const std::vector<uint8_t> &d = J.datas[list_mode ? (size_t)(S.lo + i) : 0];
-    ptr[(size_t)i] = d.data(), left[(size_t)i] = d.size(); /* the whole streams: the library keeps the read positions (pos) */
-  }
-  double &parse_s = S.parse_s;
-  auto parse = [&](int g) { /* the next kFramesPerParse frames of every stream into one group of staging sets */
+  void parse(int g) { /* the next kFramesPerParse frames of every stream into one group of staging sets */
     const auto t0 = std::chrono::steady_clock::now();
-    StagingGroup &G = grp[g];
+    const int N = N_;
+    StagingGroup &G = grp_[g];
     for (int i = 0; i < N; i++)
-      if (broken[(size_t)i]) left[(size_t)i] = 0;
+      if (broken_[(size_t)i]) left_[(size_t)i] = 0;
     xaac_parse_batch b;
     memset(&b, 0, sizeof(b));
-    b.n_streams = N, b.n_ch = n_ch, b.with_sbr = sbr, b.ps_enable = 1, b.stage = gputools ? 1 : 2, b.threads = threads;
-    b.parser = parser.data(), b.data = ptr.data(), b.bytes = left.data(), b.pos = pos.data(), b.frames = T;
-    Staging &s0 = st[g * T];
+    b.n_streams = N, b.n_ch = J_.n_ch, b.with_sbr = J_.sbr, b.ps_enable = 1, b.stage = J_.gputools ? 1 : 2, b.threads = J_.threads;
+    b.parser = parser_.data(), b.data = ptr_.data(), b.bytes = left_.data(), b.pos = pos_.data(), b.frames = T;
+    Staging &s0 = st_[g * T];
     b.spec = s0.spec, b.ics = s0.ics, b.header = s0.header, b.frame = s0.frame, b.ps_frame = s0.ps;
     b.flags = G.flags.data(), b.consumed = G.consumed.data(), b.status = G.status.data(), b.esbr_side = s0.eside;
     b.reset_pitch = G.reset_pitch.data(), b.lines = G.lines.data(), b.tools_side = s0.tside;
     const int ok = xaac_parse_batch_run(&b);
     if (ok < 0) die("xaac_parse_batch_run", ok);
     for (int t = 0; t < T; t++) {
-      Staging &s = st[g * T + t];
+      Staging &s = st_[g * T + t];
       int delivered = 0, lines = 0;
       for (int i = 0; i < N; i++) {
-        int32_t r = G.status[(size_t)t * N + i];
+        int32_t &r = G.status[(size_t)t * N + i];
         if (r < 0) {
           /* one file of a list with trailing bytes or damage must not take the other streams' output along: that stream ends
              here (what it delivered so far is written), the batch goes on */
-          if (!list_mode) die("a frame does not parse", r);
-          if (!broken[(size_t)i])
-            fprintf(stderr, "xaacdec_amd: stream %d: a frame does not parse (%d) at byte %llu: the stream ends here\n", S.lo + i, r,
-                    (unsigned long long)pos[(size_t)i]);
-          broken[(size_t)i] = 1;
+          if (!J_.list_mode) die("a frame does not parse", r);
+          if (!broken_[(size_t)i])
+            fprintf(stderr, "xaacdec_amd: stream %d: a frame does not parse (%d) at byte %llu: the stream ends here\n", lo_ + i, r,
+                    (unsigned long long)pos_[(size_t)i]);
+          broken_[(size_t)i] = 1;
           r = XAAC_PARSE_NEED_DATA;
         }
-        s.status[(size_t)i] = r;
-        s.reset_pitch[(size_t)i] = G.reset_pitch[(size_t)t * N + i];
-        for (int k = 0; k < 8; k++) s.flags[(size_t)i * 8 + k] = G.flags[((size_t)t * N + i) * 8 + k];
         if (r == 0) {
           delivered++;
           lines = G.lines[(size_t)t * N + i] > lines ? G.lines[(size_t)t * N + i] : lines;
@@ -426,482 +385,134 @@ void decode_shard(const Job &J, Shard &S) {
       s.delivered = delivered;
       s.lines = (lines + 63) & ~63;
     }
-    parse_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  };
+    parse_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
 
-  double (&phase_s)[4] = S.phase_s; /* -profile: copies up, kernels, copies down, host work on the PCM */
-  auto t_phase = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    if (!profile) return;
-    HIP(hipStreamSynchronize(stream));
-    const auto now = std::chrono::steady_clock::now();
-    phase_s[k] += std::chrono::duration<double>(now - t_phase).count();
-    t_phase = now;
-  };
-  std::vector<std::vector<int16_t>> &pcms = S.pcms;
-  pcms.assign((size_t)(list_mode ? N : 1), std::vector<int16_t>()); /* every stream's output (-ilist), or stream 0's */
-  std::vector<char> ended((size_t)N, 0);
-  std::vector<xaac_limiter_state> lim_at_end; /* -ilist, AAC-LC: the limiter state a stream leaves behind its last frame */
-  if (list_mode && !sbr) lim_at_end.resize((size_t)N);
-  long &frames = S.frames, &mismatched = S.mismatched;
-  int lines_held = 0; /* leading spectral lines that may be non-zero in d_spec */
-  bool first = true;
-  const auto t_all = std::chrono::steady_clock::now();
-  auto t_first = t_all;
-  /* one helper thread for the whole run: it parses the next staging set when told to, the main thread waits for `done` */
-  std::mutex mu;
-  std::condition_variable cv;
-  int job = 0, done = -1;
-  bool quit = false;
-  std::thread worker([&] {
-    for (int expect = 0;; expect++) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return quit || job > expect; });
-      if (quit) return;
-      lk.unlock();
-      parse(expect % 3);
-      lk.lock();
-      done = expect;
-      cv.notify_all();
-    }
-  });
-  auto start_parse = [&] {
-    std::lock_guard<std::mutex> lk(mu);
-    job++;
-    cv.notify_all();
-  };
-  auto wait_parse = [&](int step) {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return done >= step; });
-  };
-  /* what a step leaves for the host once its copy down has arrived */
-  std::vector<uint8_t> refused((size_t)N, 0); /* -ilist: streams a kernel refused a frame of (their output has ended) */
-  struct Pending {
-    bool valid, mono_twice, first;
-    int slot, which;
-    bool some_mono; /* a PS batch with streams that have no PS in this frame: their left samples also go to the right */
-  } pending = {false, false, false, 0, 0, false};
-  auto consume = [&]() {
-    if (!pending.valid) return;
-    HIP(hipEventSynchronize(ev_down[pending.slot]));
-    int16_t *h_pcm = h_pcm2[pending.slot];
-    const int32_t *h_status = h_status2[pending.slot];
-    const std::vector<int32_t> &alive = st[pending.which].status; /* 0: the stream delivered a frame in that step */
-    if (gputools) {
-      const int32_t *h_tstatus = h_tstatus2[pending.slot];
-      for (int i = 0; i < N; i++)
-        if (h_tstatus[i] < 0 && alive[(size_t)i] == 0 && !refused[(size_t)i]) { /* as for the SBR kernels' refusals below */
-          if (!list_mode) die("the AAC tools kernel refused a frame", i);
-          fprintf(stderr, "xaacdec_amd: stream %d: the AAC tools kernel refused a frame: the stream ends here\n", S.lo + i);
-          refused[(size_t)i] = 1;
-        }
-    }
-    if (sbr) { /* (rows of streams that are over re-run their last staging rows: what the kernels say about those is not looked at) */
-      const int rows = (pending.mono_twice || (n_ch == 1 && !esbr)) ? N : NC;
-      for (int i = 0; i < rows; i++) {
-        const size_t si = (size_t)(rows == N ? i : i / n_ch);
-        if (h_status[i] < 0 && alive[si] == 0 && !refused[si]) {
-          /* side info the kernels do not take (the boundary's own checks: a parser's output passes them, a damaged payload that
-             still parses may not).  One file of a list must not take the others' output along: that stream's output ends in
-             front of this frame, the batch goes on (its rows keep running; nothing more of them is written) */
-          if (!list_mode) die("the SBR kernels refused a frame", i);
-          fprintf(stderr, "xaacdec_amd: stream %zu: the SBR kernels refused a frame: the stream ends here\n", (size_t)S.lo + si);
-          refused[si] = 1;
-        }
-      }
-    }
-    if (pending.mono_twice) /* mono duplicated to stereo (api.c:3639-3660), from the back so that it can be done in place */
-      for (long k = (long)N * 2048 - 1; k >= 0; k--) h_pcm[2 * k] = h_pcm[2 * k + 1] = h_pcm[k];
-    if (pending.some_mono) { /* the same for the streams of a PS batch whose frame carried no PS: the bank pair wrote their left
-                                samples into the interleaved rows and left the right ones alone */
-      const std::vector<int32_t> &fl = st[pending.which].flags;
-      for (int i = 0; i < N; i++)
-        if (alive[(size_t)i] == 0 && fl[(size_t)i * 8 + 5] == 0)
-          for (int k = 0; k < 2048; k++) h_pcm[(size_t)i * 4096 + 2 * k + 1] = h_pcm[(size_t)i * 4096 + 2 * k];
-    }
-    lap(2);
-    const size_t skip = (!sbr && pending.first) ? (size_t)delay * out_ch : 0; /* the limiter's delay is cut from the first frame */
-    /* (with -esbr:1 the reference's command line decoder does not write an SBR stream's first frame:
-       test/decoder/ixheaacd_main.c:2181-2186) */
-    if (!(esbr && pending.first))
-      for (size_t i = 0; i < pcms.size(); i++)
-        if (alive[i] == 0 && !refused[i]) pcms[i].insert(pcms[i].end(), h_pcm + i * per * out_ch + skip, h_pcm + (i + 1) * per * out_ch);
-    for (int i = 1; verify && i < N; i++)
-      mismatched += memcmp(h_pcm, h_pcm + (size_t)i * per * out_ch, (size_t)per * out_ch * 2) != 0;
-    frames += st[pending.which].delivered;
-    if (pending.first) t_first = std::chrono::steady_clock::now(); /* the first step also loads the kernels' code objects */
-    pending.valid = false;
-    lap(3);
-  };
-  start_parse();
-  for (int step = 0;; step++) {
-    const int which = step % (3 * T), slot = step & 1;
-    if (step % T == 0) wait_parse(step / T);
-    Staging &s = st[which];
-    if (s.delivered == 0) break;
-    int16_t *d_pcm = d_pcm2[slot], *d_mono = d_mono2[slot];
-    int32_t *d_status = d_status2[slot];
-    bool mono_twice = false, some_mono = false;
-    if (s.delivered != N) {
-      if (!list_mode) die("streams of different lengths in one batch");
-      for (int i = 0; i < N; i++)
-        if (s.status[(size_t)i] != 0 && !ended[(size_t)i]) { /* this stream is over: the other rows go on, its own run idle */
-          ended[(size_t)i] = 1;
-          if (!sbr) HIP(hipMemcpy(&lim_at_end[(size_t)i], d_lim + i, sizeof(xaac_limiter_state), hipMemcpyDeviceToHost)); /* (waits for the step before) */
-        }
-    }
-    if (step % T == 0) start_parse(); /* the next group's frames are parsed while the GPU works on this one's */
-    t_phase = std::chrono::steady_clock::now();
-    { /* only the leading lines that are not zero in every delivered row go up, and what the device array still holds beyond
-         them from the step before (the host rows are zero there) */
-      const int width = s.lines > lines_held ? s.lines : lines_held;
-      lines_held = s.lines;
-      if (width >= 1024) HIP(hipMemcpyAsync(d_spec, s.spec, (size_t)NC * 4096, hipMemcpyHostToDevice, stream));
-      else if (width > 0) HIP(hipMemcpy2DAsync(d_spec, 4096, s.spec, 4096, (size_t)width * 4, (size_t)NC, hipMemcpyHostToDevice, stream));
-    }
-    HIP(hipMemcpyAsync(d_ics, s.ics, (size_t)NC * 2, hipMemcpyHostToDevice, stream));
-    if (gputools) HIP(hipMemcpyAsync(d_tside, s.tside, (size_t)N * sizeof(xaac_core_tools_side), hipMemcpyHostToDevice, stream));
-    lap(0);
-    if (gputools) { /* stage-1 spectra -> the spectra the IMDCT takes, in place (xaac_parse_batch::lines covers what they reach) */
-      xaac_aac_tools_batch tb;
-      memset(&tb, 0, sizeof(tb));
-      tb.n = N, tb.spec_stride = 1024 * n_ch, tb.spec = d_spec, tb.side = d_tside, tb.state = d_tstate, tb.status = d_tstatus2[slot];
-      XA(xaac_aac_tools_process_batch(ctx, &tb));
-    }
-    xaac_imdct_batch ib;
-    memset(&ib, 0, sizeof(ib));
-    ib.n_ch = NCD, ib.ch_fac = n_ch, ib.spec = d_spec, ib.ics = d_ics, ib.overlap = d_overlap, ib.state = d_ovl;
-    if (!sbr) { /* AAC-LC: IMDCT -> limiter -> round16 (api.c:3662-3692) */
-      ib.out32 = d_out32, ib.qshift_adj = d_qadj;
-      XA(xaac_imdct_process_batch(ctx, &ib));
-      xaac_limiter_batch lb;
-      memset(&lb, 0, sizeof(lb));
-      lb.n_streams = N, lb.frame_len = 1024, lb.samples = d_out32, lb.stride = 1024 * n_ch, lb.qshift_adj = d_qadj, lb.state = d_lim;
-      lb.num_channels = n_ch, lb.pcm16 = d_pcm, lb.workspace = d_ws, lb.workspace_bytes = ws_bytes;
-      XA(xaac_peak_limiter_process_batch(ctx, &lb));
-    } else if (esbr) { /* Path A: IMDCT -> float planes -> eSBR chain (+ transposer, float PS) -> samples_sat */
-      ib.pcm16 = d_core, ib.pcm_mode = XAAC_PCM_SBR;
-      XA(xaac_imdct_process_batch(ctx, &ib));
-      int resets = 0, with_ps = 0;
-      for (int i = 0; i < N; i++)
-        if (s.status[(size_t)i] == 0) resets += s.flags[(size_t)i * 8 + 1] != 0, with_ps += s.flags[(size_t)i * 8 + 5] != 0;
-      /* streams with and without PS in one step: the float PS launch copies left to right for those without (esbr_ps_kernel.hip) */
-      const size_t row = 64 * sizeof(float), st_pitch = sizeof(xaac_esbr_state), q_pitch = 2048 * sizeof(float);
-      float *older_re = d_older, *older_im = d_older + (size_t)NC * 24 * 64;
-      if (resets != 0 && hq) {
-        /* ixheaacd_sbr_dec_reset with -esbr_hq:1 (sbrdecoder.c:175-236): the resetting channels gathered into a compact batch (all
-           of them, or the few whose headers changed): ixheaacd_dft_hbe_data_reinit on the host (xaac_hbe_dft_state_reinit: sizes,
-           windows, matrices; a configuration is shared by the channels whose band tables are the same), then the transposer's
-           two runs over rows 8..39 and 40..71 of the QMF buffer as the frame before left it.  Its output rows are written whole
-           (rows32): the second run's last eight become the state's ph rows. */
-        std::vector<int> chs;
-        for (int i = 0; i < NC; i++)
-          if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[(size_t)(i / n_ch) * 8 + 1] != 0) chs.push_back(i);
-        const int nr = (int)chs.size();
-        if (!d_q) d_q = dev<float>((size_t)NC * 2 * 2048), d_pv = dev<float>((size_t)NC * 2 * 2048);
-        if (!d_idx) d_idx = dev<int32_t>((size_t)NC);
-        float *q_re = d_q, *q_im = d_q + (size_t)NC * 2048, *pv_re = d_pv, *pv_im = d_pv + (size_t)NC * 2048;
-        std::vector<int32_t> pitch((size_t)nr), slots((size_t)nr), ovs((size_t)nr);
-        HIP(hipStreamSynchronize(stream));
-        const auto d2d = [&](void *dst, const void *src, size_t bytes) { HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream)); };
-        static thread_local xaac_hbe_dft_state h0;
-        static thread_local xaac_hbe_dft_cfg c0;
-        static thread_local float k_re[64 * 128], k_im[64 * 128];
-        constexpr size_t kInts = sizeof(xaac_hbe_dft_state) - offsetof(xaac_hbe_dft_state, anal.analy_size); /* the integers behind the signals */
-        for (int k = 0; k < nr; k++) {
-          const int i = chs[(size_t)k];
-          const xaac_sbr_header &hd = s.header[(size_t)i];
-          memset(&h0, 0, sizeof(h0));
-          h0.max_stretch = dft_ms[(size_t)i];
-          if (xaac_hbe_dft_state_reinit(&h0, &c0, k_re, k_im, &hd)) die("the DFT transposer has no windows for the SBR band tables");
-          dft_ms[(size_t)i] = h0.max_stretch;
-          const std::string key(reinterpret_cast<const char *>(&hd.num_sf_bands[0]),
-                                reinterpret_cast<const char *>(&hd.freq_band_tbl_noise[0]) - reinterpret_cast<const char *>(&hd.num_sf_bands[0]));
-          const std::string key2 = key + std::string(reinterpret_cast<const char *>(&h0.max_stretch), 4);
-          auto it = dft_cfgs.find(key2);
-          if (it == dft_cfgs.end()) { /* a configuration no channel of the shard has had yet: its windows and matrices go up (synchronously: host temporaries) */
-            const int slot = (int)dft_cfgs.size();
-            if (slot >= NC) die("more DFT transposer configurations than channels");
-            it = dft_cfgs.emplace(key2, slot).first;
-            HIP(hipMemcpy(&d_dcfg[slot], &c0, sizeof(c0), hipMemcpyHostToDevice));
-            HIP(hipMemcpy(d_dcoef + (size_t)slot * 64 * 128, k_re, sizeof(k_re), hipMemcpyHostToDevice));
-            HIP(hipMemcpy(d_dcoef + ((size_t)NC + slot) * 64 * 128, k_im, sizeof(k_im), hipMemcpyHostToDevice));
-          }
-          dft_slot[(size_t)i] = slots[(size_t)k] = it->second;
-          HIP(hipMemcpy(&d_dft[i].anal.analy_size, &h0.anal.analy_size, kInts, hipMemcpyHostToDevice));
-          HIP(hipMemset(&d_dft[i].synth_buf[0], 0, sizeof(h0.synth_buf))); /* hbe_dft_trans.c:302 */
-          d2d(&d_dft_tmp[k], &d_dft[i], sizeof(xaac_hbe_dft_state));
-          pitch[(size_t)k] = s.reset_pitch[(size_t)(i / n_ch)];
-          ovs[(size_t)k] = dft_ovs[(size_t)i];
-          /* run 1: buffer rows 8..39 = the 24 older rows, then the state's first eight */
-          d2d(q_re + (size_t)k * 2048, older_re + (size_t)i * 24 * 64, 24 * row);
-          d2d(q_im + (size_t)k * 2048, older_im + (size_t)i * 24 * 64, 24 * row);
-          d2d(q_re + (size_t)k * 2048 + 24 * 64, &d_estate[i].qmf_re[0][0], 8 * row);
-          d2d(q_im + (size_t)k * 2048 + 24 * 64, &d_estate[i].qmf_im[0][0], 8 * row);
-        }
-        HIP(hipMemcpyAsync(d_idx, pitch.data(), (size_t)nr * 4, hipMemcpyHostToDevice, stream));
-        HIP(hipMemcpyAsync(d_dslot_tmp, slots.data(), (size_t)nr * 4, hipMemcpyHostToDevice, stream));
-        HIP(hipMemcpyAsync(d_dovs, ovs.data(), (size_t)nr * 4, hipMemcpyHostToDevice, stream));
-        HIP(hipMemcpyAsync(d_dslot, dft_slot.data(), (size_t)NC * 4, hipMemcpyHostToDevice, stream));
-        HIP(hipStreamSynchronize(stream)); /* (the vectors are host memory of this scope) */
-        xaac_hbe_dft_apply_batch db;
-        memset(&db, 0, sizeof(db));
-        db.n_ch = nr, db.qmf_re = q_re, db.qmf_im = q_im, db.pitch_in_bins = d_idx, db.oversampling = d_dovs, db.cfg_tab = d_dcfg;
-        db.coef_re = d_dcoef, db.coef_im = d_dcoef + (size_t)NC * 64 * 128, db.cfg = d_dslot_tmp, db.state = d_dft_tmp;
-        db.pv_re = pv_re, db.pv_im = pv_im, db.status = d_status, db.rows32 = 1;
-        XA(xaac_hbe_dft_apply_batch_run(ctx, &db));
-        for (int k = 0; k < nr; k++) { /* run 2: buffer rows 40..71 */
-          const int i = chs[(size_t)k];
-          d2d(q_re + (size_t)k * 2048, &d_estate[i].qmf_re[8][0], 32 * row);
-          d2d(q_im + (size_t)k * 2048, &d_estate[i].qmf_im[8][0], 32 * row);
-        }
-        XA(xaac_hbe_dft_apply_batch_run(ctx, &db));
-        for (int k = 0; k < nr; k++) {
-          const int i = chs[(size_t)k];
-          d2d(&d_estate[i].ph_re[0][0], pv_re + (size_t)k * 2048 + 24 * 64, 8 * row);
-          d2d(&d_estate[i].ph_im[0][0], pv_im + (size_t)k * 2048 + 24 * 64, 8 * row);
-          d2d(&d_dft[i], &d_dft_tmp[k], sizeof(xaac_hbe_dft_state));
-        }
-      } else if (resets != 0 && resets != s.delivered) {
-        /* Only some of the step's streams reset the SBR decoder (their headers changed: independent streams do that at
-           different frames).  The same sequence as below for every stream at once, on those streams' channels gathered into
-           a compact batch: their transposer states into d_hbe_tmp (new parameters from the band tables, delay lines
-           cleared), their rows into the first slots of the scratch planes, the two transposer runs over that batch, states
-           and ph rows back to their places.  The other streams' states are not touched. */
-        static thread_local xaac_hbe_state h0;
-        constexpr size_t kTail = sizeof(xaac_hbe_state) - offsetof(xaac_hbe_state, synth_size);
-        if (hbe_tail.empty()) hbe_tail.assign((size_t)NC * kTail, 0);
-        std::vector<int> chs;
-        for (int i = 0; i < NC; i++)
-          if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[(size_t)(i / n_ch) * 8 + 1] != 0) chs.push_back(i);
-        const int nr = (int)chs.size();
-        if (!d_hbe_tmp) d_hbe_tmp = dev<xaac_hbe_state>((size_t)NC);
-        if (!d_q) d_q = dev<float>((size_t)NC * 2 * 2048), d_pv = dev<float>((size_t)NC * 2 * 2048);
-        if (!d_idx) d_idx = dev<int32_t>((size_t)NC);
-        float *q_re = d_q, *q_im = d_q + (size_t)NC * 2048, *pv_re = d_pv, *pv_im = d_pv + (size_t)NC * 2048;
-        std::vector<int32_t> pitch((size_t)nr);
-        HIP(hipStreamSynchronize(stream));
-        const auto d2d = [&](void *dst, const void *src, size_t bytes) { HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream)); };
-        for (int k = 0; k < nr; k++) {
-          const int i = chs[(size_t)k];
-          xaac_hbe_state_init(&h0);
-          memcpy(&h0.synth_size, &hbe_tail[(size_t)i * kTail], kTail);
-          if (xaac_hbe_state_reinit(&h0, &s.header[(size_t)i])) die("the QMF transposer refused the SBR band tables");
-          memcpy(&hbe_tail[(size_t)i * kTail], &h0.synth_size, kTail);
-          d2d(&d_hbe_tmp[k], &d_hbe[i], sizeof(xaac_hbe_state));
-          HIP(hipMemcpyAsync(&d_hbe_tmp[k].synth_size, &hbe_tail[(size_t)i * kTail], kTail, hipMemcpyHostToDevice, stream));
-          HIP(hipMemsetAsync(&d_hbe_tmp[k].synth_buf[0], 0, sizeof(h0.synth_buf), stream));
-          HIP(hipMemsetAsync(&d_hbe_tmp[k].analy_buf[0], 0, sizeof(h0.analy_buf), stream));
-          pitch[(size_t)k] = s.reset_pitch[(size_t)(i / n_ch)];
-          /* run 1: buffer rows 8..39 = the 24 older rows, then the state's first eight */
-          d2d(q_re + (size_t)k * 2048, older_re + (size_t)i * 24 * 64, 24 * row);
-          d2d(q_im + (size_t)k * 2048, older_im + (size_t)i * 24 * 64, 24 * row);
-          d2d(q_re + (size_t)k * 2048 + 24 * 64, &d_estate[i].qmf_re[0][0], 8 * row);
-          d2d(q_im + (size_t)k * 2048 + 24 * 64, &d_estate[i].qmf_im[0][0], 8 * row);
-        }
-        HIP(hipMemcpyAsync(d_idx, pitch.data(), (size_t)nr * 4, hipMemcpyHostToDevice, stream));
-        HIP(hipStreamSynchronize(stream)); /* (pitch and the tails are host memory of this scope) */
-        xaac_hbe_apply_batch_desc hb;
-        memset(&hb, 0, sizeof(hb));
-        hb.n_ch = nr, hb.qmf_re = q_re, hb.qmf_im = q_im, hb.state = d_hbe_tmp, hb.pv_re = pv_re, hb.pv_im = pv_im, hb.status = d_status;
-        hb.pitch_in_bins = d_idx;
-        hb.max_synth_size = hbe_hint();
-        XA(xaac_hbe_apply_batch(ctx, &hb));
-        for (int k = 0; k < nr; k++) { /* run 2: buffer rows 40..71; its output rows 24..31 start from the state's ph rows */
-          const int i = chs[(size_t)k];
-          d2d(q_re + (size_t)k * 2048, &d_estate[i].qmf_re[8][0], 32 * row);
-          d2d(q_im + (size_t)k * 2048, &d_estate[i].qmf_im[8][0], 32 * row);
-          d2d(pv_re + (size_t)k * 2048 + 24 * 64, &d_estate[i].ph_re[0][0], 8 * row);
-          d2d(pv_im + (size_t)k * 2048 + 24 * 64, &d_estate[i].ph_im[0][0], 8 * row);
-        }
-        XA(xaac_hbe_apply_batch(ctx, &hb));
-        for (int k = 0; k < nr; k++) {
-          const int i = chs[(size_t)k];
-          d2d(&d_estate[i].ph_re[0][0], pv_re + (size_t)k * 2048 + 24 * 64, 8 * row);
-          d2d(&d_estate[i].ph_im[0][0], pv_im + (size_t)k * 2048 + 24 * 64, 8 * row);
-          d2d(&d_hbe[i], &d_hbe_tmp[k], sizeof(xaac_hbe_state));
-        }
-      } else if (resets) {
-        /* ixheaacd_sbr_dec_reset for Path A (sbrdecoder.c:175-236): the transposer's parameters from the new band tables (its
-           two delay lines cleared, hbe_trans.c:102-222), then its two runs over rows 8..39 and 40..71 of the QMF buffer (the codec bank's num_time_slots is 32) as the
-           frame before left it: rows 8..31 are what that frame found as its history rows 8..31 (d_older), rows 32..71 are
-           the state's history.  The second run's last eight output rows are the state's ph rows (bands outside
-           the transposer's range keep what they held). */
-        static thread_local xaac_hbe_state h0;
-        constexpr size_t kTail = sizeof(xaac_hbe_state) - offsetof(xaac_hbe_state, synth_size); /* the integers behind the buffers */
-        if (hbe_tail.empty()) hbe_tail.assign((size_t)NC * kTail, 0);
-        std::vector<uint8_t> &tail = hbe_tail;
-        for (int i = 0; i < NC; i++) {
-          xaac_hbe_state_init(&h0);
-          memcpy(&h0.synth_size, &tail[(size_t)i * kTail], kTail);
-          if (xaac_hbe_state_reinit(&h0, &s.header[(size_t)i])) die("the QMF transposer refused the SBR band tables");
-          memcpy(&tail[(size_t)i * kTail], &h0.synth_size, kTail);
-        }
-        HIP(hipStreamSynchronize(stream));
-        HIP(hipMemcpy2D(&d_hbe[0].synth_size, sizeof(xaac_hbe_state), tail.data(), kTail, kTail, (size_t)NC, hipMemcpyHostToDevice));
-        HIP(hipMemset2DAsync(&d_hbe[0].synth_buf[0], sizeof(xaac_hbe_state), 0, sizeof(h0.synth_buf), (size_t)NC, stream));
-        HIP(hipMemset2DAsync(&d_hbe[0].analy_buf[0], sizeof(xaac_hbe_state), 0, sizeof(h0.analy_buf), (size_t)NC, stream));
-        if (!d_q) d_q = dev<float>((size_t)NC * 2 * 2048), d_pv = dev<float>((size_t)NC * 2 * 2048);
-        float *q_re = d_q, *q_im = d_q + (size_t)NC * 2048, *pv_re = d_pv, *pv_im = d_pv + (size_t)NC * 2048;
-        xaac_hbe_apply_batch_desc hb;
-        memset(&hb, 0, sizeof(hb));
-        hb.n_ch = NC, hb.qmf_re = q_re, hb.qmf_im = q_im, hb.state = d_hbe, hb.pv_re = pv_re, hb.pv_im = pv_im, hb.status = d_status;
-        hb.max_synth_size = hbe_hint();
-        {
-          std::vector<int32_t> pitch((size_t)NC);
-          for (int i = 0; i < NC; i++) pitch[(size_t)i] = s.reset_pitch[(size_t)(i / n_ch)];
-          if (!d_idx) d_idx = dev<int32_t>((size_t)NC);
-          HIP(hipMemcpy(d_idx, pitch.data(), (size_t)NC * 4, hipMemcpyHostToDevice));
-          hb.pitch_in_bins = d_idx;
-        }
-        const auto copy_rows = [&](float *dst, size_t dpitch, const float *src, size_t spitch, int rows) {
-          HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, rows * row, (size_t)NC, hipMemcpyDeviceToDevice, stream));
-        };
-        /* run 1: buffer rows 8..39 */
-        copy_rows(q_re, q_pitch, older_re, 24 * row, 24);
-        copy_rows(q_im, q_pitch, older_im, 24 * row, 24);
-        copy_rows(q_re + 24 * 64, q_pitch, &d_estate[0].qmf_re[0][0], st_pitch, 8);
-        copy_rows(q_im + 24 * 64, q_pitch, &d_estate[0].qmf_im[0][0], st_pitch, 8);
-        XA(xaac_hbe_apply_batch(ctx, &hb));
-        /* run 2: buffer rows 40..71; its output rows 24..31 start from the state's ph rows */
-        copy_rows(q_re, q_pitch, &d_estate[0].qmf_re[8][0], st_pitch, 32);
-        copy_rows(q_im, q_pitch, &d_estate[0].qmf_im[8][0], st_pitch, 32);
-        copy_rows(pv_re + 24 * 64, q_pitch, &d_estate[0].ph_re[0][0], st_pitch, 8);
-        copy_rows(pv_im + 24 * 64, q_pitch, &d_estate[0].ph_im[0][0], st_pitch, 8);
-        XA(xaac_hbe_apply_batch(ctx, &hb));
-        copy_rows(&d_estate[0].ph_re[0][0], st_pitch, pv_re + 24 * 64, q_pitch, 8);
-        copy_rows(&d_estate[0].ph_im[0][0], st_pitch, pv_im + 24 * 64, q_pitch, 8);
-      }
-      /* what this frame finds as rows 8..31 of its history: the frame behind it may need them at a reset */
-      HIP(hipMemcpy2DAsync(older_re, 24 * row, &d_estate[0].qmf_re[8][0], st_pitch, 24 * row, (size_t)NC, hipMemcpyDeviceToDevice, stream));
-      HIP(hipMemcpy2DAsync(older_im, 24 * row, &d_estate[0].qmf_im[8][0], st_pitch, 24 * row, (size_t)NC, hipMemcpyDeviceToDevice, stream));
-      HIP(hipMemcpyAsync(d_header, s.header, (size_t)NC * sizeof(xaac_sbr_header), hipMemcpyHostToDevice, stream));
-      HIP(hipMemcpyAsync(d_frame, s.frame, (size_t)NC * sizeof(xaac_sbr_frame), hipMemcpyHostToDevice, stream));
-      HIP(hipMemcpyAsync(d_eside, s.eside, (size_t)NC * sizeof(xaac_esbr_side), hipMemcpyHostToDevice, stream));
-      xaac_esbr_core_in_batch cb = {NC, n_ch, d_core, d_fcore};
-      XA(xaac_esbr_core_from_pcm16_batch(ctx, &cb));
-      xaac_esbr_sbr_batch b;
-      memset(&b, 0, sizeof(b));
-      b.n_ch = NC, b.core = d_fcore, b.header = d_header, b.frame = d_frame, b.side = d_eside, b.state = d_estate, b.out = d_out_l;
-      b.status = d_status, b.workspace = d_ws, b.workspace_bytes = ws_bytes;
-      if (hq) {
-        b.hbe_dft_state = d_dft, b.hbe_dft_cfg_tab = d_dcfg, b.hbe_dft_cfg = d_dslot;
-        b.hbe_dft_coef_re = d_dcoef, b.hbe_dft_coef_im = d_dcoef + (size_t)NC * 64 * 128;
-        for (int i = 0; i < NC; i++) /* the flag the transposer keeps for a reset that may follow */
-          if (s.status[(size_t)(i / n_ch)] == 0 && s.frame[(size_t)i].apply_processing)
-            dft_ovs[(size_t)i] = (s.eside[(size_t)i].harmonic_sbr & XAAC_ESBR_OVERSAMPLING) ? 1 : 0;
-      } else {
-        b.hbe_state = d_hbe;
-        b.hbe_max_synth_size = hbe_hint();
-      }
-      xaac_esbr_pcm_out_batch ob = {N, 2048, d_out_l, d_out_l, d_pcm}; /* a mono channel twice (api.c:3639-3660) */
-      if (with_ps) {
-        HIP(hipMemcpyAsync(d_psf, s.ps, (size_t)N * sizeof(xaac_ps_frame), hipMemcpyHostToDevice, stream));
-        b.ps_frame = d_psf, b.ps_state = d_eps, b.out_r = d_out_r;
-        ob.right = d_out_r;
-        some_mono = with_ps != s.delivered; /* streams without PS in this step: no right channel comes back for them (their right
-                                               bank is left alone); their left samples are doubled on the host */
-      } else if (n_ch == 2) {
-        ob.stride = 4096, ob.right = d_out_l + 2048;
-      }
-      XA(xaac_esbr_sbr_process_batch(ctx, &b));
-      XA(xaac_esbr_pcm16_from_float_batch(ctx, &ob));
-    } else {
-      ib.pcm16 = d_core, ib.pcm_mode = XAAC_PCM_SBR;
-      XA(xaac_imdct_process_batch(ctx, &ib));
-      HIP(hipMemcpyAsync(d_header, s.header, (size_t)NC * sizeof(xaac_sbr_header), hipMemcpyHostToDevice, stream));
-      HIP(hipMemcpyAsync(d_frame, s.frame, (size_t)NC * sizeof(xaac_sbr_frame), hipMemcpyHostToDevice, stream));
-      { /* frames that reset the SBR decoder or fall back to plain up-sampling rewrite a few words of the resident state: on
-           the device, from the flag rows (a stream that is over keeps its last frame's flags: its row goes up as zeros) */
-        bool any = false;
-        for (int i = 0; i < N; i++) {
-          const int32_t *f = &s.flags[(size_t)i * 8];
-          any = any || (s.status[(size_t)i] == 0 && (f[1] || f[3]));
-        }
-        if (any) {
-          /* h_flags is one pinned buffer: an earlier step's copy up may still be reading it, so the stream is drained BEFORE the
-             rows are rewritten (rewriting first and draining behind, as this did, could hand that copy the new rows) */
-          HIP(hipStreamSynchronize(stream));
-          for (int i = 0; i < N; i++) {
-            const int32_t *f = &s.flags[(size_t)i * 8];
-            const bool live = s.status[(size_t)i] == 0;
-            for (int k = 0; k < 8; k++) h_flags[(size_t)i * 8 + k] = live ? f[k] : 0;
-          }
-          HIP(hipMemcpyAsync(d_flags, h_flags, (size_t)N * 8 * 4, hipMemcpyHostToDevice, stream));
-          xaac_sbr_apply_side_batch ab;
-          memset(&ab, 0, sizeof(ab));
-          ab.n_streams = N, ab.ch_fac = n_ch, ab.header = d_header, ab.flags = d_flags, ab.state = d_state;
-          ab.ps_state = n_ch == 1 ? d_ps_state : nullptr;
-          XA(xaac_sbr_state_apply_side_batch(ctx, &ab));
-        }
-      }
-      if (n_ch == 2) {
-        xaac_sbr_lp_batch b;
-        memset(&b, 0, sizeof(b));
-        b.n_ch = NC, b.in_ch_fac = 2, b.out_ch_fac = 2, b.pcm_in = d_core, b.header = d_header, b.frame = d_frame;
-        b.state = d_state, b.pcm_out = d_pcm, b.status = d_status, b.workspace = d_ws, b.workspace_bytes = ws_bytes;
-        XA(xaac_sbr_lp_process_batch(ctx, &b));
-      } else {
-        int with_ps = 0, starts = 0;
-        std::vector<int32_t> idx;
-        for (int i = 0; i < N; i++) {
-          with_ps += s.status[(size_t)i] == 0 && s.flags[(size_t)i * 8 + 5] != 0;
-          if (s.status[(size_t)i] == 0 && s.flags[(size_t)i * 8 + 6]) idx.push_back(i), starts++;
-        }
-        /* streams with and without parametric stereo in one step (independent HE-AAC / HE-AACv2 streams, or streams whose PS
-           starts at different frames): the batch runs with the PS launch, which passes a stream without PS through as the mono
-           frame it is (sbr_ps_kernel.hip: sbr_dec.c:1246) -- its right bank stays idle, its left samples are doubled on the host */
-        some_mono = with_ps != 0 && with_ps != s.delivered;
-        xaac_sbr_hq_batch b;
-        memset(&b, 0, sizeof(b));
-        b.n_ch = N, b.in_ch_fac = 1, b.out_ch_fac = 1, b.pcm_in = d_core, b.header = d_header, b.frame = d_frame;
-        b.state = d_state, b.status = d_status, b.workspace = d_ws, b.workspace_bytes = ws_bytes;
-        if (with_ps) {
-          if (starts) { /* the right bank starts from the left one's filter states (sbrdecoder.c:762-775) */
-            HIP(hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream));
-            HIP(hipStreamSynchronize(stream));
-            xaac_sbr_handover_batch hb;
-            memset(&hb, 0, sizeof(hb));
-            hb.n = starts, hb.mode = XAAC_HANDOVER_PS_START, hb.src = d_idx, hb.dst = d_idx, hb.state = d_state, hb.ps_state = d_ps_state;
-            XA(xaac_sbr_state_handover(ctx, &hb));
-          }
-          HIP(hipMemcpyAsync(d_psf, s.ps, (size_t)N * sizeof(xaac_ps_frame), hipMemcpyHostToDevice, stream));
-          b.ps_frame = d_psf, b.ps_state = d_ps_state, b.pcm_out = d_pcm;
-        } else {
-          b.pcm_out = d_mono;
-        }
-        XA(xaac_sbr_hq_process_batch(ctx, &b));
-        mono_twice = !with_ps;
-      }
-    }
-    lap(1);
-    HIP(hipEventRecord(ev_kernels[slot], stream));
-    HIP(hipStreamWaitEvent(down, ev_kernels[slot], 0));
-    if (mono_twice) HIP(hipMemcpyAsync(h_pcm2[slot], d_mono, (size_t)N * 2048 * 2, hipMemcpyDeviceToHost, down));
-    else HIP(hipMemcpyAsync(h_pcm2[slot], d_pcm, (size_t)N * per * out_ch * 2, hipMemcpyDeviceToHost, down));
-    if (sbr) HIP(hipMemcpyAsync(h_status2[slot], d_status, (size_t)NC * 4, hipMemcpyDeviceToHost, down));
-    if (gputools) HIP(hipMemcpyAsync(h_tstatus2[slot], d_tstatus2[slot], (size_t)N * 4, hipMemcpyDeviceToHost, down));
-    HIP(hipEventRecord(ev_down[slot], down));
-    consume(); /* the step before this one: its PCM has been on its way while this step's work was queued */
-    pending = {true, mono_twice, first, slot, which, some_mono};
-    if (profile) consume(); /* phase timing wants one step at a time */
-    first = false;
+  const Job &J_;
+  const int N_, lo_;
+  double &parse_s_;
+  std::vector<xaac_parser *> parser_;
+  std::vector<const uint8_t *> ptr_;
+  std::vector<uint64_t> left_, pos_;
+  std::vector<char> broken_; /* -ilist: a stream whose frame did not parse is treated as over from there on */
+  Staging st_[3 * T];
+  StagingGroup grp_[3];
+  std::mutex mu_;
+  std::condition_variable cv_;
+  int job_ = 0, done_ = -1;
+  bool quit_ = false;
+  std::thread worker_;
+};
+
+/* what the driver shows a chain or a stage: the shard's shape, its owner, the context and stream, and the per-step buffers
+   that are the same for every kind of stream */
+struct Env {
+  const Job &J;
+  int N, NC;
+  ShardOwner &mem;
+  xaac_ctx *ctx;
+  hipStream_t stream;
+  int32_t *d_spec;
+  int16_t *d_pcm[2];    /* PCM of a step, one per slot */
+  int32_t *d_status[2]; /* [NC] status words of a step's SBR kernels, one per slot */
+  xaac_imdct_batch imdct; /* the IMDCT over d_spec / d_ics / d_overlap / d_ovl; a chain adds where its output goes */
+};
+
+/* what the driver has to know of a step to bring its PCM down */
+struct StepOut {
+  const int16_t *d_pcm;
+  size_t bytes;
+  bool mono_twice; /* [N][2048] mono samples came down: the host doubles them to stereo */
+  bool some_mono;  /* a PS batch with streams that have no PS in this frame: their left samples also go to the right */
+  int status_rows; /* rows of the slot's d_status the step's kernels wrote (n_ch per stream), 0: none */
+};
+
+/* One kind of stream's work between the copies up and the copy down, with the device-resident states and buffers it needs:
+   picked once per shard.  A new kind of stream is a class with these members. */
+class Chain {
+ public:
+  virtual ~Chain() {}
+  virtual Wants wants() const = 0;
+  virtual StepOut run(const Staging &s, int slot) = 0; /* the step's own copies up and its kernels, on the shard's stream */
+  virtual void stream_ended(int) {}                    /* -ilist: stream i delivered its last frame in the step before */
+  virtual size_t first_frame_skip() const { return 0; }     /* int16 words cut from the front of every stream's first frame */
+  virtual bool drops_first_frame() const { return false; }  /* the first frame is decoded but not written */
+  virtual void finish(std::vector<std::vector<int16_t>> &) {} /* what the chain still holds of every stream's output */
+};
+
+/* -gputools:1: the tools' side rows, the streams' noise generators (zero for a new stream), the kernel's status words; the
+   driver runs this in front of whichever chain */
+class ToolsStage {
+ public:
+  explicit ToolsStage(const Env &E) : E_(E) {
+    const size_t N = (size_t)E.N;
+    d_side_ = E.mem.dev<xaac_core_tools_side>(N), d_state_ = E.mem.dev<xaac_core_tools_state>(N);
+    HIP(hipMemset(d_state_, 0, N * sizeof(xaac_core_tools_state)));
+    for (int k = 0; k < 2; k++) d_status_[k] = E.mem.dev<int32_t>(N), h_status_[k] = E.mem.pinned<int32_t>(N);
   }
-  consume();
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    quit = true;
-    cv.notify_all();
+  void send_up(const Staging &s) {
+    HIP(hipMemcpyAsync(d_side_, s.tside, (size_t)E_.N * sizeof(xaac_core_tools_side), hipMemcpyHostToDevice, E_.stream));
   }
-  worker.join();
-  const auto t_end = std::chrono::steady_clock::now();
-  S.wall = std::chrono::duration<double>(t_end - t_all).count();
-  S.steady = std::chrono::duration<double>(t_end - t_first).count();
-  if (!sbr) { /* the limiter's delay line holds the last attack_time_samples samples: api.c:2824-2866 */
+  void run(int slot) { /* stage-1 spectra -> the spectra the IMDCT takes, in place (xaac_parse_batch::lines covers what they reach) */
+    xaac_aac_tools_batch tb;
+    memset(&tb, 0, sizeof(tb));
+    tb.n = E_.N, tb.spec_stride = 1024 * E_.J.n_ch, tb.spec = E_.d_spec, tb.side = d_side_, tb.state = d_state_, tb.status = d_status_[slot];
+    XA(xaac_aac_tools_process_batch(E_.ctx, &tb));
+  }
+  void bring_down(int slot, hipStream_t down) {
+    HIP(hipMemcpyAsync(h_status_[slot], d_status_[slot], (size_t)E_.N * 4, hipMemcpyDeviceToHost, down));
+  }
+  const int32_t *status(int slot) const { return h_status_[slot]; }
+
+ private:
+  const Env E_;
+  xaac_core_tools_side *d_side_;
+  xaac_core_tools_state *d_state_;
+  int32_t *d_status_[2], *h_status_[2];
+};
+
+/* AAC-LC: IMDCT -> limiter -> round16 (api.c:3662-3692) */
+class LcChain : public Chain {
+ public:
+  explicit LcChain(const Env &E) : E_(E) {
+    const int N = E.N, n_ch = E.J.n_ch;
+    d_out32_ = E.mem.dev<int32_t>((size_t)N * 1024 * n_ch);
+    d_qadj_ = E.mem.dev<int8_t>((size_t)N * n_ch);
+    d_lim_ = E.mem.dev<xaac_limiter_state>((size_t)N);
+    xaac_limiter_state l0;
+    delay_ = xaac_peak_limiter_init(&l0, (uint32_t)n_ch, (uint32_t)E.J.rate);
+    if (delay_ < 0) die("xaac_peak_limiter_init", delay_);
+    for (int i = 0; i < N; i++) HIP(hipMemcpy(d_lim_ + i, &l0, sizeof(l0), hipMemcpyHostToDevice));
+    ws_bytes_ = xaac_peak_limiter_workspace_bytes(N);
+    d_ws_ = E.mem.workspace(ws_bytes_);
+    kept_.assign((size_t)N, 0);
+    if (E.J.list_mode) lim_at_end_.resize((size_t)N);
+  }
+  Wants wants() const override { return {false, false, false}; }
+  StepOut run(const Staging &, int slot) override {
+    const int N = E_.N, n_ch = E_.J.n_ch;
+    xaac_imdct_batch ib = E_.imdct;
+    ib.out32 = d_out32_, ib.qshift_adj = d_qadj_;
+    XA(xaac_imdct_process_batch(E_.ctx, &ib));
+    xaac_limiter_batch lb;
+    memset(&lb, 0, sizeof(lb));
+    lb.n_streams = N, lb.frame_len = 1024, lb.samples = d_out32_, lb.stride = 1024 * n_ch, lb.qshift_adj = d_qadj_, lb.state = d_lim_;
+    lb.num_channels = n_ch, lb.pcm16 = E_.d_pcm[slot], lb.workspace = d_ws_, lb.workspace_bytes = ws_bytes_;
+    XA(xaac_peak_limiter_process_batch(E_.ctx, &lb));
+    return {E_.d_pcm[slot], (size_t)N * E_.J.per * E_.J.out_ch * 2, false, false, 0};
+  }
+  void stream_ended(int i) override { /* the limiter state a stream leaves behind its last frame */
+    HIP(hipMemcpy(&lim_at_end_[(size_t)i], d_lim_ + i, sizeof(xaac_limiter_state), hipMemcpyDeviceToHost)); /* (waits for the step before) */
+    kept_[(size_t)i] = 1;
+  }
+  size_t first_frame_skip() const override { return (size_t)delay_ * E_.J.out_ch; } /* the limiter's delay is cut from the first frame */
+  void finish(std::vector<std::vector<int16_t>> &pcms) override {
+    /* the limiter's delay line holds the last attack_time_samples samples: api.c:2824-2866 */
+    const int n_ch = E_.J.n_ch;
     static thread_local xaac_limiter_state l;
     for (size_t i = 0; i < pcms.size(); i++) {
-      if (list_mode && ended[i]) l = lim_at_end[i];
-      else HIP(hipMemcpy(&l, d_lim + i, sizeof(l), hipMemcpyDeviceToHost));
+      if (kept_[i]) l = lim_at_end_[i];
+      else HIP(hipMemcpy(&l, d_lim_ + i, sizeof(l), hipMemcpyDeviceToHost));
       const uint32_t att = l.attack_time_samples, at = l.delayed_input_index;
       for (uint32_t k = 0; k < att; k++)
         for (int c = 0; c < n_ch; c++) {
@@ -913,6 +524,702 @@ void decode_shard(const Job &J, Shard &S) {
         }
     }
   }
+
+ private:
+  const Env E_;
+  int32_t *d_out32_;
+  int8_t *d_qadj_;
+  xaac_limiter_state *d_lim_;
+  void *d_ws_;
+  uint64_t ws_bytes_;
+  int delay_;
+  std::vector<xaac_limiter_state> lim_at_end_; /* -ilist: the limiter state a stream leaves behind its last frame */
+  std::vector<char> kept_;
+};
+
+/* -esbr:0, the fixed-point SBR tools: IMDCT -> low-power SBR for pairs, HQ SBR + parametric stereo for mono streams */
+class SbrChain : public Chain {
+ public:
+  explicit SbrChain(const Env &E) : E_(E), mono_(E.J.n_ch == 1) {
+    const int N = E.N, NC = E.NC;
+    d_core_ = E.mem.dev<int16_t>((size_t)NC * 1024);
+    d_header_ = E.mem.dev<xaac_sbr_header>((size_t)NC);
+    d_frame_ = E.mem.dev<xaac_sbr_frame>((size_t)NC);
+    d_state_ = E.mem.dev<xaac_sbr_state>((size_t)NC);
+    xaac_sbr_state s0;
+    xaac_sbr_state_init(&s0);
+    {
+      std::vector<xaac_sbr_state> all((size_t)NC, s0);
+      HIP(hipMemcpy(d_state_, all.data(), all.size() * sizeof(s0), hipMemcpyHostToDevice));
+    }
+    d_flags_ = E.mem.dev<int32_t>((size_t)N * 8), h_flags_ = E.mem.pinned<int32_t>((size_t)N * 8);
+    if (mono_) {
+      d_psf_ = E.mem.dev<xaac_ps_frame>((size_t)N);
+      d_ps_state_ = E.mem.dev<xaac_ps_state>((size_t)N);
+      d_mono_[0] = E.mem.dev<int16_t>((size_t)N * 2048), d_mono_[1] = E.mem.dev<int16_t>((size_t)N * 2048);
+      d_idx_ = E.mem.dev<int32_t>((size_t)N);
+      xaac_ps_state p0;
+      xaac_ps_state_init(&p0);
+      {
+        std::vector<xaac_ps_state> all((size_t)N, p0);
+        HIP(hipMemcpy(d_ps_state_, all.data(), all.size() * sizeof(p0), hipMemcpyHostToDevice));
+      }
+      ws_bytes_ = xaac_sbr_hq_workspace_bytes(N, 1);
+    } else {
+      ws_bytes_ = xaac_sbr_lp_workspace_bytes(NC);
+    }
+    d_ws_ = E.mem.workspace(ws_bytes_);
+  }
+  Wants wants() const override { return {true, mono_, false}; }
+  StepOut run(const Staging &s, int slot) override {
+    xaac_imdct_batch ib = E_.imdct;
+    ib.pcm16 = d_core_, ib.pcm_mode = XAAC_PCM_SBR;
+    XA(xaac_imdct_process_batch(E_.ctx, &ib));
+    HIP(hipMemcpyAsync(d_header_, s.header, (size_t)E_.NC * sizeof(xaac_sbr_header), hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_frame_, s.frame, (size_t)E_.NC * sizeof(xaac_sbr_frame), hipMemcpyHostToDevice, E_.stream));
+    apply_side(s);
+    return mono_ ? run_hq_ps(s, slot) : run_lp(slot);
+  }
+
+ private:
+  /* frames that reset the SBR decoder or fall back to plain up-sampling rewrite a few words of the resident state: on
+     the device, from the flag rows (a stream that is over keeps its last frame's flags: its row goes up as zeros) */
+  void apply_side(const Staging &s) {
+    const int N = E_.N;
+    bool any = false;
+    for (int i = 0; i < N; i++) {
+      const int32_t *f = &s.flags[(size_t)i * 8];
+      any = any || (s.status[(size_t)i] == 0 && (f[1] || f[3]));
+    }
+    if (!any) return;
+    /* h_flags is one pinned buffer: an earlier step's copy up may still be reading it, so the stream is drained BEFORE the
+       rows are rewritten (rewriting first and draining behind, as this did, could hand that copy the new rows) */
+    HIP(hipStreamSynchronize(E_.stream));
+    for (int i = 0; i < N; i++) {
+      const int32_t *f = &s.flags[(size_t)i * 8];
+      const bool live = s.status[(size_t)i] == 0;
+      for (int k = 0; k < 8; k++) h_flags_[(size_t)i * 8 + k] = live ? f[k] : 0;
+    }
+    HIP(hipMemcpyAsync(d_flags_, h_flags_, (size_t)N * 8 * 4, hipMemcpyHostToDevice, E_.stream));
+    xaac_sbr_apply_side_batch ab;
+    memset(&ab, 0, sizeof(ab));
+    ab.n_streams = N, ab.ch_fac = E_.J.n_ch, ab.header = d_header_, ab.flags = d_flags_, ab.state = d_state_;
+    ab.ps_state = mono_ ? d_ps_state_ : nullptr;
+    XA(xaac_sbr_state_apply_side_batch(E_.ctx, &ab));
+  }
+  StepOut run_lp(int slot) {
+    xaac_sbr_lp_batch b;
+    memset(&b, 0, sizeof(b));
+    b.n_ch = E_.NC, b.in_ch_fac = 2, b.out_ch_fac = 2, b.pcm_in = d_core_, b.header = d_header_, b.frame = d_frame_;
+    b.state = d_state_, b.pcm_out = E_.d_pcm[slot], b.status = E_.d_status[slot], b.workspace = d_ws_, b.workspace_bytes = ws_bytes_;
+    XA(xaac_sbr_lp_process_batch(E_.ctx, &b));
+    return {E_.d_pcm[slot], (size_t)E_.N * E_.J.per * E_.J.out_ch * 2, false, false, E_.NC};
+  }
+  StepOut run_hq_ps(const Staging &s, int slot) {
+    const int N = E_.N;
+    int with_ps = 0, starts = 0;
+    std::vector<int32_t> idx;
+    for (int i = 0; i < N; i++) {
+      with_ps += s.status[(size_t)i] == 0 && s.flags[(size_t)i * 8 + 5] != 0;
+      if (s.status[(size_t)i] == 0 && s.flags[(size_t)i * 8 + 6]) idx.push_back(i), starts++;
+    }
+    /* streams with and without parametric stereo in one step (independent HE-AAC / HE-AACv2 streams, or streams whose PS
+       starts at different frames): the batch runs with the PS launch, which passes a stream without PS through as the mono
+       frame it is (sbr_ps_kernel.hip: sbr_dec.c:1246) -- its right bank stays idle, its left samples are doubled on the host */
+    const bool some_mono = with_ps != 0 && with_ps != s.delivered;
+    xaac_sbr_hq_batch b;
+    memset(&b, 0, sizeof(b));
+    b.n_ch = N, b.in_ch_fac = 1, b.out_ch_fac = 1, b.pcm_in = d_core_, b.header = d_header_, b.frame = d_frame_;
+    b.state = d_state_, b.status = E_.d_status[slot], b.workspace = d_ws_, b.workspace_bytes = ws_bytes_;
+    if (with_ps) {
+      if (starts) { /* the right bank starts from the left one's filter states (sbrdecoder.c:762-775) */
+        HIP(hipMemcpyAsync(d_idx_, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, E_.stream));
+        HIP(hipStreamSynchronize(E_.stream));
+        xaac_sbr_handover_batch hb;
+        memset(&hb, 0, sizeof(hb));
+        hb.n = starts, hb.mode = XAAC_HANDOVER_PS_START, hb.src = d_idx_, hb.dst = d_idx_, hb.state = d_state_, hb.ps_state = d_ps_state_;
+        XA(xaac_sbr_state_handover(E_.ctx, &hb));
+      }
+      HIP(hipMemcpyAsync(d_psf_, s.ps, (size_t)N * sizeof(xaac_ps_frame), hipMemcpyHostToDevice, E_.stream));
+      b.ps_frame = d_psf_, b.ps_state = d_ps_state_, b.pcm_out = E_.d_pcm[slot];
+    } else {
+      b.pcm_out = d_mono_[slot];
+    }
+    XA(xaac_sbr_hq_process_batch(E_.ctx, &b));
+    if (!with_ps) return {d_mono_[slot], (size_t)N * 2048 * 2, true, some_mono, E_.NC};
+    return {E_.d_pcm[slot], (size_t)N * E_.J.per * E_.J.out_ch * 2, false, some_mono, E_.NC};
+  }
+
+  const Env E_;
+  const bool mono_;
+  int16_t *d_core_, *d_mono_[2] = {nullptr, nullptr};
+  xaac_sbr_header *d_header_;
+  xaac_sbr_frame *d_frame_;
+  xaac_sbr_state *d_state_;
+  xaac_ps_frame *d_psf_ = nullptr;
+  xaac_ps_state *d_ps_state_ = nullptr;
+  int32_t *d_idx_ = nullptr;
+  int32_t *d_flags_, *h_flags_; /* the parser's flag rows as xaac_sbr_state_apply_side_batch takes them */
+  void *d_ws_;
+  uint64_t ws_bytes_;
+};
+
+/* The channels one reset of the SBR decoder covers, and with that how their rows move between the channels' places and the
+   scratch planes of the reset-time transposer runs: every channel of the shard with a constant number of strided 2-D copies
+   (every stream's first frame: the whole batch), or the listed channels gathered into the first slots of the planes. */
+struct ResetSet {
+  bool gathered;
+  std::vector<int> chs; /* gathered: the channels, slot k of the planes holds channel chs[k] */
+  int n;                /* channels in the runs */
+  int units() const { return gathered ? n : 1; } /* a gathered channel each, or all channels at once */
+};
+struct RowMove {
+  float *scratch; /* in slot 0's plane */
+  void *home;     /* channel 0's rows; channel i's are `pitch` bytes times i further on */
+  size_t pitch;
+  int rows;
+};
+/* the scratch of the reset-time runs: [NC][32][64] planes of the transposer's input and output rows, and a word per channel */
+struct ResetScratch {
+  float *q_re, *q_im, *pv_re, *pv_im;
+  int32_t *idx;
+};
+
+/* Which harmonic transposer Path A runs with: what it keeps per channel, how a reset re-initialises it, its two reset-time
+   runs, and what it adds to a frame's batch. */
+class Transposer {
+ public:
+  virtual ~Transposer() {}
+  virtual bool always_gathers() const = 0; /* no strided form: a whole-batch reset gathers every channel */
+  virtual bool ph_rows_in() const = 0;     /* the second run's output rows 24..31 start from the state's ph rows */
+  virtual void new_parameters(const Staging &s, const ResetSet &R) = 0; /* host work in front of the drain */
+  virtual void stage(const Staging &s, const ResetSet &R, const ResetScratch &sc, int u) = 0; /* unit u's states made ready for the runs */
+  virtual void upload(const ResetSet &R, const ResetScratch &sc) = 0;   /* the runs' per-channel words */
+  virtual void run(const ResetSet &R, const ResetScratch &sc, int32_t *d_status) = 0;
+  virtual void back(const ResetSet &R, int u) = 0; /* unit u's states to their places */
+  virtual void attach(xaac_esbr_sbr_batch &b, const Staging &s) = 0;
+};
+
+/* the QMF transposer (the reference's default) */
+class QmfTransposer : public Transposer {
+ public:
+  explicit QmfTransposer(const Env &E) : E_(E) { d_hbe_ = E.mem.dev<xaac_hbe_state>((size_t)E.NC); /* all zero for a new stream */ }
+  bool always_gathers() const override { return false; }
+  bool ph_rows_in() const override { return true; }
+  /* the transposer's parameters from the new band tables (its two delay lines cleared, hbe_trans.c:102-222) */
+  void new_parameters(const Staging &s, const ResetSet &R) override {
+    static thread_local xaac_hbe_state h0;
+    if (tail_.empty()) tail_.assign((size_t)E_.NC * kTail, 0);
+    if (R.gathered && !d_tmp_) d_tmp_ = E_.mem.dev<xaac_hbe_state>((size_t)E_.NC);
+    pitch_.resize((size_t)R.n);
+    for (int k = 0; k < R.n; k++) {
+      const int i = R.gathered ? R.chs[(size_t)k] : k;
+      xaac_hbe_state_init(&h0);
+      memcpy(&h0.synth_size, &tail_[(size_t)i * kTail], kTail);
+      if (xaac_hbe_state_reinit(&h0, &s.header[(size_t)i])) die("the QMF transposer refused the SBR band tables");
+      memcpy(&tail_[(size_t)i * kTail], &h0.synth_size, kTail);
+      pitch_[(size_t)k] = s.reset_pitch[(size_t)(i / E_.J.n_ch)];
+    }
+  }
+  void stage(const Staging &, const ResetSet &R, const ResetScratch &sc, int u) override {
+    constexpr size_t kSynth = sizeof(xaac_hbe_state::synth_buf), kAnaly = sizeof(xaac_hbe_state::analy_buf);
+    if (R.gathered) { /* the channel's state into d_tmp_: new parameters from the band tables, delay lines cleared */
+      const int i = R.chs[(size_t)u];
+      HIP(hipMemcpyAsync(&d_tmp_[u], &d_hbe_[i], sizeof(xaac_hbe_state), hipMemcpyDeviceToDevice, E_.stream));
+      HIP(hipMemcpyAsync(&d_tmp_[u].synth_size, &tail_[(size_t)i * kTail], kTail, hipMemcpyHostToDevice, E_.stream));
+      HIP(hipMemsetAsync(&d_tmp_[u].synth_buf[0], 0, kSynth, E_.stream));
+      HIP(hipMemsetAsync(&d_tmp_[u].analy_buf[0], 0, kAnaly, E_.stream));
+    } else {
+      HIP(hipMemcpy2D(&d_hbe_[0].synth_size, sizeof(xaac_hbe_state), tail_.data(), kTail, kTail, (size_t)E_.NC, hipMemcpyHostToDevice));
+      HIP(hipMemset2DAsync(&d_hbe_[0].synth_buf[0], sizeof(xaac_hbe_state), 0, kSynth, (size_t)E_.NC, E_.stream));
+      HIP(hipMemset2DAsync(&d_hbe_[0].analy_buf[0], sizeof(xaac_hbe_state), 0, kAnaly, (size_t)E_.NC, E_.stream));
+      HIP(hipMemcpy(sc.idx, pitch_.data(), (size_t)R.n * 4, hipMemcpyHostToDevice));
+    }
+  }
+  void upload(const ResetSet &R, const ResetScratch &sc) override {
+    if (!R.gathered) return; /* (they went up with the states, by a copy that returns when it is done) */
+    HIP(hipMemcpyAsync(sc.idx, pitch_.data(), (size_t)R.n * 4, hipMemcpyHostToDevice, E_.stream));
+    HIP(hipStreamSynchronize(E_.stream)); /* (pitch and the tails are host memory of this scope) */
+  }
+  void run(const ResetSet &R, const ResetScratch &sc, int32_t *d_status) override {
+    xaac_hbe_apply_batch_desc hb;
+    memset(&hb, 0, sizeof(hb));
+    hb.n_ch = R.n, hb.qmf_re = sc.q_re, hb.qmf_im = sc.q_im, hb.state = R.gathered ? d_tmp_ : d_hbe_, hb.pv_re = sc.pv_re, hb.pv_im = sc.pv_im;
+    hb.status = d_status, hb.pitch_in_bins = sc.idx;
+    hb.max_synth_size = hint();
+    XA(xaac_hbe_apply_batch(E_.ctx, &hb));
+  }
+  void back(const ResetSet &R, int u) override {
+    if (R.gathered) HIP(hipMemcpyAsync(&d_hbe_[R.chs[(size_t)u]], &d_tmp_[u], sizeof(xaac_hbe_state), hipMemcpyDeviceToDevice, E_.stream));
+  }
+  void attach(xaac_esbr_sbr_batch &b, const Staging &) override {
+    b.hbe_state = d_hbe_;
+    b.hbe_max_synth_size = hint();
+  }
+
+ private:
+  static constexpr size_t kTail = sizeof(xaac_hbe_state) - offsetof(xaac_hbe_state, synth_size); /* the integers behind the buffers */
+  int32_t hint() const { /* the largest bank of the batch, as the ABI's LDS hint takes it: 8, or 0 = any */
+    int32_t smax = 0, v;
+    for (size_t i = 0; i * kTail < tail_.size(); i++) memcpy(&v, &tail_[i * kTail], 4), smax = v > smax ? v : smax;
+    return smax <= 8 ? 8 : 0;
+  }
+  const Env E_;
+  xaac_hbe_state *d_hbe_, *d_tmp_ = nullptr; /* d_tmp_: the resetting channels of a step gathered (partial resets) */
+  std::vector<uint8_t> tail_; /* every channel's transposer integers, kept between resets: some survive one (max_stretch, fft_ready) */
+  std::vector<int32_t> pitch_;
+};
+
+/* -esbr_hq:1: every channel's DFT transposer, the configurations their headers' band tables gave (shared by channels with the
+   same tables), and what the host keeps between resets: max_stretch (the re-initialisation leaves it alone when four patches
+   fit), the last processed frame's over_sampling_flag (the reset-time runs use the transposer's: sbr_dec.c:884 sets it) */
+class DftTransposer : public Transposer {
+ public:
+  explicit DftTransposer(const Env &E) : E_(E) {
+    const size_t NC = (size_t)E.NC;
+    d_dft_ = E.mem.dev<xaac_hbe_dft_state>(NC); /* all zero for a new stream: refused (last_status -1) until a header sets it up */
+    d_tmp_ = E.mem.dev<xaac_hbe_dft_state>(NC);
+    d_cfg_ = E.mem.dev<xaac_hbe_dft_cfg>(NC);
+    d_coef_ = E.mem.dev<float>(2 * NC * 64 * 128);
+    d_slot_ = E.mem.dev<int32_t>(NC), d_slot_tmp_ = E.mem.dev<int32_t>(NC), d_ovs_ = E.mem.dev<int32_t>(NC);
+    ms_.assign(NC, 0), ovs_.assign(NC, 0), slot_.assign(NC, 0);
+  }
+  bool always_gathers() const override { return true; }
+  bool ph_rows_in() const override { return false; } /* its output rows are written whole (rows32) */
+  void new_parameters(const Staging &, const ResetSet &R) override {
+    r_pitch_.resize((size_t)R.n), r_slot_.resize((size_t)R.n), r_ovs_.resize((size_t)R.n);
+  }
+  /* ixheaacd_dft_hbe_data_reinit on the host (xaac_hbe_dft_state_reinit: sizes, windows, matrices; a configuration is shared
+     by the channels whose band tables are the same), the channel's state into d_tmp_ */
+  void stage(const Staging &s, const ResetSet &R, const ResetScratch &, int u) override {
+    static thread_local xaac_hbe_dft_state h0;
+    static thread_local xaac_hbe_dft_cfg c0;
+    static thread_local float k_re[64 * 128], k_im[64 * 128];
+    constexpr size_t kInts = sizeof(xaac_hbe_dft_state) - offsetof(xaac_hbe_dft_state, anal.analy_size); /* the integers behind the signals */
+    const int i = R.chs[(size_t)u], NC = E_.NC;
+    const xaac_sbr_header &hd = s.header[(size_t)i];
+    memset(&h0, 0, sizeof(h0));
+    h0.max_stretch = ms_[(size_t)i];
+    if (xaac_hbe_dft_state_reinit(&h0, &c0, k_re, k_im, &hd)) die("the DFT transposer has no windows for the SBR band tables");
+    ms_[(size_t)i] = h0.max_stretch;
+    const std::string key(reinterpret_cast<const char *>(&hd.num_sf_bands[0]),
+                          reinterpret_cast<const char *>(&hd.freq_band_tbl_noise[0]) - reinterpret_cast<const char *>(&hd.num_sf_bands[0]));
+    const std::string key2 = key + std::string(reinterpret_cast<const char *>(&h0.max_stretch), 4);
+    auto it = cfgs_.find(key2);
+    if (it == cfgs_.end()) { /* a configuration no channel of the shard has had yet: its windows and matrices go up (synchronously: host temporaries) */
+      const int slot = (int)cfgs_.size();
+      if (slot >= NC) die("more DFT transposer configurations than channels");
+      it = cfgs_.emplace(key2, slot).first;
+      HIP(hipMemcpy(&d_cfg_[slot], &c0, sizeof(c0), hipMemcpyHostToDevice));
+      HIP(hipMemcpy(d_coef_ + (size_t)slot * 64 * 128, k_re, sizeof(k_re), hipMemcpyHostToDevice));
+      HIP(hipMemcpy(d_coef_ + ((size_t)NC + slot) * 64 * 128, k_im, sizeof(k_im), hipMemcpyHostToDevice));
+    }
+    slot_[(size_t)i] = r_slot_[(size_t)u] = it->second;
+    HIP(hipMemcpy(&d_dft_[i].anal.analy_size, &h0.anal.analy_size, kInts, hipMemcpyHostToDevice));
+    HIP(hipMemset(&d_dft_[i].synth_buf[0], 0, sizeof(h0.synth_buf))); /* hbe_dft_trans.c:302 */
+    HIP(hipMemcpyAsync(&d_tmp_[u], &d_dft_[i], sizeof(xaac_hbe_dft_state), hipMemcpyDeviceToDevice, E_.stream));
+    r_pitch_[(size_t)u] = s.reset_pitch[(size_t)(i / E_.J.n_ch)];
+    r_ovs_[(size_t)u] = ovs_[(size_t)i];
+  }
+  void upload(const ResetSet &R, const ResetScratch &sc) override {
+    HIP(hipMemcpyAsync(sc.idx, r_pitch_.data(), (size_t)R.n * 4, hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_slot_tmp_, r_slot_.data(), (size_t)R.n * 4, hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_ovs_, r_ovs_.data(), (size_t)R.n * 4, hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_slot_, slot_.data(), (size_t)E_.NC * 4, hipMemcpyHostToDevice, E_.stream));
+    HIP(hipStreamSynchronize(E_.stream)); /* (the vectors are host memory of this scope) */
+  }
+  void run(const ResetSet &R, const ResetScratch &sc, int32_t *d_status) override {
+    xaac_hbe_dft_apply_batch db;
+    memset(&db, 0, sizeof(db));
+    db.n_ch = R.n, db.qmf_re = sc.q_re, db.qmf_im = sc.q_im, db.pitch_in_bins = sc.idx, db.oversampling = d_ovs_, db.cfg_tab = d_cfg_;
+    db.coef_re = d_coef_, db.coef_im = d_coef_ + (size_t)E_.NC * 64 * 128, db.cfg = d_slot_tmp_, db.state = d_tmp_;
+    db.pv_re = sc.pv_re, db.pv_im = sc.pv_im, db.status = d_status, db.rows32 = 1;
+    XA(xaac_hbe_dft_apply_batch_run(E_.ctx, &db));
+  }
+  void back(const ResetSet &R, int u) override {
+    HIP(hipMemcpyAsync(&d_dft_[R.chs[(size_t)u]], &d_tmp_[u], sizeof(xaac_hbe_dft_state), hipMemcpyDeviceToDevice, E_.stream));
+  }
+  void attach(xaac_esbr_sbr_batch &b, const Staging &s) override {
+    b.hbe_dft_state = d_dft_, b.hbe_dft_cfg_tab = d_cfg_, b.hbe_dft_cfg = d_slot_;
+    b.hbe_dft_coef_re = d_coef_, b.hbe_dft_coef_im = d_coef_ + (size_t)E_.NC * 64 * 128;
+    for (int i = 0; i < E_.NC; i++) /* the flag the transposer keeps for a reset that may follow */
+      if (s.status[(size_t)(i / E_.J.n_ch)] == 0 && s.frame[(size_t)i].apply_processing)
+        ovs_[(size_t)i] = (s.eside[(size_t)i].harmonic_sbr & XAAC_ESBR_OVERSAMPLING) ? 1 : 0;
+  }
+
+ private:
+  const Env E_;
+  xaac_hbe_dft_state *d_dft_, *d_tmp_;
+  xaac_hbe_dft_cfg *d_cfg_;
+  float *d_coef_;                            /* [2][NC][64][128]: real matrices of the configurations, then the imaginary ones */
+  int32_t *d_slot_, *d_slot_tmp_, *d_ovs_;   /* [NC] configuration of a channel; of the gathered channels; their flags */
+  std::vector<int32_t> ms_, ovs_, slot_;     /* per channel: max_stretch, over_sampling_flag, configuration */
+  std::vector<int32_t> r_pitch_, r_slot_, r_ovs_; /* per gathered channel of the reset at hand */
+  std::map<std::string, int> cfgs_;
+};
+
+/* -esbr:1, Path A: IMDCT -> float planes -> eSBR chain (+ transposer, float PS) -> samples_sat */
+class EsbrChain : public Chain {
+ public:
+  explicit EsbrChain(const Env &E) : E_(E), mono_(E.J.n_ch == 1) {
+    const int N = E.N, NC = E.NC;
+    d_core_ = E.mem.dev<int16_t>((size_t)NC * 1024);
+    d_header_ = E.mem.dev<xaac_sbr_header>((size_t)NC);
+    d_frame_ = E.mem.dev<xaac_sbr_frame>((size_t)NC);
+    d_eside_ = E.mem.dev<xaac_esbr_side>((size_t)NC);
+    d_estate_ = E.mem.dev<xaac_esbr_state>((size_t)NC);
+    if (E.J.hq) tr_.reset(new DftTransposer(E));
+    else tr_.reset(new QmfTransposer(E));
+    d_fcore_ = E.mem.dev<float>((size_t)NC * 1024);
+    d_out_l_ = E.mem.dev<float>((size_t)NC * 2048);
+    d_older_ = E.mem.dev<float>((size_t)2 * NC * 24 * 64);
+    static thread_local xaac_esbr_state e0; /* (thread_local: one shard per device thread) */
+    xaac_esbr_state_init(&e0);
+    for (int i = 0; i < NC; i++) HIP(hipMemcpy(d_estate_ + i, &e0, sizeof(e0), hipMemcpyHostToDevice));
+    if (mono_) {
+      d_psf_ = E.mem.dev<xaac_ps_frame>((size_t)N);
+      d_eps_ = E.mem.dev<xaac_esbr_ps_state>((size_t)N);
+      d_out_r_ = E.mem.dev<float>((size_t)N * 2048);
+      static thread_local xaac_esbr_ps_state p0;
+      xaac_esbr_ps_state_init(&p0);
+      for (int i = 0; i < N; i++) HIP(hipMemcpy(d_eps_ + i, &p0, sizeof(p0), hipMemcpyHostToDevice));
+    }
+    ws_bytes_ = xaac_esbr_workspace_bytes(NC);
+    d_ws_ = E.mem.workspace(ws_bytes_);
+  }
+  Wants wants() const override { return {true, mono_, true}; }
+  /* (with -esbr:1 the reference's command line decoder does not write an SBR stream's first frame:
+     test/decoder/ixheaacd_main.c:2181-2186) */
+  bool drops_first_frame() const override { return true; }
+  StepOut run(const Staging &s, int slot) override {
+    const int N = E_.N, NC = E_.NC;
+    xaac_imdct_batch ib = E_.imdct;
+    ib.pcm16 = d_core_, ib.pcm_mode = XAAC_PCM_SBR;
+    XA(xaac_imdct_process_batch(E_.ctx, &ib));
+    int resets = 0, with_ps = 0;
+    for (int i = 0; i < N; i++)
+      if (s.status[(size_t)i] == 0) resets += s.flags[(size_t)i * 8 + 1] != 0, with_ps += s.flags[(size_t)i * 8 + 5] != 0;
+    if (resets) reset_runs(s, slot, resets == s.delivered);
+    /* what this frame finds as rows 8..31 of its history: the frame behind it may need them at a reset */
+    float *older_re = d_older_, *older_im = d_older_ + (size_t)NC * 24 * 64;
+    HIP(hipMemcpy2DAsync(older_re, 24 * kRow, &d_estate_[0].qmf_re[8][0], kStatePitch, 24 * kRow, (size_t)NC, hipMemcpyDeviceToDevice, E_.stream));
+    HIP(hipMemcpy2DAsync(older_im, 24 * kRow, &d_estate_[0].qmf_im[8][0], kStatePitch, 24 * kRow, (size_t)NC, hipMemcpyDeviceToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_header_, s.header, (size_t)NC * sizeof(xaac_sbr_header), hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_frame_, s.frame, (size_t)NC * sizeof(xaac_sbr_frame), hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_eside_, s.eside, (size_t)NC * sizeof(xaac_esbr_side), hipMemcpyHostToDevice, E_.stream));
+    xaac_esbr_core_in_batch cb = {NC, E_.J.n_ch, d_core_, d_fcore_};
+    XA(xaac_esbr_core_from_pcm16_batch(E_.ctx, &cb));
+    xaac_esbr_sbr_batch b;
+    memset(&b, 0, sizeof(b));
+    b.n_ch = NC, b.core = d_fcore_, b.header = d_header_, b.frame = d_frame_, b.side = d_eside_, b.state = d_estate_, b.out = d_out_l_;
+    b.status = E_.d_status[slot], b.workspace = d_ws_, b.workspace_bytes = ws_bytes_;
+    tr_->attach(b, s);
+    bool some_mono = false;
+    xaac_esbr_pcm_out_batch ob = {N, 2048, d_out_l_, d_out_l_, E_.d_pcm[slot]}; /* a mono channel twice (api.c:3639-3660) */
+    /* streams with and without PS in one step: the float PS launch copies left to right for those without (esbr_ps_kernel.hip) */
+    if (with_ps) {
+      HIP(hipMemcpyAsync(d_psf_, s.ps, (size_t)N * sizeof(xaac_ps_frame), hipMemcpyHostToDevice, E_.stream));
+      b.ps_frame = d_psf_, b.ps_state = d_eps_, b.out_r = d_out_r_;
+      ob.right = d_out_r_;
+      some_mono = with_ps != s.delivered; /* streams without PS in this step: no right channel comes back for them (their right
+                                             bank is left alone); their left samples are doubled on the host */
+    } else if (!mono_) {
+      ob.stride = 4096, ob.right = d_out_l_ + 2048;
+    }
+    XA(xaac_esbr_sbr_process_batch(E_.ctx, &b));
+    XA(xaac_esbr_pcm16_from_float_batch(E_.ctx, &ob));
+    return {E_.d_pcm[slot], (size_t)N * E_.J.per * E_.J.out_ch * 2, false, some_mono, NC};
+  }
+
+ private:
+  static constexpr size_t kRow = 64 * sizeof(float), kStatePitch = sizeof(xaac_esbr_state), kPlanePitch = 2048 * sizeof(float);
+
+  /* rows between the channels' places and the scratch planes, `in` to the planes or back: a strided 2-D copy per move over
+     every channel, or a copy per move for unit u's channel */
+  void move_rows(const ResetSet &R, int u, bool in, std::initializer_list<RowMove> moves) {
+    for (const RowMove &m : moves) {
+      if (R.gathered) {
+        float *plane = m.scratch + (size_t)u * 2048;
+        void *home = static_cast<char *>(m.home) + (size_t)R.chs[(size_t)u] * m.pitch;
+        HIP(hipMemcpyAsync(in ? (void *)plane : home, in ? home : (void *)plane, m.rows * kRow, hipMemcpyDeviceToDevice, E_.stream));
+      } else if (in) {
+        HIP(hipMemcpy2DAsync(m.scratch, kPlanePitch, m.home, m.pitch, m.rows * kRow, (size_t)E_.NC, hipMemcpyDeviceToDevice, E_.stream));
+      } else {
+        HIP(hipMemcpy2DAsync(m.home, m.pitch, m.scratch, kPlanePitch, m.rows * kRow, (size_t)E_.NC, hipMemcpyDeviceToDevice, E_.stream));
+      }
+    }
+  }
+
+  /* ixheaacd_sbr_dec_reset for Path A (sbrdecoder.c:175-236): the transposer's parameters from the new band tables (its
+     two delay lines cleared, hbe_trans.c:102-222; with -esbr_hq:1 ixheaacd_dft_hbe_data_reinit), then its two runs over rows
+     8..39 and 40..71 of the QMF buffer (the codec bank's num_time_slots is 32) as the frame before left it: rows 8..31 are
+     what that frame found as its history rows 8..31 (d_older_), rows 32..71 are the state's history.  The second run's last
+     eight output rows are the state's ph rows (bands outside the transposer's range keep what they held).
+     `every`: all the step's delivered streams reset (every stream's first frame) -- the QMF transposer then runs on the states
+     where they are and the rows move with strided copies over all channels.  Otherwise only some streams reset (their headers
+     changed: independent streams do that at different frames), or the transposer has no strided form: the same sequence on
+     those streams' channels gathered into a compact batch -- their transposer states into a second array, their rows into
+     the first slots of the scratch planes, the two runs over that batch, states and ph rows back to their places.  The other
+     streams' states are not touched. */
+  void reset_runs(const Staging &s, int slot, bool every) {
+    const int NC = E_.NC, n_ch = E_.J.n_ch;
+    ResetSet R;
+    R.gathered = tr_->always_gathers() || !every;
+    if (R.gathered)
+      for (int i = 0; i < NC; i++)
+        if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[(size_t)(i / n_ch) * 8 + 1] != 0) R.chs.push_back(i);
+    R.n = R.gathered ? (int)R.chs.size() : NC;
+    if (!sc_.q_re) {
+      sc_.q_re = E_.mem.dev<float>((size_t)NC * 2 * 2048), sc_.pv_re = E_.mem.dev<float>((size_t)NC * 2 * 2048);
+      sc_.q_im = sc_.q_re + (size_t)NC * 2048, sc_.pv_im = sc_.pv_re + (size_t)NC * 2048;
+      sc_.idx = E_.mem.dev<int32_t>((size_t)NC);
+    }
+    float *older_re = d_older_, *older_im = d_older_ + (size_t)NC * 24 * 64;
+    xaac_esbr_state *st = d_estate_;
+    tr_->new_parameters(s, R);
+    HIP(hipStreamSynchronize(E_.stream));
+    for (int u = 0; u < R.units(); u++) {
+      tr_->stage(s, R, sc_, u);
+      /* run 1: buffer rows 8..39 = the 24 older rows, then the state's first eight */
+      move_rows(R, u, true, {{sc_.q_re, older_re, 24 * kRow, 24}, {sc_.q_im, older_im, 24 * kRow, 24},
+                             {sc_.q_re + 24 * 64, &st[0].qmf_re[0][0], kStatePitch, 8}, {sc_.q_im + 24 * 64, &st[0].qmf_im[0][0], kStatePitch, 8}});
+    }
+    tr_->upload(R, sc_);
+    tr_->run(R, sc_, E_.d_status[slot]);
+    for (int u = 0; u < R.units(); u++) { /* run 2: buffer rows 40..71; its output rows 24..31 start from the state's ph rows */
+      move_rows(R, u, true, {{sc_.q_re, &st[0].qmf_re[8][0], kStatePitch, 32}, {sc_.q_im, &st[0].qmf_im[8][0], kStatePitch, 32}});
+      if (tr_->ph_rows_in())
+        move_rows(R, u, true, {{sc_.pv_re + 24 * 64, &st[0].ph_re[0][0], kStatePitch, 8}, {sc_.pv_im + 24 * 64, &st[0].ph_im[0][0], kStatePitch, 8}});
+    }
+    tr_->run(R, sc_, E_.d_status[slot]);
+    for (int u = 0; u < R.units(); u++) {
+      move_rows(R, u, false, {{sc_.pv_re + 24 * 64, &st[0].ph_re[0][0], kStatePitch, 8}, {sc_.pv_im + 24 * 64, &st[0].ph_im[0][0], kStatePitch, 8}});
+      tr_->back(R, u);
+    }
+  }
+
+  const Env E_;
+  const bool mono_;
+  int16_t *d_core_;
+  xaac_sbr_header *d_header_;
+  xaac_sbr_frame *d_frame_;
+  xaac_esbr_side *d_eside_;
+  xaac_esbr_state *d_estate_;
+  xaac_ps_frame *d_psf_ = nullptr;
+  xaac_esbr_ps_state *d_eps_ = nullptr;
+  float *d_fcore_, *d_out_l_, *d_out_r_ = nullptr;
+  float *d_older_; /* [2][NC][24][64]: rows 8..31 of the QMF history as the frame before found them (see the reset) */
+  ResetScratch sc_ = {nullptr, nullptr, nullptr, nullptr, nullptr}; /* made at the first reset */
+  std::unique_ptr<Transposer> tr_;
+  void *d_ws_;
+  uint64_t ws_bytes_;
+};
+
+/* What every kind of stream shares in a shard: the context and the `stream` / `down` pair with their events, spectra, window
+   info and overlap on the device, the two PCM / status slots, the narrowed copy of the spectra, the step's PCM taken one step
+   late (Pending / consume), -profile, -verify and the counters.  The parse side feeds it, a tools stage may run in front, and
+   the chain picked at construction does the rest: the step loop has no test of the kind of stream. */
+class ShardDriver {
+ public:
+  ShardDriver(const Job &J, Shard &S, ShardOwner &mem) : J_(J), S_(S), N_(S.n), NC_(S.n * J.n_ch) {
+    const int N = N_, NC = NC_;
+    stream_ = mem.stream();
+    ctx_ = mem.context(stream_);
+    XA(xaac_warm_up(ctx_)); /* the kernels' code objects are on the device before the first batch (and the run's clock) */
+    /* device-resident state and per-step device buffers */
+    int32_t *d_overlap = mem.dev<int32_t>((size_t)NC * 512);
+    d_spec_ = mem.dev<int32_t>((size_t)NC * 1024);
+    xaac_ovl_state *d_ovl = mem.dev<xaac_ovl_state>((size_t)NC);
+    d_ics_ = mem.dev<xaac_ics_info>((size_t)NC);
+    /* PCM and status of a step in two sets: the copy down of step k (a second stream) runs beside the copies up and the kernels
+       of step k + 1 */
+    down_ = mem.stream();
+    Env E = {J, N, NC, mem, ctx_, stream_, d_spec_, {nullptr, nullptr}, {nullptr, nullptr}, {}};
+    for (int k = 0; k < 2; k++) {
+      E.d_pcm[k] = mem.dev<int16_t>((size_t)N * J.per * J.out_ch), h_pcm_[k] = mem.pinned<int16_t>((size_t)N * J.per * 2);
+      E.d_status[k] = mem.dev<int32_t>((size_t)NC), h_status_[k] = mem.pinned<int32_t>((size_t)NC);
+      ev_kernels_[k] = mem.event(), ev_down_[k] = mem.event();
+    }
+    memset(&E.imdct, 0, sizeof(E.imdct));
+    E.imdct.n_ch = NC, E.imdct.ch_fac = J.n_ch, E.imdct.spec = d_spec_, E.imdct.ics = d_ics_, E.imdct.overlap = d_overlap, E.imdct.state = d_ovl;
+    for (int k = 0; k < 2; k++) d_status_[k] = E.d_status[k];
+    if (J.gputools) tools_.reset(new ToolsStage(E));
+    /* the chain, picked once */
+    if (!J.sbr) chain_.reset(new LcChain(E));
+    else if (J.esbr) chain_.reset(new EsbrChain(E));
+    else chain_.reset(new SbrChain(E));
+    parse_.reset(new ParseSide(J, S, mem, chain_->wants()));
+    S.pcms.assign((size_t)(J.list_mode ? N : 1), std::vector<int16_t>()); /* every stream's output (-ilist), or stream 0's */
+    ended_.assign((size_t)N, 0), refused_.assign((size_t)N, 0);
+  }
+
+  void run() {
+    constexpr int T = ParseSide::T;
+    const auto t_all = std::chrono::steady_clock::now();
+    t_first_ = t_all;
+    bool first = true;
+    parse_->start();
+    for (int step = 0;; step++) {
+      const int which = step % (3 * T), slot = step & 1;
+      if (step % T == 0) parse_->wait(step / T);
+      const Staging &s = parse_->step(which);
+      if (s.delivered == 0) break;
+      if (s.delivered != N_) note_ended(s);
+      if (step % T == 0) parse_->start(); /* the next group's frames are parsed while the GPU works on this one's */
+      t_phase_ = std::chrono::steady_clock::now();
+      send_up(s);
+      lap(0);
+      if (tools_) tools_->run(slot);
+      const StepOut o = chain_->run(s, slot);
+      lap(1);
+      bring_down(o, slot);
+      consume(); /* the step before this one: its PCM has been on its way while this step's work was queued */
+      pending_ = {true, first, slot, &s, o};
+      if (J_.profile) consume(); /* phase timing wants one step at a time */
+      first = false;
+    }
+    consume();
+    parse_->stop();
+    const auto t_end = std::chrono::steady_clock::now();
+    S_.wall = std::chrono::duration<double>(t_end - t_all).count();
+    S_.steady = std::chrono::duration<double>(t_end - t_first_).count();
+    chain_->finish(S_.pcms);
+  }
+
+ private:
+  void lap(int k) { /* -profile: copies up, kernels, copies down, host work on the PCM */
+    if (!J_.profile) return;
+    HIP(hipStreamSynchronize(stream_));
+    const auto now = std::chrono::steady_clock::now();
+    S_.phase_s[k] += std::chrono::duration<double>(now - t_phase_).count();
+    t_phase_ = now;
+  }
+  void note_ended(const Staging &s) {
+    if (!J_.list_mode) die("streams of different lengths in one batch");
+    for (int i = 0; i < N_; i++)
+      if (s.status[(size_t)i] != 0 && !ended_[(size_t)i]) { /* this stream is over: the other rows go on, its own run idle */
+        ended_[(size_t)i] = 1;
+        chain_->stream_ended(i);
+      }
+  }
+  void send_up(const Staging &s) {
+    { /* only the leading lines that are not zero in every delivered row go up, and what the device array still holds beyond
+         them from the step before (the host rows are zero there) */
+      const int width = s.lines > lines_held_ ? s.lines : lines_held_;
+      lines_held_ = s.lines;
+      if (width >= 1024) HIP(hipMemcpyAsync(d_spec_, s.spec, (size_t)NC_ * 4096, hipMemcpyHostToDevice, stream_));
+      else if (width > 0) HIP(hipMemcpy2DAsync(d_spec_, 4096, s.spec, 4096, (size_t)width * 4, (size_t)NC_, hipMemcpyHostToDevice, stream_));
+    }
+    HIP(hipMemcpyAsync(d_ics_, s.ics, (size_t)NC_ * 2, hipMemcpyHostToDevice, stream_));
+    if (tools_) tools_->send_up(s);
+  }
+  void bring_down(const StepOut &o, int slot) {
+    HIP(hipEventRecord(ev_kernels_[slot], stream_));
+    HIP(hipStreamWaitEvent(down_, ev_kernels_[slot], 0));
+    HIP(hipMemcpyAsync(h_pcm_[slot], o.d_pcm, o.bytes, hipMemcpyDeviceToHost, down_));
+    if (o.status_rows) HIP(hipMemcpyAsync(h_status_[slot], d_status_[slot], (size_t)o.status_rows * 4, hipMemcpyDeviceToHost, down_));
+    if (tools_) tools_->bring_down(slot, down_);
+    HIP(hipEventRecord(ev_down_[slot], down_));
+  }
+  /* a kernel refused a frame of stream i: one file of a list must not take the others' output along, that stream's output ends
+     in front of this frame, the batch goes on (its rows keep running; nothing more of them is written) */
+  void refuse(size_t i, int row, const char *who) {
+    if (!J_.list_mode) die((std::string("the ") + who + " refused a frame").c_str(), row);
+    fprintf(stderr, "xaacdec_amd: stream %zu: the %s refused a frame: the stream ends here\n", (size_t)S_.lo + i, who);
+    refused_[i] = 1;
+  }
+  void consume() { /* what a step leaves for the host once its copy down has arrived */
+    if (!pending_.valid) return;
+    const int N = N_, per = J_.per, out_ch = J_.out_ch, n_ch = J_.n_ch;
+    HIP(hipEventSynchronize(ev_down_[pending_.slot]));
+    int16_t *h_pcm = h_pcm_[pending_.slot];
+    const int32_t *h_status = h_status_[pending_.slot];
+    const int32_t *alive = pending_.s->status; /* 0: the stream delivered a frame in that step */
+    if (tools_) {
+      const int32_t *h_tstatus = tools_->status(pending_.slot);
+      for (int i = 0; i < N; i++)
+        if (h_tstatus[i] < 0 && alive[i] == 0 && !refused_[(size_t)i]) /* as for the SBR kernels' refusals below */
+          refuse((size_t)i, i, "AAC tools kernel");
+    }
+    /* (rows of streams that are over re-run their last staging rows: what the kernels say about those is not looked at) */
+    for (int i = 0; i < pending_.out.status_rows; i++) {
+      const size_t si = (size_t)(i / n_ch);
+      /* side info the kernels do not take (the boundary's own checks: a parser's output passes them, a damaged payload that
+         still parses may not) */
+      if (h_status[i] < 0 && alive[si] == 0 && !refused_[si])
+        refuse(si, i, "SBR kernels");
+    }
+    if (pending_.out.mono_twice) /* mono duplicated to stereo (api.c:3639-3660), from the back so that it can be done in place */
+      for (long k = (long)N * 2048 - 1; k >= 0; k--) h_pcm[2 * k] = h_pcm[2 * k + 1] = h_pcm[k];
+    if (pending_.out.some_mono) { /* the same for the streams of a PS batch whose frame carried no PS: the bank pair wrote their left
+                                     samples into the interleaved rows and left the right ones alone */
+      const int32_t *fl = pending_.s->flags;
+      for (int i = 0; i < N; i++)
+        if (alive[i] == 0 && fl[(size_t)i * 8 + 5] == 0)
+          for (int k = 0; k < 2048; k++) h_pcm[(size_t)i * 4096 + 2 * k + 1] = h_pcm[(size_t)i * 4096 + 2 * k];
+    }
+    lap(2);
+    const size_t skip = pending_.first ? chain_->first_frame_skip() : 0;
+    std::vector<std::vector<int16_t>> &pcms = S_.pcms;
+    if (!(pending_.first && chain_->drops_first_frame()))
+      for (size_t i = 0; i < pcms.size(); i++)
+        if (alive[i] == 0 && !refused_[i]) pcms[i].insert(pcms[i].end(), h_pcm + i * per * out_ch + skip, h_pcm + (i + 1) * per * out_ch);
+    for (int i = 1; J_.verify && i < N; i++)
+      S_.mismatched += memcmp(h_pcm, h_pcm + (size_t)i * per * out_ch, (size_t)per * out_ch * 2) != 0;
+    S_.frames += pending_.s->delivered;
+    if (pending_.first) t_first_ = std::chrono::steady_clock::now(); /* the first step also loads the kernels' code objects */
+    pending_.valid = false;
+    lap(3);
+  }
+
+  const Job &J_;
+  Shard &S_;
+  const int N_, NC_;
+  xaac_ctx *ctx_;
+  hipStream_t stream_, down_;
+  hipEvent_t ev_kernels_[2], ev_down_[2];
+  int32_t *d_spec_;
+  xaac_ics_info *d_ics_;
+  int16_t *h_pcm_[2];
+  int32_t *d_status_[2], *h_status_[2];
+  std::unique_ptr<ToolsStage> tools_;
+  std::unique_ptr<Chain> chain_;
+  std::unique_ptr<ParseSide> parse_;
+  int lines_held_ = 0; /* leading spectral lines that may be non-zero in d_spec */
+  std::chrono::steady_clock::time_point t_phase_, t_first_;
+  std::vector<char> ended_;
+  std::vector<uint8_t> refused_; /* -ilist: streams a kernel refused a frame of (their output has ended) */
+  struct Pending { /* what a step leaves for the host once its copy down has arrived */
+    bool valid, first;
+    int slot;
+    const Staging *s;
+    StepOut out;
+  } pending_ = {false, false, 0, nullptr, {nullptr, 0, false, false, 0}};
+};
+
+/* a look at a stream's frame 0: sampling rate, channels, SBR or not (api.c:3369-3373: the SBR tools run for frames with an SBR
+   payload; a stream at 24 kHz and below has an SBR decoder object by implicit signalling, api.c:2160, which is never called
+   without payloads).  `report`: the parser's code goes into the message (the batch's first stream). */
+struct FirstFrame {
+  int rate, n_ch, sbr;
+};
+FirstFrame first_frame(const std::vector<uint8_t> &data, bool report) {
+  xaac_adts_header hdr;
+  if (xaac_adts_parse_header(data.data(), data.size(), &hdr)) die("ADTS header");
+  xaac_parser *probe = nullptr;
+  XA(xaac_parser_create(&probe));
+  xaac_core_frame cf;
+  size_t used = 0;
+  const int32_t rc = xaac_parse_adts_frame(probe, data.data(), data.size(), 1, &cf, &used);
+  if (rc) die("first frame", report ? rc : 0);
+  xaac_parser_destroy(probe);
+  return {hdr.sampling_rate, cf.n_ch, cf.sbr_bytes > 0};
+}
+
+void decode_shard(const Job &J, Shard &S) {
+  S.first_frames = S.n;
+  S.mem.reset(new ShardOwner(S.device)); /* main releases it behind the run's clock: the rates it prints never held a tear-down */
+  ShardDriver(J, S, *S.mem).run();
 }
 
 }  // namespace
@@ -975,36 +1282,16 @@ int main(int argc, char **argv) {
     fclose(f);
     datas[k].resize((size_t)n);
   }
-  const std::vector<uint8_t> &data = datas[0];
-  /* a look at frame 0: channels, SBR or not (api.c:3369-3373: the SBR tools run for frames with an SBR payload; a stream at
-     24 kHz and below has an SBR decoder object by implicit signalling, api.c:2160, which is never called without payloads) */
-  xaac_adts_header hdr;
-  if (xaac_adts_parse_header(data.data(), data.size(), &hdr)) die("ADTS header");
-  int n_ch, sbr;
-  {
-    xaac_parser *probe = nullptr;
-    XA(xaac_parser_create(&probe));
-    std::vector<xaac_core_frame> cf(1);
-    size_t used = 0;
-    const int32_t rc = xaac_parse_adts_frame(probe, data.data(), data.size(), 1, cf.data(), &used);
-    if (rc) die("first frame", rc);
-    n_ch = cf[0].n_ch;
-    sbr = cf[0].sbr_bytes > 0;
-    xaac_parser_destroy(probe);
-    for (size_t k = 1; k < datas.size(); k++) { /* -ilist: one kind of stream per batch */
-      xaac_adts_header h2;
-      if (xaac_adts_parse_header(datas[k].data(), datas[k].size(), &h2)) die("ADTS header");
-      XA(xaac_parser_create(&probe));
-      if (xaac_parse_adts_frame(probe, datas[k].data(), datas[k].size(), 1, cf.data(), &used)) die("first frame");
-      if (h2.sampling_rate != hdr.sampling_rate || cf[0].n_ch != n_ch || (cf[0].sbr_bytes > 0) != (sbr != 0))
-        die("-ilist: streams of different kinds (sampling rate, channels, SBR) in one batch");
-      xaac_parser_destroy(probe);
-    }
+  const FirstFrame f0 = first_frame(datas[0], true);
+  for (size_t k = 1; k < datas.size(); k++) { /* -ilist: one kind of stream per batch */
+    const FirstFrame f = first_frame(datas[k], false);
+    if (f.rate != f0.rate || f.n_ch != f0.n_ch || f.sbr != f0.sbr)
+      die("-ilist: streams of different kinds (sampling rate, channels, SBR) in one batch");
   }
+  const int n_ch = f0.n_ch, sbr = f0.sbr;
   if (!sbr) esbr = 0; /* AAC-LC streams decode the same either way */
   const int out_ch = sbr ? 2 : n_ch; /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC as coded */
-  const int N = ilist.empty() ? copies : (int)datas.size(), rate = hdr.sampling_rate, out_rate = sbr ? 2 * rate : rate, per = sbr ? 2048 : 1024;
-
+  const int N = ilist.empty() ? copies : (int)datas.size(), rate = f0.rate, out_rate = sbr ? 2 * rate : rate, per = sbr ? 2048 : 1024;
 
   /* the split: contiguous stream ranges over the devices, as bench.py --gpus N splits over ranks (a shard without streams is
      not started: -gpus larger than the batch uses as many devices as there are streams) */
@@ -1035,9 +1322,8 @@ int main(int argc, char **argv) {
   }
   Job J;
   J.datas = std::move(datas);
-  J.hdr = hdr;
   J.hq = hq;
-  J.n_ch = n_ch, J.sbr = sbr, J.esbr = esbr, J.out_ch = out_ch, J.rate = rate, J.out_rate = out_rate, J.per = per;
+  J.n_ch = n_ch, J.sbr = sbr, J.esbr = esbr, J.out_ch = out_ch, J.rate = rate, J.per = per;
   J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode, J.gputools = gputools;
   const auto t_run = std::chrono::steady_clock::now();
   if (gpus == 1) {
@@ -1048,6 +1334,7 @@ int main(int argc, char **argv) {
     for (auto &t : team) t.join();
   }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_run).count();
+  for (Shard &S : shards) S.mem.reset(); /* the shards are done: streams waited for, everything they allocated released */
   long frames = 0, mismatched = 0, first_frames = 0;
   double parse_s = 0, steady = 0, phase_s[4] = {0, 0, 0, 0};
   for (const Shard &S : shards) {
@@ -1061,16 +1348,17 @@ int main(int argc, char **argv) {
   const std::vector<int16_t> &pcm = shards[0].pcms[0];
   if (list_mode) {
     for (const Shard &S : shards)
-    for (size_t i = 0; i < S.pcms.size(); i++) {
-      std::string base = inputs[(size_t)S.lo + i];
-      const size_t slash = base.find_last_of('/');
-      if (slash != std::string::npos) base = base.substr(slash + 1);
-      const size_t dot = base.find_last_of('.');
-      if (dot != std::string::npos) base = base.substr(0, dot);
-      write_wav(odir + "/" + base + ".wav", S.pcms[i], out_ch, out_rate);
-    }
-  } else
-  write_wav(out, pcm, out_ch, out_rate);
+      for (size_t i = 0; i < S.pcms.size(); i++) {
+        std::string base = inputs[(size_t)S.lo + i];
+        const size_t slash = base.find_last_of('/');
+        if (slash != std::string::npos) base = base.substr(slash + 1);
+        const size_t dot = base.find_last_of('.');
+        if (dot != std::string::npos) base = base.substr(0, dot);
+        write_wav(odir + "/" + base + ".wav", S.pcms[i], out_ch, out_rate);
+      }
+  } else {
+    write_wav(out, pcm, out_ch, out_rate);
+  }
   if (!quiet && gpus > 1) { /* (the run's own line stays the last one) */
     printf("{\"per_gpu_frames_per_s\": [");
     for (size_t r = 0; r < shards.size(); r++) printf("%s%.1f", r ? ", " : "", shards[r].wall > 0 ? shards[r].frames / shards[r].wall : 0.0);
