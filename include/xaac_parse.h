@@ -51,7 +51,7 @@ typedef struct xaac_adts_header {
 
 /* one decoded AAC-LC core frame: what ixheaacd_imdct_process (decoder/ixheaacd_lpfuncs.c:347) is handed per channel */
 typedef struct xaac_core_frame {
-  int32_t n_ch;            /* 1 (SCE) or 2 (CPE) */
+  int32_t n_ch;            /* 1 (SCE, LFE) or 2 (CPE) */
   int32_t element_id;      /* 0 SCE, 1 CPE, 3 LFE */
   int32_t common_window;
   int32_t sbr_ext_type;    /* 0: no SBR payload; 13 SBR_EXTENSION, 14 SBR_EXTENSION_CRC */
@@ -103,6 +103,28 @@ XAAC_API int32_t xaac_adts_parse_header(const uint8_t *data, size_t n, xaac_adts
 XAAC_API int32_t xaac_parse_adts_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, xaac_core_frame *out,
                               size_t *consumed);
 
+/* The same for a stream of several channel elements -- ADTS channel_config 3 .. 6: SCE CPE | SCE CPE SCE | SCE CPE CPE |
+   SCE CPE CPE LFE --: one xaac_core_frame per channel element in bitstream order into elems[0 .. *n_elems) (element_id 3 marks
+   the LFE), with the FIL / DSE / PCE elements between them read as xaac_parse_adts_frame reads them; a CCE is
+   XAAC_PARSE_ERR_UNSUPPORTED.  Such a stream's spectra carry the reference's arithmetic for more than two channels in every
+   element (scale factors with q_factor 34, block.c:1263; three bits down behind the stereo tools, channel.c:642-652; the 32-bit
+   TNS variant, pns_js_thumb.c:328-475), and every element has its own noise generator and window state, as the reference keeps
+   one core decoder instance per element (api.c:2433-2458).  The one thing its elements share, the seeds of correlated noise
+   bands (xaac_core_tools_state::pns_corr_seed: scratch memory there), is per element here; it shows only in a right channel
+   that substitutes noise in a correlated band whose left channel does not, and a frame with such a band is
+   XAAC_PARSE_ERR_UNSUPPORTED rather than decoded differently.
+   A stream of any other channel_config is taken with one channel element per frame, as xaac_parse_adts_frame takes it.
+   THIS FRONT END'S RULE, not the reference's: the first frame fixes the stream's element sequence; a later frame with another
+   sequence, or a frame whose sequence is not the one of its channel_config, is XAAC_PARSE_ERR_UNSUPPORTED (the reference
+   routes whatever elements a frame brings to the slots its first frame set up).  cap: the length of elems (4 is enough);
+   a frame with more elements than that is XAAC_PARSE_ERR_SYNTAX.  xaac_parse_adts_frame itself keeps returning
+   XAAC_PARSE_ERR_UNSUPPORTED for a frame with a second channel element. */
+XAAC_API int32_t xaac_parse_adts_frame_mc(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, xaac_core_frame *elems,
+                                          int32_t cap, int32_t *n_elems, size_t *consumed);
+/* ... and xaac_parse_core_tools_side for channel element `element` of the frame xaac_parse_adts_frame_mc decoded last; the
+   caller keeps an xaac_core_tools_state per element */
+XAAC_API int32_t xaac_parse_core_tools_side_mc(xaac_parser *p, int32_t element, xaac_core_tools_side *side);
+
 /* The SBR / PS side info of the frame xaac_parse_adts_frame decoded last (its payload is in the parser; a frame without
    one counts as a frame whose SBR data is missing, as in the reference).  ps_enable: parametric stereo allowed (mono
    streams).  The first call fixes the stream's SBR configuration (output rate = twice the core rate).  Returns
@@ -143,7 +165,7 @@ XAAC_API int32_t xaac_inverse_quant(int32_t magnitude, int32_t *out);
  * entry points take -- that one cudaMemcpyAsync per array then moves.  Streams are independent, so is their parsing. */
 typedef struct xaac_parse_batch {
   int32_t n_streams;
-  int32_t n_ch;               /* core channels of every stream (1 or 2) */
+  int32_t n_ch;               /* core channels of every stream (1 or 2; 3 .. 6 with channel_config below) */
   int32_t with_sbr;           /* also decode the SBR / PS side info (ps_enable as in xaac_parse_sbr_side) */
   int32_t ps_enable;
   int32_t stage;              /* as in xaac_parse_adts_frame */
@@ -184,6 +206,15 @@ typedef struct xaac_parse_batch {
                                  the tools on the GPU (xaac_aac_tools_process_batch).  `lines` then also covers what the tools can
                                  make non-zero: every line below the top of band max_sfb in the frame's last window, and the few
                                  lines a TNS filter runs beyond it */
+  int32_t channel_config;     /* 0: everything above as it stands (one channel element per frame).  3 .. 6 (appended with the
+                                 multichannel entry points; anything else is a bad descriptor): streams of that ADTS channel_config,
+                                 parsed as xaac_parse_adts_frame_mc parses them.  n_ch must be the configuration's channel count
+                                 (3, 4, 5, 6) and with_sbr 0, otherwise the call returns XAAC_PARSE_ERR_UNSUPPORTED.  spec is
+                                 [n_streams][n_ch][1024] and ics [n_streams][n_ch][2] with the channels in bitstream order; tools is
+                                 the OR over the elements, lines the maximum over the channels; tools_side is ELEMENT-MAJOR,
+                                 [frames][n_elems][n_streams] (n_elems = 2, 3, 3, 4): one element index's rows of all streams
+                                 lie together, as one xaac_aac_tools_process_batch call per element index takes them.  A stream
+                                 of another configuration gets the status XAAC_PARSE_ERR_UNSUPPORTED */
 } xaac_parse_batch;
 
 /* returns the number of streams whose status is XAAC_PARSE_OK, or a negative XAAC_PARSE_ERR_* for a bad descriptor */

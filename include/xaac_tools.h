@@ -30,7 +30,11 @@ typedef struct xaac_core_tools_channel {
   uint8_t num_groups;      /* 1 for long windows */
   uint8_t pns_active;
   uint8_t tns_present;
-  uint8_t reserved[3];
+  uint8_t wide;            /* the stream has more than two channels: the reference then keeps three more bits in the spectra up
+                              to the stereo tools (scale factors with q_factor 34, block.c:1263; shifted down behind them,
+                              channel.c:642-652) and runs the 32-bit TNS variant (pns_js_thumb.c:328-475).  The same in every
+                              channel of a stream */
+  uint8_t reserved[2];
   uint8_t group_len[8];    /* windows per group; they add up to 8 in an EIGHT_SHORT frame */
   uint8_t n_filt[8];       /* TNS filters per window (long windows: n_filt[0] only) */
   uint8_t cb[XAAC_TOOLS_BANDS];       /* code book per band: 13 noise, 14 / 15 intensity */

@@ -501,17 +501,21 @@ class XaacContext:
         if rc != 0:
             raise XaacError(rc, "xaac_imdct_process_batch")
 
-    def aac_tools_process_batch(self, spec, side, state, status=None, spec_stride=None):
+    def aac_tools_process_batch(self, spec, side, state, status=None, spec_stride=None, first_row=0):
         """The AAC spectral tools (M/S, intensity, PNS, TNS: the tool half of ixheaacd_channel_pair_process) on device tensors
         (asynchronous), in front of imdct_process_batch: spec int32[N, 2, 1024] (or [N, 1024] for mono elements) as the host
         parser's stage 1 delivers it, in / out; side uint8[N, CORE_TOOLS_SIDE_BYTES] (xaac_parse_core_tools_side); state
         uint8[N, CORE_TOOLS_STATE_BYTES] in / out (zero for a new stream); optional status int32[N]: 0, or -1 for side info
-        the tools refuse (that element is left untouched)."""
+        the tools refuse (that element is left untouched).  first_row: the element's first channel is row first_row of the
+        spec_stride / 1024 rows every stream has in spec (streams of several channel elements: one call per element index)."""
         n = side.shape[0]
         stride = int(spec_stride) if spec_stride is not None else spec.numel() // max(n, 1)
+        first_row = int(first_row)
+        if first_row < 0 or (first_row + 1) * 1024 > stride:
+            raise ValueError("first_row outside the rows of a stream")
         b = _AacToolsBatch()
         b.n, b.spec_stride = n, stride
-        b.spec = _ptr(spec, "int32", n * stride, device_ok=True)
+        b.spec = _ptr(spec, "int32", n * stride, device_ok=True) + 4096 * first_row
         b.side = _ptr(side, "uint8", n * CORE_TOOLS_SIDE_BYTES, device_ok=True)
         b.state = _ptr(state, "uint8", n * CORE_TOOLS_STATE_BYTES, device_ok=True)
         b.status = _ptr(status, "int32", n, allow_none=True, device_ok=True)

@@ -231,6 +231,47 @@ FX_HD int16_t xt_tns_parcor(const xaac_tns_filter_side &flt, int i) {
   return flt.resolution ? xt_tns_coef4[flt.coef[i] + 8] : xt_tns_coef3[flt.coef[i] + 4];
 }
 
+/* ... and the 32-bit variant streams of more than two channels take (pns_js_thumb.c:328-475): parcor and LPC coefficients in
+   Q31, the scale starts at 1 (aac_tns.c:93-145); z / w: work arrays of order + 1 words */
+FX_HD void xt_parcor_to_lpc32(const int32_t *parcor, int32_t *lpc, int *scale_out, int order, int32_t *z, int32_t *w) {
+  int status = 1, scale = 1;
+  while (status) {
+    status = 0;
+    for (int j = 0; j <= order; j++) z[j] = 0, w[j] = 0;
+    int32_t accu1 = 0x40000000 >> (scale - 1);
+    for (int i = 0; i <= order; i++) {
+      const int32_t z1 = accu1;
+      for (int j = 0; j < order; j++) {
+        w[j] = accu1;
+        accu1 = fx_add_sat(accu1, xt_mul32_shl_sat(parcor[j], z[j]));
+        if (fx_abs_sat(accu1) == 0x7fffffff) status = 1;
+      }
+      for (int j = order - 1; j >= 0; j--) {
+        const int32_t accu2 = fx_add_sat(z[j], xt_mul32_shl_sat(parcor[j], w[j]));
+        z[j + 1] = accu2;
+        if (fx_abs_sat(accu2) == 0x7fffffff) status = 1;
+      }
+      z[0] = z1;
+      lpc[i] = accu1;
+      accu1 = 0;
+    }
+    if (status) scale = (int16_t)(scale + 1);
+  }
+  *scale_out = scale;
+}
+FX_HD int32_t xt_tns_parcor32(const xaac_tns_filter_side &flt, int i) {
+  return flt.resolution ? xt_tns_coef4_q31[flt.coef[i] + 8] : xt_tns_coef3_q31[flt.coef[i] + 4];
+}
+/* the bits the filter keeps free above the region's lines: four; the 32-bit variant more, the more headroom the region leaves
+   (pns_js_thumb.c:391-401) */
+FX_HD int xt_tns_scale_spec(int headroom, int scale_lpc, int wide) {
+  return headroom - (wide ? (headroom > 17 ? 6 : headroom > 11 ? 5 : 4) : 4) - scale_lpc;
+}
+/* the lines of channel c that lose the three bits a stream of more than two channels carries up to here (channel.c:642-652) */
+FX_HD int xt_wide_shift_lines(const xaac_core_tools_side *s, int c) {
+  return xt_is_short(s->ch[c]) ? 1024 : xt_swb_long[s->sr_index][s->ch[c].max_sfb];
+}
+
 /* where one filter of window `win` works (pns_js_thumb.c:300-340, :420-450) */
 struct XtTnsPlan {
   int start, size; /* the region: lines start .. start + size - 1 of the window */
@@ -358,6 +399,31 @@ static inline void xt_tns_ar_filter(int32_t *x, int size, int inc, int16_t *lpc,
   }
 }
 
+/* ---- the serial filter of the 32-bit variant (streams of more than two channels) ---------------------------------------- */
+/* aac_tns.c:204-250: the all-pole filter on 32-bit coefficients, every product added up with saturation; the order is rounded
+   up to a multiple of four as in the 16-bit variant, and that many lines are filtered whether the region has them or not */
+static inline void xt_tns_ar_filter32(int32_t *x, int size, int inc, int32_t *lpc, int order, int shift_value, int scale_spec) {
+  int32_t state[32 + 1];
+  if (order & 3) {
+    int i;
+    for (i = order + 1; i < (order & ~3) + 4; i++) lpc[i] = 0;
+    lpc[i] = 0;
+    order = ((order & ~3) + 4) & 31;
+  }
+  const int n = size > order ? size : order;
+  for (int i = 0; i < n; i++) {
+    int32_t y = fx_shl_sat(*x, scale_spec), acc = 0;
+    for (int j = i < order ? i : order; j > 0; j--) {
+      acc = fx_add_sat(acc, fx_mulhi(state[j - 1], lpc[j]));
+      state[j] = state[j - 1];
+    }
+    y = fx_sub_sat(y, fx_shl_sat(acc, 1));
+    state[0] = fx_shl_sat(y, shift_value);
+    *x = y >> scale_spec;
+    x += inc;
+  }
+}
+
 /* spec: the channel's 1024 lines with XT_SLACK words of the caller's on either side */
 static inline void xt_tns_host(const xaac_core_tools_side *s, const xaac_core_tools_channel &ch, int32_t *spec) {
   const bool is_short = xt_is_short(ch);
@@ -372,15 +438,34 @@ static inline void xt_tns_host(const xaac_core_tools_side *s, const xaac_core_to
          an order above 12 (aac_core.cpp, channel.c:1021) */
       int16_t parcor[XAAC_TOOLS_TNS_MAX_ORDER + 1], lpc[XAAC_TOOLS_TNS_MAX_ORDER + 4 + 1], t1[XAAC_TOOLS_TNS_MAX_ORDER + 1],
           t2[XAAC_TOOLS_TNS_MAX_ORDER + 1];
-      for (int i = 0; i < flt.order; i++) parcor[i] = xt_tns_parcor(flt, i);
+      int32_t parcor32[XAAC_TOOLS_TNS_MAX_ORDER + 1], lpc32[XAAC_TOOLS_TNS_MAX_ORDER + 4 + 1];
       int scale_lpc;
-      xt_parcor_to_lpc(parcor, lpc, &scale_lpc, flt.order, t1, t2);
+      if (ch.wide) {
+        for (int i = 0; i < flt.order; i++) parcor32[i] = xt_tns_parcor32(flt, i);
+        int32_t z[XAAC_TOOLS_TNS_MAX_ORDER + 1], w[XAAC_TOOLS_TNS_MAX_ORDER + 1];
+        xt_parcor_to_lpc32(parcor32, lpc32, &scale_lpc, flt.order, z, w);
+      } else {
+        for (int i = 0; i < flt.order; i++) parcor[i] = xt_tns_parcor(flt, i);
+        xt_parcor_to_lpc(parcor, lpc, &scale_lpc, flt.order, t1, t2);
+      }
       int32_t *region = spec + (win << 7) + pl.start;
       int32_t m = 0;
       for (int i = 0; i < pl.size; i++) m |= xt_tns_mag_bits(region[i]);
-      int scale_spec = fx_norm32(m) - 4 - scale_lpc;
+      int scale_spec = xt_tns_scale_spec(fx_norm32(m), scale_lpc, ch.wide);
       int32_t *at = spec + pl.first;
-      if (scale_spec > 0) {
+      if (ch.wide) {
+        if (scale_spec > 0) {
+          if (scale_spec > 31) scale_spec = 31;
+          xt_tns_ar_filter32(at, pl.size, pl.inc, lpc32, flt.order, scale_lpc, scale_spec);
+        } else { /* as below */
+          int32_t *down = spec + pl.start;
+          scale_spec = -scale_spec;
+          if (scale_spec > 31) scale_spec = 31;
+          for (int i = 0; i < pl.size; i++) down[i] >>= scale_spec;
+          xt_tns_ar_filter32(at, pl.size, pl.inc, lpc32, flt.order, scale_lpc, 0);
+          for (int i = 0; i < pl.size; i++) region[i] = fx_shlw(region[i], scale_spec);
+        }
+      } else if (scale_spec > 0) {
         if (scale_spec > 31) scale_spec = 31;
         xt_tns_ar_filter(at, pl.size, pl.inc, lpc, flt.order, scale_lpc, scale_spec);
       } else {
@@ -452,6 +537,10 @@ static inline void xt_apply_host(const xaac_core_tools_side *s, xaac_core_tools_
   if (s->n_ch == 2) xt_stereo_host(s, spec0, spec1);
   for (int c = 0; c < s->n_ch; c++) {
     int32_t *spec = c ? spec1 : spec0;
+    if (s->ch[c].wide) { /* channel.c:642-652: the three bits the scale factors left on top (q_factor 34 instead of 37) come off here */
+      const int n = xt_wide_shift_lines(s, c);
+      for (int k = 0; k < n; k++) spec[k] >>= 3;
+    }
     xt_pns_host(s, c, spec, st);
     if (s->ch[c].tns_present) xt_tns_host(s, s->ch[c], spec);
   }

@@ -73,8 +73,9 @@ __device__ void xk_tns_run(int32_t *x, int first, int inc, int lines, int32_t lp
   }
 }
 
-struct XkRowWork { /* per DPP row: the filter being set up */
+struct XkRowWork { /* per DPP row: the filter being set up (the 32-bit members: streams of more than two channels) */
   int16_t parcor[16], lpc[20], t1[16], t2[16];
+  int32_t parcor32[16], lpc32[20], z[16], w[16];
   int32_t scale;
 };
 
@@ -147,6 +148,13 @@ __global__ __launch_bounds__(64) void xaac_aac_tools_kernel(XaacAacToolsParams p
       s_spec[1][i] = r;
     }
   }
+  __syncthreads();
+  /* a stream of more than two channels: the three bits its scale factors left on top come off behind the stereo tools */
+  for (int c = 0; c < n_ch; c++)
+    if (sd->ch[c].wide) {
+      const int n = xt_wide_shift_lines(sd, c);
+      for (int i = lane; i < n; i += 64) s_spec[c][i] >>= 3;
+    }
   __syncthreads();
 
   /* ---- PNS ------------------------------------------------------------------------------------------------------------ */
@@ -229,20 +237,26 @@ __global__ __launch_bounds__(64) void xaac_aac_tools_kernel(XaacAacToolsParams p
           const xaac_tns_filter_side &flt = ch.tns[is_short ? win : f];
           XtTnsPlan pl;
           if (!xt_tns_plan(sd, ch, win, flt, &pl)) continue;
+          const bool wide = ch.wide != 0;
           if (t == 0) {
-            for (int i = 0; i < flt.order; i++) wk.parcor[i] = xt_tns_parcor(flt, i);
             int scale;
-            xt_parcor_to_lpc(wk.parcor, wk.lpc, &scale, flt.order, wk.t1, wk.t2);
+            if (wide) { /* the 32-bit variant: the taps are whole words, the recursion below is the same */
+              for (int i = 0; i < flt.order; i++) wk.parcor32[i] = xt_tns_parcor32(flt, i);
+              xt_parcor_to_lpc32(wk.parcor32, wk.lpc32, &scale, flt.order, wk.z, wk.w);
+            } else {
+              for (int i = 0; i < flt.order; i++) wk.parcor[i] = xt_tns_parcor(flt, i);
+              xt_parcor_to_lpc(wk.parcor, wk.lpc, &scale, flt.order, wk.t1, wk.t2);
+            }
             wk.scale = scale;
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
           __builtin_amdgcn_wave_barrier();
           const int scale_lpc = wk.scale;
-          const int32_t lpc_hi = t < flt.order ? (int32_t)((uint32_t)(uint16_t)wk.lpc[t + 1] << 16) : 0;
+          const int32_t lpc_hi = t >= flt.order ? 0 : wide ? wk.lpc32[t + 1] : (int32_t)((uint32_t)(uint16_t)wk.lpc[t + 1] << 16);
           int32_t *region = x + (win << 7) + pl.start;
           int32_t m = 0;
           for (int i = t; i < pl.size; i += 16) m |= xt_tns_mag_bits(region[i]);
-          int scale_spec = fx_norm32(xk_row_or(m)) - 4 - scale_lpc;
+          int scale_spec = xt_tns_scale_spec(fx_norm32(xk_row_or(m)), scale_lpc, wide);
           if (scale_spec > 0) {
             if (scale_spec > 31) scale_spec = 31;
             xk_tns_run(x, pl.first, pl.inc, pl.lines, lpc_hi, t, row_base, scale_lpc, scale_spec);

@@ -119,6 +119,13 @@ __device__ __forceinline__ void st_(T *p, const T (&v)[N]) {
     uint32_t t;
     __builtin_memcpy(&t, &v[0], 4);
     *reinterpret_cast<uint32_t *>(p) = t;
+  } else if (N > 2 && (N & 1) == 0 && sizeof(T) == 2) { /* an even number of PCM16 words per sample: 4-byte aligned at every sample */
+#pragma unroll
+    for (int c = 0; c < N; c += 2) {
+      uint32_t t;
+      __builtin_memcpy(&t, &v[c], 4);
+      reinterpret_cast<uint32_t *>(p)[c >> 1] = t;
+    }
   } else {
 #pragma unroll
     for (int c = 0; c < N; c++) p[c] = v[c];
@@ -154,8 +161,13 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
   const int8_t *qs = p.qshift_adj + (int64_t)s * p.num_channels;
   const int C = CT ? CT : p.num_channels, L = p.frame_len;
   const int A = (int)st->attack_time_samples, dii0 = (int)st->delayed_input_index;
-  const bool planar = p.planar != 0;
-  constexpr int N = CT == 2 ? 2 : 1;
+  const bool planar = CT > 2 || p.planar != 0; /* (3 .. 6: launched for planar blocks only) */
+  /* channels a lane holds of its samples: both of a pair; all of 3 .. 6 (the planar loads of a pass are then in flight together and a
+     sample's PCM16 words leave as one run); one at a time where the count is only known at run time.
+     K: samples per lane and pass.  With every channel in registers a pass of 8 would hold 8 N words each of `now` and `before` beside
+     the 8 N of `line` (about 170 VGPRs at N = 6: two waves per SIMD); passes of 4 keep it near 128 (four waves). */
+  constexpr int N = CT >= 2 ? CT : 1;
+  constexpr int K = N > 2 ? 4 : 8, PASSES = 16 / K;
   const int end_pos = (dii0 + L) % A; /* delayed_input_index after the frame */
   float min_gain = 1.0f;
   for (int j = 0; j < C; j += N) {
@@ -174,12 +186,12 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
       if (i < A && i < L) ld<N>(st->delayed_input + pos * C + j, line[k]);
     }
 #pragma unroll
-    for (int half = 1; half >= 0; half--) { /* upper half first: it still needs the lower half's input */
-      int32_t now[8][N], before[8][N];
-      float gain[8];
+    for (int half = PASSES - 1; half >= 0; half--) { /* from the top down: a pass still needs the input of the ones below it */
+      int32_t now[K][N], before[K][N];
+      float gain[K];
 #pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const int i = lane + 64 * (k + 8 * half);
+      for (int k = 0; k < K; k++) {
+        const int i = lane + 64 * (k + K * half);
 #pragma unroll
         for (int c = 0; c < N; c++) now[k][c] = before[k][c] = 0;
         gain[k] = 1.0f;
@@ -190,8 +202,8 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
         }
       }
 #pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const int i = lane + 64 * (k + 8 * half);
+      for (int k = 0; k < K; k++) {
+        const int i = lane + 64 * (k + K * half);
         if (i < L) {
           int32_t v[N];
           int16_t v16[N];
@@ -199,7 +211,7 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
 #pragma unroll
           for (int c = 0; c < N; c++) {
             float old = xl_scaled(before[k][c], q[c]);
-            if (half == 0 && i < A) old = line[k][c];
+            if (K * half < 8 && i < A) old = line[(k + K * half) & 7][c]; /* (A <= 480: the first 8 samples of a lane at most) */
             v[c] = active ? xl_apply(old, gain[k]) : xl_passthrough(old);
             v16[c] = xl_round16(v[c]);
             keep[c] = xl_scaled(now[k][c], q[c]);
@@ -229,7 +241,8 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
 
 }  // namespace
 
-/* CT: channel count known at compile time (1, 2: the loads of a phase are then all in flight together), 0: any */
+/* CT: channel count known at compile time (1, 2, and 3 .. 6 -- the multichannel configurations: the loads of a phase are then
+   all in flight together), 0: any */
 template <int CT>
 __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParams p) {
   __shared__ float s_w[kMaxW]; /* W: the state's window in time order, then the frame's magnitudes */
@@ -268,7 +281,13 @@ __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParam
     const int i = lane + 64 * k;
     float tmp = 0.0f;
     if (i < L) {
-      if (p.planar) {
+      if (CT > 2) { /* (planar: the launcher's condition) every channel's load in flight before the first magnitude */
+        int32_t v[CT > 2 ? CT : 1];
+#pragma unroll
+        for (int j = 0; j < CT; j++) v[j] = x[j * L + i];
+#pragma unroll
+        for (int j = 0; j < CT; j++) tmp = xl_peak(tmp, v[j], qs[j]);
+      } else if (p.planar) {
         for (int j = 0; j < C; j++) tmp = xl_peak(tmp, x[j * L + i], qs[j]);
       } else if (CT == 2) {
         const int2 v = reinterpret_cast<const int2 *>(x)[i];
@@ -526,19 +545,31 @@ __global__ __launch_bounds__(64) void xaac_limiter_apply_kernel(XaacLimiterParam
 
 extern "C" hipError_t xaac_launch_limiter(const XaacLimiterParams *p, hipStream_t stream) {
   const dim3 grid(p->n_streams), block(64);
-  if (p->num_channels == 1)
-    hipLaunchKernelGGL(xaac_limiter_front_kernel<1>, grid, block, 0, stream, *p);
-  else if (p->num_channels == 2)
-    hipLaunchKernelGGL(xaac_limiter_front_kernel<2>, grid, block, 0, stream, *p);
-  else
-    hipLaunchKernelGGL(xaac_limiter_front_kernel<0>, grid, block, 0, stream, *p);
+  /* 3 .. 6 channels from a planar block (what the multichannel decode chain hands over): the instantiations that hold all
+     channels of a sample in one lane; every other shape of more than two channels walks them one at a time */
+  /* (they store a sample's PCM16 words as 32-bit words where the count is even: a PCM buffer that is not 4-byte aligned keeps
+     the generic path's 2-byte stores) */
+  const bool pcm_fits = (p->num_channels & 1) || (reinterpret_cast<uintptr_t>(p->pcm16) & 3) == 0;
+  const int ct = p->num_channels <= 2 ? p->num_channels : (p->planar && p->num_channels <= 6 && pcm_fits ? p->num_channels : 0);
+  switch (ct) {
+    case 1: hipLaunchKernelGGL(xaac_limiter_front_kernel<1>, grid, block, 0, stream, *p); break;
+    case 2: hipLaunchKernelGGL(xaac_limiter_front_kernel<2>, grid, block, 0, stream, *p); break;
+    case 3: hipLaunchKernelGGL(xaac_limiter_front_kernel<3>, grid, block, 0, stream, *p); break;
+    case 4: hipLaunchKernelGGL(xaac_limiter_front_kernel<4>, grid, block, 0, stream, *p); break;
+    case 5: hipLaunchKernelGGL(xaac_limiter_front_kernel<5>, grid, block, 0, stream, *p); break;
+    case 6: hipLaunchKernelGGL(xaac_limiter_front_kernel<6>, grid, block, 0, stream, *p); break;
+    default: hipLaunchKernelGGL(xaac_limiter_front_kernel<0>, grid, block, 0, stream, *p); break;
+  }
   hipLaunchKernelGGL(xaac_limiter_gain_kernel, dim3((p->n_streams + 63) / 64), block, 0, stream, *p);
-  if (p->num_channels == 1)
-    hipLaunchKernelGGL(xaac_limiter_apply_kernel<1>, grid, block, 0, stream, *p);
-  else if (p->num_channels == 2)
-    hipLaunchKernelGGL(xaac_limiter_apply_kernel<2>, grid, block, 0, stream, *p);
-  else
-    hipLaunchKernelGGL(xaac_limiter_apply_kernel<0>, grid, block, 0, stream, *p);
+  switch (ct) {
+    case 1: hipLaunchKernelGGL(xaac_limiter_apply_kernel<1>, grid, block, 0, stream, *p); break;
+    case 2: hipLaunchKernelGGL(xaac_limiter_apply_kernel<2>, grid, block, 0, stream, *p); break;
+    case 3: hipLaunchKernelGGL(xaac_limiter_apply_kernel<3>, grid, block, 0, stream, *p); break;
+    case 4: hipLaunchKernelGGL(xaac_limiter_apply_kernel<4>, grid, block, 0, stream, *p); break;
+    case 5: hipLaunchKernelGGL(xaac_limiter_apply_kernel<5>, grid, block, 0, stream, *p); break;
+    case 6: hipLaunchKernelGGL(xaac_limiter_apply_kernel<6>, grid, block, 0, stream, *p); break;
+    default: hipLaunchKernelGGL(xaac_limiter_apply_kernel<0>, grid, block, 0, stream, *p); break;
+  }
   return hipGetLastError();
 }
 

@@ -58,7 +58,8 @@ class TnsFilterSide(ctypes.Structure):
 class CoreToolsChannel(ctypes.Structure):
     # struct xaac_core_tools_channel
     _fields_ = [("window_sequence", ctypes.c_uint8), ("max_sfb", ctypes.c_uint8), ("num_groups", ctypes.c_uint8),
-                ("pns_active", ctypes.c_uint8), ("tns_present", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3),
+                ("pns_active", ctypes.c_uint8), ("tns_present", ctypes.c_uint8), ("wide", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 2),
                 ("group_len", ctypes.c_uint8 * 8), ("n_filt", ctypes.c_uint8 * 8), ("cb", ctypes.c_uint8 * 128),
                 ("sf", ctypes.c_int16 * 128), ("pns_used", ctypes.c_uint8 * 128), ("tns", TnsFilterSide * 8)]
 
@@ -97,6 +98,10 @@ def load_host_library():
         lib.xaac_parse_adts_frame.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32,
                                               ctypes.POINTER(CoreFrame), ctypes.POINTER(ctypes.c_size_t)]
         lib.xaac_parse_sbr_side.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(SbrSide)]
+        lib.xaac_parse_adts_frame_mc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_void_p,
+                                                 ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_size_t)]
+        lib.xaac_parse_core_tools_side_mc.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        lib.xaac_parse_core_tools_side_mc.restype = ctypes.c_int32
         for fn in ("xaac_sbr_state_init", "xaac_ps_state_init", "xaac_esbr_state_init", "xaac_esbr_ps_state_init",
                    "xaac_hbe_state_init"):
             getattr(lib, fn).argtypes = [ctypes.c_void_p]
@@ -215,12 +220,77 @@ def parse_stream(data, stage=2, esbr=False):
     return out
 
 
+# ADTS channel_config 3 .. 6: (channel elements in bitstream order -- 0 SCE, 1 CPE, 3 LFE --, the output channel of every
+# bitstream channel, the WAV channel mask).  The reference gives the first CPE the first two output channels, then the first
+# SCE, the LFE, the second CPE, the second SCE (ixheaacd_get_channel_mask, common_lpfuncs.c:107-173; api.c:3176-3177).
+MC_LAYOUT = {3: ((0, 1), (2, 0, 1), 0x7), 4: ((0, 1, 0), (2, 0, 1, 3), 0x107), 5: ((0, 1, 1), (2, 0, 1, 3, 4), 0x37),
+             6: ((0, 1, 1, 3), (2, 0, 1, 4, 5, 3), 0x3f)}
+MC_MAX_ELEMENTS = 4
+
+
+def probe_first_frame(data):
+    """-> (channels, channel elements, frame 0 carries an SBR payload, channel_config of the header) of an ADTS stream, through
+    a parser of its own (xaac_parse_adts_frame_mc: streams of one element as well as channel_config 3 .. 6)"""
+    lib = load_host_library()
+    data = bytes(data)
+    hdr = AdtsHeader()
+    rc = lib.xaac_adts_parse_header(data[:16], min(16, len(data)), ctypes.byref(hdr))
+    if rc:
+        raise ParseError(rc, 0)
+    elems, n, used, probe = (CoreFrame * MC_MAX_ELEMENTS)(), ctypes.c_int32(), ctypes.c_size_t(), ctypes.c_void_p()
+    lib.xaac_parser_create(ctypes.byref(probe))
+    rc = lib.xaac_parse_adts_frame_mc(probe, data, len(data), 1, elems, MC_MAX_ELEMENTS, ctypes.byref(n), ctypes.byref(used))
+    lib.xaac_parser_destroy(probe)
+    if rc:
+        raise ParseError(rc, 0)
+    return (sum(elems[k].n_ch for k in range(n.value)), n.value, any(elems[k].sbr_bytes > 0 for k in range(n.value)),
+            hdr.channel_config)
+
+
+def parse_stream_mc(data, stage=2):
+    """the CPU half alone for a stream of several channel elements (xaac_parse_adts_frame_mc): per frame
+    (spec int32[channels, 1024], ics int16[channels, 4], [XAAC_TOOL_* bits per element], [element_id per element],
+    [xaac_core_tools_side bytes per element]), channels in bitstream order"""
+    lib = load_host_library()
+    data = bytes(data)
+    buf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
+    p = ctypes.c_void_p()
+    if lib.xaac_parser_create(ctypes.byref(p)):
+        raise RuntimeError("xaac_parser_create failed")
+    elems, n, used = (CoreFrame * MC_MAX_ELEMENTS)(), ctypes.c_int32(), ctypes.c_size_t()
+    out, pos = [], 0
+    try:
+        while len(data) - pos >= 7:
+            rc = lib.xaac_parse_adts_frame_mc(p, ctypes.byref(buf, pos), len(data) - pos, stage, elems, MC_MAX_ELEMENTS,
+                                              ctypes.byref(n), ctypes.byref(used))
+            if rc == 1:
+                break
+            if rc:
+                raise ParseError(rc, len(out))
+            pos += used.value
+            spec, ics, sides = [], [], []
+            for k in range(n.value):
+                m = elems[k].n_ch
+                spec.append(np.ctypeslib.as_array(elems[k].spec)[:m].copy())
+                ics.append(np.ctypeslib.as_array(elems[k].ics)[:m].copy())
+                side = (ctypes.c_uint8 * CORE_TOOLS_SIDE_BYTES)()
+                if lib.xaac_parse_core_tools_side_mc(p, k, side):
+                    raise ParseError(-2, len(out))
+                sides.append(bytes(side))
+            out.append((np.concatenate(spec), np.concatenate(ics), [int(elems[k].tools) for k in range(n.value)],
+                        [int(elems[k].element_id) for k in range(n.value)], sides))
+    finally:
+        lib.xaac_parser_destroy(p)
+    return out
+
+
 class _ParseBatch(ctypes.Structure):
     # struct xaac_parse_batch
     _fields_ = [(n, ctypes.c_int32) for n in ("n_streams", "n_ch", "with_sbr", "ps_enable", "stage", "threads")] + \
                [(n, ctypes.c_void_p) for n in ("parser", "data", "bytes", "spec", "ics", "header", "frame", "ps_frame", "flags",
                                                "tools", "consumed", "status", "esbr_side", "reset_pitch", "pos")] + \
-               [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p), ("tools_side", ctypes.c_void_p)]
+               [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p), ("tools_side", ctypes.c_void_p),
+                ("channel_config", ctypes.c_int32)]
 
 
 F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(8)
@@ -350,15 +420,18 @@ class BatchParser:
         if rc:
             raise ParseError(rc, 0)
         self.core_rate, self.n_ch = hdr.sampling_rate, (2 if hdr.channel_config == 2 else 1)
-        core = CoreFrame()
-        used = ctypes.c_size_t()
-        probe = ctypes.c_void_p()
-        self.lib.xaac_parser_create(ctypes.byref(probe))
-        rc = self.lib.xaac_parse_adts_frame(probe, bytes(streams[0]), len(streams[0]), 1, ctypes.byref(core), ctypes.byref(used))
-        self.lib.xaac_parser_destroy(probe)
-        if rc:
-            raise ParseError(rc, 0)
-        self.sbr = bool(core.sbr_bytes > 0)
+        channels, n_elems, sbr, config = probe_first_frame(streams[0])
+        self.sbr = bool(sbr)
+        # several channel elements (channel_config 3 .. 6): the multichannel form of the batch call, AAC-LC only
+        self.channel_config, self.n_elems = (config, n_elems) if n_elems > 1 else (0, 1)
+        for d in streams[1:]:   # a multichannel stream only beside streams of its own channel_config, whichever comes first
+            other = (((d[2] & 1) << 2) | (d[3] >> 6)) if len(d) >= 4 else -1
+            if other != config and (3 <= other <= 6 or 3 <= config <= 6):
+                raise ValueError("streams of different channel configurations in one batch")
+        if self.channel_config:
+            if self.sbr:
+                raise ValueError("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported")
+            self.n_ch = channels
 
     def close(self):
         if getattr(self, "_in_flight", False):   # (a caller that gave up between start_step() and wait_step(): the team must get its batch back)
@@ -386,6 +459,7 @@ class BatchParser:
         b.frames = int(frames)
         b.lines = None if lines is None else lines.ctypes.data
         b.tools_side = ptr(tools_side)   # uint8[frames, n, CORE_TOOLS_SIDE_BYTES]: the tools' side info of a stage-1 parse
+        b.channel_config = self.channel_config   # (with it: tools_side is uint8[frames, n_elems, n, ...], element-major)
         return b
 
     def _advance(self, ok, status=None):
@@ -488,7 +562,7 @@ class Staging:
         want = lambda name, *shape: pinned(T, *shape) if name in arrays else None
         self.bp, self.T = bp, T
         self.spec, self.ics = pinned(T, nc, 1024, dtype=torch.int32), pinned(T, nc, 2)
-        self.tside = pinned(T, n, CORE_TOOLS_SIDE_BYTES) if tools else None
+        self.tside = pinned(T, n * bp.n_elems, CORE_TOOLS_SIDE_BYTES) if tools else None   # element-major within a step
         self.hdr, self.frm = want("hdr", nc, SBR_HEADER_BYTES), want("frm", nc, SBR_FRAME_BYTES)
         self.psf, self.eside = want("psf", n, PS_FRAME_BYTES), want("eside", nc, ESBR_SIDE_BYTES)
         self.flags = self.flags_pin = None
@@ -523,20 +597,29 @@ class Staging:
 
 class _ToolsStage:
     """gpu_tools: the M/S, intensity, PNS and TNS tools in front of whichever chain's IMDCT -- the tools' side rows (two device
-    sets like the spectra), the streams' noise generators, the kernel's status words"""
+    sets like the spectra), the noise generators, the kernel's status words: a row per stream and channel element, element-major.
+    first_rows: the row of every element's first channel among a stream's n_ch rows on the device"""
 
-    def __init__(self, ctx, n, dz, pinned):
-        self.ctx = ctx
-        self.side_d2 = [dz(n, CORE_TOOLS_SIDE_BYTES) for _ in range(2)]
-        self.state = dz(n, CORE_TOOLS_STATE_BYTES)
-        self.status2 = [dz(n, dtype=torch.int32) for _ in range(2)]
-        self.status_h2 = [pinned(n, dtype=torch.int32) for _ in range(2)]
+    def __init__(self, ctx, n, dz, pinned, n_ch, first_rows=(0,)):
+        self.ctx, self.n, self.n_ch, self.first_rows = ctx, n, n_ch, tuple(first_rows)
+        rows = n * len(self.first_rows)
+        self.side_d2 = [dz(rows, CORE_TOOLS_SIDE_BYTES) for _ in range(2)]
+        self.state = dz(rows, CORE_TOOLS_STATE_BYTES)
+        self.status2 = [dz(rows, dtype=torch.int32) for _ in range(2)]
+        self.status_h2 = [pinned(rows, dtype=torch.int32) for _ in range(2)]
 
     def send_up(self, step, slot):
         self.side_d2[slot].copy_(step.tside, non_blocking=True)
 
     def run(self, spec_d, slot):   # stage-1 spectra -> the spectra the IMDCT takes, in place (ended streams' rows run idle, unlooked at)
-        self.ctx.aac_tools_process_batch(spec_d, self.side_d2[slot], self.state, self.status2[slot])
+        n = self.n
+        for k, row in enumerate(self.first_rows):   # one launch per element index over all streams
+            rows = slice(k * n, (k + 1) * n)
+            self.ctx.aac_tools_process_batch(spec_d, self.side_d2[slot][rows], self.state[rows], self.status2[slot][rows],
+                                             spec_stride=1024 * self.n_ch, first_row=row)
+
+    def refused(self, slot, got):   # a delivered frame's element the kernel did not take
+        return int(self.status_h2[slot].numpy().reshape(len(self.first_rows), self.n)[:, got].min(initial=0)) < 0
 
 
 class _Chain:
@@ -587,8 +670,11 @@ class _LcChain(_Chain):
         for i in np.nonzero(~got & ~self.lim_taken)[0]:
             self.lim_at_end[int(i)] = self.lim[int(i)].cpu().numpy()     # (waits for the kernels of the step before)
             self.lim_taken[i] = True
-        self.ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, out32=self.out32, qshift_adj=self.qadj, ch_fac=self.n_ch)
-        self.ctx.peak_limiter_process_batch(self.out32, self.qadj, self.lim, self.n_ch, self.ws, pcm16=self.pcm2[slot])
+        # more than two channels: a row per channel (the pipeline sent them up in output channel order), the limiter reads them planar
+        planar = self.n_ch > 2
+        self.ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, out32=self.out32, qshift_adj=self.qadj,
+                                     ch_fac=1 if planar else self.n_ch)
+        self.ctx.peak_limiter_process_batch(self.out32, self.qadj, self.lim, self.n_ch, self.ws, pcm16=self.pcm2[slot], planar=planar)
         return (self.n, 1024, self.n_ch), (self.delay if first else 0), False   # the limiter's delay is cut from the first frame
 
     def finish(self, out, keep_pcm):
@@ -806,11 +892,19 @@ class _Pipeline:
             ctx = XaacContext(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
         self.ctx = ctx
         self.bp = bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2)
+        # more than two channels: bitstream channel c of a stream goes up as row route[c] of its rows (the reference's output order)
+        self.route = MC_LAYOUT[bp.channel_config][1] if bp.channel_config else None
+        self.ics_routed = [alloc.pinned(bp.n * bp.n_ch, 2) for _ in range(4)] if self.route else None
         self.n, self.nc, self.keep_pcm, self.overlap = bp.n, bp.n * bp.n_ch, keep_pcm, overlap
         self.T = T = max(1, int(frames_per_parse))
         kind = _LcChain if not bp.sbr else _EsbrChain if esbr else _SbrChain
         self.chain = chain = kind(ctx, lib, dev, bp.n, bp.n_ch, bp.core_rate, alloc, trace)
-        self.tools = _ToolsStage(ctx, bp.n, alloc.dz, alloc.pinned) if gpu_tools else None
+        first_rows = (0,)
+        if bp.channel_config:   # every element's first bitstream channel, where the routed upload puts it
+            elements, route, _ = MC_LAYOUT[bp.channel_config]
+            starts = np.concatenate([[0], np.cumsum([2 if e == 1 else 1 for e in elements])[:-1]])
+            first_rows = tuple(route[int(c)] for c in starts)
+        self.tools = _ToolsStage(ctx, bp.n, alloc.dz, alloc.pinned, bp.n_ch, first_rows) if gpu_tools else None
         # two sets of device input arrays: step k + 1 is copied up (its own stream) while step k's kernels read theirs
         self.spec_d2 = [alloc.dz(self.nc, 1024, dtype=torch.int32) for _ in range(2)]
         self.ics_d2 = [alloc.dz(self.nc, 2) for _ in range(2)]
@@ -838,7 +932,7 @@ class _Pipeline:
         chain, tools = self.chain, self.tools
         if chain.status_h2 is not None and int(chain.status_h2[slot].numpy().reshape(self.n, -1)[got].min(initial=0)) < 0:
             raise RuntimeError("the SBR kernels refused a frame")
-        if tools is not None and int(tools.status_h2[slot].numpy()[got].min(initial=0)) < 0:
+        if tools is not None and tools.refused(slot, got):
             raise RuntimeError("the AAC tools kernel refused a frame")
         if self.keep_pcm and not drop:
             block = chain.pcm_h2[slot].numpy().reshape(shape)
@@ -874,13 +968,25 @@ class _Pipeline:
             lines_now = min(1024, (int(cur.lines[got].max()) + 63) & ~63)
             width = max(lines_now, self.lines_held[slot])
             self.lines_held[slot] = lines_now
-            if width >= 1024:
+            if self.route:      # one strided copy per channel, to its output place; the window info through a routed host copy
+                n_ch, n = self.bp.n_ch, self.n
+                ics_h = self.ics_routed[step_no & 3]
+                for c, to in enumerate(self.route):
+                    if width > 0:
+                        rc = self.hip.hipMemcpy2DAsync(spec_d.data_ptr() + 4096 * to, 4096 * n_ch, cur.spec.data_ptr() + 4096 * c,
+                                                       4096 * n_ch, 4 * width, n, 1, up.cuda_stream)
+                        if rc != 0:
+                            raise RuntimeError("hipMemcpy2DAsync: %d" % rc)
+                    ics_h.numpy().reshape(n, n_ch, 2)[:, to] = cur.ics.numpy().reshape(n, n_ch, 2)[:, c]
+                self.ics_d2[slot].copy_(ics_h, non_blocking=True)
+            elif width >= 1024:
                 spec_d.copy_(cur.spec, non_blocking=True)
             elif width > 0:
                 rc = self.hip.hipMemcpy2DAsync(spec_d.data_ptr(), 4096, cur.spec.data_ptr(), 4096, 4 * width, self.nc, 1, up.cuda_stream)
                 if rc != 0:
                     raise RuntimeError("hipMemcpy2DAsync: %d" % rc)
-            self.ics_d2[slot].copy_(cur.ics, non_blocking=True)
+            if not self.route:
+                self.ics_d2[slot].copy_(cur.ics, non_blocking=True)
             if self.tools is not None:
                 self.tools.send_up(cur, slot)
             self.chain.send_up(cur, slot, got)
@@ -955,8 +1061,8 @@ class _Pipeline:
 
 def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True, timing=None, overlap=True, esbr=False,
                    _trace=None, frames_per_parse=4, gpu_tools=False):
-    """Decodes N ADTS streams of the same kind (all AAC-LC stereo, all HE-AAC stereo, or all HE-AAC / HE-AACv2 mono) in
-    lock step: per step one frame of every stream is parsed on CPU threads into pinned staging arrays, copied to the GPU
+    """Decodes N ADTS streams of the same kind (all AAC-LC mono or stereo, all AAC-LC of one channel_config 3 .. 6 -- 3.0 to
+    5.1, output channels in the reference's order, MC_LAYOUT --, all HE-AAC stereo, or all HE-AAC / HE-AACv2 mono) in lock step: per step one frame of every stream is parsed on CPU threads into pinned staging arrays, copied to the GPU
     (spectra + window info, SBR / PS side info: nothing else crosses the bus on the way in), run through the GPU entry
     points against the streams' device-resident states, and the PCM copied back.
     -> (list of int16 [samples, channels] arrays, output sampling rate).  keep_pcm False: the PCM still comes back to the host
@@ -975,7 +1081,8 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     state).
     gpu_tools: the M/S, intensity, PNS and TNS tools run on the GPU (xaac_aac_tools_process_batch in front of the IMDCT) instead of
     in the parser: the streams are parsed at stage 1, the tools' side rows go up beside the spectra and every stream's noise
-    generator lives on the device.  Off by default; the PCM is the same either way."""
+    generator lives on the device (one per channel element).  Off by default; the PCM is the same either way.  An SBR payload in
+    a stream of more than two channels is a ValueError."""
     global torch
     import torch
     with _TorchCpuThreads():

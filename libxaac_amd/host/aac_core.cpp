@@ -301,13 +301,13 @@ int spectral_short(XhBits *br, int cb, int32_t *x, const int16_t *swb, int start
   return err ? XH_ERR_ESCAPE : 0;
 }
 
-/* ---- scale factor gains: block.c:1242-1343 (at most two channels: q_factor 37) ------------------------------------ */
-void apply_scale_factor(int sf, int32_t *x, int width) {
+/* ---- scale factor gains: block.c:1242-1343 (q_factor 37; 34 in a stream of more than two channels) --------------- */
+void apply_scale_factor(int sf, int32_t *x, int width, int q_factor) {
   if (sf < 24) {
     for (int j = 0; j < width; j++) x[j] = 0;
     return;
   }
-  const int shift = 37 - (sf >> 2);
+  const int shift = q_factor - (sf >> 2);
   const int16_t g = (int16_t)xh_scale_tab[sf & 3];
   if (shift > 0) {
     for (int j = 0; j < width; j++) x[j] = fx_shr(fx_mul32x16_shl(x[j], g), shift);
@@ -456,6 +456,7 @@ int read_tns(XhBits *br, XhChannel *c) { /* channel.c:961-1053 */
 
 int read_spectrum(const XhCoreState *st, XhBits *br, XhChannel *c) { /* channel.c:749-905 */
   const XhIcs &ics = c->ics;
+  const int q_factor = st->wide ? 34 : 37;
   int32_t *spec = c->spec();
   memset(c->spec_mem, 0, XH_SPEC_WORDS * sizeof(int32_t));
   if (ics.window_sequence != XH_EIGHT_SHORT) {
@@ -482,7 +483,7 @@ int read_spectrum(const XhCoreState *st, XhBits *br, XhChannel *c) { /* channel.
     /* (bands without spectral data -- code book 0, noise, intensity -- hold zeros, and zeros they stay whatever the gain) */
     for (int sfb = 0, lo = 0; sfb < ics.max_sfb; lo += st->width_long[sfb], sfb++)
       if ((c->cb[sfb] > XH_ZERO_HCB && c->cb[sfb] < XH_NOISE_HCB) || c->pulse.present)
-        apply_scale_factor(c->sf[sfb], spec + lo, st->width_long[sfb]);
+        apply_scale_factor(c->sf[sfb], spec + lo, st->width_long[sfb], q_factor);
   } else {
     int win = 0;
     for (int g = 0; g < ics.num_groups; g++) {
@@ -497,7 +498,7 @@ int read_spectrum(const XhCoreState *st, XhBits *br, XhChannel *c) { /* channel.
       }
       for (int w = 0; w < ics.group_len[g]; w++, win++)
         for (int sfb = 0, lo = 0; sfb < ics.max_sfb; lo += st->width_short[sfb], sfb++)
-          apply_scale_factor(c->sf[16 * g + sfb], spec + 128 * win + lo, st->width_short[sfb]);
+          apply_scale_factor(c->sf[16 * g + sfb], spec + 128 * win + lo, st->width_short[sfb], q_factor);
     }
   }
   return br->overrun ? XH_ERR_BITS : 0;
@@ -585,6 +586,7 @@ void xh_export_tools_side(const XhCoreState *st, XhElement *el, xaac_core_tools_
     o.num_groups = (uint8_t)ch.ics.num_groups;
     o.pns_active = (uint8_t)ch.pns_active;
     o.tns_present = (uint8_t)ch.tns.present;
+    o.wide = (uint8_t)(st->wide != 0);
     memcpy(o.group_len, ch.ics.group_len, 8);
     for (int g = 0; g < ch.ics.num_groups; g++) {
       const int at = 16 * g, n = ch.ics.max_sfb;
@@ -643,11 +645,22 @@ int xh_core_init(XhCoreState *st, int sr_index) {
 }
 
 int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stage) {
+  xaac_core_tools_state *tools = &st->tools;
+  int n = 0;
+  return xh_parse_raw_data_block_mc(st, br, &el, &tools, 1, &n, stage);
+}
+
+int xh_parse_raw_data_block_mc(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
+                               int *n_els, int stage) {
   const size_t block_start = br->pos;
   int prev = XH_ID_END, have_channels = 0;
-  el->n_ch = 0;
-  el->sbr_bytes = 0;
-  el->sbr_ext_type = 0;
+  XhElement *el = els[0]; /* the channel element parsed last: a FIL element behind it carries its SBR payload */
+  for (int k = 0; k < cap; k++) {
+    els[k]->n_ch = 0;
+    els[k]->sbr_bytes = 0;
+    els[k]->sbr_ext_type = 0;
+  }
+  *n_els = 0;
   for (;;) {
     if (br->left() < 3) return XH_ERR_BITS;
     const int id = (int)br->get(3);
@@ -656,8 +669,11 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stag
       case XH_ID_SCE:
       case XH_ID_LFE:
       case XH_ID_CPE: {
-        if (have_channels) return XH_ERR_UNSUPPORTED; /* a second channel element: beyond two channels */
-        have_channels = 1;
+        if (have_channels >= cap) return XH_ERR_UNSUPPORTED; /* more channel elements than the caller takes */
+        el = els[have_channels];
+        xaac_core_tools_state *const tool_state = tools[have_channels];
+        have_channels++;
+        *n_els = have_channels;
         el->id = id;
         el->n_ch = id == XH_ID_CPE ? 2 : 1;
         el->tag = (int)br->get(4);
@@ -691,10 +707,11 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stag
         }
         if (stage >= 2) { /* channel.c:602-692 */
           static thread_local xaac_core_tools_side side; /* only the bands below max_sfb are written and read */
-          /* (a single channel without noise substitution and TNS has no tool to run: most frames of a mono stream) */
-          if (el->n_ch == 2 || el->ch[0].pns_active || el->ch[0].tns.present) {
+          /* (a single channel without noise substitution and TNS has no tool to run: most frames of a mono stream; in a
+             stream of more than two channels the three extra bits still have to come off) */
+          if (el->n_ch == 2 || el->ch[0].pns_active || el->ch[0].tns.present || st->wide) {
             xh_export_tools_side(st, el, &side);
-            xt_apply_host(&side, &st->tools, el->ch[0].spec(), el->ch[1].spec());
+            xt_apply_host(&side, tool_state, el->ch[0].spec(), el->ch[1].spec());
           }
         }
         break;

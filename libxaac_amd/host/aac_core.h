@@ -3,9 +3,9 @@
  * decoder/ixheaacd_aacdecoder.c:362-647) -> the spectra of its SCE / CPE exactly as the reference hands them to
  * ixheaacd_imdct_process (Q-format, rounding and the reference's quirks included), plus the raw SBR extension payload.
  * CPU code: the bitstream syntax is serial; everything behind this seam runs on the GPU.
- * Scope: AAC-LC objects (AOT 2; 5 / 29 through the SBR payload), 1024-line frames, one SCE or CPE per raw_data_block
- * (at most two channels: the reference's q_factor / TNS variants for more than two channels are not built), no LTP, no
- * gain control, no DRC payload handling (read and ignored), no error concealment.
+ * Scope: AAC-LC objects (AOT 2; 5 / 29 through the SBR payload), 1024-line frames, one SCE or CPE per raw_data_block, or the
+ * SCE / CPE / LFE sequence of channel_config 3 .. 6 (with the reference's q_factor / TNS variants for more than two
+ * channels: XhCoreState::wide); no CCE, no LTP, no gain control, no DRC payload handling (read and ignored), no error concealment.
  */
 #ifndef XAAC_HOST_AAC_CORE_H
 #define XAAC_HOST_AAC_CORE_H
@@ -73,6 +73,8 @@ struct XhCoreState {
   int16_t swb_long[52], swb_short[16];
   const int8_t *width_long, *width_short;
   int num_swb_long, num_swb_short;
+  int wide;                /* the stream has more than two channels (set by the caller behind xh_core_init): scale factors with
+                              q_factor 34 and the 32-bit TNS variant (block.c:1263, channel.c:642, pns_js_thumb.c:328) */
   xaac_core_tools_state tools; /* the noise generator: pns_seed = pstr_pns_rand_vec_data->current_seed (starts at 0, runs on
                                   from frame to frame); pns_corr_seed = pstr_pns_corr_info->random_vector: the left channel's
                                   seed of a band whose noise the M/S flag correlates; a right channel that substitutes noise
@@ -108,6 +110,13 @@ int xh_core_init(XhCoreState *st, int sr_index);
    `stage`: 2 = everything; 1 = stop before the tools (spectra as at the entry of ixheaacd_channel_pair_process).
    Returns 0 or a negative XH_ERR_*. */
 int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stage);
+
+/* The same for a block of up to `cap` channel elements (SCE / CPE / LFE in bitstream order; one more is
+   XH_ERR_UNSUPPORTED): element k into els[k], its noise generator tools[k] -- the reference keeps one core decoder instance,
+   and so one generator, per element (api.c:2433-2458) --; *n_els = how many the block held.  The SBR payload of a FIL element
+   goes to the channel element in front of it. */
+int xh_parse_raw_data_block_mc(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
+                               int *n_els, int stage);
 
 /* What the tools read of the element parsed last, as the boundary struct of include/xaac_tools.h (ms_used and
    pns_correlated as the tools apply them).  Writes the bands below max_sfb, the filters n_filt counts and the scalar

@@ -29,6 +29,26 @@
 
 static const int32_t k_sample_rate[12] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000};
 
+/* channel_config -> its channel elements in bitstream order (ISO/IEC 14496-3 table 1.19), 3 .. 6: what the multichannel
+   entry points take */
+static const int8_t k_config_elements[7][5] = {{0},
+                                               {1, XH_ID_SCE},
+                                               {1, XH_ID_CPE},
+                                               {2, XH_ID_SCE, XH_ID_CPE},
+                                               {3, XH_ID_SCE, XH_ID_CPE, XH_ID_SCE},
+                                               {3, XH_ID_SCE, XH_ID_CPE, XH_ID_CPE},
+                                               {4, XH_ID_SCE, XH_ID_CPE, XH_ID_CPE, XH_ID_LFE}};
+static const int8_t k_config_channels[7] = {0, 1, 2, 3, 4, 5, 6};
+#define XP_MAX_ELEMENTS 4
+
+/* what a stream of more than one channel element needs beside the parser's first element: allocated by the first
+   multichannel call, so that a mono / stereo stream's parser stays as small as it was */
+struct XpMore {
+  XhElement el[XP_MAX_ELEMENTS - 1];
+  xaac_core_tools_state tools[XP_MAX_ELEMENTS - 1]; /* one noise generator per element, as the reference's core instances */
+  int have_sequence, sequence_n, sequence[XP_MAX_ELEMENTS]; /* the first frame's element ids: later frames must repeat them */
+};
+
 struct xaac_parser {
   int sr_index;
   XhCoreState core;
@@ -46,7 +66,11 @@ struct xaac_parser {
   int blocks_left, block_crc;
   size_t frame_left;
   int frame_ok; /* the last parse_frame delivered an element: p->el is whole (xaac_parse_core_tools_side) */
+  int channel_config; /* of the ADTS header read last */
+  int n_els;    /* ... and how many (more than one: the others are in more->el) */
+  XpMore *more;
 };
+static inline XhElement *element_of(xaac_parser *p, int k) { return k == 0 ? &p->el : &p->more->el[k - 1]; }
 
 /* A small persistent team for xaac_parse_batch_run.  Workers wait for the next call on a generation counter: a short spin
    (batches of a running decoder follow each other within microseconds), then asleep in the kernel on a futex -- a host
@@ -211,7 +235,10 @@ int32_t xaac_parser_create(xaac_parser **p) {
   return XAAC_PARSE_OK;
 }
 
-void xaac_parser_destroy(xaac_parser *p) { delete p; }
+void xaac_parser_destroy(xaac_parser *p) {
+  if (p) delete p->more;
+  delete p;
+}
 
 int32_t xaac_adts_parse_header(const uint8_t *data, size_t n, xaac_adts_header *h) { /* headerdecode.c:316-368, :838-849 */
   if (n < 7) return XAAC_PARSE_NEED_DATA;
@@ -257,24 +284,40 @@ static int32_t tools_of(const XhElement &el) {
 }
 
 /* the frame at data[0 .. n) into p->el */
-static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed);
-static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed) {
+static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap);
+/* one raw data block of at most `cap` channel elements into p->el (and p->more->el) */
+static int32_t parse_block(xaac_parser *p, XhBits *br, int32_t stage, int cap) {
+  /* the frame's lines live in a buffer of the calling thread until the caller has copied them out (the entry points do,
+     before they return): nothing of a stream outlives the frame there */
+  static thread_local int32_t lines[2][XH_SPEC_WORDS];
+  p->el.ch[0].spec_mem = lines[0], p->el.ch[1].spec_mem = lines[1];
+  if (cap <= 1) {
+    p->n_els = 1;
+    return xh_parse_raw_data_block(&p->core, br, &p->el, stage);
+  }
+  static thread_local int32_t lines_more[XP_MAX_ELEMENTS - 1][2][XH_SPEC_WORDS];
+  XhElement *els[XP_MAX_ELEMENTS];
+  xaac_core_tools_state *tools[XP_MAX_ELEMENTS];
+  els[0] = &p->el, tools[0] = &p->core.tools;
+  for (int k = 1; k < XP_MAX_ELEMENTS; k++) {
+    els[k] = &p->more->el[k - 1], tools[k] = &p->more->tools[k - 1];
+    els[k]->ch[0].spec_mem = lines_more[k - 1][0], els[k]->ch[1].spec_mem = lines_more[k - 1][1];
+  }
+  return xh_parse_raw_data_block_mc(&p->core, br, els, tools, cap < XP_MAX_ELEMENTS ? cap : XP_MAX_ELEMENTS, &p->n_els, stage);
+}
+static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap = 1) {
   p->frame_ok = 0;
-  const int32_t r = parse_frame_inner(p, data, n, stage, consumed);
+  const int32_t r = parse_frame_inner(p, data, n, stage, consumed, cap);
   p->frame_ok = r == 0;
   return r;
 }
-static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed) {
-  /* the frame's lines live in a buffer of the calling thread until the caller has copied them out (both entry points do,
-     before they return): nothing of a stream outlives the frame there */
-  static thread_local int32_t lines[2][XH_SPEC_WORDS];
+static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap) {
   if (p->blocks_left > 0) {
     /* the next raw data block of the ADTS frame the call before started (data points behind what that call consumed): the
        reference reads a header only when its block count has run out (api.c:2914) */
     if (n < p->frame_left) return XAAC_PARSE_NEED_DATA;
     XhBits br(data, p->frame_left);
-    p->el.ch[0].spec_mem = lines[0], p->el.ch[1].spec_mem = lines[1];
-    const int32_t r = xh_parse_raw_data_block(&p->core, &br, &p->el, stage);
+    const int32_t r = parse_block(p, &br, stage, cap);
     if (r) {
       p->blocks_left = 0; /* (the rest of the frame goes with it: the caller looks for the next header) */
       if (consumed) *consumed = p->frame_left;
@@ -302,9 +345,11 @@ static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, 
     p->sr_index = h.sr_index;
     p->sampling_rate = h.sampling_rate;
   }
+  /* more than two channels (channel_config 3 .. 7): the reference's other q_factor and TNS variant, in every element */
+  p->core.wide = h.channel_config >= 3;
+  p->channel_config = h.channel_config;
   XhBits br(data + h.header_bytes, (size_t)(h.frame_bytes - h.header_bytes));
-  p->el.ch[0].spec_mem = lines[0], p->el.ch[1].spec_mem = lines[1];
-  const int32_t r = xh_parse_raw_data_block(&p->core, &br, &p->el, stage);
+  const int32_t r = parse_block(p, &br, stage, cap);
   if (r || h.raw_blocks == 0) return r;
   /* number_of_raw_data_blocks_in_frame > 0 (headerdecode.c:353): this call delivers the first block and consumes the header
      and that block (+ its CRC in a protected frame); the calls that follow deliver the others, one each */
@@ -317,11 +362,67 @@ static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, 
   return XAAC_PARSE_OK;
 }
 
-int32_t xaac_parse_adts_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, xaac_core_frame *out,
-                              size_t *consumed) {
-  const int32_t r = parse_frame(p, data, n, stage, consumed);
+/* the frame parse_frame delivered: its element sequence against the one of its channel_config (3 .. 6; every other
+   configuration: one element, as the single-element entry takes it) and against the stream's first frame */
+static int32_t check_sequence(xaac_parser *p) {
+  const int cc = p->channel_config;
+  if (cc >= 3 && cc <= 6) {
+    if (p->n_els != k_config_elements[cc][0]) return XAAC_PARSE_ERR_UNSUPPORTED;
+    for (int k = 0; k < p->n_els; k++)
+      if (element_of(p, k)->id != k_config_elements[cc][1 + k]) return XAAC_PARSE_ERR_UNSUPPORTED;
+  } else if (p->n_els != 1) {
+    return XAAC_PARSE_ERR_UNSUPPORTED;
+  }
+  XpMore *m = p->more;
+  if (!m->have_sequence) {
+    m->have_sequence = 1, m->sequence_n = p->n_els;
+    for (int k = 0; k < p->n_els; k++) m->sequence[k] = element_of(p, k)->id;
+    return XAAC_PARSE_OK;
+  }
+  if (m->sequence_n != p->n_els) return XAAC_PARSE_ERR_UNSUPPORTED;
+  for (int k = 0; k < p->n_els; k++)
+    if (m->sequence[k] != element_of(p, k)->id) return XAAC_PARSE_ERR_UNSUPPORTED;
+  return XAAC_PARSE_OK;
+}
+
+/* A stream of several elements: the one place where per-element state is not the reference's.  It keeps the seeds of correlated
+   noise bands (pns_corr_seed) in scratch memory that its elements share; they matter only to a right channel that substitutes
+   noise in a correlated band whose left channel does not (it then starts from whatever seed was left there, by any element).
+   Such a frame is refused rather than decoded differently. */
+static bool stale_correlated_seed(xaac_parser *p) {
+  if (p->n_els < 2) return false;
+  for (int k = 0; k < p->n_els; k++) {
+    const XhElement &el = *element_of(p, k);
+    if (el.n_ch != 2 || !el.common_window || !(el.ch[0].pns_active || el.ch[1].pns_active)) continue;
+    for (int g = 0; g < el.ch[0].ics.num_groups; g++)
+      for (int sfb = 0; sfb < el.ch[0].ics.max_sfb; sfb++)
+        if (el.ms_used[g][sfb] && el.ch[1].pns_used[16 * g + sfb] && !el.ch[0].pns_used[16 * g + sfb]) return true;
+  }
+  return false;
+}
+
+/* parse_frame for the multichannel entry points: up to XP_MAX_ELEMENTS channel elements, the sequence checked.  A frame the
+   check refuses leaves the multi-block bookkeeping where it was, as a frame that did not parse */
+static int32_t parse_frame_mc(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed) {
+  if (!p->more) {
+    p->more = new (std::nothrow) XpMore;
+    if (!p->more) return XAAC_PARSE_ERR_UNSUPPORTED;
+    memset(static_cast<void *>(p->more), 0, sizeof(*p->more));
+  }
+  const int32_t keep_blocks = p->blocks_left, keep_crc = p->block_crc;
+  const size_t keep_left = p->frame_left;
+  int32_t r = parse_frame(p, data, n, stage, consumed, XP_MAX_ELEMENTS);
   if (r) return r;
-  const XhElement &el = p->el;
+  r = check_sequence(p);
+  if (r == 0 && stale_correlated_seed(p)) r = XAAC_PARSE_ERR_UNSUPPORTED;
+  if (r) {
+    p->frame_ok = 0;
+    p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
+  }
+  return r;
+}
+
+static void fill_core_frame(const XhElement &el, xaac_core_frame *out) {
   out->n_ch = el.n_ch;
   out->element_id = el.id;
   out->common_window = el.common_window;
@@ -336,6 +437,28 @@ int32_t xaac_parse_adts_frame(xaac_parser *p, const uint8_t *data, size_t n, int
     out->ics[c].num_window_groups = (int16_t)el.ch[c].ics.num_groups;
     memcpy(out->spec[c], const_cast<XhElement &>(el).ch[c].spec(), sizeof(out->spec[c]));
   }
+}
+
+int32_t xaac_parse_adts_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, xaac_core_frame *out,
+                              size_t *consumed) {
+  const int32_t r = parse_frame(p, data, n, stage, consumed);
+  if (r) return r;
+  fill_core_frame(p->el, out);
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_adts_frame_mc(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, xaac_core_frame *elems, int32_t cap,
+                                 int32_t *n_elems, size_t *consumed) {
+  if (!p || !elems || !n_elems || cap < 1) return XAAC_PARSE_ERR_SYNTAX;
+  *n_elems = 0;
+  const int32_t r = parse_frame_mc(p, data, n, stage, consumed);
+  if (r) return r;
+  if (p->n_els > cap) { /* the caller's array is too short for this stream */
+    p->frame_ok = 0;
+    return XAAC_PARSE_ERR_SYNTAX;
+  }
+  for (int k = 0; k < p->n_els; k++) fill_core_frame(*element_of(p, k), elems + k);
+  *n_elems = p->n_els;
   return XAAC_PARSE_OK;
 }
 
@@ -358,6 +481,13 @@ int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side) {
   if (!p || !side || p->sr_index < 0 || p->el.n_ch < 1 || !p->frame_ok) return XAAC_PARSE_ERR_SYNTAX;
   memset(side, 0, sizeof(*side));
   xh_export_tools_side(&p->core, &p->el, side);
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_core_tools_side_mc(xaac_parser *p, int32_t element, xaac_core_tools_side *side) {
+  if (!p || !side || p->sr_index < 0 || !p->frame_ok || element < 0 || element >= p->n_els) return XAAC_PARSE_ERR_SYNTAX;
+  memset(side, 0, sizeof(*side));
+  xh_export_tools_side(&p->core, element_of(p, element), side);
   return XAAC_PARSE_OK;
 }
 
@@ -410,7 +540,9 @@ struct BatchJob {
 BatchJob g_job;
 
 /* frame t (of the call's b->frames) of stream i; the arrays of step t lie one step's array behind those of step t - 1 */
+int32_t parse_one_mc(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok);
 int32_t parse_one(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok) {
+  if (b->channel_config) return parse_one_mc(b, i, t, ok);
   const int n_ch = b->n_ch;
   const size_t S = (size_t)b->n_streams * (size_t)t, SC = S * (size_t)n_ch; /* streams / channels in front of this step's rows */
   xaac_parser *p = b->parser[i];
@@ -491,6 +623,67 @@ int32_t parse_one(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok)
   return 0;
 }
 
+/* the same for a batch with channel_config 3 .. 6: every channel element of the frame, channels in bitstream order, the tools'
+   side rows element-major */
+int32_t parse_one_mc(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok) {
+  const int n_ch = b->n_ch, n_els = k_config_elements[b->channel_config][0];
+  const size_t S = (size_t)b->n_streams * (size_t)t, SC = S * (size_t)n_ch;
+  xaac_parser *p = b->parser[i];
+  size_t used = 0;
+  const uint64_t at = b->pos ? (b->pos[i] < b->bytes[i] ? b->pos[i] : b->bytes[i]) : 0;
+  const int32_t keep_blocks = p->blocks_left, keep_crc = p->block_crc;
+  const size_t keep_left = p->frame_left;
+  int32_t r = parse_frame_mc(p, b->data[i] + at, (size_t)(b->bytes[i] - at), b->stage, &used);
+  if (r == 0 && p->channel_config != b->channel_config) { /* (a stream of another configuration: its rows would not fit) */
+    r = XAAC_PARSE_ERR_UNSUPPORTED;
+    p->frame_ok = 0;
+    p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
+  }
+  b->status[S + i] = r;
+  if (r) return r;
+  (*ok)++;
+  b->consumed[i] += used;
+  if (b->pos) b->pos[i] = at + used;
+  int32_t tools = 0;
+  int top = 0;
+  size_t row = SC + (size_t)i * n_ch;
+  for (int k = 0; k < n_els; k++) {
+    XhElement *el = element_of(p, k);
+    tools |= tools_of(*el);
+    for (int c = 0; c < el->n_ch; c++, row++) {
+      const int32_t *x = el->ch[c].spec();
+      memcpy(b->spec + row * 1024, x, 1024 * sizeof(int32_t));
+      b->ics[row * 2 + 0] = (uint8_t)el->ch[c].ics.window_sequence;
+      b->ics[row * 2 + 1] = (uint8_t)el->ch[c].ics.window_shape;
+      if (b->lines) {
+        int blk = 1024 / 16;
+        for (; blk > top; blk--) {
+          const int32_t *q = x + 16 * (blk - 1);
+          int32_t any = 0;
+          for (int j = 0; j < 16; j++) any |= q[j];
+          if (any) break;
+        }
+        top = blk > top ? blk : top;
+        if (b->tools_side) {
+          const XhIcs &ics = el->ch[c].ics;
+          const bool is_short = ics.window_sequence == XH_EIGHT_SHORT;
+          const int reach = (is_short ? 7 * 128 + p->core.swb_short[ics.max_sfb] : p->core.swb_long[ics.max_sfb]) + XT_SLACK;
+          const int reach_blk = reach >= 1024 ? 64 : (reach + 15) / 16;
+          top = reach_blk > top ? reach_blk : top;
+        }
+      }
+    }
+    if (b->tools_side) {
+      xaac_core_tools_side *side = b->tools_side + ((size_t)t * n_els + k) * (size_t)b->n_streams + i;
+      memset(side, 0, sizeof(*side));
+      xh_export_tools_side(&p->core, el, side);
+    }
+  }
+  if (b->tools) b->tools[S + i] = tools;
+  if (b->lines) b->lines[S + i] = 16 * top;
+  return 0;
+}
+
 /* one stream's frames of the call, one behind the other while its parser state and its bytes are in this core's caches */
 void parse_item(const xaac_parse_batch *b, int i, std::atomic<int> *ok) {
   const int frames = b->frames > 1 ? b->frames : 1;
@@ -505,9 +698,15 @@ void parse_item(const xaac_parse_batch *b, int i, std::atomic<int> *ok) {
 }
 
 bool batch_ok(const xaac_parse_batch *b) {
-  return b && b->n_streams >= 0 && (b->n_ch == 1 || b->n_ch == 2) && b->parser && b->data && b->bytes && b->spec && b->ics &&
+  const bool mc = b && b->channel_config >= 3 && b->channel_config <= 6;
+  return b && b->n_streams >= 0 && (b->n_ch == 1 || b->n_ch == 2 || mc) && (mc || b->channel_config == 0) && b->parser && b->data && b->bytes && b->spec && b->ics &&
          b->consumed && b->status && (!b->with_sbr || (b->header && b->frame && b->flags)) && b->frames >= 0 &&
          (b->frames <= 1 || b->pos); /* several frames per call: the positions are the library's */
+}
+
+/* a multichannel batch: the configuration's channel count, and no SBR side info (per-element SBR is not built) */
+bool batch_unsupported(const xaac_parse_batch *b) {
+  return b->channel_config && (b->n_ch != k_config_channels[b->channel_config] || b->with_sbr);
 }
 
 int batch_threads(const xaac_parse_batch *b) {
@@ -555,6 +754,7 @@ int32_t xaac_parse_batch_run_sized(const xaac_parse_batch *b_in, uint64_t struct
   if (!batch_sized(b_in, struct_size, &full)) return XAAC_PARSE_ERR_SYNTAX;
   const xaac_parse_batch *b = &full;
   if (!batch_ok(b)) return XAAC_PARSE_ERR_SYNTAX;
+  if (batch_unsupported(b)) return XAAC_PARSE_ERR_UNSUPPORTED;
   /* between this thread's _start and its _wait the team belongs to that batch: waiting for it here would wait for the caller's
      own _wait (another thread's batch in flight is simply waited for, as two _run calls wait for each other) */
   if (g_job.in_flight.load(std::memory_order_acquire) && g_job.owner.load(std::memory_order_relaxed) == this_thread())
@@ -571,6 +771,7 @@ int32_t xaac_parse_batch_start_sized(const xaac_parse_batch *b_in, uint64_t stru
   if (!batch_sized(b_in, struct_size, &full)) return XAAC_PARSE_ERR_SYNTAX;
   const xaac_parse_batch *b = &full;
   if (!batch_ok(b)) return XAAC_PARSE_ERR_SYNTAX;
+  if (batch_unsupported(b)) return XAAC_PARSE_ERR_UNSUPPORTED;
   /* a second _start (or a _run) of the thread whose _start is unanswered is an error it gets back, not a wait for a release that
      only its own _wait would bring; behind another thread's batch the call waits like any other */
   if (g_job.in_flight.load(std::memory_order_acquire) && g_job.owner.load(std::memory_order_relaxed) == this_thread())

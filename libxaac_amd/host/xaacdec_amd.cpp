@@ -223,9 +223,28 @@ struct StagingGroup {
   std::vector<uint64_t> consumed;
 };
 
-void write_wav(const std::string &path, const std::vector<int16_t> &pcm, int channels, int rate) {
+/* More than two channels: the reference's WAVE_FORMAT_EXTENSIBLE header (test/decoder/ixheaacd_main.c: a 40-byte fmt chunk with the
+   channel mask of ixheaacd_get_channel_mask and the PCM sub-format GUID; its RIFF size counts 36 bytes in front of the data as
+   for the plain header), 68 bytes in front of the samples */
+void write_wav_extensible(FILE *f, size_t samples, int channels, int rate, uint32_t mask) {
+  const uint32_t data = (uint32_t)(samples * 2), riff = 36 + data, fmt = 40, byte_rate = (uint32_t)(rate * channels * 2), sr = (uint32_t)rate;
+  const uint16_t tag = 0xfffe, ch = (uint16_t)channels, align = (uint16_t)(channels * 2), bits = 16, cb = 22;
+  static const uint8_t pcm_guid[16] = {0x01, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xaa, 0x00, 0x38, 0x9b, 0x71};
+  fwrite("RIFF", 1, 4, f), fwrite(&riff, 4, 1, f), fwrite("WAVEfmt ", 1, 8, f), fwrite(&fmt, 4, 1, f);
+  fwrite(&tag, 2, 1, f), fwrite(&ch, 2, 1, f), fwrite(&sr, 4, 1, f), fwrite(&byte_rate, 4, 1, f);
+  fwrite(&align, 2, 1, f), fwrite(&bits, 2, 1, f), fwrite(&cb, 2, 1, f), fwrite(&bits, 2, 1, f), fwrite(&mask, 4, 1, f);
+  fwrite(pcm_guid, 1, 16, f), fwrite("data", 1, 4, f), fwrite(&data, 4, 1, f);
+}
+
+void write_wav(const std::string &path, const std::vector<int16_t> &pcm, int channels, int rate, uint32_t mask = 0) {
   FILE *f = fopen(path.c_str(), "wb");
   if (!f) die("fopen(output)");
+  if (channels > 2) {
+    write_wav_extensible(f, pcm.size(), channels, rate, mask);
+    fwrite(pcm.data(), 2, pcm.size(), f);
+    fclose(f);
+    return;
+  }
   const uint32_t data = (uint32_t)(pcm.size() * 2), riff = 36 + data, fmt = 16, byte_rate = (uint32_t)(rate * channels * 2);
   const uint16_t pcm_tag = 1, ch = (uint16_t)channels, align = (uint16_t)(channels * 2), bits = 16;
   const uint32_t sr = (uint32_t)rate;
@@ -240,6 +259,10 @@ void write_wav(const std::string &path, const std::vector<int16_t> &pcm, int cha
 struct Job {
   std::vector<std::vector<uint8_t>> datas; /* -ilist: one per stream; else the one input */
   int n_ch, sbr, esbr, out_ch, rate, per;
+  int channel_config; /* 3 .. 6: a stream of several channel elements (AAC-LC only); 0: one element, the mono / stereo paths */
+  int n_els;          /* channel elements of a frame: 1, or the configuration's 2 .. 4 */
+  int first_ch[4];    /* ... and the first bitstream channel of each */
+  int slot[8];        /* ... output channel of bitstream channel c: where the reference routes its elements (layout_of) */
   int hq; /* -esbr_hq:1: the DFT harmonic transposer in the QMF one's place (Path A only) */
   int threads, verify, profile;
   int gputools; /* -gputools:1: parse at stage 1, the spectral tools run on the GPU in front of the IMDCT */
@@ -291,7 +314,8 @@ class ParseSide {
       xaac_sbr_frame *frame = w.sbr ? mem.pinned<xaac_sbr_frame>((size_t)T * NC) : nullptr;
       xaac_ps_frame *psf = w.ps ? mem.pinned<xaac_ps_frame>((size_t)T * N) : nullptr;
       xaac_esbr_side *eside = w.esbr ? mem.pinned<xaac_esbr_side>((size_t)T * NC) : nullptr;
-      xaac_core_tools_side *tside = J.gputools ? mem.pinned<xaac_core_tools_side>((size_t)T * N) : nullptr;
+      const int NE = J.n_els; /* the tools' side rows: one per channel element, element-major within a step */
+      xaac_core_tools_side *tside = J.gputools ? mem.pinned<xaac_core_tools_side>((size_t)T * N * NE) : nullptr;
       StagingGroup &G = grp_[g];
       G.flags.assign((size_t)T * N * 8, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N, 0);
       G.lines.assign((size_t)T * N, 0), G.consumed.assign((size_t)N, 0);
@@ -300,7 +324,7 @@ class ParseSide {
         s.spec = spec + (size_t)t * NC * 1024, s.ics = ics + (size_t)t * NC * 2;
         s.header = header ? header + (size_t)t * NC : nullptr, s.frame = frame ? frame + (size_t)t * NC : nullptr;
         s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
-        s.tside = tside ? tside + (size_t)t * N : nullptr;
+        s.tside = tside ? tside + (size_t)t * N * NE : nullptr;
         s.flags = &G.flags[(size_t)t * N * 8], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N];
         s.delivered = 0, s.lines = 1024;
       }
@@ -355,6 +379,7 @@ class ParseSide {
     xaac_parse_batch b;
     memset(&b, 0, sizeof(b));
     b.n_streams = N, b.n_ch = J_.n_ch, b.with_sbr = J_.sbr, b.ps_enable = 1, b.stage = J_.gputools ? 1 : 2, b.threads = J_.threads;
+    b.channel_config = J_.channel_config;
     b.parser = parser_.data(), b.data = ptr_.data(), b.bytes = left_.data(), b.pos = pos_.data(), b.frames = T;
     Staging &s0 = st_[g * T];
     b.spec = s0.spec, b.ics = s0.ics, b.header = s0.header, b.frame = s0.frame, b.ps_frame = s0.ps;
@@ -444,28 +469,36 @@ class Chain {
    driver runs this in front of whichever chain */
 class ToolsStage {
  public:
-  explicit ToolsStage(const Env &E) : E_(E) {
-    const size_t N = (size_t)E.N;
-    d_side_ = E.mem.dev<xaac_core_tools_side>(N), d_state_ = E.mem.dev<xaac_core_tools_state>(N);
-    HIP(hipMemset(d_state_, 0, N * sizeof(xaac_core_tools_state)));
-    for (int k = 0; k < 2; k++) d_status_[k] = E.mem.dev<int32_t>(N), h_status_[k] = E.mem.pinned<int32_t>(N);
+  explicit ToolsStage(const Env &E) : E_(E), rows_((size_t)E.N * E.J.n_els) {
+    d_side_ = E.mem.dev<xaac_core_tools_side>(rows_), d_state_ = E.mem.dev<xaac_core_tools_state>(rows_);
+    HIP(hipMemset(d_state_, 0, rows_ * sizeof(xaac_core_tools_state)));
+    for (int k = 0; k < 2; k++) d_status_[k] = E.mem.dev<int32_t>(rows_), h_status_[k] = E.mem.pinned<int32_t>(rows_);
   }
   void send_up(const Staging &s) {
-    HIP(hipMemcpyAsync(d_side_, s.tside, (size_t)E_.N * sizeof(xaac_core_tools_side), hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_side_, s.tside, rows_ * sizeof(xaac_core_tools_side), hipMemcpyHostToDevice, E_.stream));
   }
-  void run(int slot) { /* stage-1 spectra -> the spectra the IMDCT takes, in place (xaac_parse_batch::lines covers what they reach) */
-    xaac_aac_tools_batch tb;
-    memset(&tb, 0, sizeof(tb));
-    tb.n = E_.N, tb.spec_stride = 1024 * E_.J.n_ch, tb.spec = E_.d_spec, tb.side = d_side_, tb.state = d_state_, tb.status = d_status_[slot];
-    XA(xaac_aac_tools_process_batch(E_.ctx, &tb));
+  /* stage-1 spectra -> the spectra the IMDCT takes, in place (xaac_parse_batch::lines covers what they reach).  Side, state and
+     status rows are element-major: one launch per element index over all streams, from the element's first channel row (a pair's
+     channels are neighbouring rows in the output order too), the stream's rows apart */
+  void run(int slot) {
+    const size_t N = (size_t)E_.N;
+    for (int k = 0; k < E_.J.n_els; k++) {
+      xaac_aac_tools_batch tb;
+      memset(&tb, 0, sizeof(tb));
+      const int row = E_.J.channel_config ? E_.J.slot[E_.J.first_ch[k]] : 0;
+      tb.n = E_.N, tb.spec_stride = 1024 * E_.J.n_ch, tb.spec = E_.d_spec + (size_t)row * 1024;
+      tb.side = d_side_ + k * N, tb.state = d_state_ + k * N, tb.status = d_status_[slot] + k * N;
+      XA(xaac_aac_tools_process_batch(E_.ctx, &tb));
+    }
   }
   void bring_down(int slot, hipStream_t down) {
-    HIP(hipMemcpyAsync(h_status_[slot], d_status_[slot], (size_t)E_.N * 4, hipMemcpyDeviceToHost, down));
+    HIP(hipMemcpyAsync(h_status_[slot], d_status_[slot], rows_ * 4, hipMemcpyDeviceToHost, down));
   }
-  const int32_t *status(int slot) const { return h_status_[slot]; }
+  const int32_t *status(int slot) const { return h_status_[slot]; } /* [n_els][N] */
 
  private:
   const Env E_;
+  const size_t rows_;
   xaac_core_tools_side *d_side_;
   xaac_core_tools_state *d_state_;
   int32_t *d_status_[2], *h_status_[2];
@@ -498,6 +531,7 @@ class LcChain : public Chain {
     memset(&lb, 0, sizeof(lb));
     lb.n_streams = N, lb.frame_len = 1024, lb.samples = d_out32_, lb.stride = 1024 * n_ch, lb.qshift_adj = d_qadj_, lb.state = d_lim_;
     lb.num_channels = n_ch, lb.pcm16 = E_.d_pcm[slot], lb.workspace = d_ws_, lb.workspace_bytes = ws_bytes_;
+    lb.planar = E_.imdct.ch_fac == 1 && n_ch > 1; /* more than two channels: the IMDCT writes [stream][channel][1024] */
     XA(xaac_peak_limiter_process_batch(E_.ctx, &lb));
     return {E_.d_pcm[slot], (size_t)N * E_.J.per * E_.J.out_ch * 2, false, false, 0};
   }
@@ -1036,12 +1070,15 @@ class ShardDriver {
     down_ = mem.stream();
     Env E = {J, N, NC, mem, ctx_, stream_, d_spec_, {nullptr, nullptr}, {nullptr, nullptr}, {}};
     for (int k = 0; k < 2; k++) {
-      E.d_pcm[k] = mem.dev<int16_t>((size_t)N * J.per * J.out_ch), h_pcm_[k] = mem.pinned<int16_t>((size_t)N * J.per * 2);
+      E.d_pcm[k] = mem.dev<int16_t>((size_t)N * J.per * J.out_ch), h_pcm_[k] = mem.pinned<int16_t>((size_t)N * J.per * (J.out_ch > 2 ? J.out_ch : 2));
       E.d_status[k] = mem.dev<int32_t>((size_t)NC), h_status_[k] = mem.pinned<int32_t>((size_t)NC);
       ev_kernels_[k] = mem.event(), ev_down_[k] = mem.event();
     }
     memset(&E.imdct, 0, sizeof(E.imdct));
-    E.imdct.n_ch = NC, E.imdct.ch_fac = J.n_ch, E.imdct.spec = d_spec_, E.imdct.ics = d_ics_, E.imdct.overlap = d_overlap, E.imdct.state = d_ovl;
+    /* more than two channels: every channel a row of its own (ch_fac 1), the rows of a stream in output channel order --
+       send_up puts them there --, so that the overlap, window state and qshift_adj rows and the planar block the limiter reads are
+       in that order too */
+    E.imdct.n_ch = NC, E.imdct.ch_fac = J.channel_config ? 1 : J.n_ch, E.imdct.spec = d_spec_, E.imdct.ics = d_ics_, E.imdct.overlap = d_overlap, E.imdct.state = d_ovl;
     for (int k = 0; k < 2; k++) d_status_[k] = E.d_status[k];
     if (J.gputools) tools_.reset(new ToolsStage(E));
     /* the chain, picked once */
@@ -1051,6 +1088,8 @@ class ShardDriver {
     parse_.reset(new ParseSide(J, S, mem, chain_->wants()));
     S.pcms.assign((size_t)(J.list_mode ? N : 1), std::vector<int16_t>()); /* every stream's output (-ilist), or stream 0's */
     ended_.assign((size_t)N, 0), refused_.assign((size_t)N, 0);
+    if (J.channel_config)
+      for (auto &h : h_ics_routed_) h = mem.pinned<uint8_t>((size_t)NC * 2);
   }
 
   void run() {
@@ -1067,7 +1106,8 @@ class ShardDriver {
       if (s.delivered != N_) note_ended(s);
       if (step % T == 0) parse_->start(); /* the next group's frames are parsed while the GPU works on this one's */
       t_phase_ = std::chrono::steady_clock::now();
-      send_up(s);
+      if (J_.channel_config) send_up_routed(s, which);
+      else send_up(s);
       lap(0);
       if (tools_) tools_->run(slot);
       const StepOut o = chain_->run(s, slot);
@@ -1113,6 +1153,27 @@ class ShardDriver {
     HIP(hipMemcpyAsync(d_ics_, s.ics, (size_t)NC_ * 2, hipMemcpyHostToDevice, stream_));
     if (tools_) tools_->send_up(s);
   }
+  /* more than two channels: bitstream channel c of every stream to row J.slot[c] of the stream's rows -- one strided copy per
+     channel for the spectra; the window info through a routed copy of the step's own (its staging set comes round again 3 T
+     steps later, long behind the copy) */
+  void send_up_routed(const Staging &s, int which) {
+    const int n_ch = J_.n_ch, N = N_;
+    const int width = s.lines > lines_held_ ? s.lines : lines_held_;
+    lines_held_ = s.lines;
+    uint8_t *ics = h_ics_routed_[which];
+    for (int c = 0; c < n_ch; c++) {
+      const int to = J_.slot[c];
+      if (width > 0)
+        HIP(hipMemcpy2DAsync(d_spec_ + (size_t)to * 1024, (size_t)n_ch * 4096, s.spec + (size_t)c * 1024, (size_t)n_ch * 4096, (size_t)width * 4,
+                             (size_t)N, hipMemcpyHostToDevice, stream_));
+      for (int i = 0; i < N; i++) {
+        const size_t a = ((size_t)i * n_ch + to) * 2, b = ((size_t)i * n_ch + c) * 2;
+        ics[a] = s.ics[b], ics[a + 1] = s.ics[b + 1];
+      }
+    }
+    HIP(hipMemcpyAsync(d_ics_, ics, (size_t)NC_ * 2, hipMemcpyHostToDevice, stream_));
+    if (tools_) tools_->send_up(s);
+  }
   void bring_down(const StepOut &o, int slot) {
     HIP(hipEventRecord(ev_kernels_[slot], stream_));
     HIP(hipStreamWaitEvent(down_, ev_kernels_[slot], 0));
@@ -1137,9 +1198,10 @@ class ShardDriver {
     const int32_t *alive = pending_.s->status; /* 0: the stream delivered a frame in that step */
     if (tools_) {
       const int32_t *h_tstatus = tools_->status(pending_.slot);
-      for (int i = 0; i < N; i++)
-        if (h_tstatus[i] < 0 && alive[i] == 0 && !refused_[(size_t)i]) /* as for the SBR kernels' refusals below */
-          refuse((size_t)i, i, "AAC tools kernel");
+      for (int k = 0; k < J_.n_els; k++)
+        for (int i = 0; i < N; i++)
+          if (h_tstatus[(size_t)k * N + i] < 0 && alive[i] == 0 && !refused_[(size_t)i]) /* as for the SBR kernels' refusals below */
+            refuse((size_t)i, i, "AAC tools kernel");
     }
     /* (rows of streams that are over re-run their last staging rows: what the kernels say about those is not looked at) */
     for (int i = 0; i < pending_.out.status_rows; i++) {
@@ -1181,6 +1243,7 @@ class ShardDriver {
   int32_t *d_spec_;
   xaac_ics_info *d_ics_;
   int16_t *h_pcm_[2];
+  uint8_t *h_ics_routed_[3 * ParseSide::T] = {nullptr};
   int32_t *d_status_[2], *h_status_[2];
   std::unique_ptr<ToolsStage> tools_;
   std::unique_ptr<Chain> chain_;
@@ -1202,18 +1265,33 @@ class ShardDriver {
    without payloads).  `report`: the parser's code goes into the message (the batch's first stream). */
 struct FirstFrame {
   int rate, n_ch, sbr;
+  int channel_config; /* 3 .. 6: several channel elements (the frame's sequence is the configuration's, or it would not have parsed); else 0 */
 };
 FirstFrame first_frame(const std::vector<uint8_t> &data, bool report) {
   xaac_adts_header hdr;
   if (xaac_adts_parse_header(data.data(), data.size(), &hdr)) die("ADTS header");
   xaac_parser *probe = nullptr;
   XA(xaac_parser_create(&probe));
-  xaac_core_frame cf;
+  static thread_local xaac_core_frame cf[4];
   size_t used = 0;
-  const int32_t rc = xaac_parse_adts_frame(probe, data.data(), data.size(), 1, &cf, &used);
+  int32_t n_elems = 0;
+  const int32_t rc = xaac_parse_adts_frame_mc(probe, data.data(), data.size(), 1, cf, 4, &n_elems, &used);
   if (rc) die("first frame", report ? rc : 0);
   xaac_parser_destroy(probe);
-  return {hdr.sampling_rate, cf.n_ch, cf.sbr_bytes > 0};
+  int n_ch = 0, sbr = 0;
+  for (int k = 0; k < n_elems; k++) n_ch += cf[k].n_ch, sbr |= cf[k].sbr_bytes > 0;
+  return {hdr.sampling_rate, n_ch, sbr, n_elems > 1 ? hdr.channel_config : 0};
+}
+
+/* Where the reference puts the channels of channel_config 3 .. 6 and the mask it writes into the WAV header
+   (ixheaacd_get_channel_mask, common_lpfuncs.c:107-173, through the slot / element routing of api.c:3176-3177): the first CPE
+   takes the first two output channels, then the first SCE, the LFE, the second CPE, the second SCE.  slot[c]: output channel of
+   bitstream channel c. */
+uint32_t layout_of(int channel_config, int *slot) {
+  static const int k_slot[4][6] = {{2, 0, 1}, {2, 0, 1, 3}, {2, 0, 1, 3, 4}, {2, 0, 1, 4, 5, 3}};
+  static const uint32_t k_mask[4] = {0x7, 0x107, 0x37, 0x3f};
+  for (int c = 0; c < 6; c++) slot[c] = k_slot[channel_config - 3][c];
+  return k_mask[channel_config - 3];
 }
 
 void decode_shard(const Job &J, Shard &S) {
@@ -1285,10 +1363,12 @@ int main(int argc, char **argv) {
   const FirstFrame f0 = first_frame(datas[0], true);
   for (size_t k = 1; k < datas.size(); k++) { /* -ilist: one kind of stream per batch */
     const FirstFrame f = first_frame(datas[k], false);
-    if (f.rate != f0.rate || f.n_ch != f0.n_ch || f.sbr != f0.sbr)
-      die("-ilist: streams of different kinds (sampling rate, channels, SBR) in one batch");
+    if (f.rate != f0.rate || f.n_ch != f0.n_ch || f.sbr != f0.sbr || f.channel_config != f0.channel_config)
+      die("-ilist: streams of different kinds (sampling rate, channels, channel configuration, SBR) in one batch");
   }
   const int n_ch = f0.n_ch, sbr = f0.sbr;
+  if (f0.channel_config && sbr) die("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported");
+
   if (!sbr) esbr = 0; /* AAC-LC streams decode the same either way */
   const int out_ch = sbr ? 2 : n_ch; /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC as coded */
   const int N = ilist.empty() ? copies : (int)datas.size(), rate = f0.rate, out_rate = sbr ? 2 * rate : rate, per = sbr ? 2048 : 1024;
@@ -1324,6 +1404,15 @@ int main(int argc, char **argv) {
   J.datas = std::move(datas);
   J.hq = hq;
   J.n_ch = n_ch, J.sbr = sbr, J.esbr = esbr, J.out_ch = out_ch, J.rate = rate, J.per = per;
+  J.channel_config = f0.channel_config;
+  memset(J.slot, 0, sizeof(J.slot));
+  const uint32_t mask = J.channel_config ? layout_of(J.channel_config, J.slot) : 0;
+  J.n_els = 1, J.first_ch[0] = J.first_ch[1] = J.first_ch[2] = J.first_ch[3] = 0;
+  if (J.channel_config) { /* SCE CPE [SCE | CPE [LFE]] */
+    static const int k_first[4][4] = {{0, 1}, {0, 1, 3}, {0, 1, 3}, {0, 1, 3, 5}};
+    J.n_els = J.channel_config == 3 ? 2 : (J.channel_config == 6 ? 4 : 3);
+    for (int k = 0; k < 4; k++) J.first_ch[k] = k_first[J.channel_config - 3][k];
+  }
   J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode, J.gputools = gputools;
   const auto t_run = std::chrono::steady_clock::now();
   if (gpus == 1) {
@@ -1354,10 +1443,10 @@ int main(int argc, char **argv) {
         if (slash != std::string::npos) base = base.substr(slash + 1);
         const size_t dot = base.find_last_of('.');
         if (dot != std::string::npos) base = base.substr(0, dot);
-        write_wav(odir + "/" + base + ".wav", S.pcms[i], out_ch, out_rate);
+        write_wav(odir + "/" + base + ".wav", S.pcms[i], out_ch, out_rate, mask);
       }
   } else {
-    write_wav(out, pcm, out_ch, out_rate);
+    write_wav(out, pcm, out_ch, out_rate, mask);
   }
   if (!quiet && gpus > 1) { /* (the run's own line stays the last one) */
     printf("{\"per_gpu_frames_per_s\": [");
