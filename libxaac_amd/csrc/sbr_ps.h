@@ -429,6 +429,14 @@ FX_HD void xp_rotate(int32_t *l, int32_t *r, int16_t h11, int16_t h12, int16_t h
   *r = fx_shl(nr, 2);
 }
 
+/* the same with the coefficients as fx_mul32x16's multiplier words: the int16 in the high half, the low half zero */
+FX_HD void xp_rotate_w(int32_t *l, int32_t *r, uint32_t h11, uint32_t h12, uint32_t h21, uint32_t h22) {
+  const int32_t nl = fx_add_sat(fx_mulhi(*l, (int32_t)h11), fx_mulhi(*r, (int32_t)h21));
+  const int32_t nr = fx_add_sat(fx_mulhi(*l, (int32_t)h12), fx_mulhi(*r, (int32_t)h22));
+  *l = fx_shl(nl, 2);
+  *r = fx_shl(nr, 2);
+}
+
 /* ps_dec.c:856: advance the interpolated coefficients by one slot and mix left / decorrelated into the
    output pair, in the hybrid domain for QMF bands 0..2 (their sub-bands are then summed back) */
 template <class PS>

@@ -38,6 +38,8 @@
 #ifndef XAAC_SBR_PS_FRAME_H
 #define XAAC_SBR_PS_FRAME_H
 
+#include <stddef.h>
+
 #include "sbr_ps.h"
 
 #ifndef XP_T
@@ -50,9 +52,11 @@
 #if defined(__HIPCC__)
 #define XP_UNROLL _Pragma("unroll")
 #define XP_NOUNROLL _Pragma("nounroll")
+#define XP_LAMBDA_INLINE __attribute__((always_inline))
 #else
 #define XP_UNROLL
 #define XP_NOUNROLL
+#define XP_LAMBDA_INLINE
 #endif
 
 struct XpFrameWork {
@@ -69,8 +73,12 @@ struct XpFrameWork {
     int16_t ratio[32][20];   /* ... compacted in place into the transient ratios (entry i lands inside entry i / 2) */
   };
   uint32_t ap_h[32][11];     /* outputs of the hybrid sub-bands' all-pass chains (re, im pairs); column 10: the other lanes' */
-  int16_t seg_h[XP_MAX_SEG][4][24]; /* per segment and group: H11, H12, H21, H22 before the segment's first slot */
-  int16_t seg_d[XP_MAX_SEG][4][24]; /* per-slot increments */
+  uint32_t seg_hd[XP_MAX_SEG][4][24]; /* per segment and group: H11, H12, H21, H22 before the segment's first slot (high
+                                          half) and their per-slot increments (low half): a border reloads four words */
+};
+template <bool B>
+struct XpBool {
+  static constexpr bool value = B;
 };
 
 FX_HD int xp_popc(uint32_t v) { return __builtin_popcount(v); }
@@ -79,13 +87,28 @@ FX_HD uint32_t xp_pack16(int16_t lo, int16_t hi) { return (uint32_t)(uint16_t)lo
 FX_HD int16_t xp_lo16(uint32_t v) { return (int16_t)(v & 0xffffu); }
 FX_HD int16_t xp_hi16(uint32_t v) { return (int16_t)(v >> 16); }
 
-/* a.lo * b.lo + a.hi * b.hi of two packed pairs of int16, wrapping: one v_dot2_i32_i16 on the GPU */
+/* a.lo * b.lo + a.hi * b.hi of two packed pairs of int16, wrapping: one v_dot2_i32_i16 on the GPU.  Written out: the
+   builtin (__builtin_amdgcn_sdot2 with a zero addend) is selected as the accumulating two-operand v_dot2c_i32_i16 with a
+   v_mov_b32 of zero in front of it -- eight extra instructions in every slot of the walk. */
 FX_HD int32_t xp_dot2(uint32_t a, uint32_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  typedef short xp_short2 __attribute__((ext_vector_type(2)));
-  return __builtin_amdgcn_sdot2(__builtin_bit_cast(xp_short2, a), __builtin_bit_cast(xp_short2, b), 0, false);
+  int32_t r;
+  asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
+  return r;
 #else
   return (int32_t)((uint32_t)((int32_t)xp_lo16(a) * xp_lo16(b)) + (uint32_t)((int32_t)xp_hi16(a) * xp_hi16(b)));
+#endif
+}
+/* a segment's word of XpFrameWork::seg_hd n slots into the segment: H + n * delta, wrapping as the reference's int16 adds do */
+FX_HD int16_t xp_seg_coeff(uint32_t hd, int n) { return (int16_t)(xp_hi16(hd) + n * xp_lo16(hd)); }
+/* two neighbouring int16 of an array, the first at an even index of a word-aligned row, as one packed pair: one LDS word
+   read on the GPU */
+FX_HD uint32_t xp_load_pair(const int16_t *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef uint32_t __attribute__((may_alias)) xp_u32_alias;
+  return *reinterpret_cast<const xp_u32_alias *>(p);
+#else
+  return xp_pack16(p[0], p[1]);
 #endif
 }
 /* a complex 16-bit rotation factor (re, im) as the two pairs the products of xp_allpass take: (re, -im) gives the real
@@ -101,27 +124,71 @@ FX_HD XpPhase xp_phase_pairs(int16_t re, int16_t im) {
   p.im_pair = xp_pack16(im, re);
   return p;
 }
+/* The chain's 16-bit arithmetic on (re, im) pairs, both halves at once.  (int16_t)(v >> 15) is bits 15..30 of v; of a
+   product with twice the factor those are the word's high half, which a byte permute moves -- so a sample pair times a
+   decay factor is two 24-bit multiplies and one v_perm_b32, and the wrapping adds and subtracts are packed ones.  (As
+   single int16 values every product was a multiply, a shift and its own add, 17 instructions per link; now 13.) */
+FX_HD uint32_t xp_q15_pair(int32_t a, int32_t b) { /* ((int16_t)(a >> 15), (int16_t)(b >> 15)) */
+  return (((uint32_t)a >> 15) & 0xffffu) | (((uint32_t)b << 1) & 0xffff0000u);
+}
+FX_HD uint32_t xp_hi_pair(int32_t a, int32_t b) { /* the high halves of a and b */
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x07060302u);
+#else
+  return ((uint32_t)a >> 16) | ((uint32_t)b & 0xffff0000u);
+#endif
+}
+/* xs_mult16_shl of both halves of p with the factor f, handed in as 2 * f (17 bits) */
+FX_HD uint32_t xp_mult16_shl_pair(uint32_t p, int32_t f2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return xp_hi_pair(__mul24(xp_lo16(p), f2), __mul24(xp_hi16(p), f2));
+#else
+  return xp_hi_pair((int32_t)((uint32_t)(int32_t)xp_lo16(p) * (uint32_t)f2), (int32_t)((uint32_t)(int32_t)xp_hi16(p) * (uint32_t)f2));
+#endif
+}
+/* xp_m16x16_shl (sbr_ps.h) with the doubling moved into the second factor: one 24-bit multiply per product */
+FX_HD int32_t xp_m16x16_shl_pre(int16_t a, int32_t b2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __mul24(a, b2);
+#else
+  return (int32_t)((uint32_t)(int32_t)a * (uint32_t)b2);
+#endif
+}
+FX_HD uint32_t xp_add16_pair(uint32_t a, uint32_t b) { /* wrapping, per half */
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef short xp_short2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, (xp_short2)(__builtin_bit_cast(xp_short2, a) + __builtin_bit_cast(xp_short2, b)));
+#else
+  return ((a + b) & 0xffffu) | ((a & 0xffff0000u) + (b & 0xffff0000u));
+#endif
+}
+FX_HD uint32_t xp_sub16_pair(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef short xp_short2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(uint32_t, (xp_short2)(__builtin_bit_cast(xp_short2, a) - __builtin_bit_cast(xp_short2, b)));
+#else
+  return ((a - b) & 0xffffu) | ((a & 0xffff0000u) - (b & 0xffff0000u));
+#endif
+}
 /* xp_allpass (sbr_ps.h, ps_dec.c:236 / :339) on packed (re, im) pairs: d0 = the 2-slot line's oldest entry (replaced by the
    new sample), e0 / e1 / e2 = the three links' entries at their read positions (replaced); returns the chain's output pair */
 FX_HD uint32_t xp_allpass_packed(uint32_t &d0, uint32_t new_pair, const XpPhase &ph, uint32_t &e0, uint32_t &e1, uint32_t &e2,
                                  const XpPhase &p0, const XpPhase &p1, const XpPhase &p2, int16_t decay0, int16_t decay1,
                                  int16_t decay2) {
-  int16_t in_re = (int16_t)(xp_dot2(d0, ph.re_pair) >> 15), in_im = (int16_t)(xp_dot2(d0, ph.im_pair) >> 15);
+  uint32_t in = xp_q15_pair(xp_dot2(d0, ph.re_pair), xp_dot2(d0, ph.im_pair));
   d0 = new_pair;
   uint32_t *e[3] = {&e0, &e1, &e2};
   const XpPhase *pp[3] = {&p0, &p1, &p2};
-  const int16_t decay[3] = {decay0, decay1, decay2};
+  const int32_t decay2x[3] = {2 * decay0, 2 * decay1, 2 * decay2};
   XP_UNROLL
   for (int m = 0; m < 3; m++) {
     const uint32_t s = *e[m];
-    int16_t t_re = (int16_t)(xp_dot2(s, pp[m]->re_pair) >> 15), t_im = (int16_t)(xp_dot2(s, pp[m]->im_pair) >> 15);
-    t_re = (int16_t)(t_re - xs_mult16_shl(in_re, decay[m]));
-    t_im = (int16_t)(t_im - xs_mult16_shl(in_im, decay[m]));
-    *e[m] = xp_pack16((int16_t)(in_re + xs_mult16_shl(t_re, decay[m])), (int16_t)(in_im + xs_mult16_shl(t_im, decay[m])));
-    in_re = t_re;
-    in_im = t_im;
+    const uint32_t t = xp_sub16_pair(xp_q15_pair(xp_dot2(s, pp[m]->re_pair), xp_dot2(s, pp[m]->im_pair)),
+                                     xp_mult16_shl_pair(in, decay2x[m]));
+    *e[m] = xp_add16_pair(in, xp_mult16_shl_pair(t, decay2x[m]));
+    in = t;
   }
-  return xp_pack16(in_re, in_im);
+  return in;
 }
 
 /* env_calc.c:1099 on one word, without a branch: a left count and a right count of which at most one is not zero (a shift
@@ -234,14 +301,10 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   /* ---- P2: the envelope walk of qmf_dec.c:1019 ("if slot == border[env]: init_rot_env; env++").  Segment 0
      continues the last frame's interpolation from the state; every border reached starts a new one. */
   XS_PAR(g, 0, XAAC_PS_GROUPS) {
-    w->seg_h[0][0][g] = ps->H11_H12[2 * g];
-    w->seg_h[0][1][g] = ps->H11_H12[2 * g + 1];
-    w->seg_h[0][2][g] = ps->H21_H22[2 * g];
-    w->seg_h[0][3][g] = ps->H21_H22[2 * g + 1];
-    w->seg_d[0][0][g] = ps->delta_h11_h12[2 * g];
-    w->seg_d[0][1][g] = ps->delta_h11_h12[2 * g + 1];
-    w->seg_d[0][2][g] = ps->delta_h21_h22[2 * g];
-    w->seg_d[0][3][g] = ps->delta_h21_h22[2 * g + 1];
+    w->seg_hd[0][0][g] = xp_pack16(ps->delta_h11_h12[2 * g], ps->H11_H12[2 * g]);
+    w->seg_hd[0][1][g] = xp_pack16(ps->delta_h11_h12[2 * g + 1], ps->H11_H12[2 * g + 1]);
+    w->seg_hd[0][2][g] = xp_pack16(ps->delta_h21_h22[2 * g], ps->H21_H22[2 * g]);
+    w->seg_hd[0][3][g] = xp_pack16(ps->delta_h21_h22[2 * g + 1], ps->H21_H22[2 * g + 1]);
   }
   const int usb_prev = cx.uni(ps->usb);
   uint32_t seg_mask = 0; /* bit l: a border was reached at slot l -- segment popcount(bits 0..l) starts there (a scalar) */
@@ -255,14 +318,10 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         cx.sync();
         xp_rot_env_coeffs(cx, T, ps, pf, env); /* ps->H.. = the old targets, ps->delta.., ps->h.._vec = the new ones */
         XS_PAR(g, 0, XAAC_PS_GROUPS) {
-          w->seg_h[nseg][0][g] = ps->H11_H12[2 * g];
-          w->seg_h[nseg][1][g] = ps->H11_H12[2 * g + 1];
-          w->seg_h[nseg][2][g] = ps->H21_H22[2 * g];
-          w->seg_h[nseg][3][g] = ps->H21_H22[2 * g + 1];
-          w->seg_d[nseg][0][g] = ps->delta_h11_h12[2 * g];
-          w->seg_d[nseg][1][g] = ps->delta_h11_h12[2 * g + 1];
-          w->seg_d[nseg][2][g] = ps->delta_h21_h22[2 * g];
-          w->seg_d[nseg][3][g] = ps->delta_h21_h22[2 * g + 1];
+          w->seg_hd[nseg][0][g] = xp_pack16(ps->delta_h11_h12[2 * g], ps->H11_H12[2 * g]);
+          w->seg_hd[nseg][1][g] = xp_pack16(ps->delta_h11_h12[2 * g + 1], ps->H11_H12[2 * g + 1]);
+          w->seg_hd[nseg][2][g] = xp_pack16(ps->delta_h21_h22[2 * g], ps->H21_H22[2 * g]);
+          w->seg_hd[nseg][3][g] = xp_pack16(ps->delta_h21_h22[2 * g + 1], ps->H21_H22[2 * g + 1]);
         }
         seg_mask |= 1u << l;
         nseg++;
@@ -392,6 +451,11 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     const int is0 = cx.uni(ps->idx_ser[0]), is1 = cx.uni(ps->idx_ser[1]), is2 = cx.uni(ps->idx_ser[2]);
     const int clear_lo = (usb > usb_prev && usb_prev) ? usb_prev : 64; /* ps_dec.c:733-757: bands that just became active */
     const int clear_hi = usb < 23 ? usb : 23;
+    const int p14_0 = idx_long0 % 14;
+    const int cs_right = common_shift < 0 ? (-common_shift > 31 ? 31 : -common_shift) : 0;
+    uint32_t events = seg_mask | (1u << 6) | (1u << 14); /* bit l: slot l sets lane state of the walk again (see there) */
+    if (clear_slot < NS) events |= 1u << clear_slot;
+    if (clear_slot + 14 < NS) events |= 1u << (clear_slot + 14);
     XS_PAR(sb, 0, 64) {
       /* -- the lane's chain, if it has one */
       const int qmf_chain = sb >= 3 && sb < 23, hyb_chain = sb >= 32 && sb < 42, chain = qmf_chain || hyb_chain;
@@ -432,17 +496,23 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
       /* -- the lane's band */
       const int g = T->band_to_group[sb];
       const int bin_sb = sb < 23 ? T->delay_to_bin[sb] : (sb < 35 ? 18 : 19); /* the band's transient-detector bin */
-      /* segment 0 continues the last frame's interpolation */
-      int16_t h11 = w->seg_h[0][0][g], h12 = w->seg_h[0][1][g], h21 = w->seg_h[0][2][g], h22 = w->seg_h[0][3][g];
-      int16_t d11 = w->seg_d[0][0][g], d12 = w->seg_d[0][1][g], d21 = w->seg_d[0][2][g], d22 = w->seg_d[0][3][g];
+      /* The interpolated coefficients of the band's group, as fx_mul32x16's multiplier words: the int16 in the high half, the
+         low half zero.  Adding the increment's word wraps exactly as the reference's int16 add does, and the rotation takes
+         the words as they are (as int16 values they cost an add and a shift each in every slot). */
+      uint32_t h11, h12, h21, h22, d11, d12, d21, d22;
+      const auto seg_load = [&](int s) {
+        const uint32_t a = w->seg_hd[s][0][g], b = w->seg_hd[s][1][g], c = w->seg_hd[s][2][g], d = w->seg_hd[s][3][g];
+        h11 = a & 0xffff0000u, h12 = b & 0xffff0000u, h21 = c & 0xffff0000u, h22 = d & 0xffff0000u;
+        d11 = a << 16, d12 = b << 16, d21 = c << 16, d22 = d << 16;
+      };
+      seg_load(0); /* segment 0 continues the last frame's interpolation */
       uint32_t prev = sb >= 35 ? xp_pack16(ps->sd[2 * (sb - 35)], ps->sd[2 * (sb - 35) + 1]) : 0u;
       /* The walk: four slots per pass of the loop (the delay lines of 2 and 4 slots are back in place after four
          steps, the 3- and 5-slot ones cost a few moves), the next pass's eight row words and the next slot's LDS
          operands in flight meanwhile.  The body has no lane-dependent branches: every lane runs the chain arithmetic
          (on don't-care values where it has no chain), band classes are selects, only the stores are predicated. */
       const int is_ap = sb < 23, is_d14 = sb >= 23 && sb < 35;
-      /* the band's scale shift as the two counts of xp_adj_word, for the overlap slots (l < 6) and for the others: lane
-         constants, chosen per slot by a uniform condition (worked out per word they were a dozen instructions of every slot) */
+      /* the band's scale shift as the two counts of xp_adj_word, for the overlap slots (l < 6) and for the others */
       int shl_ov, shr_ov, shl_lb, shr_lb;
       {
         const int s_ov = sb < lsb ? ov_lb_shift : (sb < usb ? hb_shift : 0), s_lb = sb < lsb ? lb_shift : (sb < usb ? hb_shift : 0);
@@ -450,121 +520,140 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         shl_ov = c_ov > 0 ? c_ov : 0, shr_ov = c_ov < 0 ? -c_ov : 0;
         shl_lb = c_lb > 0 ? c_lb : 0, shr_lb = c_lb < 0 ? -c_lb : 0;
       }
+      /* What depends on the slot but changes a few times per frame at most is lane state, set again at the slots named by
+         `events` (one uniform bit test per slot; worked out in every slot these were three dozen instructions of it):
+           shl / shr     the shift counts in force                           (slot 6)
+           active        the band lies below the slot's band limit           (clear_slot)
+           fed14         the slot 14 back put the band's sample into the 14-slot line  (slots 14 and clear_slot + 14)
+           h.. / d..     the coefficient words                               (the borders)
+         and the three links' lines of newly active bands are cleared at clear_slot. */
+      int shl = shl_ov, shr = shr_ov;
+      bool active = sb < usb_prev, fed14 = false;
       const int ldj = is_d14 ? 2 * (sb - 23) : 0, dlj = is_d14 ? sb - 23 : 12, apj = hyb_chain ? csb : 10;
+      int ld_at = 24 * p14_0; /* the slot's row of the 14-slot ring (as an offset into ps->ld): a counter that wraps */
+      const int16_t *const ld_lane = &ps->ld[0][ldj];
+      static_assert(sizeof(ps->ld[0]) == 24 * sizeof(int16_t), "rows of the 14-slot ring: 24 int16, whole words");
+      static_assert(offsetof(PS, ld) % 4 == 0 && alignof(PS) % 4 == 0, "the 14-slot ring starts on a word of a word-aligned state");
       int16_t tr_nx = w->ratio[0][bin_sb];
       int32_t hre_nx = w->hyb_l[0][csb], him_nx = w->hyb_l[0][10 + csb];
-      uint32_t ld_nx = xp_pack16(ps->ld[idx_long0 % 14][ldj], ps->ld[idx_long0 % 14][ldj + 1]);
+      uint32_t ld_nx = xp_load_pair(ld_lane + ld_at); /* (ldj is even and the rows are whole words) */
       int32_t nre[4], nim[4];
       XP_UNROLL
       for (int j = 0; j < 4; j++) {
         nre[j] = xl[j * 128 + sb];
         nim[j] = xl[j * 128 + 64 + sb];
       }
-      XP_NOUNROLL
-      for (int l0 = 0; l0 < NS; l0 += 4) {
-        int32_t cre[4], cim[4];
-        XP_UNROLL
-        for (int j = 0; j < 4; j++) {
-          cre[j] = nre[j];
-          cim[j] = nim[j];
-        }
-        if (l0 + 4 < NS) {
+      /* common_shift is the frame's: its sign is decided once, in front of the walk, and the walk exists twice -- with the
+         plain arithmetic shift of every chain met so far (common_shift <= 0) and with the saturating left shift */
+      const auto walk = [&](auto cs_positive) XP_LAMBDA_INLINE {
+        XP_NOUNROLL
+        for (int l0 = 0; l0 < NS; l0 += 4) {
+          int32_t cre[4], cim[4];
           XP_UNROLL
           for (int j = 0; j < 4; j++) {
-            nre[j] = xl[(l0 + 4 + j) * 128 + sb];
-            nim[j] = xl[(l0 + 4 + j) * 128 + 64 + sb];
+            cre[j] = nre[j];
+            cim[j] = nim[j];
           }
-        }
-        XP_UNROLL
-        for (int j = 0; j < 4; j++) {
-          const int l = l0 + j;
-          if (NS % 4 != 0 && l >= NS) break; /* (30 slots: the last pass has two) */
-          const int usb_l = l >= clear_slot ? usb : usb_prev;
-          const int16_t tr = tr_nx;
-          const int32_t hre = hre_nx, him = him_nx;
-          const uint32_t ld_cur = ld_nx;
-          {
-            const int ln = l + 1 < NS ? l + 1 : NS - 1, pn = (idx_long0 + ln) % 14;
-            tr_nx = w->ratio[ln][bin_sb];
-            hre_nx = w->hyb_l[ln][csb];
-            him_nx = w->hyb_l[ln][10 + csb];
-            ld_nx = xp_pack16(ps->ld[pn][ldj], ps->ld[pn][ldj + 1]);
+          if (l0 + 4 < NS) {
+            XP_UNROLL
+            for (int j = 0; j < 4; j++) {
+              nre[j] = xl[(l0 + 4 + j) * 128 + sb];
+              nim[j] = xl[(l0 + 4 + j) * 128 + 64 + sb];
+            }
           }
-          const int shl = l < 6 ? shl_ov : shl_lb, shr = l < 6 ? shr_ov : shr_lb;
-          const int32_t re0 = (int32_t)((uint32_t)cre[j] << shl) >> shr, im0 = (int32_t)((uint32_t)cim[j] << shl) >> shr;
-          const int16_t q_re = fx_round16(re0), q_im = fx_round16(im0);
-          const uint32_t q = xp_pack16(q_re, q_im);
-          /* the chain */
-          if (l == clear_slot) { /* (uniform) the three links' lines of the bands that just became active */
+          const uint32_t events4 = events >> l0;
+          XP_UNROLL
+          for (int j = 0; j < 4; j++) {
+            const int l = l0 + j;
+            if (NS % 4 != 0 && l >= NS) break; /* (30 slots: the last pass has two) */
+            const int16_t tr = tr_nx;
+            const int32_t hre = hre_nx, him = him_nx;
+            const uint32_t ld_cur = ld_nx; /* what the state held at the slot's ring position */
+            {
+              const int ln = l + 1 < NS ? l + 1 : NS - 1;
+              ld_at = ld_at + 24 == 14 * 24 ? 0 : ld_at + 24;
+              tr_nx = w->ratio[ln][bin_sb];
+              hre_nx = w->hyb_l[ln][csb];
+              him_nx = w->hyb_l[ln][10 + csb];
+              ld_nx = xp_load_pair(ld_lane + ld_at); /* (after the last slot: a row of the ring, not used) */
+            }
+            if ((events4 >> j) & 1u) { /* (uniform) */
 #if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile(""); /* keeps this a scalar branch taken once per frame: as twelve selects it ran in every slot */
+              asm volatile(""); /* keeps this a scalar branch taken a few times per frame: as selects it ran in every slot */
 #endif
-            const int c = qmf_chain && sb >= clear_lo && sb < clear_hi;
-            XP_UNROLL
-            for (int m = 0; m < 3; m++) r0[m] = c ? 0u : r0[m];
-            XP_UNROLL
-            for (int m = 0; m < 4; m++) r1[m] = c ? 0u : r1[m];
-            XP_UNROLL
-            for (int m = 0; m < 5; m++) r2[m] = c ? 0u : r2[m];
-          }
-          const uint32_t in_pair = hyb_chain ? xp_pack16(fx_round16(hre), fx_round16(him)) : q;
-          uint32_t dv = d0[0], e0 = r0[0], e1 = r1[0], e2 = r2[0];
-          const uint32_t o_chain = xp_allpass_packed(dv, in_pair, phase, e0, e1, e2, ps0, ps1, ps2, dec0, dec1, dec2);
-          d0[0] = d0[1];
-          d0[1] = dv;
-          r0[0] = r0[1]; r0[1] = r0[2];
-          r0[2] = e0;
-          r1[0] = r1[1]; r1[1] = r1[2]; r1[2] = r1[3];
-          r1[3] = e1;
-          r2[0] = r2[1]; r2[1] = r2[2]; r2[2] = r2[3]; r2[3] = r2[4];
-          r2[4] = e2;
-          w->ap_h[l][apj] = o_chain; /* lanes without a hybrid chain write the spare column */
-          /* the interpolated coefficients of the band's group */
-          if ((seg_mask >> l) & 1u) { /* (uniform) a border: they restart from the old targets */
-            const int s = xp_popc(seg_mask & (0xffffffffu >> (31 - l)));
-            h11 = w->seg_h[s][0][g]; h12 = w->seg_h[s][1][g]; h21 = w->seg_h[s][2][g]; h22 = w->seg_h[s][3][g];
-            d11 = w->seg_d[s][0][g]; d12 = w->seg_d[s][1][g]; d21 = w->seg_d[s][2][g]; d22 = w->seg_d[s][3][g];
-          }
-          h11 = (int16_t)(h11 + d11); /* the interpolation advances whether or not the band is rotated */
-          h12 = (int16_t)(h12 + d12);
-          h21 = (int16_t)(h21 + d21);
-          h22 = (int16_t)(h22 + d22);
-          /* the decorrelated sample of the band: all-pass output, or the input of 14 slots / 1 slot ago.  The 14-slot
-             line holds what slot l - 14 put in if that slot ran with the band active, else what the state held. */
-          const int active = sb < usb_l;
-          const int fed14 = l >= 14 && sb < (l - 14 >= clear_slot ? usb : usb_prev);
-          /* (both candidates are read by every lane -- a lane without a delay line reads entries it does not use -- and
-             the value is a select: no predicated region inside the walk) */
-          const uint32_t o14_new = w->dl[l >= 14 ? l - 14 : 0][dlj];
-          const uint32_t o14_old = l < 14 ? ld_cur : xp_pack16(ps->ld[(idx_long0 + l) % 14][ldj], ps->ld[(idx_long0 + l) % 14][ldj + 1]);
-          const uint32_t o14 = fed14 ? o14_new : o14_old;
-          const uint32_t o = is_ap ? o_chain : (is_d14 ? o14 : prev);
-          w->dl[l][dlj] = q; /* lanes without a 14-slot line write the spare column */
-          prev = active ? q : prev;
-          int32_t re = re0, im = im0;
-          int32_t r_re = xp_m16x16_shl(xp_lo16(o), tr), r_im = xp_m16x16_shl(xp_hi16(o), tr);
-          xp_rotate(&re, &r_re, h11, h12, h21, h22);
-          xp_rotate(&im, &r_im, h11, h12, h21, h22);
-          re = active ? re : re0; /* above usb: the left sample passes, the right one is zero */
-          im = active ? im : im0;
-          r_re = active ? r_re : 0;
-          r_im = active ? r_im : 0;
-          if (common_shift < 0) {
-            const int cs = -common_shift > 31 ? 31 : -common_shift;
-            re = fx_shr(re, cs);
-            im = fx_shr(im, cs);
-          } else if (common_shift > 0) {
-            re = fx_shl_sat(re, common_shift);
-            im = fx_shl_sat(im, common_shift);
-          }
-          if (sb >= 3) {
-            xl[l * 128 + sb] = re;
-            xl[l * 128 + 64 + sb] = im;
-            xr[l * 128 + sb] = r_re;
-            xr[l * 128 + 64 + sb] = r_im;
+              shl = l < 6 ? shl_ov : shl_lb;
+              shr = l < 6 ? shr_ov : shr_lb;
+              active = sb < (l >= clear_slot ? usb : usb_prev);
+              fed14 = l >= 14 && sb < (l - 14 >= clear_slot ? usb : usb_prev);
+              if (l == clear_slot) { /* the three links' lines of the bands that just became active */
+                const int c = qmf_chain && sb >= clear_lo && sb < clear_hi;
+                XP_UNROLL
+                for (int m = 0; m < 3; m++) r0[m] = c ? 0u : r0[m];
+                XP_UNROLL
+                for (int m = 0; m < 4; m++) r1[m] = c ? 0u : r1[m];
+                XP_UNROLL
+                for (int m = 0; m < 5; m++) r2[m] = c ? 0u : r2[m];
+              }
+              if ((seg_mask >> l) & 1u) /* a border: the coefficients restart from the old targets */
+                seg_load(xp_popc(seg_mask & (0xffffffffu >> (31 - l))));
+            }
+            const int32_t re0 = (int32_t)((uint32_t)cre[j] << shl) >> shr, im0 = (int32_t)((uint32_t)cim[j] << shl) >> shr;
+            const int16_t q_re = fx_round16(re0), q_im = fx_round16(im0);
+            const uint32_t q = xp_pack16(q_re, q_im);
+            /* the chain */
+            const uint32_t in_pair = hyb_chain ? xp_pack16(fx_round16(hre), fx_round16(him)) : q;
+            uint32_t dv = d0[0], e0 = r0[0], e1 = r1[0], e2 = r2[0];
+            const uint32_t o_chain = xp_allpass_packed(dv, in_pair, phase, e0, e1, e2, ps0, ps1, ps2, dec0, dec1, dec2);
+            d0[0] = d0[1];
+            d0[1] = dv;
+            r0[0] = r0[1]; r0[1] = r0[2];
+            r0[2] = e0;
+            r1[0] = r1[1]; r1[1] = r1[2]; r1[2] = r1[3];
+            r1[3] = e1;
+            r2[0] = r2[1]; r2[1] = r2[2]; r2[2] = r2[3]; r2[3] = r2[4];
+            r2[4] = e2;
+            w->ap_h[l][apj] = o_chain; /* lanes without a hybrid chain write the spare column */
+            h11 += d11; /* the interpolation advances whether or not the band is rotated */
+            h12 += d12;
+            h21 += d21;
+            h22 += d22;
+            /* the decorrelated sample of the band: all-pass output, or the input of 14 slots / 1 slot ago.  The 14-slot
+               line holds what slot l - 14 put in if that slot ran with the band active, else what the state held.
+               (Both candidates are read by every lane -- a lane without a delay line reads entries it does not use -- and
+               the value is a select: no predicated region inside the walk.) */
+            const uint32_t o14_new = w->dl[l >= 14 ? l - 14 : 0][dlj];
+            const uint32_t o14 = fed14 ? o14_new : ld_cur;
+            const uint32_t o = is_ap ? o_chain : (is_d14 ? o14 : prev);
+            w->dl[l][dlj] = q; /* lanes without a 14-slot line write the spare column */
+            prev = active ? q : prev;
+            int32_t re = re0, im = im0;
+            int32_t r_re = xp_m16x16_shl_pre(xp_lo16(o), 2 * tr), r_im = xp_m16x16_shl_pre(xp_hi16(o), 2 * tr);
+            xp_rotate_w(&re, &r_re, h11, h12, h21, h22);
+            xp_rotate_w(&im, &r_im, h11, h12, h21, h22);
+            re = active ? re : re0; /* above usb: the left sample passes, the right one is zero */
+            im = active ? im : im0;
+            r_re = active ? r_re : 0;
+            r_im = active ? r_im : 0;
+            if (decltype(cs_positive)::value) {
+              re = fx_shl_sat(re, common_shift);
+              im = fx_shl_sat(im, common_shift);
+            } else {
+              re = re >> cs_right;
+              im = im >> cs_right;
+            }
+            if (sb >= 3) {
+              xl[l * 128 + sb] = re;
+              xl[l * 128 + 64 + sb] = im;
+              xr[l * 128 + sb] = r_re;
+              xr[l * 128 + 64 + sb] = r_im;
+            }
           }
         }
-      }
+      };
+      if (common_shift > 0)
+        walk(XpBool<true>());
+      else
+        walk(XpBool<false>());
       /* -- the delay lines as the slot loop leaves them */
       if (chain) {
         XP_UNROLL
@@ -629,10 +718,8 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     int32_t acc_l = 0, acc_r = 0;
     for (int k = 0; k < n; k++) {
       const int sb = p + k;
-      const int16_t h11 = (int16_t)(w->seg_h[s][0][sb] + nn * w->seg_d[s][0][sb]);
-      const int16_t h12 = (int16_t)(w->seg_h[s][1][sb] + nn * w->seg_d[s][1][sb]);
-      const int16_t h21 = (int16_t)(w->seg_h[s][2][sb] + nn * w->seg_d[s][2][sb]);
-      const int16_t h22 = (int16_t)(w->seg_h[s][3][sb] + nn * w->seg_d[s][3][sb]);
+      const int16_t h11 = xp_seg_coeff(w->seg_hd[s][0][sb], nn), h12 = xp_seg_coeff(w->seg_hd[s][1][sb], nn);
+      const int16_t h21 = xp_seg_coeff(w->seg_hd[s][2][sb], nn), h22 = xp_seg_coeff(w->seg_hd[s][3][sb], nn);
       const int16_t tr = w->ratio[l][T->hybrid_to_bin[sb]];
       const uint32_t o = w->ap_h[l][sb];
       int32_t lv = w->hyb_l[l][10 * c + sb];
@@ -651,10 +738,10 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   {
     const int s = xp_popc(seg_mask), n = NS - (seg_mask ? 31 - xp_clz(seg_mask) : 0);
     XS_PAR(g, 0, XAAC_PS_GROUPS) {
-      ps->H11_H12[2 * g] = (int16_t)(w->seg_h[s][0][g] + n * w->seg_d[s][0][g]);
-      ps->H11_H12[2 * g + 1] = (int16_t)(w->seg_h[s][1][g] + n * w->seg_d[s][1][g]);
-      ps->H21_H22[2 * g] = (int16_t)(w->seg_h[s][2][g] + n * w->seg_d[s][2][g]);
-      ps->H21_H22[2 * g + 1] = (int16_t)(w->seg_h[s][3][g] + n * w->seg_d[s][3][g]);
+      ps->H11_H12[2 * g] = xp_seg_coeff(w->seg_hd[s][0][g], n);
+      ps->H11_H12[2 * g + 1] = xp_seg_coeff(w->seg_hd[s][1][g], n);
+      ps->H21_H22[2 * g] = xp_seg_coeff(w->seg_hd[s][2][g], n);
+      ps->H21_H22[2 * g + 1] = xp_seg_coeff(w->seg_hd[s][3][g], n);
     }
   }
   cx.sync();

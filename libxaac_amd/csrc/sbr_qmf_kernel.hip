@@ -782,7 +782,7 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
     const int ch = lane >> 5, slot = lane & 31;
     const int shift = -((ch ? st_syn1 : st_syn0) - 3) + 1;
     const int32_t hi = FX_MAX32 >> shift, lo = FX_MIN32 >> shift;
-    /* round16(shl_sat(a, b)) == round16(clamp(a, MIN >> b, MAX >> b) << b): the clamped value's top 17 bits decide */
+    /* round16(shl_sat(a, b)) == round16(clamp(a, MIN >> b, MAX >> b) << b) for 0 <= b <= 16: the clamped value's top 17 bits decide */
     int16_t *row = reinterpret_cast<int16_t *>(E + (ch * EROWS + 9 + slot) * RS);
     if (w == 0) { /* x = real half, o = imaginary half: b[c] -> low half of E[slot][c] */
 #pragma unroll
@@ -797,6 +797,20 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
         int32_t a = fx_add_sat(x[63 - c], o[63 - c]);
         a = clamp_med3(a, lo, hi);
         row[2 * RS + 2 * c + 1] = fx_round16(fx_shlw(a, shift));
+      }
+    }
+    /* Every real chain has b = 4 - st_syn_scale inside 0..16.  A carried synthesis scale above 4 makes the count negative, which
+       the reference's shl32_sat -- and the oracle's -- takes modulo 32 as the shifter does (17 .. 31); from 17 on the clamped
+       maximum has lost bits that round16 sees.  Those workgroups (a uniform test, never true in real use) write the samples
+       again in the exact form. */
+    if ((unsigned)(-(st_syn0 - 3) + 1) > 16u || (unsigned)(-(st_syn1 - 3) + 1) > 16u) {
+      const int bx = shift & 31;
+      if (w == 0) {
+#pragma unroll
+        for (int c = 0; c < 64; c++) row[2 * c] = fx_round16(fx_shl_sat(fx_sub_sat(o[c], x[c]), bx));
+      } else {
+#pragma unroll
+        for (int c = 0; c < 64; c++) row[2 * RS + 2 * c + 1] = fx_round16(fx_shl_sat(fx_add_sat(x[63 - c], o[63 - c]), bx));
       }
     }
     int16_t *hrow = reinterpret_cast<int16_t *>(E + (w * EROWS) * RS);

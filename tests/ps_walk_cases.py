@@ -1,0 +1,116 @@
+"""Chains for the slot walk of the parametric-stereo tool (libxaac_amd/csrc/sbr_ps_frame.h, P5 + P7), shared by
+tests/test_ps_walk_cpu.py and tests/test_ps_walk_gpu.py: the first 24 golden HE-AACv2 records, five frames each, fuzzed
+PS side info, +-3000 core PCM, and the carried synthesis scale raised in front of the frames so that the shift in front
+of the left synthesis bank (common_shift = st_syn_scale - ps_scale - 8, generic:1610) comes out negative, zero and
+positive -- real chains only ever make it negative, and the walk has one arrangement for <= 0 and one for > 0.
+
+  plain   borders as a parser makes them (0 = b0 < b1 < ... <= 32)
+  moving  first border not at slot 0, a band limit that moves between frames (so that the slot at which the new limit
+          takes over, and the delay lines of newly active bands are cleared, lies inside a frame) and one frame with the
+          synthesis bank's upper limit below the all-pass bands (23), back at its old value in the next
+
+The oracle's slot loop (xo_sbr_dec_hq) is run once per variant and kept."""
+import ctypes
+import functools
+import os
+
+import numpy as np
+
+import sbr_capture as cap
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P16 = ctypes.POINTER(ctypes.c_int16)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "sbr_hq_ps_records.bin.gz")
+STREAMS, FRAMES = 24, 5
+RAISE = [0, 9, 8, 12, 5]      # added to the carried State.st_syn_scale in front of frame 0, 1, ...
+SEED, AMP = 5, 3000
+
+
+def _fuzz_ps(rng, pf):
+    """parser-like PS side info: tests/test_ps_frame_cpu.py's generator at wild = 0 (the same draws in the same order)"""
+    pf.iid_quant = int(rng.integers(0, 2))
+    nenv = int(rng.integers(1, 6))
+    borders = [0] + sorted(rng.choice(np.arange(1, 32), nenv - 1, replace=False).tolist()) + [32]
+    for e in range(7):
+        pf.border_position[e] = int(borders[e]) if e < len(borders) else int(rng.integers(0, 33))
+    lim = 15 if pf.iid_quant else 7
+    for e in range(7):
+        for b in range(34):
+            pf.iid_par_table[e][b] = int(rng.integers(-lim, lim + 1))
+            pf.icc_par_table[e][b] = int(rng.integers(0, 8))
+
+
+def _borders_off_zero(rng, pf):
+    nenv = int(rng.integers(1, 5))
+    borders = sorted(rng.choice(np.arange(1, 32), nenv, replace=False).tolist()) + [32]
+    for e in range(7):
+        pf.border_position[e] = int(borders[e]) if e < len(borders) else 0
+
+
+@functools.lru_cache(maxsize=None)
+def records():
+    return cap.read_records(GOLDEN, limit=STREAMS)
+
+
+def run(lib_fn, h, f, st, pf, ps, pcm):
+    """one frame through an oracle entry point on copies of the states -> (rc, pcm, state, ps state)"""
+    s, p = cap.State.from_buffer_copy(bytes(st)), cap.PsState.from_buffer_copy(bytes(ps))
+    out = np.zeros(4096, np.int16)
+    rc = lib_fn(ctypes.byref(h), ctypes.byref(f), ctypes.byref(s), ctypes.byref(pf), ctypes.byref(p),
+                pcm.ctypes.data_as(P16), 1, out.ctypes.data_as(P16), 2)
+    return rc, out, s, p
+
+
+_chains = {}
+
+
+def chain(oracle, variant):
+    """-> list over frames of dict(frames, ps_frames, pcm, st_in, ps_in, want, common_shift): lists over the streams;
+    want[i] = (rc, pcm, state, ps state) of the slot loop; st_in already carries the raised synthesis scale"""
+    if variant in _chains:
+        return _chains[variant]
+    recs = records()
+    rng = np.random.default_rng(SEED)
+    states = [cap.State.from_buffer_copy(bytes(r["st0"])) for r in recs]
+    pstates = [cap.PsState.from_buffer_copy(bytes(r["ps0"])) for r in recs]
+    steps = []
+    for step in range(FRAMES):
+        d = dict(frames=[], ps_frames=[], pcm=[], st_in=[], ps_in=[], want=[], common_shift=[])
+        for i, r in enumerate(recs):
+            f = cap.Frame.from_buffer_copy(bytes(r["frame"]))
+            pf = cap.PsFrame.from_buffer_copy(bytes(r["ps_frame"]))
+            _fuzz_ps(rng, pf)
+            st = cap.State.from_buffer_copy(bytes(states[i]))
+            st.st_syn_scale += RAISE[step]
+            if variant == "moving":
+                _borders_off_zero(rng, pf)
+                if step in (1, 3, 4):
+                    f.max_qmf_subband_aac = int(np.clip(f.max_qmf_subband_aac + rng.integers(-6, 7), r["header"].sub_band_start, 32))
+                if step == 2:
+                    st.syn_usb = int(rng.integers(8, 23))
+                if step == 3:     # ... and back up: bands become active, inside the frame, whose delay lines are cleared
+                    st.syn_usb = r["st0"].syn_usb
+            pcm = rng.integers(-AMP, AMP + 1, 1024).astype(np.int16)
+            want = run(oracle.lib.xo_sbr_dec_hq, r["header"], f, st, pf, pstates[i], pcm)
+            d["frames"].append(f); d["ps_frames"].append(pf); d["pcm"].append(pcm)
+            d["st_in"].append(st); d["ps_in"].append(pstates[i]); d["want"].append(want)
+            d["common_shift"].append(int(st.st_syn_scale) - int(want[2].ps_scale) - 8)
+            states[i], pstates[i] = want[2], want[3]
+        steps.append(d)
+    _chains[variant] = steps
+    return steps
+
+
+def check_range(steps):
+    """every common_shift inside -31..31 (fx_shl_sat's range)"""
+    cs = np.array([c for d in steps for c in d["common_shift"]])
+    print("common_shift: %d negative, %d zero, %d positive, range %d..%d" % ((cs < 0).sum(), (cs == 0).sum(), (cs > 0).sum(),
+                                                                          cs.min(), cs.max()))
+    assert cs.min() >= -31 and cs.max() <= 31, (cs.min(), cs.max())
+    return cs
+
+
+def check_signs(steps):
+    """... and each sign in at least three stream-frames"""
+    cs = check_range(steps)
+    assert (cs < 0).sum() >= 3 and (cs == 0).sum() >= 3 and (cs > 0).sum() >= 3, ((cs < 0).sum(), (cs == 0).sum(), (cs > 0).sum())
