@@ -15,12 +15,13 @@
  *   P1 hybrid analysis of all NS slots            lane = slot / (band, slot)
  *   P2 envelope walk: segments of constant delta  scalar; coefficients of each border: lane = parameter group
  *   P3 band powers, all-pass / delay inputs       lane = QMF band, loop over slots (coalesced row reads)
- *      group sums of the upper bins               lane = (slot, group): the addends are >= 0, so the saturating
- *                                                 sum is min(MAX, exact sum) whatever the order
+ *      group sums of the upper bins               a running sum over the band lanes per slot, then lane = (slot, group):
+ *                                                 the addends are >= 0, so the saturating sum is min(MAX, exact sum)
+ *                                                 whatever the order (xp_gsum_*)
  *   P4 transient detector                         lane = bin, loop over slots (the recursion), then the 640 ratios
  *                                                 (one division each) lane-parallel
  *   P5 all-pass chains                            lane = chain (30), loop over slots (the recursion)
- *   P6 rotation in the hybrid domain + its sums   lane = (slot, sub-band)
+ *   P6 rotation in the hybrid domain + its sums   lane = (slot, re | im), loop over the ten sub-bands
  *   P7 delays, rotation, output scaling           lane = QMF band, loop over slots (coalesced row reads / writes)
  * Every value is computed by the same operations in the same order as in the slot loop (sbr_ps.h, which stays the
  * oracle's restatement of the reference); what changes is only when.  The same source compiled for the host with
@@ -62,7 +63,8 @@
 struct XpFrameWork {
   union {                    /* scratch areas that are never live together */
     int32_t hyb_u[3][2][44]; /* P1: hybrid filter input of QMF bands 0..2: 12 slots of history + this frame's NS */
-    int32_t gsum[8][56];     /* P3: addends of the group sums, bands 9..63 of eight slots */
+    uint32_t gscan[32][8];   /* P3: per slot the running sum of the group addends at the last band of groups 0..5; column 6:
+                                the other lanes' stores */
     int32_t peak[32][20];    /* P4: transient peak difference */
     uint32_t dl[32][13];     /* P5/P7: rounded samples of QMF bands 23..34 (the 14-slot delay looks 14 slots back); column
                                 12 takes the other lanes' stores, so that the store needs no predicate */
@@ -213,6 +215,57 @@ FX_HD int32_t xp_bin_power_hyb(const XpTables *T, int bin, const int32_t *re, co
   return xp_power(re[sb], im[sb]);
 }
 
+/* ---- the group sums of transient-detector bins 14..19 (ps_dec.c:520-545; sbr_ps.h: xp_bin_power, bin >= 14) as
+   differences of a running sum.  The reference adds a group's shifted band powers with saturating adds; the addends are
+   >= 0, so that is min(0x7fffffff, exact sum) whatever the order -- and with the table's shifts the exact sum of every
+   group fits an unsigned word (xp_gsum_fits: bands x (0x7fffffff >> shift) < 2^32).  So the sums may wrap: with
+   S[k] = addend[0] + .. + addend[k] modulo 2^32 over all 64 bands (bands below 9, bands at or above the slot's band limit
+   and whatever else a group does not read add zero or cancel), group [b0, b1) is
+       min(0x7fffffff, (S[b1 - 1] - S[b0 - 1]) mod 2^32),
+   bit for bit the reference's value.  On the GPU the lane is the band and S is six data-parallel-primitive adds (the scan of
+   sbr_core.h: xs_prefix_max with + for max); on the host it is the running sum of the band loop. */
+/* the band's addend: its power in its group's scale if a group reads it, else nothing */
+FX_HD uint32_t xp_gsum_addend(int32_t pw, int group_shift, bool counts) { return counts ? (uint32_t)(pw >> group_shift) : 0u; }
+/* S of this band: `run` carries the sum over the bands before it where bands are walked one after the other (the host) */
+FX_HD uint32_t xp_gsum_scan(const XsCx &cx, uint32_t a, uint32_t &run) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int32_t r = (int32_t)a;
+#define XP_DPP_ADD(ctrl, rows) r += __builtin_amdgcn_update_dpp(0, r, ctrl, rows, 0xf, false); /* no source lane: adds 0 */
+  XP_DPP_ADD(0x111, 0xf) /* row_shr:1 */
+  XP_DPP_ADD(0x112, 0xf) /* row_shr:2 */
+  XP_DPP_ADD(0x114, 0xf) /* row_shr:4 */
+  XP_DPP_ADD(0x118, 0xf) /* row_shr:8 */
+  XP_DPP_ADD(0x142, 0xa) /* row_bcast:15 into rows 1 and 3 */
+  XP_DPP_ADD(0x143, 0xc) /* row_bcast:31 into rows 2 and 3 */
+#undef XP_DPP_ADD
+  (void)cx;
+  (void)run;
+  return (uint32_t)r;
+#else
+  (void)cx;
+  run += a;
+  return run;
+#endif
+}
+/* the group's sum from S at its last band and S at the band in front of its first */
+FX_HD int32_t xp_gsum_sum(uint32_t s_last, uint32_t s_before) {
+  const uint32_t d = s_last - s_before;
+  return (int32_t)(d < 0x7fffffffu ? d : 0x7fffffffu);
+}
+/* The bound the wrapping sums rest on, worked out from the tables themselves (borders_group[16..22] = 9 11 14 18 23 35 64,
+   group_shift = 0 1 1 2 3 4: 2, 3, 4, 5, 12, 29 bands of at most 0x7fffffff >> shift, the largest sum 29 * (2^27 - 1)).  The
+   tables are generated data and no constant expressions, so this is a function and not a static_assert:
+   tests/test_ps_phases_cpu.py calls it on the tables the library is built with, a changed table fails there. */
+FX_HD bool xp_gsum_fits(const XpTables *T) {
+  if (T->borders_group[16] != 9) return false; /* the first group starts where the addends start (xp_ps_frame, P3) */
+  for (int g = 0; g < 6; g++) {
+    const int b0 = T->borders_group[16 + g], b1 = T->borders_group[17 + g], shift = T->group_shift[g];
+    if (b1 <= b0 || b1 > 64 || shift < 0 || shift > 31) return false;
+    if ((uint64_t)(b1 - b0) * (uint64_t)(0x7fffffff >> shift) >= ((uint64_t)1 << 32)) return false;
+  }
+  return true;
+}
+
 /* One frame of NS slots (32, or 30).  xl: the stream's QMF matrix, slot 0 at xl (rows of 64 re | 64 im; rows 0..NS + 5
    are read, rows 0..NS - 1 are rewritten with the left channel in the scale the synthesis bank expects); xr: NS rows out,
    the right channel.  lb/ov_lb/hb_scale, st_syn, lsb, usb: what the SBR core left for the synthesis bank.  Returns
@@ -334,10 +387,12 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   XP_T(3);
 
   /* ---- P3: band powers (ps_dec.c:520-545).  A lane walks its band through eight slots at a time: the sixteen row
-     words of the next eight are in flight while these are worked on. */
+     words of the next eight are in flight while these are worked on.  Bands 9..63 feed the group sums of bins 14..19
+     (xp_gsum_*): per slot one running sum over the bands, of which the six lanes that end a group keep their value. */
   {
     XP_UNROLL
     for (int c = 0; c < 4; c++) {
+      uint32_t run[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* (host: the running sums of the eight slots over the band loop) */
       XS_PAR(sb, 0, 64) {
         int32_t rre[8], rim[8];
         XP_UNROLL
@@ -351,12 +406,15 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
 #endif
         }
         const int gsh = sb < 11 ? 0 : (sb < 18 ? 1 : (sb < 23 ? 2 : (sb < 35 ? 3 : 4))); /* group_shift of the band's group */
-        /* where the band's power goes: bands 3..8 are bins of their own, bands 9.. addends of the group sums, bands 0..2
-           (whose bins come from the hybrid sub-bands) write the spare column 55 of gsum -- one store per slot through a
-           lane pointer and a lane stride instead of a tree of predicated regions */
+        /* where the lane's word of a slot goes: bands 3..8 are bins of their own (their power), the last band of group g
+           keeps the running sum in column g of gscan, every other lane writes the spare column 6 -- one store per slot
+           through a lane pointer and a lane stride instead of a tree of predicated regions */
         const bool own_bin = sb >= 3 && sb < 9;
-        int32_t *dst = sb < 3 ? &w->gsum[0][55] : (own_bin ? &w->binpw[8 * c][sb + 5] : &w->gsum[0][sb - 9]);
-        const int dstride = own_bin ? 20 : 56;
+        int gcol = 6;
+        XP_UNROLL
+        for (int g = 0; g < 6; g++) gcol = sb == T->borders_group[17 + g] - 1 ? g : gcol;
+        int32_t *dst = own_bin ? &w->binpw[8 * c][sb + 5] : reinterpret_cast<int32_t *>(&w->gscan[8 * c][gcol]);
+        const int dstride = own_bin ? 20 : 8;
         XP_UNROLL
         for (int ls = 0; ls < 8; ls++) {
           const int l = 8 * c + ls;
@@ -364,31 +422,20 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
           const int sh = sb < lsb ? (l < 6 ? ov_lb_shift : lb_shift) : (sb < usb ? hb_shift : 0);
           const int32_t re = xp_adj_word(rre[ls], sh), im = xp_adj_word(rim[ls], sh);
           const int32_t pw = xp_power(re, im);
-          dst[ls * dstride] = own_bin ? pw : (sb < usb_l ? (pw >> gsh) : 0);
+          const uint32_t s = xp_gsum_scan(cx, xp_gsum_addend(pw, gsh, sb >= 9 && sb < usb_l), run[ls]);
+          dst[ls * dstride] = own_bin ? pw : (int32_t)s;
         }
       }
-      cx.sync();
-      XS_PAR(i, 0, 48) { /* bins 14..19 = sums over the groups [9,11) [11,14) [14,18) [18,23) [23,35) [35,64) */
-        const int ls = i / 6, g = i % 6;
-        const int b0 = T->borders_group[16 + g], b1 = T->borders_group[17 + g];
-        int32_t acc = 0;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(XP_OLD_GSUM)
-        /* the same saturating adds in the same order, eight addends fetched at a time (a group has up to 29: one LDS
-           latency per eight instead of one per addend; slots past the group's end re-read its last word and add zero) */
-        for (int sb = b0; sb < b1; sb += 8) {
-          int32_t t[8];
-          XP_UNROLL
-          for (int j = 0; j < 8; j++) t[j] = w->gsum[ls][(sb + j < b1 ? sb + j : b1 - 1) - 9];
-          XP_UNROLL
-          for (int j = 0; j < 8; j++) acc = fx_add_sat(acc, sb + j < b1 ? t[j] : 0);
-        }
-#else
-        for (int sb = b0; sb < b1; sb++) acc = fx_add_sat(acc, w->gsum[ls][sb - 9]);
-#endif
-        w->binpw[8 * c + ls][14 + g] = acc;
-      }
-      cx.sync();
     }
+  }
+  cx.sync();
+  XS_PAR(i, 0, 6 * NS) { /* bins 14..19 = sums over the groups [9,11) [11,14) [14,18) [18,23) [23,35) [35,64) */
+    const int l = i / 6, g = i % 6;
+    /* the running sum in front of the group: the group before ends there; in front of the first group (band 9) nothing
+       has been added.  (Read by every lane and selected: no predicated region.) */
+    const uint32_t prev = w->gscan[l][g > 0 ? g - 1 : 0];
+    const uint32_t before = g > 0 ? prev : 0u;
+    w->binpw[l][14 + g] = xp_gsum_sum(w->gscan[l][g], before);
   }
   XS_PAR(i, 0, 8 * NS) {
     const int l = i >> 3, bin = i & 7;
@@ -709,15 +756,18 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   XP_T(6);
 
   /* ---- P6: rotation of the hybrid sub-bands (ps_dec.c:856, groups 0..9) and hybrid synthesis of QMF bands 0..2
-     (the saturating sums of ps_dec.c:899-925, in sub-band order), one (slot, band, re | im) per lane */
-  XS_PAR(i, 0, 6 * NS) {
-    const int l = i / 6, b = (i % 6) >> 1, c = i & 1;
-    const int p = b == 0 ? 0 : 4 + 2 * b, n = b == 0 ? 6 : 2;
+     (the saturating sums of ps_dec.c:899-925, in sub-band order), one (slot, re | im) per lane: 2 * NS lanes, one trip.
+     The lane walks the ten sub-bands in order with one pair of sums per QMF band (sub-bands 0..5, 6..7, 8..9): the
+     sub-band is a constant of the unrolled body and no lane waits for a band with more sub-bands than its own. */
+  XS_PAR(i, 0, 2 * NS) {
+    const int l = i >> 1, c = i & 1;
     const uint32_t below = seg_mask & (0xffffffffu >> (31 - l));     /* borders at or before slot l */
     const int s = xp_popc(below), nn = l - (below ? 31 - xp_clz(below) : 0) + 1; /* slots since the segment began */
-    int32_t acc_l = 0, acc_r = 0;
-    for (int k = 0; k < n; k++) {
-      const int sb = p + k;
+    int32_t acc_l[3] = {0, 0, 0}, acc_r[3] = {0, 0, 0};
+    XP_UNROLL
+    for (int sb = 0; sb < 10; sb++) {
+      const int b = sb < 6 ? 0 : (sb < 8 ? 1 : 2);
+      const bool first = sb == 0 || sb == 6 || sb == 8;
       const int16_t h11 = xp_seg_coeff(w->seg_hd[s][0][sb], nn), h12 = xp_seg_coeff(w->seg_hd[s][1][sb], nn);
       const int16_t h21 = xp_seg_coeff(w->seg_hd[s][2][sb], nn), h22 = xp_seg_coeff(w->seg_hd[s][3][sb], nn);
       const int16_t tr = w->ratio[l][T->hybrid_to_bin[sb]];
@@ -725,15 +775,19 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
       int32_t lv = w->hyb_l[l][10 * c + sb];
       int32_t rv = xp_m16x16_shl(c ? xp_hi16(o) : xp_lo16(o), tr);
       xp_rotate(&lv, &rv, h11, h12, h21, h22);
-      acc_l = k == 0 ? lv : fx_add_sat(acc_l, lv);
-      acc_r = k == 0 ? rv : fx_add_sat(acc_r, rv);
+      acc_l[b] = first ? lv : fx_add_sat(acc_l[b], lv);
+      acc_r[b] = first ? rv : fx_add_sat(acc_r[b], rv);
     }
-    if (common_shift < 0)
-      acc_l = fx_shr(acc_l, -common_shift > 31 ? 31 : -common_shift);
-    else if (common_shift > 0)
-      acc_l = fx_shl_sat(acc_l, common_shift);
-    xl[l * 128 + 64 * c + b] = acc_l;
-    xr[l * 128 + 64 * c + b] = acc_r;
+    XP_UNROLL
+    for (int b = 0; b < 3; b++) {
+      int32_t v = acc_l[b];
+      if (common_shift < 0)
+        v = fx_shr(v, -common_shift > 31 ? 31 : -common_shift);
+      else if (common_shift > 0)
+        v = fx_shl_sat(v, common_shift);
+      xl[l * 128 + 64 * c + b] = v;
+      xr[l * 128 + 64 * c + b] = acc_r[b];
+    }
   }
   {
     const int s = xp_popc(seg_mask), n = NS - (seg_mask ? 31 - xp_clz(seg_mask) : 0);
