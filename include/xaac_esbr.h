@@ -183,11 +183,49 @@ typedef struct xaac_esbr_pcm_out_batch {
   int16_t *pcm;                    /* [n][2048][2] */
 } xaac_esbr_pcm_out_batch;
 
+/* ---- streams of more than two channels (ADTS channel_config 3 .. 6) -----------------------------------------------------
+ * The reference keeps one SBR decoder per channel element and runs it on the element's channels of the frame's interleaved
+ * block: stride total_channels, from the element's slot (decoder/ixheaacd_api.c:3176-3178, :3373-3500).  Here every channel is
+ * a row of its own, in BITSTREAM order (SCE CPE | SCE CPE SCE | SCE CPE CPE | SCE CPE CPE LFE), through the per-channel batch
+ * entry points above; the three hand-offs below are what the element-strided block asks for on either side.
+ * The core's samples: xaac_imdct_process_batch with ch_fac 1, out32 and qshift_adj (no pcm16) -> xaac_mc_core_from_out32_batch,
+ * which makes the 16-bit conversion of ixheaacd_allocate_sbr_scr (api.c:351-359) as the reference makes it in that block:
+ *  - channel j of an ELEMENT is shifted by qshift_adj[j] of the FRAME -- the j-th channel the frame decoded: the first SCE's for an
+ *    element's first channel, the first pair's left channel's for a pair's second;
+ *  - the conversion runs in place, channel after channel, so the WORD16 results of a pair's first channel overwrite halves of
+ *    WORD32 words that are still to be converted where slot and channel count put them on the pair's second channel: its samples
+ *    n = 0 .. 511 take the first channel's PCM sample 2 n + 1 as their LOW half when total_channels = slot + 2 (the second pair of
+ *    channel_config 5 and 6; the stereo quirk of XAAC_PCM_SBR), as their HIGH half when total_channels = slot + 3 (the pair of
+ *    channel_config 3, whose right channel the reference therefore decodes to noise in the first half of every frame). */
+typedef struct xaac_mc_core_in_batch {
+  int32_t n_streams;
+  int32_t channel_config;          /* 3 .. 6 */
+  const int32_t *out32;            /* [n_streams][n_ch][1024] WORD32 time samples, channels in bitstream order */
+  const int8_t *qshift_adj;        /* [n_streams][n_ch] */
+  float *core;                     /* [n_streams][n_ch][1024] */
+} xaac_mc_core_in_batch;
+
+/* The planes the SBR calls leave -> the frame's block in the reference's output channel order.  float planes: the Path A branch's
+ * output through ixheaacd_samples_sat_mc (decoder/ixheaacd_decode_main.c:130-175: clamped to [-32768, 32767], truncated towards
+ * zero); int16 planes: the low-power synthesis bank's PCM as it is. */
+typedef struct xaac_mc_pcm_out_batch {
+  int32_t n_streams;
+  int32_t n_ch;                    /* 3 .. 6 */
+  int32_t stride;                  /* floats / int16 words between consecutive planes: even, >= 2048 */
+  int32_t slot[6];                 /* output channel of plane c: a permutation of 0 .. n_ch - 1 */
+  const void *planes;              /* stream i's plane c at element (i * n_ch + c) * stride, 2048 samples; 8-byte aligned (float) /
+                                      4-byte aligned (int16) */
+  int16_t *pcm;                    /* [n_streams][2048][n_ch] */
+} xaac_mc_pcm_out_batch;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 XAAC_API int32_t xaac_esbr_core_from_pcm16_batch(xaac_ctx *ctx, const xaac_esbr_core_in_batch *batch);
 XAAC_API int32_t xaac_esbr_pcm16_from_float_batch(xaac_ctx *ctx, const xaac_esbr_pcm_out_batch *batch);
+XAAC_API int32_t xaac_mc_core_from_out32_batch(xaac_ctx *ctx, const xaac_mc_core_in_batch *batch);
+XAAC_API int32_t xaac_mc_pcm16_from_float_batch(xaac_ctx *ctx, const xaac_mc_pcm_out_batch *batch);
+XAAC_API int32_t xaac_mc_pcm16_from_planes_batch(xaac_ctx *ctx, const xaac_mc_pcm_out_batch *batch); /* int16 planes */
 /* One frame of every channel through the Path A branch of ixheaacd_sbr_dec (mono / stereo channels; with ps_* set:
  * HE-AACv2 streams, ixheaacd_esbr_apply_ps ps_dec_flt.c:389 between regrouping and the two synthesis banks):
  * history shift (sbr_dec.c:835-857), ixheaacd_esbr_analysis_filt_block, ixheaacd_generate_hf (sbrdec_lpfuncs.c:981),

@@ -113,6 +113,8 @@ XAAC_API int32_t xaac_parse_adts_frame(xaac_parser *p, const uint8_t *data, size
    bands (xaac_core_tools_state::pns_corr_seed: scratch memory there), is per element here; it shows only in a right channel
    that substitutes noise in a correlated band whose left channel does not, and a frame with such a band is
    XAAC_PARSE_ERR_UNSUPPORTED rather than decoded differently.
+   Every element keeps the SBR extension payload of the FIL element behind it (xaac_core_frame::sbr; the LFE never has one): see
+   xaac_parse_sbr_side_mc below.
    A stream of any other channel_config is taken with one channel element per frame, as xaac_parse_adts_frame takes it.
    THIS FRONT END'S RULE, not the reference's: the first frame fixes the stream's element sequence; a later frame with another
    sequence, or a frame whose sequence is not the one of its channel_config, is XAAC_PARSE_ERR_UNSUPPORTED (the reference
@@ -124,6 +126,16 @@ XAAC_API int32_t xaac_parse_adts_frame_mc(xaac_parser *p, const uint8_t *data, s
 /* ... and xaac_parse_core_tools_side for channel element `element` of the frame xaac_parse_adts_frame_mc decoded last; the
    caller keeps an xaac_core_tools_state per element */
 XAAC_API int32_t xaac_parse_core_tools_side_mc(xaac_parser *p, int32_t element, xaac_core_tools_side *side);
+
+/* ... and the SBR side info of channel element `element` of that frame, from the element's own SBR front end: the reference keeps
+   one SBR decoder per channel element, the LFE included (api.c:2389-2517), and parametric stereo is off as soon as a frame has
+   more than one element (:2384-2387).  An element without payload is a frame whose SBR data is missing, as in the reference: the
+   LFE's normal case, whose decoder therefore stays in the up-sampling state (side->apply 0).  side->frame[1] is in use for a
+   pair.  xaac_parser_set_esbr applies to all elements (before the first of these calls); xaac_parse_esbr_side_mc /
+   xaac_parse_reset_pitch_mc are xaac_parse_esbr_side / xaac_parse_reset_pitch for one element. */
+XAAC_API int32_t xaac_parse_sbr_side_mc(xaac_parser *p, int32_t element, xaac_sbr_side *side);
+XAAC_API int32_t xaac_parse_esbr_side_mc(xaac_parser *p, int32_t element, int32_t channel, xaac_esbr_side *side);
+XAAC_API int32_t xaac_parse_reset_pitch_mc(xaac_parser *p, int32_t element, int32_t *pitch_in_bins);
 
 /* The SBR / PS side info of the frame xaac_parse_adts_frame decoded last (its payload is in the parser; a frame without
    one counts as a frame whose SBR data is missing, as in the reference).  ps_enable: parametric stereo allowed (mono
@@ -209,12 +221,19 @@ typedef struct xaac_parse_batch {
   int32_t channel_config;     /* 0: everything above as it stands (one channel element per frame).  3 .. 6 (appended with the
                                  multichannel entry points; anything else is a bad descriptor): streams of that ADTS channel_config,
                                  parsed as xaac_parse_adts_frame_mc parses them.  n_ch must be the configuration's channel count
-                                 (3, 4, 5, 6) and with_sbr 0, otherwise the call returns XAAC_PARSE_ERR_UNSUPPORTED.  spec is
+                                 (3, 4, 5, 6) and with_sbr 0 (or mc_sbr 1, below), otherwise the call returns XAAC_PARSE_ERR_UNSUPPORTED.  spec is
                                  [n_streams][n_ch][1024] and ics [n_streams][n_ch][2] with the channels in bitstream order; tools is
                                  the OR over the elements, lines the maximum over the channels; tools_side is ELEMENT-MAJOR,
                                  [frames][n_elems][n_streams] (n_elems = 2, 3, 3, 4): one element index's rows of all streams
                                  lie together, as one xaac_aac_tools_process_batch call per element index takes them.  A stream
                                  of another configuration gets the status XAAC_PARSE_ERR_UNSUPPORTED */
+  int32_t mc_sbr;             /* 0: as above.  1 (appended with per-element SBR; only looked at with channel_config 3 .. 6): with_sbr 1
+                                 is taken -- every channel element's SBR payload through the element's own front end
+                                 (xaac_parse_sbr_side_mc; ps_enable is not looked at: no parametric stereo in such a frame).
+                                 header / frame / esbr_side are [frames][n_streams][n_ch], one row per channel in bitstream order, the
+                                 channels of a pair with copies of the pair's header; flags is [frames][n_streams][n_elems][8] and
+                                 reset_pitch [frames][n_streams][n_elems], one row per channel ELEMENT (n_elems = 2, 3, 3, 4); ps_frame
+                                 is not written.  The LFE's rows say apply 0 (its SBR data is always missing) */
 } xaac_parse_batch;
 
 /* returns the number of streams whose status is XAAC_PARSE_OK, or a negative XAAC_PARSE_ERR_* for a bad descriptor */

@@ -85,6 +85,18 @@ class _EsbrCoreInBatch(ctypes.Structure):
     _fields_ = [("n_ch", ctypes.c_int32), ("ch_fac", ctypes.c_int32), ("pcm", ctypes.c_void_p), ("core", ctypes.c_void_p)]
 
 
+class _McCoreInBatch(ctypes.Structure):
+    # struct xaac_mc_core_in_batch
+    _fields_ = [("n_streams", ctypes.c_int32), ("channel_config", ctypes.c_int32), ("out32", ctypes.c_void_p),
+                ("qshift_adj", ctypes.c_void_p), ("core", ctypes.c_void_p)]
+
+
+class _McPcmOutBatch(ctypes.Structure):
+    # struct xaac_mc_pcm_out_batch
+    _fields_ = [("n_streams", ctypes.c_int32), ("n_ch", ctypes.c_int32), ("stride", ctypes.c_int32), ("slot", ctypes.c_int32 * 6),
+                ("planes", ctypes.c_void_p), ("pcm", ctypes.c_void_p)]
+
+
 class _EsbrPcmOutBatch(ctypes.Structure):
     # struct xaac_esbr_pcm_out_batch
     _fields_ = [("n", ctypes.c_int32), ("stride", ctypes.c_int32), ("left", ctypes.c_void_p), ("right", ctypes.c_void_p),
@@ -667,6 +679,40 @@ class XaacContext:
         rc = self._lib.xaac_esbr_pcm16_from_float_batch(self._h, ctypes.byref(b))
         if rc != 0:
             raise XaacError(rc, "xaac_esbr_pcm16_from_float_batch")
+
+    def mc_core_from_out32(self, out32, qshift_adj, core, channel_config):
+        """more than two channels: the IMDCT's WORD32 rows (int32[n * n_ch, 1024], ch_fac 1, channels in bitstream order) and
+        their qshift_adj (int8[n * n_ch]) -> the float planes core float32[n * n_ch, 1024] the Path A branch reads, through the
+        reference's in-place 16-bit conversion of every channel element in the frame's block (xaac_mc_core_in_batch)"""
+        b = _McCoreInBatch()
+        rows = int(core.shape[0])
+        b.n_streams, b.channel_config = rows // int(channel_config), int(channel_config)
+        if b.n_streams * b.channel_config != rows:
+            raise ValueError("rows are no multiple of the channel count")
+        b.out32 = _ptr(out32, "int32", rows * 1024, device_ok=True)
+        b.qshift_adj = _ptr(qshift_adj, "int8", rows, device_ok=True)
+        b.core = _ptr(core, "float32", rows * 1024, device_ok=True)
+        rc = self._lib.xaac_mc_core_from_out32_batch(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, "xaac_mc_core_from_out32_batch")
+
+    def mc_pcm16_from_planes(self, planes, pcm, slot, stride=2048):
+        """more than two channels: stream i's plane c (float32: clamped and truncated as ixheaacd_samples_sat_mc does; int16: as it
+        is) at element (i * n_ch + c) * stride of `planes` -> pcm int16[n * 2048 * n_ch], plane c as output channel slot[c]"""
+        n_ch = len(slot)
+        b = _McPcmOutBatch()
+        b.n_streams, b.n_ch, b.stride = pcm.numel() // (2048 * n_ch), n_ch, int(stride)
+        for c, to in enumerate(slot):
+            b.slot[c] = int(to)
+        flt = str(planes.dtype).endswith("float32")
+        b.planes = _ptr(planes, "float32" if flt else "int16", device_ok=True)
+        if planes.numel() < (b.n_streams * n_ch - 1) * b.stride + 2048:
+            raise ValueError("planes are shorter than the batch")
+        b.pcm = _ptr(pcm, "int16", b.n_streams * 2048 * n_ch, device_ok=True)
+        fn = "xaac_mc_pcm16_from_float_batch" if flt else "xaac_mc_pcm16_from_planes_batch"
+        rc = getattr(self._lib, fn)(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, fn)
 
     def sbr_state_handover(self, mode, src, dst, state, ps_state=None):
         """ixheaacd_sbrdecoder.c:762-806 for the listed streams: mode HANDOVER_PS_START (dst indexes ps_state) or

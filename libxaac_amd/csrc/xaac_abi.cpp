@@ -27,6 +27,7 @@
 #include "hbe_kernel.h"
 #include "pvc_kernel.h"
 #include "aac_tools_kernel.h"
+#include "mc_sbr_kernel.h"
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -131,7 +132,7 @@ int32_t xaac_set_stream(xaac_ctx *c, void *hip_stream) {
 extern "C" {
 hipError_t xaac_warm_imdct(void), xaac_warm_sbr_qmf(void), xaac_warm_sbr_core(void), xaac_warm_sbr_ps(void), xaac_warm_limiter(void),
     xaac_warm_esbr_qmf(void), xaac_warm_esbr_core(void), xaac_warm_esbr_ps(void), xaac_warm_hbe(void), xaac_warm_usac_imdct(void),
-    xaac_warm_imdct960(void), xaac_warm_imdct_ld(void), xaac_warm_pvc(void), xaac_warm_sbr_ld_core(void), xaac_warm_aac_tools(void);
+    xaac_warm_imdct960(void), xaac_warm_imdct_ld(void), xaac_warm_pvc(void), xaac_warm_sbr_ld_core(void), xaac_warm_aac_tools(void), xaac_warm_mc_sbr(void);
 }
 
 int32_t xaac_warm_up(xaac_ctx *c) {
@@ -140,7 +141,7 @@ int32_t xaac_warm_up(xaac_ctx *c) {
   hipError_t (*const hooks[])(void) = {xaac_warm_imdct,     xaac_warm_sbr_qmf,   xaac_warm_sbr_core, xaac_warm_sbr_ps,     xaac_warm_limiter,
                                        xaac_warm_esbr_qmf,  xaac_warm_esbr_core, xaac_warm_esbr_ps,  xaac_warm_hbe,        xaac_warm_usac_imdct,
                                        xaac_warm_imdct960,  xaac_warm_imdct_ld,  xaac_warm_pvc,      xaac_warm_sbr_ld_core,
-                                       xaac_warm_aac_tools};
+                                       xaac_warm_aac_tools, xaac_warm_mc_sbr};
   for (auto h : hooks)
     if (!hip_ok(h())) return XAAC_FATAL_HIP;
   return XAAC_OK;
@@ -479,6 +480,54 @@ int32_t xaac_esbr_pcm16_from_float_batch(xaac_ctx *c, const xaac_esbr_pcm_out_ba
   if (!hip_ok(xaac_launch_esbr_pcm16_from_float(&p, c->stream))) return XAAC_FATAL_HIP;
   return XAAC_OK;
 }
+
+/* channel_config 3 .. 6: the element of every bitstream channel (SCE CPE | SCE CPE SCE | SCE CPE CPE | SCE CPE CPE LFE) and the
+   slot the reference gives it in the frame's block (api.c:3176-3177: the first pair, the first SCE, the LFE, the second pair, the
+   second SCE) */
+int32_t xaac_mc_core_from_out32_batch(xaac_ctx *c, const xaac_mc_core_in_batch *b) {
+  if (!c || !b) return XAAC_FATAL_NULL_ARG;
+  if (b->n_streams < 0 || b->channel_config < 3 || b->channel_config > 6) return XAAC_FATAL_BAD_ARG;
+  if (b->n_streams == 0) return XAAC_OK;
+  if (!b->out32 || !b->qshift_adj || !b->core) return XAAC_FATAL_NULL_ARG;
+  static const int8_t k_pair_at[4][2] = {{1, -1}, {1, -1}, {1, 3}, {1, 3}};  /* first channel of the pairs, bitstream order */
+  static const int8_t k_pair_slot[4][2] = {{0, -1}, {0, -1}, {0, 3}, {0, 4}}; /* ... and their slots */
+  const int n_ch = b->channel_config;
+  XaacMcCoreInParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_streams = b->n_streams, p.n_ch = n_ch, p.out32 = b->out32, p.qshift_adj = b->qshift_adj, p.core = b->core;
+  for (int k = 0; k < 2; k++) {
+    const int at = k_pair_at[n_ch - 3][k], slot = k_pair_slot[n_ch - 3][k];
+    if (at < 0) continue;
+    p.q_src[at + 1] = 1; /* (every other channel is its element's first: q_src 0) */
+    p.mix[at + 1] = n_ch == slot + 2 ? 1 : (n_ch == slot + 3 ? 2 : 0);
+  }
+  if (!hip_ok(hipSetDevice(c->device))) return XAAC_FATAL_HIP;
+  if (!hip_ok(xaac_launch_mc_core_from_out32(&p, c->stream))) return XAAC_FATAL_HIP;
+  return XAAC_OK;
+}
+
+static int32_t mc_pcm_out(xaac_ctx *c, const xaac_mc_pcm_out_batch *b, bool flt) {
+  if (!c || !b) return XAAC_FATAL_NULL_ARG;
+  if (b->n_streams < 0 || b->n_ch < 3 || b->n_ch > XAAC_MC_MAX_CH || b->stride < 2048 || (b->stride & 1)) return XAAC_FATAL_BAD_ARG;
+  uint32_t seen = 0;
+  for (int k = 0; k < b->n_ch; k++) {
+    if (b->slot[k] < 0 || b->slot[k] >= b->n_ch) return XAAC_FATAL_BAD_ARG;
+    seen |= 1u << b->slot[k];
+  }
+  if (seen != (1u << b->n_ch) - 1) return XAAC_FATAL_BAD_ARG;
+  if (b->n_streams == 0) return XAAC_OK;
+  if (!b->planes || !b->pcm) return XAAC_FATAL_NULL_ARG;
+  if (((uintptr_t)b->planes & (flt ? 7u : 3u)) || ((uintptr_t)b->pcm & 3u)) return XAAC_FATAL_BAD_ARG;
+  XaacMcPcmOutParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_streams = b->n_streams, p.n_ch = b->n_ch, p.stride = b->stride, p.planes = b->planes, p.pcm = b->pcm;
+  for (int k = 0; k < b->n_ch; k++) p.slot[k] = b->slot[k];
+  if (!hip_ok(hipSetDevice(c->device))) return XAAC_FATAL_HIP;
+  if (!hip_ok(flt ? xaac_launch_mc_pcm16_from_float(&p, c->stream) : xaac_launch_mc_pcm16_from_planes(&p, c->stream))) return XAAC_FATAL_HIP;
+  return XAAC_OK;
+}
+int32_t xaac_mc_pcm16_from_float_batch(xaac_ctx *c, const xaac_mc_pcm_out_batch *b) { return mc_pcm_out(c, b, true); }
+int32_t xaac_mc_pcm16_from_planes_batch(xaac_ctx *c, const xaac_mc_pcm_out_batch *b) { return mc_pcm_out(c, b, false); }
 
 int32_t xaac_sbr_state_handover(xaac_ctx *c, const xaac_sbr_handover_batch *b) {
   if (!c || !b) return XAAC_FATAL_NULL_ARG;

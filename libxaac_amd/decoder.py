@@ -290,7 +290,7 @@ class _ParseBatch(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("parser", "data", "bytes", "spec", "ics", "header", "frame", "ps_frame", "flags",
                                                "tools", "consumed", "status", "esbr_side", "reset_pitch", "pos")] + \
                [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p), ("tools_side", ctypes.c_void_p),
-                ("channel_config", ctypes.c_int32)]
+                ("channel_config", ctypes.c_int32), ("mc_sbr", ctypes.c_int32)]
 
 
 F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(8)
@@ -388,7 +388,7 @@ class BatchParser:
     """N ADTS streams of one kind through the host front end in lock step: xaac_parse_batch_run parses one frame of every
     stream on a team of CPU threads, straight into the (pinned) staging arrays handed to step()."""
 
-    def __init__(self, streams, threads=0, stage=2, esbr=False):
+    def __init__(self, streams, threads=0, stage=2, esbr=False, mc_sbr=False):
         self.lib = load_host_library()
         self.lib.xaac_parse_batch_run.argtypes = [ctypes.c_void_p]       # (the original layout's symbols: no pos / frames / lines)
         self.lib.xaac_parse_batch_start.argtypes = [ctypes.c_void_p]
@@ -413,7 +413,6 @@ class BatchParser:
             self.parsers[i] = h
         self.threads, self.stage = int(threads), int(stage)
         self.consumed, self.status = np.zeros(n, np.uint64), np.zeros(n, np.int32)
-        self.reset_pitch = np.zeros(n, np.int32)   # at frames with a reset flag: xaac_parse_reset_pitch
         self.frames = np.zeros(n, np.int64)
         hdr = AdtsHeader()
         rc = self.lib.xaac_adts_parse_header(bytes(streams[0][:16]), min(16, len(streams[0])), ctypes.byref(hdr))
@@ -422,16 +421,20 @@ class BatchParser:
         self.core_rate, self.n_ch = hdr.sampling_rate, (2 if hdr.channel_config == 2 else 1)
         channels, n_elems, sbr, config = probe_first_frame(streams[0])
         self.sbr = bool(sbr)
-        # several channel elements (channel_config 3 .. 6): the multichannel form of the batch call, AAC-LC only
+        # several channel elements (channel_config 3 .. 6): the multichannel form of the batch call; with SBR payloads only when
+        # the caller asked for per-element SBR (mc_sbr: flags int32[n, n_elems, 8] and reset_pitch int32[n, n_elems], a row per
+        # channel element; header / frame / eside rows per channel in bitstream order)
         self.channel_config, self.n_elems = (config, n_elems) if n_elems > 1 else (0, 1)
         for d in streams[1:]:   # a multichannel stream only beside streams of its own channel_config, whichever comes first
             other = (((d[2] & 1) << 2) | (d[3] >> 6)) if len(d) >= 4 else -1
             if other != config and (3 <= other <= 6 or 3 <= config <= 6):
                 raise ValueError("streams of different channel configurations in one batch")
         if self.channel_config:
-            if self.sbr:
+            if self.sbr and not mc_sbr:
                 raise ValueError("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported")
             self.n_ch = channels
+        self.mc_sbr = bool(mc_sbr) and bool(self.channel_config) and self.sbr
+        self.reset_pitch = np.zeros(n * (self.n_elems if self.mc_sbr else 1), np.int32)   # at frames with a reset flag: xaac_parse_reset_pitch
 
     def close(self):
         if getattr(self, "_in_flight", False):   # (a caller that gave up between start_step() and wait_step(): the team must get its batch back)
@@ -460,6 +463,7 @@ class BatchParser:
         b.lines = None if lines is None else lines.ctypes.data
         b.tools_side = ptr(tools_side)   # uint8[frames, n, CORE_TOOLS_SIDE_BYTES]: the tools' side info of a stage-1 parse
         b.channel_config = self.channel_config   # (with it: tools_side is uint8[frames, n_elems, n, ...], element-major)
+        b.mc_sbr = int(self.mc_sbr)
         return b
 
     def _advance(self, ok, status=None):
@@ -567,12 +571,13 @@ class Staging:
         self.psf, self.eside = want("psf", n, PS_FRAME_BYTES), want("eside", nc, ESBR_SIDE_BYTES)
         self.flags = self.flags_pin = None
         if "flags" in arrays:
-            self.flags = np.zeros((T, n, 8), np.int32)
+            self.flags = np.zeros((T, n, bp.n_elems, 8) if bp.mc_sbr else (T, n, 8), np.int32)   # (mc_sbr: a row per channel element)
             self.flags_pin = pinned(T, n, 8, dtype=torch.int32)   # the rows as they go up for xaac_sbr_state_apply_side_batch
         self.seconds = 0.0
         self.sent = [torch.cuda.Event() for _ in range(T)]   # step t's copies up are over (sent[T - 1]: the parser may write the set again)
         self.sent_once = False
-        self.status, self.reset_pitch = np.zeros((T, n), np.int32), np.zeros((T, n), np.int32)   # this set's own
+        self.status = np.zeros((T, n), np.int32)   # this set's own
+        self.reset_pitch = np.zeros((T, n, bp.n_elems) if bp.mc_sbr else (T, n), np.int32)
         self.lines = np.zeros((T, n), np.int32)   # leading spectral lines that may be non-zero, per step and stream
         self.steps = None
 
@@ -813,9 +818,14 @@ class _EsbrChain(_SbrBase):
         as the frame before left it: rows 8..31 are what that frame found as rows 8..31 of its history (`older`), rows 32..71 are
         the state's history (the codec bank's num_time_slots is 32 here).  The second run's last eight output rows become the
         state's ph rows (bands outside the transposer's range keep what they held)."""
-        ctx, dev, n_ch, dz = self.ctx, self.dev, self.n_ch, self.dz
-        k = touched.size * n_ch
+        n_ch = self.n_ch
         rows_h = (touched[:, None] * n_ch + np.arange(n_ch)[None, :]).ravel()
+        self.reset_rows(step, rows_h, np.repeat(step.reset_pitch[touched], n_ch))
+
+    def reset_rows(self, step, rows_h, pitch_h):
+        """... on the channel rows rows_h, with the pitch every row's reset hands its transposer runs"""
+        ctx, dev, n_ch, dz = self.ctx, self.dev, self.n_ch, self.dz
+        k = len(rows_h)
         rows = torch.from_numpy(rows_h).to(dev)
         hb = self.hbe.index_select(0, rows)
         tail_off = HBE_STATE_BYTES - 48
@@ -828,7 +838,7 @@ class _EsbrChain(_SbrBase):
         hb[:, tail_off:] = torch.from_numpy(tails).to(dev)
         hb32 = hb.view(torch.float32)
         hb32[:, 1088:1088 + 1280 + 640] = 0.0          # synth_buf, analy_buf (behind input_buf[1024 + 64])
-        pitch = torch.from_numpy(np.repeat(step.reset_pitch[touched], n_ch).astype(np.int32)).to(dev)
+        pitch = torch.from_numpy(np.ascontiguousarray(pitch_h, np.int32)).to(dev)
         st32 = self.state.view(torch.float32)
         hist, old = st32.index_select(0, rows), self.older.index_select(0, rows)
         q_re, q_im = dz(k, 32, 64, dtype=torch.float32), dz(k, 32, 64, dtype=torch.float32)
@@ -876,6 +886,49 @@ class _EsbrChain(_SbrBase):
         return (self.n, 2048, 2), 0, first      # the first frame's output is not written in this mode
 
 
+class _McEsbrChain(_EsbrChain):
+    """Path A for streams of more than two channels (channel_config 3 .. 6): one SBR decoder per channel element as the reference
+    keeps them, which here is every channel a row of its own -- in bitstream order -- through the same batch entry points.  The
+    IMDCT leaves WORD32 rows (ch_fac 1); xaac_mc_core_from_out32_batch makes the in-place 16-bit conversion of every element in the
+    frame's block; xaac_mc_pcm16_from_float_batch puts the planes into the block in output channel order (ixheaacd_samples_sat_mc;
+    no limiter: api.c:3381).  No parametric stereo in such a frame.  Flags and reset pitch come per channel element."""
+
+    def allocate(self, dz, pinned):
+        _EsbrChain.allocate(self, dz, pinned)
+        n, n_ch = self.n, self.n_ch
+        elements, self.route, _ = MC_LAYOUT[n_ch]
+        self.el_of_ch = np.repeat(np.arange(len(elements)), [2 if e == 1 else 1 for e in elements])
+        self.out_ch = n_ch
+        self.out32, self.qadj = dz(self.nc, 1024, dtype=torch.int32), dz(self.nc, dtype=torch.int8)
+        self.pcm2 = [dz(n * 2048 * n_ch, dtype=torch.int16) for _ in range(2)]
+        self.pcm_h2 = [pinned(n * 2048 * n_ch, dtype=torch.int16) for _ in range(2)]
+
+    def send_up(self, step, slot, got):
+        self.hdr_d2[slot].copy_(step.hdr, non_blocking=True)
+        self.frm_d2[slot].copy_(step.frm, non_blocking=True)
+        self.eside_d2[slot].copy_(step.eside, non_blocking=True)
+
+    def run(self, step, slot, got, first, spec_d, ics_d):
+        ctx, n_ch, state = self.ctx, self.n_ch, self.state
+        hdr_d, frm_d, eside_d = self.hdr_d2[slot], self.frm_d2[slot], self.eside_d2[slot]
+        ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, out32=self.out32, qshift_adj=self.qadj, ch_fac=1)
+        # channel rows whose element resets in this frame (the LFE's never does: it has no header)
+        reset = (step.flags[:, self.el_of_ch, F_RESET] != 0) & got[:, None]
+        rows_h = np.nonzero(reset.ravel())[0]
+        if rows_h.size:
+            self.reset_rows(step, rows_h, step.reset_pitch[:, self.el_of_ch].ravel()[rows_h])
+        st32 = state.view(torch.float32)
+        self.older[:, 0] = st32[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 32 * 64]
+        self.older[:, 1] = st32[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 32 * 64]
+        ctx.mc_core_from_out32(self.out32, self.qadj, self.core, n_ch)
+        if self.trace is not None:
+            self.trace(dict(state=state, hbe=self.hbe, ps_state=None, core=self.core, side=eside_d, header=hdr_d, frame=frm_d))
+        ctx.esbr_sbr_process_batch(self.core, hdr_d, frm_d, eside_d, state, self.out_l, self.ws, status=self.status2[slot],
+                                   hbe_state=self.hbe, hbe_max_synth_size=self.hbe_hint())
+        ctx.mc_pcm16_from_planes(self.out_l, self.pcm2[slot], self.route)
+        return (self.n, 2048, n_ch), 0, first
+
+
 class _Pipeline:
     """The lock-step driver behind decode_streams.  Three staging sets go round: the parse of step k + 1 | the copies up and
     kernels of step k | the copy down of step k - 1.  Copies up have a stream of their own (`up`) into two sets of device
@@ -884,26 +937,36 @@ class _Pipeline:
     later.  What runs between the two is the chain's business (_LcChain, _SbrChain or _EsbrChain, picked once in here), with
     the spectral tools in front of it when gpu_tools says so."""
 
-    def __init__(self, streams, ctx, device, threads, keep_pcm, overlap, esbr, trace, frames_per_parse, gpu_tools):
+    def __init__(self, streams, ctx, device, threads, keep_pcm, overlap, esbr, trace, frames_per_parse, gpu_tools, mc_sbr=False):
         self.dev = dev = torch.device(device)
         alloc, lib = _Alloc(dev), load_host_library()
         self.own = ctx is None
         if self.own:   # the context launches on torch's current stream, so that its kernels and torch's copies stay in order
             ctx = XaacContext(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
         self.ctx = ctx
-        self.bp = bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2)
-        # more than two channels: bitstream channel c of a stream goes up as row route[c] of its rows (the reference's output order)
-        self.route = MC_LAYOUT[bp.channel_config][1] if bp.channel_config else None
+        self.bp = bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2, mc_sbr=mc_sbr)
+        if bp.mc_sbr:   # what per-element SBR does not cover
+            try:
+                if not esbr:
+                    raise ValueError("mc_sbr with esbr=False (the fixed-point SBR tools in a stream of more than two channels) is not supported")
+                if 2 * bp.core_rate > 48000:
+                    raise ValueError("mc_sbr with a down-sampled bank (an output rate above 48 kHz) is not supported")
+            except ValueError:
+                bp.close()
+                raise
+        # more than two channels: bitstream channel c of a stream goes up as row route[c] of its rows (the reference's output order);
+        # with SBR the rows stay in bitstream order (the hand-off behind the SBR calls routes them)
+        self.route = MC_LAYOUT[bp.channel_config][1] if bp.channel_config and not bp.sbr else None
         self.ics_routed = [alloc.pinned(bp.n * bp.n_ch, 2) for _ in range(4)] if self.route else None
         self.n, self.nc, self.keep_pcm, self.overlap = bp.n, bp.n * bp.n_ch, keep_pcm, overlap
         self.T = T = max(1, int(frames_per_parse))
-        kind = _LcChain if not bp.sbr else _EsbrChain if esbr else _SbrChain
+        kind = _LcChain if not bp.sbr else _McEsbrChain if bp.mc_sbr else _EsbrChain if esbr else _SbrChain
         self.chain = chain = kind(ctx, lib, dev, bp.n, bp.n_ch, bp.core_rate, alloc, trace)
         first_rows = (0,)
         if bp.channel_config:   # every element's first bitstream channel, where the routed upload puts it
             elements, route, _ = MC_LAYOUT[bp.channel_config]
             starts = np.concatenate([[0], np.cumsum([2 if e == 1 else 1 for e in elements])[:-1]])
-            first_rows = tuple(route[int(c)] for c in starts)
+            first_rows = tuple(route[int(c)] if self.route else int(c) for c in starts)
         self.tools = _ToolsStage(ctx, bp.n, alloc.dz, alloc.pinned, bp.n_ch, first_rows) if gpu_tools else None
         # two sets of device input arrays: step k + 1 is copied up (its own stream) while step k's kernels read theirs
         self.spec_d2 = [alloc.dz(self.nc, 1024, dtype=torch.int32) for _ in range(2)]
@@ -1060,7 +1123,7 @@ class _Pipeline:
 
 
 def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True, timing=None, overlap=True, esbr=False,
-                   _trace=None, frames_per_parse=4, gpu_tools=False):
+                   _trace=None, frames_per_parse=4, gpu_tools=False, mc_sbr=False):
     """Decodes N ADTS streams of the same kind (all AAC-LC mono or stereo, all AAC-LC of one channel_config 3 .. 6 -- 3.0 to
     5.1, output channels in the reference's order, MC_LAYOUT --, all HE-AAC stereo, or all HE-AAC / HE-AACv2 mono) in lock step: per step one frame of every stream is parsed on CPU threads into pinned staging arrays, copied to the GPU
     (spectra + window info, SBR / PS side info: nothing else crosses the bus on the way in), run through the GPU entry
@@ -1081,9 +1144,13 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     state).
     gpu_tools: the M/S, intensity, PNS and TNS tools run on the GPU (xaac_aac_tools_process_batch in front of the IMDCT) instead of
     in the parser: the streams are parsed at stage 1, the tools' side rows go up beside the spectra and every stream's noise
-    generator lives on the device (one per channel element).  Off by default; the PCM is the same either way.  An SBR payload in
-    a stream of more than two channels is a ValueError."""
+    generator lives on the device (one per channel element).  Off by default; the PCM is the same either way.
+    mc_sbr: take HE-AAC streams of channel_config 3 .. 6 (an SBR payload per channel element; one SBR decoder per element, as the
+    reference keeps them; output channels in the reference's order at twice the core's rate, no limiter).  esbr=True only: with
+    esbr=False, or with an output rate above 48 kHz (the down-sampled bank), such a stream is a ValueError; without mc_sbr an SBR
+    payload in a stream of more than two channels is a ValueError as before."""
     global torch
     import torch
     with _TorchCpuThreads():
-        return _Pipeline(streams, ctx, device, threads, keep_pcm, overlap, esbr, _trace, frames_per_parse, bool(gpu_tools)).run(timing)
+        return _Pipeline(streams, ctx, device, threads, keep_pcm, overlap, esbr, _trace, frames_per_parse, bool(gpu_tools),
+                         bool(mc_sbr)).run(timing)

@@ -1406,6 +1406,10 @@ void xs_init(XsDecoder *d, int core_sampling_rate, int core_channels, int ps_ena
   }
   d->hdr.out_sampling_freq = 2 * core_sampling_rate;
   d->hdr.sync_state = XS_NOT_INITIALIZED;
+  /* sbrdec_initfuncs.c:685: what the float regrouping takes every band below of from the analysis bank's rows (sbr_dec.c:380) in a
+     decoder that never sees a payload -- the LFE's of a stream of several elements: sbrdecoder.c:427-431 puts it into the
+     up-sampling state without ixheaacd_prepare_upsamp, frame after frame */
+  if (enh) d->hdr.sub_band_start = 64;
   for (int c = 0; c < 2; c++) d->prev[c].end_position = kTimeSlots; /* sbrdec_initfuncs.c:884-898 */
   for (int c = 0; c < 2; c++) d->fd[c].fi.transient_env = 0;
 }

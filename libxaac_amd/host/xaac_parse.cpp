@@ -49,6 +49,13 @@ struct XpMore {
   int have_sequence, sequence_n, sequence[XP_MAX_ELEMENTS]; /* the first frame's element ids: later frames must repeat them */
 };
 
+/* ... and the SBR front ends of such a stream, one per channel element as the reference keeps one SBR decoder per element
+   (api.c:2389-2517): allocated by the first xaac_parse_sbr_side_mc call */
+struct XpSbrMc {
+  XsDecoder dec[XP_MAX_ELEMENTS];
+  int ready[XP_MAX_ELEMENTS];
+};
+
 struct xaac_parser {
   int sr_index;
   XhCoreState core;
@@ -69,6 +76,7 @@ struct xaac_parser {
   int channel_config; /* of the ADTS header read last */
   int n_els;    /* ... and how many (more than one: the others are in more->el) */
   XpMore *more;
+  XpSbrMc *sbr_mc;
 };
 static inline XhElement *element_of(xaac_parser *p, int k) { return k == 0 ? &p->el : &p->more->el[k - 1]; }
 
@@ -237,6 +245,7 @@ int32_t xaac_parser_create(xaac_parser **p) {
 
 void xaac_parser_destroy(xaac_parser *p) {
   if (p) delete p->more;
+  if (p) delete p->sbr_mc;
   delete p;
 }
 
@@ -477,6 +486,46 @@ int32_t xaac_parse_sbr_side(xaac_parser *p, int32_t ps_enable, xaac_sbr_side *si
   return XAAC_PARSE_OK;
 }
 
+/* one channel element's SBR payload through the element's own front end: parametric stereo is off in a frame of several elements
+   (api.c:2384-2387), an element without payload -- the LFE always -- is a frame whose SBR data is missing */
+static int32_t sbr_side_mc(xaac_parser *p, int element, xaac_sbr_side *side) {
+  if (!p->sbr_mc) {
+    p->sbr_mc = new (std::nothrow) XpSbrMc;
+    if (!p->sbr_mc) return XAAC_PARSE_ERR_UNSUPPORTED;
+    memset(static_cast<void *>(p->sbr_mc), 0, sizeof(*p->sbr_mc));
+  }
+  XhElement *el = element_of(p, element);
+  XsDecoder *d = &p->sbr_mc->dec[element];
+  if (!p->sbr_mc->ready[element]) {
+    xs_init(d, p->sampling_rate, el->n_ch, 0, p->esbr);
+    p->sbr_mc->ready[element] = 1;
+  }
+  XsFrameResult r;
+  if (xs_decode_frame(d, el->sbr, el->sbr_bytes, el->sbr_ext_type, &side->header, side->frame, &side->ps_frame, &r)) return XAAC_PARSE_ERR_SYNTAX;
+  xs_frame_done(d, &r);
+  side->apply = r.apply, side->reset = r.reset, side->reset_channels = r.reset_channels, side->upsampling = r.upsampling;
+  side->stereo = r.stereo, side->ps = r.ps, side->ps_start = r.ps_start, side->frame_ok = r.frame_ok;
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_sbr_side_mc(xaac_parser *p, int32_t element, xaac_sbr_side *side) {
+  if (!p || !side || p->sr_index < 0 || !p->frame_ok || !p->more || element < 0 || element >= p->n_els) return XAAC_PARSE_ERR_SYNTAX;
+  return sbr_side_mc(p, element, side);
+}
+
+int32_t xaac_parse_esbr_side_mc(xaac_parser *p, int32_t element, int32_t channel, xaac_esbr_side *side) {
+  if (!p || !side || !p->esbr || !p->sbr_mc || element < 0 || element >= XP_MAX_ELEMENTS || !p->sbr_mc->ready[element] || channel < 0 || channel > 1)
+    return XAAC_PARSE_ERR_SYNTAX;
+  xs_export_esbr_side(&p->sbr_mc->dec[element], channel, side);
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_reset_pitch_mc(xaac_parser *p, int32_t element, int32_t *pitch_in_bins) {
+  if (!p || !pitch_in_bins || !p->sbr_mc || element < 0 || element >= XP_MAX_ELEMENTS || !p->sbr_mc->ready[element]) return XAAC_PARSE_ERR_SYNTAX;
+  *pitch_in_bins = p->sbr_mc->dec[element].reset_pitch;
+  return XAAC_PARSE_OK;
+}
+
 int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side) {
   if (!p || !side || p->sr_index < 0 || p->el.n_ch < 1 || !p->frame_ok) return XAAC_PARSE_ERR_SYNTAX;
   memset(side, 0, sizeof(*side));
@@ -505,7 +554,7 @@ int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_t
 }
 
 int32_t xaac_parser_set_esbr(xaac_parser *p, int32_t esbr) {
-  if (!p || p->sbr_ready || (esbr != 0 && esbr != 1)) return XAAC_PARSE_ERR_SYNTAX;
+  if (!p || p->sbr_ready || p->sbr_mc || (esbr != 0 && esbr != 1)) return XAAC_PARSE_ERR_SYNTAX;
   p->esbr = esbr;
   return XAAC_PARSE_OK;
 }
@@ -639,6 +688,31 @@ int32_t parse_one_mc(const xaac_parse_batch *b, int i, int t, std::atomic<int> *
     p->frame_ok = 0;
     p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
   }
+  /* mc_sbr: every element's SBR side info, the rows per channel (a pair's channels get copies of the header), flags and reset
+     pitch per element */
+  if (r == 0 && b->with_sbr) {
+    static thread_local xaac_sbr_side side; /* copied into the batch's arrays */
+    size_t ch_row = SC + (size_t)i * n_ch;
+    for (int k = 0; k < n_els && r == 0; k++) {
+      XhElement *el = element_of(p, k);
+      r = sbr_side_mc(p, k, &side);
+      if (r) break;
+      const size_t e_row = (S + i) * (size_t)n_els + k;
+      for (int c = 0; c < el->n_ch; c++, ch_row++) {
+        b->header[ch_row] = side.header;
+        b->frame[ch_row] = side.frame[c];
+        if (b->esbr_side && p->esbr) xs_export_esbr_side(&p->sbr_mc->dec[k], c, b->esbr_side + ch_row);
+      }
+      int32_t *f = b->flags + e_row * 8;
+      f[0] = side.apply, f[1] = side.reset, f[2] = side.reset_channels, f[3] = side.upsampling;
+      f[4] = side.stereo, f[5] = side.ps, f[6] = side.ps_start, f[7] = side.frame_ok;
+      if (b->reset_pitch && side.reset) b->reset_pitch[e_row] = p->sbr_mc->dec[k].reset_pitch;
+    }
+    if (r) {
+      p->frame_ok = 0;
+      p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
+    }
+  }
   b->status[S + i] = r;
   if (r) return r;
   (*ok)++;
@@ -701,12 +775,14 @@ bool batch_ok(const xaac_parse_batch *b) {
   const bool mc = b && b->channel_config >= 3 && b->channel_config <= 6;
   return b && b->n_streams >= 0 && (b->n_ch == 1 || b->n_ch == 2 || mc) && (mc || b->channel_config == 0) && b->parser && b->data && b->bytes && b->spec && b->ics &&
          b->consumed && b->status && (!b->with_sbr || (b->header && b->frame && b->flags)) && b->frames >= 0 &&
-         (b->frames <= 1 || b->pos); /* several frames per call: the positions are the library's */
+         (b->frames <= 1 || b->pos) && /* several frames per call: the positions are the library's */
+         (b->mc_sbr == 0 || b->mc_sbr == 1);
 }
 
-/* a multichannel batch: the configuration's channel count, and no SBR side info (per-element SBR is not built) */
+/* a multichannel batch: the configuration's channel count, and SBR side info only where the caller asked for the per-element
+   layout (mc_sbr) */
 bool batch_unsupported(const xaac_parse_batch *b) {
-  return b->channel_config && (b->n_ch != k_config_channels[b->channel_config] || b->with_sbr);
+  return b->channel_config && (b->n_ch != k_config_channels[b->channel_config] || (b->with_sbr && !b->mc_sbr));
 }
 
 int batch_threads(const xaac_parse_batch *b) {

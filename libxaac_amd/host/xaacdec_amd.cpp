@@ -7,7 +7,10 @@
  *
  *   xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:<0|1>] [-copies:<N>] [-verify] [-threads:<T>] [-quiet]
  *   xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-esbr:<0|1>] [-threads:<T>] [-quiet]
- *   ... [-gpus:<G>] [-device:<k>] [-plan] [-gputools:<0|1>]
+ *   ... [-gpus:<G>] [-device:<k>] [-plan] [-gputools:<0|1>] [-mcsbr:<0|1>]
+ *
+ * -mcsbr:1 (default 0) takes HE-AAC streams of more than two channels (channel_config 3 .. 6 with SBR payloads): one SBR decoder per
+ * channel element, as the reference keeps them; default flags (-esbr:1) only.  Without the flag such a stream is refused.
  *
  * -gputools:1 (default 0) runs the M/S, intensity, PNS and TNS tools on the GPU: the streams are parsed up to the entry of
  * ixheaacd_channel_pair_process (stage 1), the tools' side rows go up beside the spectra and xaac_aac_tools_process_batch runs in
@@ -259,10 +262,17 @@ void write_wav(const std::string &path, const std::vector<int16_t> &pcm, int cha
 struct Job {
   std::vector<std::vector<uint8_t>> datas; /* -ilist: one per stream; else the one input */
   int n_ch, sbr, esbr, out_ch, rate, per;
-  int channel_config; /* 3 .. 6: a stream of several channel elements (AAC-LC only); 0: one element, the mono / stereo paths */
+  int channel_config; /* 3 .. 6: a stream of several channel elements (with sbr: -mcsbr:1, Path A only); 0: one element, the mono / stereo paths */
   int n_els;          /* channel elements of a frame: 1, or the configuration's 2 .. 4 */
   int first_ch[4];    /* ... and the first bitstream channel of each */
   int slot[8];        /* ... output channel of bitstream channel c: where the reference routes its elements (layout_of) */
+  int el_of_ch[8];    /* ... channel element of bitstream channel c */
+  /* the row of a step's flag / reset pitch vectors that covers channel row i of the shard: per stream, or -- more than two channels
+     with SBR -- per channel element of the stream (xaac_parse_batch::mc_sbr) */
+  size_t flag_row(int i) const { return channel_config && sbr ? (size_t)(i / n_ch) * n_els + el_of_ch[i % n_ch] : (size_t)(i / n_ch); }
+  /* such a stream's rows stay in bitstream order on the device (the hand-off behind the SBR calls routes them); an AAC-LC one's
+     are routed on their way up */
+  bool routed_up() const { return channel_config && !sbr; }
   int hq; /* -esbr_hq:1: the DFT harmonic transposer in the QMF one's place (Path A only) */
   int threads, verify, profile;
   int gputools; /* -gputools:1: parse at stage 1, the spectral tools run on the GPU in front of the IMDCT */
@@ -317,7 +327,8 @@ class ParseSide {
       const int NE = J.n_els; /* the tools' side rows: one per channel element, element-major within a step */
       xaac_core_tools_side *tside = J.gputools ? mem.pinned<xaac_core_tools_side>((size_t)T * N * NE) : nullptr;
       StagingGroup &G = grp_[g];
-      G.flags.assign((size_t)T * N * 8, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N, 0);
+      const int NF = J.channel_config && J.sbr ? NE : 1; /* flag rows of a stream: one, or one per channel element (mc_sbr) */
+      G.flags.assign((size_t)T * N * NF * 8, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N * NF, 0);
       G.lines.assign((size_t)T * N, 0), G.consumed.assign((size_t)N, 0);
       for (int t = 0; t < T; t++) {
         Staging &s = st_[g * T + t];
@@ -325,7 +336,7 @@ class ParseSide {
         s.header = header ? header + (size_t)t * NC : nullptr, s.frame = frame ? frame + (size_t)t * NC : nullptr;
         s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
         s.tside = tside ? tside + (size_t)t * N * NE : nullptr;
-        s.flags = &G.flags[(size_t)t * N * 8], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N];
+        s.flags = &G.flags[(size_t)t * N * NF * 8], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N * NF];
         s.delivered = 0, s.lines = 1024;
       }
     }
@@ -379,7 +390,7 @@ class ParseSide {
     xaac_parse_batch b;
     memset(&b, 0, sizeof(b));
     b.n_streams = N, b.n_ch = J_.n_ch, b.with_sbr = J_.sbr, b.ps_enable = 1, b.stage = J_.gputools ? 1 : 2, b.threads = J_.threads;
-    b.channel_config = J_.channel_config;
+    b.channel_config = J_.channel_config, b.mc_sbr = J_.channel_config && J_.sbr;
     b.parser = parser_.data(), b.data = ptr_.data(), b.bytes = left_.data(), b.pos = pos_.data(), b.frames = T;
     Staging &s0 = st_[g * T];
     b.spec = s0.spec, b.ics = s0.ics, b.header = s0.header, b.frame = s0.frame, b.ps_frame = s0.ps;
@@ -485,7 +496,7 @@ class ToolsStage {
     for (int k = 0; k < E_.J.n_els; k++) {
       xaac_aac_tools_batch tb;
       memset(&tb, 0, sizeof(tb));
-      const int row = E_.J.channel_config ? E_.J.slot[E_.J.first_ch[k]] : 0;
+      const int row = E_.J.routed_up() ? E_.J.slot[E_.J.first_ch[k]] : E_.J.first_ch[k];
       tb.n = E_.N, tb.spec_stride = 1024 * E_.J.n_ch, tb.spec = E_.d_spec + (size_t)row * 1024;
       tb.side = d_side_ + k * N, tb.state = d_state_ + k * N, tb.status = d_status_[slot] + k * N;
       XA(xaac_aac_tools_process_batch(E_.ctx, &tb));
@@ -752,7 +763,7 @@ class QmfTransposer : public Transposer {
       memcpy(&h0.synth_size, &tail_[(size_t)i * kTail], kTail);
       if (xaac_hbe_state_reinit(&h0, &s.header[(size_t)i])) die("the QMF transposer refused the SBR band tables");
       memcpy(&tail_[(size_t)i * kTail], &h0.synth_size, kTail);
-      pitch_[(size_t)k] = s.reset_pitch[(size_t)(i / E_.J.n_ch)];
+      pitch_[(size_t)k] = s.reset_pitch[E_.J.flag_row(i)];
     }
   }
   void stage(const Staging &, const ResetSet &R, const ResetScratch &sc, int u) override {
@@ -852,7 +863,7 @@ class DftTransposer : public Transposer {
     HIP(hipMemcpy(&d_dft_[i].anal.analy_size, &h0.anal.analy_size, kInts, hipMemcpyHostToDevice));
     HIP(hipMemset(&d_dft_[i].synth_buf[0], 0, sizeof(h0.synth_buf))); /* hbe_dft_trans.c:302 */
     HIP(hipMemcpyAsync(&d_tmp_[u], &d_dft_[i], sizeof(xaac_hbe_dft_state), hipMemcpyDeviceToDevice, E_.stream));
-    r_pitch_[(size_t)u] = s.reset_pitch[(size_t)(i / E_.J.n_ch)];
+    r_pitch_[(size_t)u] = s.reset_pitch[E_.J.flag_row(i)];
     r_ovs_[(size_t)u] = ovs_[(size_t)i];
   }
   void upload(const ResetSet &R, const ResetScratch &sc) override {
@@ -895,9 +906,10 @@ class DftTransposer : public Transposer {
 /* -esbr:1, Path A: IMDCT -> float planes -> eSBR chain (+ transposer, float PS) -> samples_sat */
 class EsbrChain : public Chain {
  public:
-  explicit EsbrChain(const Env &E) : E_(E), mono_(E.J.n_ch == 1) {
+  explicit EsbrChain(const Env &E) : E_(E), mono_(E.J.n_ch == 1), mc_(E.J.channel_config != 0) {
     const int N = E.N, NC = E.NC;
-    d_core_ = E.mem.dev<int16_t>((size_t)NC * 1024);
+    if (mc_) d_out32_ = E.mem.dev<int32_t>((size_t)NC * 1024), d_qadj_ = E.mem.dev<int8_t>((size_t)NC);
+    else d_core_ = E.mem.dev<int16_t>((size_t)NC * 1024);
     d_header_ = E.mem.dev<xaac_sbr_header>((size_t)NC);
     d_frame_ = E.mem.dev<xaac_sbr_frame>((size_t)NC);
     d_eside_ = E.mem.dev<xaac_esbr_side>((size_t)NC);
@@ -928,12 +940,15 @@ class EsbrChain : public Chain {
   StepOut run(const Staging &s, int slot) override {
     const int N = E_.N, NC = E_.NC;
     xaac_imdct_batch ib = E_.imdct;
-    ib.pcm16 = d_core_, ib.pcm_mode = XAAC_PCM_SBR;
+    if (mc_) ib.out32 = d_out32_, ib.qshift_adj = d_qadj_; /* every channel a row (ch_fac 1): the hand-in below converts them */
+    else ib.pcm16 = d_core_, ib.pcm_mode = XAAC_PCM_SBR;
     XA(xaac_imdct_process_batch(E_.ctx, &ib));
-    int resets = 0, with_ps = 0;
-    for (int i = 0; i < N; i++)
-      if (s.status[(size_t)i] == 0) resets += s.flags[(size_t)i * 8 + 1] != 0, with_ps += s.flags[(size_t)i * 8 + 5] != 0;
-    if (resets) reset_runs(s, slot, resets == s.delivered);
+    int resets = 0, with_ps = 0; /* channel rows that reset; streams with PS (never with more than two channels) */
+    for (int i = 0; i < NC; i++)
+      if (s.status[(size_t)(i / E_.J.n_ch)] == 0) resets += s.flags[E_.J.flag_row(i) * 8 + 1] != 0;
+    for (int i = 0; i < N && !mc_; i++)
+      if (s.status[(size_t)i] == 0) with_ps += s.flags[(size_t)i * 8 + 5] != 0;
+    if (resets) reset_runs(s, slot, resets == s.delivered * E_.J.n_ch);
     /* what this frame finds as rows 8..31 of its history: the frame behind it may need them at a reset */
     float *older_re = d_older_, *older_im = d_older_ + (size_t)NC * 24 * 64;
     HIP(hipMemcpy2DAsync(older_re, 24 * kRow, &d_estate_[0].qmf_re[8][0], kStatePitch, 24 * kRow, (size_t)NC, hipMemcpyDeviceToDevice, E_.stream));
@@ -941,8 +956,13 @@ class EsbrChain : public Chain {
     HIP(hipMemcpyAsync(d_header_, s.header, (size_t)NC * sizeof(xaac_sbr_header), hipMemcpyHostToDevice, E_.stream));
     HIP(hipMemcpyAsync(d_frame_, s.frame, (size_t)NC * sizeof(xaac_sbr_frame), hipMemcpyHostToDevice, E_.stream));
     HIP(hipMemcpyAsync(d_eside_, s.eside, (size_t)NC * sizeof(xaac_esbr_side), hipMemcpyHostToDevice, E_.stream));
-    xaac_esbr_core_in_batch cb = {NC, E_.J.n_ch, d_core_, d_fcore_};
-    XA(xaac_esbr_core_from_pcm16_batch(E_.ctx, &cb));
+    if (mc_) { /* the in-place conversion of every element's channels in the frame's block, as the reference's layout has it */
+      xaac_mc_core_in_batch cb = {N, E_.J.channel_config, d_out32_, d_qadj_, d_fcore_};
+      XA(xaac_mc_core_from_out32_batch(E_.ctx, &cb));
+    } else {
+      xaac_esbr_core_in_batch cb = {NC, E_.J.n_ch, d_core_, d_fcore_};
+      XA(xaac_esbr_core_from_pcm16_batch(E_.ctx, &cb));
+    }
     xaac_esbr_sbr_batch b;
     memset(&b, 0, sizeof(b));
     b.n_ch = NC, b.core = d_fcore_, b.header = d_header_, b.frame = d_frame_, b.side = d_eside_, b.state = d_estate_, b.out = d_out_l_;
@@ -961,7 +981,15 @@ class EsbrChain : public Chain {
       ob.stride = 4096, ob.right = d_out_l_ + 2048;
     }
     XA(xaac_esbr_sbr_process_batch(E_.ctx, &b));
-    XA(xaac_esbr_pcm16_from_float_batch(E_.ctx, &ob));
+    if (mc_) { /* every element's planes into the frame's block, output channel order (ixheaacd_samples_sat_mc; no limiter: api.c:3381) */
+      xaac_mc_pcm_out_batch mb;
+      memset(&mb, 0, sizeof(mb));
+      mb.n_streams = N, mb.n_ch = E_.J.n_ch, mb.stride = 2048, mb.planes = d_out_l_, mb.pcm = E_.d_pcm[slot];
+      for (int c = 0; c < E_.J.n_ch; c++) mb.slot[c] = E_.J.slot[c];
+      XA(xaac_mc_pcm16_from_float_batch(E_.ctx, &mb));
+    } else {
+      XA(xaac_esbr_pcm16_from_float_batch(E_.ctx, &ob));
+    }
     return {E_.d_pcm[slot], (size_t)N * E_.J.per * E_.J.out_ch * 2, false, some_mono, NC};
   }
 
@@ -1001,7 +1029,7 @@ class EsbrChain : public Chain {
     R.gathered = tr_->always_gathers() || !every;
     if (R.gathered)
       for (int i = 0; i < NC; i++)
-        if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[(size_t)(i / n_ch) * 8 + 1] != 0) R.chs.push_back(i);
+        if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[E_.J.flag_row(i) * 8 + 1] != 0) R.chs.push_back(i);
     R.n = R.gathered ? (int)R.chs.size() : NC;
     if (!sc_.q_re) {
       sc_.q_re = E_.mem.dev<float>((size_t)NC * 2 * 2048), sc_.pv_re = E_.mem.dev<float>((size_t)NC * 2 * 2048);
@@ -1033,8 +1061,10 @@ class EsbrChain : public Chain {
   }
 
   const Env E_;
-  const bool mono_;
-  int16_t *d_core_;
+  const bool mono_, mc_; /* mc_: more than two channels, every channel element's channels through the batch as rows of their own */
+  int16_t *d_core_ = nullptr;
+  int32_t *d_out32_ = nullptr; /* mc_: the IMDCT's WORD32 rows and their qshift_adj, what the in-place conversion starts from */
+  int8_t *d_qadj_ = nullptr;
   xaac_sbr_header *d_header_;
   xaac_sbr_frame *d_frame_;
   xaac_esbr_side *d_eside_;
@@ -1106,7 +1136,7 @@ class ShardDriver {
       if (s.delivered != N_) note_ended(s);
       if (step % T == 0) parse_->start(); /* the next group's frames are parsed while the GPU works on this one's */
       t_phase_ = std::chrono::steady_clock::now();
-      if (J_.channel_config) send_up_routed(s, which);
+      if (J_.routed_up()) send_up_routed(s, which);
       else send_up(s);
       lap(0);
       if (tools_) tools_->run(slot);
@@ -1304,7 +1334,7 @@ void decode_shard(const Job &J, Shard &S) {
 
 int main(int argc, char **argv) {
   std::string in, out, ilist, odir;
-  int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0, gputools = 0;
+  int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0, gputools = 0, mcsbr = 0;
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     if (a.rfind("-ifile:", 0) == 0) in = a.substr(7);
@@ -1322,6 +1352,9 @@ int main(int argc, char **argv) {
     else if (a == "-profile") profile = 1; /* synchronise behind every phase of a step and report the seconds spent in each */
     else if (a == "-gputools:0") gputools = 0;
     else if (a == "-gputools:1") gputools = 1;
+    else if (a == "-mcsbr:0") mcsbr = 0;
+    else if (a == "-mcsbr:1") mcsbr = 1;
+    else if (a.rfind("-mcsbr", 0) == 0) die("-mcsbr:0 or -mcsbr:1");
     else if (a == "-esbr:0") esbr = 0;
     else if (a == "-esbr:1") esbr = 1;
     else if (a == "-esbr_hq:1") hq = 1;
@@ -1345,7 +1378,8 @@ int main(int argc, char **argv) {
     inputs.push_back(in);
   }
   if (inputs.empty() || (ilist.empty() && out.empty() && !plan) || copies < 1 || gpus < 1 || device0 < 0) {
-    fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-gputools:0|1] [-quiet]\n");
+    fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-gputools:0|1] [-mcsbr:0|1] [-quiet]\n"
+                    "  -mcsbr:1  decode HE-AAC streams of more than two channels (channel_config 3 .. 6, SBR per channel element; default flags only)\n");
     return 1;
   }
   std::vector<std::vector<uint8_t>> datas(inputs.size());
@@ -1367,10 +1401,16 @@ int main(int argc, char **argv) {
       die("-ilist: streams of different kinds (sampling rate, channels, channel configuration, SBR) in one batch");
   }
   const int n_ch = f0.n_ch, sbr = f0.sbr;
-  if (f0.channel_config && sbr) die("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported");
+  if (f0.channel_config && sbr) {
+    if (!mcsbr) die("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported");
+    if (hq) die("-mcsbr:1 with -esbr_hq:1 (the DFT transposer in a stream of more than two channels) is not supported");
+    if (!esbr) die("-mcsbr:1 with -esbr:0 (the fixed-point SBR tools in a stream of more than two channels) is not supported");
+    if (2 * f0.rate > 48000) die("-mcsbr:1 with a down-sampled bank (an output rate above 48 kHz) is not supported");
+  }
 
   if (!sbr) esbr = 0; /* AAC-LC streams decode the same either way */
-  const int out_ch = sbr ? 2 : n_ch; /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC as coded */
+  /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC, and everything with more than two channels, as coded */
+  const int out_ch = sbr && !f0.channel_config ? 2 : n_ch;
   const int N = ilist.empty() ? copies : (int)datas.size(), rate = f0.rate, out_rate = sbr ? 2 * rate : rate, per = sbr ? 2048 : 1024;
 
   /* the split: contiguous stream ranges over the devices, as bench.py --gpus N splits over ranks (a shard without streams is
@@ -1412,6 +1452,11 @@ int main(int argc, char **argv) {
     static const int k_first[4][4] = {{0, 1}, {0, 1, 3}, {0, 1, 3}, {0, 1, 3, 5}};
     J.n_els = J.channel_config == 3 ? 2 : (J.channel_config == 6 ? 4 : 3);
     for (int k = 0; k < 4; k++) J.first_ch[k] = k_first[J.channel_config - 3][k];
+  }
+  for (int c = 0; c < 8; c++) {
+    J.el_of_ch[c] = 0;
+    for (int k = 1; k < J.n_els; k++)
+      if (c >= J.first_ch[k]) J.el_of_ch[c] = k;
   }
   J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode, J.gputools = gputools;
   const auto t_run = std::chrono::steady_clock::now();
