@@ -368,6 +368,58 @@ typedef struct xaac_limiter_batch {
   uint64_t workspace_bytes;
 } xaac_limiter_batch;
 
+/* ---- the output stage behind the limiter / the SBR tools: downmix to stereo, mono mix, mono written twice --------------
+ * What the reference's -downmix:1, -dmix:1 and -tostereo:1 do to a frame's interleaved PCM16 block, as an epilogue of the
+ * calls that write that block (the channels of a sample sit in one lane there), so that only the mapped block exists:
+ *  XAAC_OUT_MAP_DOWNMIX_STEREO  3 .. 6 channels -> 2: ixheaacd_dec_downmix_to_stereo (decoder/ixheaacd_multichannel.c:364-422).  A
+ *      walk over the channel elements: an SCE (type 0) or LFE (3) at slot s adds (M[k][0][s] x[s]) >> 30 to the left and
+ *      (M[k][1][s] x[s]) >> 30 to the right sum, a CPE (1) at slots s, s + 1 adds (M[k][0][s] x[s]) >> 30 to the left and
+ *      (M[k][1][s + 1] x[s + 1]) >> 30 to the right; every term floors, the sums are WORD16.  M: down_mix_martix (Q30),
+ *      `matrix` = k: 0 the 5.0 matrix (the reference takes it for 3, 4 and 5 channels), 1 the 5.1 matrix (6 channels).
+ *  XAAC_OUT_MAP_MONO_MIX        2 -> 1: (l >> 1) + (r >> 1) (decoder/ixheaacd_api.c:3735-3757)
+ *  XAAC_OUT_MAP_MONO_MIX_DUP    2 -> 2: that word in both channels
+ *  XAAC_OUT_MAP_DUP_STEREO      1 -> 2: the mono word in both channels (api.c:3645-3661)
+ * The mapped pcm16 of a call equals xaac_out_map_apply_host (include/xaac_parse.h, the CPU twin) of the unmapped call's. */
+enum {
+  XAAC_OUT_MAP_NONE = 0,
+  XAAC_OUT_MAP_DOWNMIX_STEREO = 1,
+  XAAC_OUT_MAP_MONO_MIX = 2,
+  XAAC_OUT_MAP_MONO_MIX_DUP = 3,
+  XAAC_OUT_MAP_DUP_STEREO = 4
+};
+#define XAAC_OUT_MAP_MAX_ELEMENTS 4
+typedef struct xaac_out_map {
+  int32_t kind;                                    /* XAAC_OUT_MAP_* */
+  int32_t matrix;                                  /* DOWNMIX_STEREO: k (0 or 1) */
+  int32_t n_elements;                              /* DOWNMIX_STEREO: the channel elements of a frame, 1 .. 4 ... */
+  int32_t element_type[XAAC_OUT_MAP_MAX_ELEMENTS]; /* ... 0 SCE, 1 CPE, 3 LFE */
+  int32_t element_slot[XAAC_OUT_MAP_MAX_ELEMENTS]; /* ... and the element's (first) channel in the block; the elements cover every
+                                                      channel once */
+} xaac_out_map;
+
+/* xaac_limiter_batch plus the map: everything but pcm16 is as in xaac_peak_limiter_process_batch -- samples and the limiter
+ * states come out bit-equal to the unmapped call's -- and pcm16 is dense at the mapped channel count.
+ * More than two channels: 3 .. 6, planar or interleaved samples. */
+typedef struct xaac_limiter_map_batch {
+  xaac_limiter_batch lim;     /* lim.pcm16: [n_streams][frame_len][mapped channels], 4-byte aligned where that count is 2 */
+  xaac_out_map map;           /* not XAAC_OUT_MAP_NONE */
+} xaac_limiter_map_batch;
+
+/* The limiter-off hand-off (-peak_limiter_off:1: ixheaacd_scale_adjust, decoder/ixheaacd_peak_limiter.c:324-334, and the
+ * round16 loop of api.c:3676-3681) with the optional map: WORD32 samples and qshift_adj as xaac_imdct_process_batch leaves
+ * them -> interleaved PCM16.  Nothing is written back to `samples`. */
+typedef struct xaac_scale_adjust_map_batch {
+  int32_t n_streams;
+  int32_t frame_len;          /* samples per channel, 1 .. 1024 */
+  int32_t num_channels;       /* 1 .. 6 */
+  int32_t planar;             /* samples: 1 [n_streams][num_channels][frame_len], 0 [n_streams][frame_len][num_channels] */
+  const int32_t *samples;     /* stream s at s * stride */
+  int64_t stride;             /* >= frame_len * num_channels */
+  const int8_t *qshift_adj;   /* [n_streams][num_channels], each 0 .. 31 */
+  int16_t *pcm16;             /* [n_streams][frame_len][mapped channels], 4-byte aligned where that count is 2 */
+  xaac_out_map map;           /* XAAC_OUT_MAP_NONE: [n_streams][frame_len][num_channels] */
+} xaac_scale_adjust_map_batch;
+
 /* ---- eSBR ("Path A", the reference's default -esbr:1) QMF banks ---------------------------------------------------
  * xaac_esbr_qmf_analysis_batch  <-> ixheaacd_esbr_analysis_filt_block
  *      def decoder/ixheaacd_sbr_dec.c:185 (32 analysis channels: HE-AAC 2:1), call site sbr_dec.c:892
@@ -598,6 +650,9 @@ XAAC_API int32_t xaac_peak_limiter_init(xaac_limiter_state *state, uint32_t num_
 /* One frame of every stream through the limiter (device pointers, asynchronous). */
 XAAC_API uint64_t xaac_peak_limiter_workspace_bytes(int32_t n_streams);
 XAAC_API int32_t xaac_peak_limiter_process_batch(xaac_ctx *ctx, const xaac_limiter_batch *batch);
+/* ... with an output map on the PCM16 hand-off, and the limiter-off hand-off with one (device pointers, asynchronous). */
+XAAC_API int32_t xaac_peak_limiter_process_map_batch(xaac_ctx *ctx, const xaac_limiter_map_batch *batch);
+XAAC_API int32_t xaac_pcm16_scale_adjust_map_batch(xaac_ctx *ctx, const xaac_scale_adjust_map_batch *batch);
 
 /* Launch geometry the library used for the last batch (for reports). */
 XAAC_API int32_t xaac_last_launch(xaac_ctx *ctx, int32_t *grid, int32_t *block, int32_t *lds_bytes);

@@ -218,6 +218,14 @@ typedef struct xaac_mc_pcm_out_batch {
   int16_t *pcm;                    /* [n_streams][2048][n_ch] */
 } xaac_mc_pcm_out_batch;
 
+/* The same with an output map (include/xaac_amd.h: xaac_out_map, XAAC_OUT_MAP_DOWNMIX_STEREO): a sample's channels become its
+ * stereo pair on their way out, pcm is [n_streams][2048][2], 4-byte aligned.  What it writes equals xaac_out_map_apply_host of
+ * the unmapped call's block. */
+typedef struct xaac_mc_pcm_out_map_batch {
+  xaac_mc_pcm_out_batch out;
+  xaac_out_map map;
+} xaac_mc_pcm_out_map_batch;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -226,6 +234,8 @@ XAAC_API int32_t xaac_esbr_pcm16_from_float_batch(xaac_ctx *ctx, const xaac_esbr
 XAAC_API int32_t xaac_mc_core_from_out32_batch(xaac_ctx *ctx, const xaac_mc_core_in_batch *batch);
 XAAC_API int32_t xaac_mc_pcm16_from_float_batch(xaac_ctx *ctx, const xaac_mc_pcm_out_batch *batch);
 XAAC_API int32_t xaac_mc_pcm16_from_planes_batch(xaac_ctx *ctx, const xaac_mc_pcm_out_batch *batch); /* int16 planes */
+XAAC_API int32_t xaac_mc_pcm16_from_float_map_batch(xaac_ctx *ctx, const xaac_mc_pcm_out_map_batch *batch);
+XAAC_API int32_t xaac_mc_pcm16_from_planes_map_batch(xaac_ctx *ctx, const xaac_mc_pcm_out_map_batch *batch); /* int16 planes */
 /* One frame of every channel through the Path A branch of ixheaacd_sbr_dec (mono / stereo channels; with ps_* set:
  * HE-AACv2 streams, ixheaacd_esbr_apply_ps ps_dec_flt.c:389 between regrouping and the two synthesis banks):
  * history shift (sbr_dec.c:835-857), ixheaacd_esbr_analysis_filt_block, ixheaacd_generate_hf (sbrdec_lpfuncs.c:981),

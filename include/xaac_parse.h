@@ -300,6 +300,18 @@ XAAC_API void xaac_sbr_state_apply_side(xaac_sbr_state *s, const xaac_sbr_side *
 /* the same for the right channel's synthesis bank kept in the PS state (channel 1 of a mono + PS stream) */
 XAAC_API void xaac_ps_state_apply_side(xaac_ps_state *s, const xaac_sbr_side *side);
 
+/* ---- the output maps on the host (include/xaac_amd.h: xaac_out_map) -------------------------------------------------------
+ * The CPU twin of the mapped GPU calls, from the same arithmetic header (libxaac_amd/csrc/out_map.h): n_samples samples of
+ * num_channels interleaved PCM16 words -> the mapped block (XAAC_OUT_MAP_NONE copies).  in == out is allowed: no map writes a
+ * word it still has to read, except XAAC_OUT_MAP_DUP_STEREO, which is then done from the back.  Returns the mapped channel
+ * count, or -1 where the map does not take num_channels channels or its element list does not cover them. */
+XAAC_API int32_t xaac_out_map_apply_host(const xaac_out_map *map, int32_t num_channels, const int16_t *in, int64_t n_samples,
+                                         int16_t *out);
+/* What a downmix sum can reach: the largest sum of ceil(M / 2^15) over the rows of matrix k (0: 5.0, 1: 5.1), every term at its
+   extreme; *row_sum (optional) the largest plain sum of a row's Q30 coefficients.  Negative for another k or a coefficient
+   outside [0, 2^30). */
+XAAC_API int32_t xaac_out_map_row_bound(int32_t matrix, int64_t *row_sum);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,47 @@ class _McPcmOutBatch(ctypes.Structure):
                 ("planes", ctypes.c_void_p), ("pcm", ctypes.c_void_p)]
 
 
+OUT_MAP_NONE, OUT_MAP_DOWNMIX_STEREO, OUT_MAP_MONO_MIX, OUT_MAP_MONO_MIX_DUP, OUT_MAP_DUP_STEREO = 0, 1, 2, 3, 4   # XAAC_OUT_MAP_*
+
+
+class OutMap(ctypes.Structure):
+    # struct xaac_out_map (include/xaac_amd.h)
+    _fields_ = [("kind", ctypes.c_int32), ("matrix", ctypes.c_int32), ("n_elements", ctypes.c_int32),
+                ("element_type", ctypes.c_int32 * 4), ("element_slot", ctypes.c_int32 * 4)]
+
+
+# channel_config -> the frame's channel elements as (type: 0 SCE, 1 CPE, 3 LFE; slot in the output block), bitstream order
+_OUT_MAP_ELEMENTS = {3: ((0, 2), (1, 0)), 4: ((0, 2), (1, 0), (0, 3)), 5: ((0, 2), (1, 0), (1, 3)),
+                     6: ((0, 2), (1, 0), (1, 4), (3, 3))}
+_OUT_MAP_NAMES = {"downmix": OUT_MAP_DOWNMIX_STEREO, "mono": OUT_MAP_MONO_MIX, "mono_dup": OUT_MAP_MONO_MIX_DUP,
+                  "dup": OUT_MAP_DUP_STEREO}
+
+
+def out_map(kind, channel_config=0):
+    """the xaac_out_map of a kind ("downmix" | "mono" | "mono_dup" | "dup" or an OUT_MAP_* value); a downmix takes the element
+    list of ADTS channel_config 3 .. 6 and the matrix the reference picks for it (5.1 for six channels, else 5.0)"""
+    m = OutMap()
+    m.kind = _OUT_MAP_NAMES[kind] if isinstance(kind, str) else int(kind)
+    if m.kind == OUT_MAP_DOWNMIX_STEREO:
+        els = _OUT_MAP_ELEMENTS[int(channel_config)]
+        m.matrix, m.n_elements = int(channel_config == 6), len(els)
+        for k, (ty, slot) in enumerate(els):
+            m.element_type[k], m.element_slot[k] = ty, slot
+    return m
+
+
+def out_map_channels(m, num_channels):
+    """channels the map leaves of num_channels (0: it does not take that many)"""
+    return {OUT_MAP_NONE: num_channels, OUT_MAP_DOWNMIX_STEREO: 2 if 3 <= num_channels <= 6 else 0,
+            OUT_MAP_MONO_MIX: int(num_channels == 2), OUT_MAP_MONO_MIX_DUP: 2 * int(num_channels == 2),
+            OUT_MAP_DUP_STEREO: 2 * int(num_channels == 1)}.get(m.kind, 0)
+
+
+class _McPcmOutMapBatch(ctypes.Structure):
+    # struct xaac_mc_pcm_out_map_batch
+    _fields_ = [("out", _McPcmOutBatch), ("map", OutMap)]
+
+
 class _EsbrPcmOutBatch(ctypes.Structure):
     # struct xaac_esbr_pcm_out_batch
     _fields_ = [("n", ctypes.c_int32), ("stride", ctypes.c_int32), ("left", ctypes.c_void_p), ("right", ctypes.c_void_p),
@@ -267,6 +308,18 @@ class _LimiterBatch(ctypes.Structure):
                 ("status", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
+class _LimiterMapBatch(ctypes.Structure):
+    # struct xaac_limiter_map_batch
+    _fields_ = [("lim", _LimiterBatch), ("map", OutMap)]
+
+
+class _ScaleAdjustMapBatch(ctypes.Structure):
+    # struct xaac_scale_adjust_map_batch
+    _fields_ = [("n_streams", ctypes.c_int32), ("frame_len", ctypes.c_int32), ("num_channels", ctypes.c_int32),
+                ("planar", ctypes.c_int32), ("samples", ctypes.c_void_p), ("stride", ctypes.c_int64),
+                ("qshift_adj", ctypes.c_void_p), ("pcm16", ctypes.c_void_p), ("map", OutMap)]
+
+
 LIM_MAX_ATTACK, LIM_MAX_CH = 480, 8
 
 
@@ -390,6 +443,10 @@ def load_library():
     lib.xaac_peak_limiter_init.restype = ctypes.c_int32
     lib.xaac_peak_limiter_process_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_LimiterBatch)]
     lib.xaac_peak_limiter_process_batch.restype = ctypes.c_int32
+    lib.xaac_peak_limiter_process_map_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_LimiterMapBatch)]
+    lib.xaac_peak_limiter_process_map_batch.restype = ctypes.c_int32
+    lib.xaac_pcm16_scale_adjust_map_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ScaleAdjustMapBatch)]
+    lib.xaac_pcm16_scale_adjust_map_batch.restype = ctypes.c_int32
     lib.xaac_peak_limiter_workspace_bytes.argtypes = [ctypes.c_int32]
     lib.xaac_peak_limiter_workspace_bytes.restype = ctypes.c_uint64
     for f in ("xaac_create", "xaac_destroy", "xaac_sync", "xaac_set_stream", "xaac_imdct_process_batch",
@@ -696,21 +753,26 @@ class XaacContext:
         if rc != 0:
             raise XaacError(rc, "xaac_mc_core_from_out32_batch")
 
-    def mc_pcm16_from_planes(self, planes, pcm, slot, stride=2048):
+    def mc_pcm16_from_planes(self, planes, pcm, slot, stride=2048, out_map=None):
         """more than two channels: stream i's plane c (float32: clamped and truncated as ixheaacd_samples_sat_mc does; int16: as it
-        is) at element (i * n_ch + c) * stride of `planes` -> pcm int16[n * 2048 * n_ch], plane c as output channel slot[c]"""
+        is) at element (i * n_ch + c) * stride of `planes` -> pcm int16[n * 2048 * n_ch], plane c as output channel slot[c].
+        out_map (an OutMap of kind OUT_MAP_DOWNMIX_STEREO): the downmix to stereo on the way out, pcm int16[n * 2048 * 2]"""
         n_ch = len(slot)
-        b = _McPcmOutBatch()
-        b.n_streams, b.n_ch, b.stride = pcm.numel() // (2048 * n_ch), n_ch, int(stride)
+        mb = _McPcmOutMapBatch()
+        b = mb.out
+        b.n_streams, b.n_ch, b.stride = pcm.numel() // (2048 * (2 if out_map is not None else n_ch)), n_ch, int(stride)
         for c, to in enumerate(slot):
             b.slot[c] = int(to)
         flt = str(planes.dtype).endswith("float32")
         b.planes = _ptr(planes, "float32" if flt else "int16", device_ok=True)
         if planes.numel() < (b.n_streams * n_ch - 1) * b.stride + 2048:
             raise ValueError("planes are shorter than the batch")
-        b.pcm = _ptr(pcm, "int16", b.n_streams * 2048 * n_ch, device_ok=True)
+        b.pcm = _ptr(pcm, "int16", b.n_streams * 2048 * (2 if out_map is not None else n_ch), device_ok=True)
         fn = "xaac_mc_pcm16_from_float_batch" if flt else "xaac_mc_pcm16_from_planes_batch"
-        rc = getattr(self._lib, fn)(self._h, ctypes.byref(b))
+        if out_map is not None:
+            mb.map = out_map
+            fn = fn.replace("_batch", "_map_batch")
+        rc = getattr(self._lib, fn)(self._h, ctypes.byref(mb if out_map is not None else b))
         if rc != 0:
             raise XaacError(rc, fn)
 
@@ -1038,6 +1100,49 @@ class XaacContext:
 
     def peak_limiter_workspace_bytes(self, n_streams):
         return int(self._lib.xaac_peak_limiter_workspace_bytes(int(n_streams)))
+
+    def peak_limiter_process_map_batch(self, samples, qshift_adj, state, num_channels, workspace, pcm16, out_map, frame_len=1024,
+                                       stride=None, status=None, planar=False):
+        """peak_limiter_process_batch with an output map (an OutMap: out_map()) on the PCM16 hand-off: pcm16
+        int16[n_streams * frame_len * mapped channels]; samples and state come out as from the unmapped call."""
+        n = state.shape[0]
+        if stride is None:
+            stride = frame_len * num_channels
+        mb = _LimiterMapBatch()
+        b = mb.lim
+        b.n_streams, b.frame_len, b.num_channels, b.stride = n, int(frame_len), int(num_channels), int(stride)
+        b.planar = int(bool(planar))
+        b.samples = _ptr(samples, "int32", n * stride, device_ok=True)
+        b.qshift_adj = _ptr(qshift_adj, "int8", n * num_channels, device_ok=True)
+        b.state = _ptr(state, "uint8", n * LIMITER_STATE_BYTES, device_ok=True)
+        b.pcm16 = _ptr(pcm16, "int16", n * frame_len * max(1, out_map_channels(out_map, num_channels)), device_ok=True)
+        b.status = _ptr(status, "int32", n, allow_none=True, device_ok=True)
+        b.workspace = _ptr(workspace, "uint8", device_ok=True)
+        b.workspace_bytes = workspace.numel()
+        mb.map = out_map
+        rc = self._lib.xaac_peak_limiter_process_map_batch(self._h, ctypes.byref(mb))
+        if rc != 0:
+            raise XaacError(rc, "xaac_peak_limiter_process_map_batch")
+
+    def pcm16_scale_adjust_map_batch(self, samples, qshift_adj, num_channels, pcm16, out_map=None, frame_len=1024, stride=None,
+                                     planar=False):
+        """The limiter-off hand-off (ixheaacd_scale_adjust + round16) with an optional output map: samples
+        int32[n_streams * stride] (planar or interleaved), qshift_adj int8[n_streams * num_channels] -> pcm16
+        int16[n_streams * frame_len * mapped channels]."""
+        n = qshift_adj.numel() // num_channels
+        if stride is None:
+            stride = frame_len * num_channels
+        b = _ScaleAdjustMapBatch()
+        b.n_streams, b.frame_len, b.num_channels, b.stride = n, int(frame_len), int(num_channels), int(stride)
+        b.planar = int(bool(planar))
+        if out_map is not None:
+            b.map = out_map
+        b.samples = _ptr(samples, "int32", n * stride, device_ok=True)
+        b.qshift_adj = _ptr(qshift_adj, "int8", n * num_channels, device_ok=True)
+        b.pcm16 = _ptr(pcm16, "int16", n * frame_len * max(1, out_map_channels(b.map, num_channels)), device_ok=True)
+        rc = self._lib.xaac_pcm16_scale_adjust_map_batch(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, "xaac_pcm16_scale_adjust_map_batch")
 
     def peak_limiter_process_batch(self, samples, qshift_adj, state, num_channels, workspace, frame_len=1024,
                                    pcm16=None, stride=None, status=None, planar=False):

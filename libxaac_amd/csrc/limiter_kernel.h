@@ -19,12 +19,15 @@ typedef struct XaacLimiterParams {
   float *ws_gain;   /* [n_streams][1024]: target gains -> gains of the streams the recursion runs on */
   int32_t *ws_flag; /* [n_streams][2]: finished by the front kernel?, first sample of the recursion */
   long long *dbg; /* phase timers (profiling builds) */
+  int32_t map_kind;        /* xaac_launch_limiter_map: XAAC_OUT_MAP_* on the PCM16 hand-off, pcm16 dense at the mapped channel count */
+  int32_t map_coef[2][6];  /* ... DOWNMIX_STEREO: left / right Q30 coefficient of every slot (out_map.h: xo_resolve) */
 } XaacLimiterParams;
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 hipError_t xaac_launch_limiter(const XaacLimiterParams *p, hipStream_t stream);
+hipError_t xaac_launch_limiter_map(const XaacLimiterParams *p, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@
  *      samples, the frame's own input after that) x gain -> clamp -> WORD32 (in place) / PCM16; the frame's last
  *      attack_time_samples inputs become the new delay line.  All global reads of a pass happen before its
  *      writes, so the block is processed in place like the reference does.
+ *      MAP != 0 (xaac_peak_limiter_process_map_batch): the instantiations that hold every channel of a sample in one lane
+ *      (1, 2, 3 .. 6 channels) put the sample's PCM16 words through an output map of out_map.h on their way out -- downmix to
+ *      stereo, mono mix, mono twice -- so only the mapped block is stored; nothing else of the frame changes.
  * A state whose max_idx does not point at its window's maximum (it cannot come from init + process, but the
  * reference would still run on it), and windows shorter than a chunk (rates below 12.8 kHz), take the plain
  * per-sample walk in step 2-3, which is the reference's loop verbatim on W.
@@ -37,6 +40,7 @@
 
 #include "limiter.h"
 #include "limiter_kernel.h"
+#include "out_map.h"
 
 namespace {
 
@@ -153,15 +157,34 @@ __device__ __forceinline__ void st_block(int32_t *x, int i, int j, int C, int L,
   }
 }
 
+/* the PCM16 words of one sample (all N channels) through output map MAP; `at`: stream * frame_len + sample */
+template <int N, int MAP>
+__device__ __forceinline__ void st_map(const XaacLimiterParams &p, int64_t at, const int16_t (&v)[N]) {
+  if constexpr (MAP == XAAC_OUT_MAP_DOWNMIX_STEREO) {
+    int32_t cl[N], cr[N];
+#pragma unroll
+    for (int c = 0; c < N; c++) cl[c] = p.map_coef[0][c], cr[c] = p.map_coef[1][c];
+    int16_t o[2];
+    xo_downmix<N>(cl, cr, v, o[0], o[1]);
+    st_<2>(p.pcm16 + at * 2, o);
+  } else if constexpr (MAP == XAAC_OUT_MAP_MONO_MIX) {
+    p.pcm16[at] = xo_mono_mix(v[0], v[N - 1]);
+  } else {
+    const int16_t m = MAP == XAAC_OUT_MAP_MONO_MIX_DUP ? xo_mono_mix(v[0], v[N - 1]) : v[0];
+    const int16_t o[2] = {m, m};
+    st_<2>(p.pcm16 + at * 2, o);
+  }
+}
+
 /* ---- step 6: gains from `gain_of(i)` applied to the delayed samples of stream s ---- */
-template <int CT, typename GainOf>
+template <int CT, int MAP, typename GainOf>
 __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, int lane, bool active, GainOf gain_of) {
   xaac_limiter_state *st = p.state + s;
   int32_t *x = p.samples + (int64_t)s * p.stride;
   const int8_t *qs = p.qshift_adj + (int64_t)s * p.num_channels;
   const int C = CT ? CT : p.num_channels, L = p.frame_len;
   const int A = (int)st->attack_time_samples, dii0 = (int)st->delayed_input_index;
-  const bool planar = CT > 2 || p.planar != 0; /* (3 .. 6: launched for planar blocks only) */
+  const bool planar = (CT > 2 && MAP == 0) || p.planar != 0; /* (3 .. 6 without a map: launched for planar blocks only) */
   /* channels a lane holds of its samples: both of a pair; all of 3 .. 6 (the planar loads of a pass are then in flight together and a
      sample's PCM16 words leave as one run); one at a time where the count is only known at run time.
      K: samples per lane and pass.  With every channel in registers a pass of 8 would hold 8 N words each of `now` and `before` beside
@@ -218,7 +241,11 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
           }
           if (active) min_gain = gain[k] < min_gain ? gain[k] : min_gain;
           st_block<N>(x, i, j, C, L, planar, v);
-          if (p.pcm16) st_<N>(p.pcm16 + ((int64_t)s * L + i) * C + j, v16);
+          if constexpr (MAP == 0) {
+            if (p.pcm16) st_<N>(p.pcm16 + ((int64_t)s * L + i) * C + j, v16);
+          } else if (p.pcm16) {
+            st_map<N, MAP>(p, (int64_t)s * L + i, v16); /* (N = C: one trip of the channel loop) */
+          }
           if (i >= L - A) { /* one of the frame's last attack_time_samples inputs: stays in the delay line */
             int pos = end_pos - (L - i);
             pos = pos < 0 ? pos + A : pos;
@@ -242,8 +269,8 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
 }  // namespace
 
 /* CT: channel count known at compile time (1, 2, and 3 .. 6 -- the multichannel configurations: the loads of a phase are then
-   all in flight together), 0: any */
-template <int CT>
+   all in flight together), 0: any.  MAP: the output map on the PCM16 hand-off (CT != 0), 0: none */
+template <int CT, int MAP = 0>
 __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParams p) {
   __shared__ float s_w[kMaxW]; /* W: the state's window in time order, then the frame's magnitudes */
   __shared__ float s_g[kMaxW]; /* run suffix maxima, then window maxima; the walk's target gains */
@@ -269,7 +296,7 @@ __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParam
   const bool active = xl_active(st->limiter_on, psg0);
   if (!active) { /* peak_limiter.c:288-300: a plain delay */
     if (lane == 0) p.ws_flag[2 * s] = 1;
-    apply_frame<CT>(p, s, lane, false, [](int) { return 1.0f; });
+    apply_frame<CT, MAP>(p, s, lane, false, [](int) { return 1.0f; });
     return;
   }
 
@@ -281,7 +308,7 @@ __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParam
     const int i = lane + 64 * k;
     float tmp = 0.0f;
     if (i < L) {
-      if (CT > 2) { /* (planar: the launcher's condition) every channel's load in flight before the first magnitude */
+      if (CT > 2 && (MAP == 0 || p.planar)) { /* (planar: the launcher's condition without a map) every channel's load in flight before the first magnitude */
         int32_t v[CT > 2 ? CT : 1];
 #pragma unroll
         for (int j = 0; j < CT; j++) v[j] = x[j * L + i];
@@ -462,7 +489,7 @@ __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParam
       p.ws_flag[2 * s] = 1;
       if (L > 0) st->gain_modified = 1.0f;
     }
-    apply_frame<CT>(p, s, lane, true, [](int) { return 1.0f; });
+    apply_frame<CT, MAP>(p, s, lane, true, [](int) { return 1.0f; });
     XL_T(5);
     return;
   }
@@ -535,12 +562,41 @@ __global__ __launch_bounds__(64) void xaac_limiter_gain_kernel(XaacLimiterParams
   }
 }
 
-template <int CT>
+template <int CT, int MAP = 0>
 __global__ __launch_bounds__(64) void xaac_limiter_apply_kernel(XaacLimiterParams p) {
   const int lane = threadIdx.x, s = blockIdx.x;
   if (p.ws_flag[2 * s] != 0) return; /* finished by the front kernel */
   const float *row = p.ws_gain + (int64_t)s * 1024;
-  apply_frame<CT>(p, s, lane, true, [row](int i) { return row[i]; });
+  apply_frame<CT, MAP>(p, s, lane, true, [row](int i) { return row[i]; });
+}
+
+namespace {
+template <int CT, int MAP>
+hipError_t launch_mapped(const XaacLimiterParams *p, hipStream_t stream) {
+  const dim3 grid(p->n_streams), block(64);
+  hipLaunchKernelGGL((xaac_limiter_front_kernel<CT, MAP>), grid, block, 0, stream, *p);
+  hipLaunchKernelGGL(xaac_limiter_gain_kernel, dim3((p->n_streams + 63) / 64), block, 0, stream, *p);
+  hipLaunchKernelGGL((xaac_limiter_apply_kernel<CT, MAP>), grid, block, 0, stream, *p);
+  return hipGetLastError();
+}
+}  // namespace
+
+/* the limiter with an output map on its PCM16 hand-off: the map's channel count is the batch's (xaac_abi.cpp checks) */
+extern "C" hipError_t xaac_launch_limiter_map(const XaacLimiterParams *p, hipStream_t stream) {
+  switch (p->map_kind) {
+    case XAAC_OUT_MAP_DOWNMIX_STEREO:
+      switch (p->num_channels) {
+        case 3: return launch_mapped<3, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
+        case 4: return launch_mapped<4, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
+        case 5: return launch_mapped<5, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
+        case 6: return launch_mapped<6, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
+      }
+      break;
+    case XAAC_OUT_MAP_MONO_MIX: if (p->num_channels == 2) return launch_mapped<2, XAAC_OUT_MAP_MONO_MIX>(p, stream); break;
+    case XAAC_OUT_MAP_MONO_MIX_DUP: if (p->num_channels == 2) return launch_mapped<2, XAAC_OUT_MAP_MONO_MIX_DUP>(p, stream); break;
+    case XAAC_OUT_MAP_DUP_STEREO: if (p->num_channels == 1) return launch_mapped<1, XAAC_OUT_MAP_DUP_STEREO>(p, stream); break;
+  }
+  return hipErrorInvalidValue; /* a missing kernel is an error */
 }
 
 extern "C" hipError_t xaac_launch_limiter(const XaacLimiterParams *p, hipStream_t stream) {

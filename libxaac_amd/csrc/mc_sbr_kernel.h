@@ -15,6 +15,11 @@ typedef struct XaacMcPcmOutParams {
   int16_t *pcm;                     /* [n_streams][2048][n_ch] */
 } XaacMcPcmOutParams;
 
+typedef struct XaacMcMapCoef {
+  int32_t src[XAAC_MC_MAX_CH];      /* plane of output channel o */
+  int32_t coef[2][XAAC_MC_MAX_CH];  /* left / right Q30 downmix coefficient of output channel o */
+} XaacMcMapCoef;
+
 typedef struct XaacMcCoreInParams {
   int32_t n_streams, n_ch;
   int32_t q_src[XAAC_MC_MAX_CH];    /* channel of the stream whose qshift_adj channel c is converted with */
@@ -29,6 +34,9 @@ extern "C" {
 #endif
 hipError_t xaac_launch_mc_pcm16_from_float(const XaacMcPcmOutParams *p, hipStream_t stream);
 hipError_t xaac_launch_mc_pcm16_from_planes(const XaacMcPcmOutParams *p, hipStream_t stream);
+/* the downmix to stereo on the way out: pcm is [n_streams][2048][2]; coef[side][output channel] from xo_resolve (out_map.h) */
+hipError_t xaac_launch_mc_pcm16_from_float_map(const XaacMcPcmOutParams *p, const int32_t (*coef)[6], hipStream_t stream);
+hipError_t xaac_launch_mc_pcm16_from_planes_map(const XaacMcPcmOutParams *p, const int32_t (*coef)[6], hipStream_t stream);
 hipError_t xaac_launch_mc_core_from_out32(const XaacMcCoreInParams *p, hipStream_t stream);
 hipError_t xaac_warm_mc_sbr(void);
 #ifdef __cplusplus

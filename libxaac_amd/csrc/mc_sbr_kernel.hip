@@ -7,6 +7,7 @@
  *                                    through the 16-bit conversion ixheaacd_allocate_sbr_scr makes IN PLACE in that block
  *   xaac_mc_pcm_out_kernel           the planes the SBR calls leave (float: ixheaacd_samples_sat_mc; PCM16: the low-power
  *                                    synthesis bank's) -> the [stream][2048][channel] PCM16 block in output channel order
+ *   xaac_mc_pcm_out_map_kernel       ... -> the [stream][2048][2] block of the downmix to stereo (out_map.h)
  *
  * Vector stores only.
  */
@@ -15,6 +16,7 @@
 
 #include "fx.h"
 #include "mc_sbr_kernel.h"
+#include "out_map.h"
 
 namespace {
 
@@ -63,6 +65,31 @@ __global__ __launch_bounds__(256) void xaac_mc_pcm_out_kernel(XaacMcPcmOutParams
   for (int d = 0; d < NCH; d++) dst[d] = (uint32_t)(uint16_t)w[2 * d] | ((uint32_t)(uint16_t)w[2 * d + 1] << 16);
 }
 
+/* The same with the downmix to stereo (out_map.h) on the way out: the lane's 2 * NCH words become two stereo pairs, and only
+   [stream][2048][2] is stored.  cl / cr: the left / right Q30 coefficient of every output channel. */
+template <int NCH, class T>
+__global__ __launch_bounds__(256) void xaac_mc_pcm_out_map_kernel(XaacMcPcmOutParams p, XaacMcMapCoef m) {
+  typedef typename Pair<T>::type T2;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; /* (stream, sample pair) */
+  if (e >= (size_t)p.n_streams * 1024) return;
+  const size_t i = e >> 10;
+  const int k = (int)(e & 1023) * 2;
+  const T *planes = static_cast<const T *>(p.planes);
+  T2 v[NCH];
+#pragma unroll
+  for (int o = 0; o < NCH; o++) v[o] = *reinterpret_cast<const T2 *>(planes + (i * NCH + (size_t)m.src[o]) * (size_t)p.stride + k);
+  int16_t a[NCH], b[NCH];
+  int32_t cl[NCH], cr[NCH];
+#pragma unroll
+  for (int o = 0; o < NCH; o++) a[o] = mc_sat(v[o].x), b[o] = mc_sat(v[o].y), cl[o] = m.coef[0][o], cr[o] = m.coef[1][o];
+  int16_t l0, r0, l1, r1;
+  xo_downmix<NCH>(cl, cr, a, l0, r0);
+  xo_downmix<NCH>(cl, cr, b, l1, r1);
+  uint32_t *dst = reinterpret_cast<uint32_t *>(p.pcm) + (i * 2048 + (size_t)k);
+  dst[0] = (uint32_t)(uint16_t)l0 | ((uint32_t)(uint16_t)r0 << 16);
+  dst[1] = (uint32_t)(uint16_t)l1 | ((uint32_t)(uint16_t)r1 << 16);
+}
+
 /* ixheaacd_allocate_sbr_scr (api.c:351-359) for an element of a block of more than two channels, then api.c:3414-3434.  The
    element's channel j is converted with qshift_adj[j] of the FRAME (the j-th channel the frame decoded, whichever element it
    belongs to), and the conversion runs in place, channel after channel: the WORD16 results of a pair's first channel land in
@@ -102,6 +129,31 @@ hipError_t launch_out(const XaacMcPcmOutParams *p, hipStream_t stream) {
 
 extern "C" hipError_t xaac_launch_mc_pcm16_from_float(const XaacMcPcmOutParams *p, hipStream_t stream) { return launch_out<float>(p, stream); }
 extern "C" hipError_t xaac_launch_mc_pcm16_from_planes(const XaacMcPcmOutParams *p, hipStream_t stream) { return launch_out<int16_t>(p, stream); }
+
+namespace {
+template <class T>
+hipError_t launch_out_map(const XaacMcPcmOutParams *p, const int32_t (*coef)[6], hipStream_t stream) {
+  XaacMcMapCoef m;
+  for (int c = 0; c < 6; c++) m.src[c] = 0, m.coef[0][c] = coef[0][c], m.coef[1][c] = coef[1][c];
+  for (int c = 0; c < p->n_ch; c++) m.src[p->slot[c]] = c;
+  const dim3 grid((unsigned)(((size_t)p->n_streams * 1024 + 255) / 256)), block(256);
+  switch (p->n_ch) {
+    case 3: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<3, T>), grid, block, 0, stream, *p, m); break;
+    case 4: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<4, T>), grid, block, 0, stream, *p, m); break;
+    case 5: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<5, T>), grid, block, 0, stream, *p, m); break;
+    case 6: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<6, T>), grid, block, 0, stream, *p, m); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" hipError_t xaac_launch_mc_pcm16_from_float_map(const XaacMcPcmOutParams *p, const int32_t (*coef)[6], hipStream_t stream) {
+  return launch_out_map<float>(p, coef, stream);
+}
+extern "C" hipError_t xaac_launch_mc_pcm16_from_planes_map(const XaacMcPcmOutParams *p, const int32_t (*coef)[6], hipStream_t stream) {
+  return launch_out_map<int16_t>(p, coef, stream);
+}
 
 extern "C" hipError_t xaac_launch_mc_core_from_out32(const XaacMcCoreInParams *p, hipStream_t stream) {
   hipLaunchKernelGGL(xaac_mc_core_from_out32_kernel, dim3((unsigned)((size_t)p->n_streams * p->n_ch * 4)), dim3(256), 0, stream, *p);

@@ -28,6 +28,8 @@
 #include "pvc_kernel.h"
 #include "aac_tools_kernel.h"
 #include "mc_sbr_kernel.h"
+#include "out_map.h"
+#include "out_map_kernel.h"
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -133,6 +135,7 @@ extern "C" {
 hipError_t xaac_warm_imdct(void), xaac_warm_sbr_qmf(void), xaac_warm_sbr_core(void), xaac_warm_sbr_ps(void), xaac_warm_limiter(void),
     xaac_warm_esbr_qmf(void), xaac_warm_esbr_core(void), xaac_warm_esbr_ps(void), xaac_warm_hbe(void), xaac_warm_usac_imdct(void),
     xaac_warm_imdct960(void), xaac_warm_imdct_ld(void), xaac_warm_pvc(void), xaac_warm_sbr_ld_core(void), xaac_warm_aac_tools(void), xaac_warm_mc_sbr(void);
+/* (xaac_warm_out_map: out_map_kernel.h) */
 }
 
 int32_t xaac_warm_up(xaac_ctx *c) {
@@ -141,7 +144,7 @@ int32_t xaac_warm_up(xaac_ctx *c) {
   hipError_t (*const hooks[])(void) = {xaac_warm_imdct,     xaac_warm_sbr_qmf,   xaac_warm_sbr_core, xaac_warm_sbr_ps,     xaac_warm_limiter,
                                        xaac_warm_esbr_qmf,  xaac_warm_esbr_core, xaac_warm_esbr_ps,  xaac_warm_hbe,        xaac_warm_usac_imdct,
                                        xaac_warm_imdct960,  xaac_warm_imdct_ld,  xaac_warm_pvc,      xaac_warm_sbr_ld_core,
-                                       xaac_warm_aac_tools, xaac_warm_mc_sbr};
+                                       xaac_warm_aac_tools, xaac_warm_mc_sbr,    xaac_warm_out_map};
   for (auto h : hooks)
     if (!hip_ok(h())) return XAAC_FATAL_HIP;
   return XAAC_OK;
@@ -506,7 +509,8 @@ int32_t xaac_mc_core_from_out32_batch(xaac_ctx *c, const xaac_mc_core_in_batch *
   return XAAC_OK;
 }
 
-static int32_t mc_pcm_out(xaac_ctx *c, const xaac_mc_pcm_out_batch *b, bool flt) {
+static int32_t out_map_check(const xaac_out_map *m, int num_channels, const int16_t *pcm16, int32_t coef[2][6]); /* (below, with the limiter) */
+static int32_t mc_pcm_out(xaac_ctx *c, const xaac_mc_pcm_out_batch *b, bool flt, const xaac_out_map *map = nullptr) {
   if (!c || !b) return XAAC_FATAL_NULL_ARG;
   if (b->n_streams < 0 || b->n_ch < 3 || b->n_ch > XAAC_MC_MAX_CH || b->stride < 2048 || (b->stride & 1)) return XAAC_FATAL_BAD_ARG;
   uint32_t seen = 0;
@@ -522,9 +526,24 @@ static int32_t mc_pcm_out(xaac_ctx *c, const xaac_mc_pcm_out_batch *b, bool flt)
   memset(&p, 0, sizeof(p));
   p.n_streams = b->n_streams, p.n_ch = b->n_ch, p.stride = b->stride, p.planes = b->planes, p.pcm = b->pcm;
   for (int k = 0; k < b->n_ch; k++) p.slot[k] = b->slot[k];
+  int32_t coef[2][6];
+  if (map) { /* the downmix to stereo on the way out */
+    if (map->kind != XAAC_OUT_MAP_DOWNMIX_STEREO) return XAAC_FATAL_BAD_ARG;
+    const int32_t rc = out_map_check(map, b->n_ch, b->pcm, coef);
+    if (rc != XAAC_OK) return rc;
+  }
   if (!hip_ok(hipSetDevice(c->device))) return XAAC_FATAL_HIP;
-  if (!hip_ok(flt ? xaac_launch_mc_pcm16_from_float(&p, c->stream) : xaac_launch_mc_pcm16_from_planes(&p, c->stream))) return XAAC_FATAL_HIP;
+  hipError_t e;
+  if (map) e = flt ? xaac_launch_mc_pcm16_from_float_map(&p, coef, c->stream) : xaac_launch_mc_pcm16_from_planes_map(&p, coef, c->stream);
+  else e = flt ? xaac_launch_mc_pcm16_from_float(&p, c->stream) : xaac_launch_mc_pcm16_from_planes(&p, c->stream);
+  if (!hip_ok(e)) return XAAC_FATAL_HIP;
   return XAAC_OK;
+}
+int32_t xaac_mc_pcm16_from_float_map_batch(xaac_ctx *c, const xaac_mc_pcm_out_map_batch *b) {
+  return b ? mc_pcm_out(c, &b->out, true, &b->map) : XAAC_FATAL_NULL_ARG;
+}
+int32_t xaac_mc_pcm16_from_planes_map_batch(xaac_ctx *c, const xaac_mc_pcm_out_map_batch *b) {
+  return b ? mc_pcm_out(c, &b->out, false, &b->map) : XAAC_FATAL_NULL_ARG;
 }
 int32_t xaac_mc_pcm16_from_float_batch(xaac_ctx *c, const xaac_mc_pcm_out_batch *b) { return mc_pcm_out(c, b, true); }
 int32_t xaac_mc_pcm16_from_planes_batch(xaac_ctx *c, const xaac_mc_pcm_out_batch *b) { return mc_pcm_out(c, b, false); }
@@ -941,7 +960,20 @@ uint64_t xaac_peak_limiter_workspace_bytes(int32_t n_streams) {
   return (uint64_t)n_streams * (1024 * sizeof(float) + 2 * sizeof(int32_t)) + 256;
 }
 
-int32_t xaac_peak_limiter_process_batch(xaac_ctx *c, const xaac_limiter_batch *b) {
+/* the map of a mapped call: its kind takes num_channels channels, a downmix's element list covers them (-> coef, per slot), and
+   a two-channel pcm16 is stored as 32-bit words */
+static int32_t out_map_check(const xaac_out_map *m, int num_channels, const int16_t *pcm16, int32_t coef[2][6]) {
+  const int oc = xo_out_channels(m->kind, num_channels);
+  if (!oc || num_channels > 6) return XAAC_FATAL_BAD_ARG;
+  int32_t full[2][8];
+  for (int s = 0; s < 8; s++) full[0][s] = full[1][s] = 0;
+  if (m->kind == XAAC_OUT_MAP_DOWNMIX_STEREO && xo_resolve(m, num_channels, full)) return XAAC_FATAL_BAD_ARG;
+  for (int s = 0; s < 6; s++) coef[0][s] = full[0][s], coef[1][s] = full[1][s];
+  if (oc == 2 && ((uintptr_t)pcm16 & 3u)) return XAAC_FATAL_BAD_ARG;
+  return XAAC_OK;
+}
+
+static int32_t limiter_run(xaac_ctx *c, const xaac_limiter_batch *b, const xaac_out_map *map) {
   if (!c || !b) return XAAC_FATAL_NULL_ARG;
   if (b->n_streams < 0 || b->frame_len < 1 || b->frame_len > 1024) return XAAC_FATAL_BAD_ARG;
   if (b->num_channels < 1 || b->num_channels > XAAC_LIM_MAX_CH) return XAAC_FATAL_BAD_ARG;
@@ -958,8 +990,49 @@ int32_t xaac_peak_limiter_process_batch(xaac_ctx *c, const xaac_limiter_batch *b
   p.samples = b->samples; p.stride = b->stride; p.qshift_adj = b->qshift_adj; p.state = b->state;
   p.pcm16 = b->pcm16; p.status = b->status;
   p.dbg = reinterpret_cast<long long *>(XAAC_DBG_BUF(b->status, b->n_streams)); /* phase timers of -DXL_PROFILE builds */
-  if (!hip_ok(xaac_launch_limiter(&p, c->stream))) return XAAC_FATAL_HIP;
+  if (map) {
+    if (!b->pcm16) return XAAC_FATAL_NULL_ARG;
+    p.map_kind = map->kind;
+    if (map->kind == XAAC_OUT_MAP_NONE) return XAAC_FATAL_BAD_ARG;
+    const int32_t rc = out_map_check(map, b->num_channels, b->pcm16, p.map_coef);
+    if (rc != XAAC_OK) return rc;
+    if (!hip_ok(xaac_launch_limiter_map(&p, c->stream))) return XAAC_FATAL_HIP;
+  } else if (!hip_ok(xaac_launch_limiter(&p, c->stream))) {
+    return XAAC_FATAL_HIP;
+  }
   c->last_grid = b->n_streams; c->last_block = 64; c->last_lds = 2 * (XAAC_LIM_MAX_ATTACK + 1024) * 4 + 256;
+  return XAAC_OK;
+}
+
+int32_t xaac_peak_limiter_process_batch(xaac_ctx *c, const xaac_limiter_batch *b) { return limiter_run(c, b, nullptr); }
+
+int32_t xaac_peak_limiter_process_map_batch(xaac_ctx *c, const xaac_limiter_map_batch *b) {
+  if (!c || !b) return XAAC_FATAL_NULL_ARG;
+  return limiter_run(c, &b->lim, &b->map);
+}
+
+/* ixheaacd_scale_adjust + round16 (+ the map): the limiter-off hand-off */
+int32_t xaac_pcm16_scale_adjust_map_batch(xaac_ctx *c, const xaac_scale_adjust_map_batch *b) {
+  if (!c || !b) return XAAC_FATAL_NULL_ARG;
+  if (b->n_streams < 0 || b->frame_len < 1 || b->frame_len > 1024) return XAAC_FATAL_BAD_ARG;
+  if (b->num_channels < 1 || b->num_channels > 6) return XAAC_FATAL_BAD_ARG;
+  if (b->stride < (int64_t)b->frame_len * b->num_channels) return XAAC_FATAL_BAD_ARG;
+  XaacScaleAdjustParams p = {};
+  const int oc = xo_out_channels(b->map.kind, b->num_channels);
+  if (!oc) return XAAC_FATAL_BAD_ARG;
+  if (b->n_streams == 0) return XAAC_OK;
+  if (!b->samples || !b->qshift_adj || !b->pcm16) return XAAC_FATAL_NULL_ARG;
+  if (b->map.kind == XAAC_OUT_MAP_NONE) {
+    if ((b->num_channels & 1) == 0 && ((uintptr_t)b->pcm16 & 3u)) return XAAC_FATAL_BAD_ARG;
+  } else {
+    const int32_t rc = out_map_check(&b->map, b->num_channels, b->pcm16, p.map_coef);
+    if (rc != XAAC_OK) return rc;
+  }
+  p.n_streams = b->n_streams; p.frame_len = b->frame_len; p.num_channels = b->num_channels; p.planar = b->planar ? 1 : 0;
+  p.samples = b->samples; p.stride = b->stride; p.qshift_adj = b->qshift_adj; p.pcm16 = b->pcm16; p.map_kind = b->map.kind;
+  if (!hip_ok(hipSetDevice(c->device))) return XAAC_FATAL_HIP;
+  if (!hip_ok(xaac_launch_scale_adjust_map(&p, c->stream))) return XAAC_FATAL_HIP;
+  c->last_grid = (int32_t)(((int64_t)b->n_streams * b->frame_len + 255) / 256); c->last_block = 256; c->last_lds = 0;
   return XAAC_OK;
 }
 

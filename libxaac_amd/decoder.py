@@ -18,7 +18,8 @@ import numpy as np
 
 from . import (ESBR_PS_STATE_BYTES, ESBR_SIDE_BYTES, ESBR_STATE_BYTES, HANDOVER_PS_START, HBE_STATE_BYTES, LIMITER_STATE_BYTES,
                PCM_LC, PCM_SBR, PS_FRAME_BYTES, PS_STATE_BYTES, SBR_FRAME_BYTES, SBR_HEADER_BYTES, SBR_STATE_BYTES, LimiterState,
-               XaacContext, peak_limiter_init)
+               XaacContext, out_map_channels, peak_limiter_init)
+from . import out_map as make_out_map
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _host = None
@@ -120,8 +121,32 @@ def load_host_library():
         lib.xaac_sbr_state_apply_side.restype = None
         lib.xaac_ps_state_apply_side.argtypes = [ctypes.c_void_p, ctypes.POINTER(SbrSide)]
         lib.xaac_ps_state_apply_side.restype = None
+        lib.xaac_out_map_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        lib.xaac_out_map_apply_host.restype = ctypes.c_int32
+        lib.xaac_out_map_row_bound.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
+        lib.xaac_out_map_row_bound.restype = ctypes.c_int32
         _host = lib
     return _host
+
+
+def out_map_apply_host(m, pcm):
+    """xaac_out_map_apply_host, the CPU twin of the mapped GPU calls: pcm int16[samples, channels] through the OutMap m (None:
+    as it is) -> int16[samples, mapped channels]"""
+    pcm = np.ascontiguousarray(pcm, np.int16)
+    if m is None:
+        return pcm.copy()
+    samples, n_ch = pcm.shape
+    out = np.zeros((samples, max(1, n_ch, 2)), np.int16)
+    oc = load_host_library().xaac_out_map_apply_host(ctypes.byref(m), n_ch, pcm.ctypes.data, samples, out.ctypes.data)
+    if oc <= 0:
+        raise ValueError("the output map does not take %d channels" % n_ch)
+    return out.reshape(-1)[:samples * oc].reshape(samples, oc).copy()
+
+
+def out_map_row_bound(matrix):
+    """xaac_out_map_row_bound -> (what a downmix sum of matrix k can reach, the largest plain sum of a row)"""
+    row_sum = ctypes.c_int64(0)
+    return int(load_host_library().xaac_out_map_row_bound(int(matrix), ctypes.byref(row_sum))), int(row_sum.value)
 
 
 class ParseError(RuntimeError):
@@ -638,8 +663,9 @@ class _Chain:
     host_arrays = ()
     status2 = status_h2 = None
 
-    def __init__(self, ctx, lib, dev, n, n_ch, rate, alloc, trace=None):
+    def __init__(self, ctx, lib, dev, n, n_ch, rate, alloc, trace=None, out_map=None, limiter=True):
         self.ctx, self.lib, self.dev, self.dz, self.trace = ctx, lib, dev, alloc.dz, trace
+        self.out_map, self.limiter = out_map, limiter   # what the PCM hand-off does to a sample's channels (an OutMap); AAC-LC: limiter on
         self.n, self.n_ch, self.nc, self.rate = n, n_ch, n * n_ch, rate
         self.ovl, self.ovl_state = alloc.dz(self.nc, 512, dtype=torch.int32), alloc.dz(self.nc, 2)   # the IMDCT's overlap halves, window state
         self.allocate(alloc.dz, alloc.pinned)
@@ -661,26 +687,43 @@ class _LcChain(_Chain):
     def allocate(self, dz, pinned):
         ctx, dev, n, n_ch, rate = self.ctx, self.dev, self.n, self.n_ch, self.rate
         self.out_ch, self.out_rate = n_ch, rate     # as coded
+        if self.out_map is not None:                # ... or what the map leaves: only that block exists on the device and comes down
+            self.out_ch = out_map_channels(self.out_map, n_ch)
+        out_ch = self.out_ch
         self.out32, self.qadj = dz(n * 1024 * n_ch, dtype=torch.int32), dz(n * n_ch, dtype=torch.int8)
         lim0, self.delay = peak_limiter_init(n_ch, rate)
         self.lim = torch.from_numpy(np.tile(np.frombuffer(bytes(lim0), np.uint8), (n, 1)).copy()).to(dev)
         self.lim_at_end, self.lim_taken = {}, np.zeros(n, bool)
         self.ws = dz(max(ctx.peak_limiter_workspace_bytes(n), 16))
-        self.pcm2 = [dz(n * 1024 * n_ch, dtype=torch.int16) for _ in range(2)]
-        self.pcm_h2 = [pinned(n * 1024 * n_ch, dtype=torch.int16) for _ in range(2)]
+        self.pcm2 = [dz(n * 1024 * out_ch, dtype=torch.int16) for _ in range(2)]
+        self.pcm_h2 = [pinned(n * 1024 * out_ch, dtype=torch.int16) for _ in range(2)]
 
     def run(self, step, slot, got, first, spec_d, ics_d):
+        shape, cut = (self.n, 1024, self.out_ch), (self.delay if first else 0)   # the limiter's delay is cut from the first frame
+        planar = self.n_ch > 2
+        if not self.limiter:    # ixheaacd_scale_adjust + round16 in the limiter's place: the IMDCT's own hand-off, or -- with a map, or
+            # more than two channels -- the kernel behind it in which a sample's channels meet in one lane
+            if self.out_map is None and not planar:
+                self.ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, pcm16=self.pcm2[slot], ch_fac=self.n_ch)
+            else:
+                self.ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, out32=self.out32, qshift_adj=self.qadj,
+                                             ch_fac=1 if planar else self.n_ch)
+                self.ctx.pcm16_scale_adjust_map_batch(self.out32, self.qadj, self.n_ch, self.pcm2[slot], self.out_map, planar=planar)
+            return shape, cut, False
         # a stream that ended with the step before: its limiter state as its last frame left it (the rows of ended
         # streams go on running idle through the kernels; the delay line flushed behind a stream is the one it ended on)
         for i in np.nonzero(~got & ~self.lim_taken)[0]:
             self.lim_at_end[int(i)] = self.lim[int(i)].cpu().numpy()     # (waits for the kernels of the step before)
             self.lim_taken[i] = True
         # more than two channels: a row per channel (the pipeline sent them up in output channel order), the limiter reads them planar
-        planar = self.n_ch > 2
         self.ctx.imdct_process_batch(spec_d, ics_d, self.ovl, self.ovl_state, out32=self.out32, qshift_adj=self.qadj,
                                      ch_fac=1 if planar else self.n_ch)
-        self.ctx.peak_limiter_process_batch(self.out32, self.qadj, self.lim, self.n_ch, self.ws, pcm16=self.pcm2[slot], planar=planar)
-        return (self.n, 1024, self.n_ch), (self.delay if first else 0), False   # the limiter's delay is cut from the first frame
+        if self.out_map is not None:    # the map is the limiter's epilogue
+            self.ctx.peak_limiter_process_map_batch(self.out32, self.qadj, self.lim, self.n_ch, self.ws, self.pcm2[slot], self.out_map,
+                                                    planar=planar)
+        else:
+            self.ctx.peak_limiter_process_batch(self.out32, self.qadj, self.lim, self.n_ch, self.ws, pcm16=self.pcm2[slot], planar=planar)
+        return shape, cut, False
 
     def finish(self, out, keep_pcm):
         if not keep_pcm:
@@ -689,6 +732,9 @@ class _LcChain(_Chain):
         self.ctx.sync()
         lim_h, n_ch = self.lim.cpu().numpy(), self.n_ch
         for i in range(self.n):
+            if not self.limiter:    # the reference flushes the delay line all the same, and nothing ever went into it
+                out[i].append(np.zeros((self.delay, self.out_ch), np.int16))
+                continue
             st = LimiterState.from_buffer_copy((self.lim_at_end[i] if i in self.lim_at_end else lim_h[i]).tobytes())
             att, idx = st.attack_time_samples, st.delayed_input_index
             d = np.ctypeslib.as_array(st.delayed_input)[:att * n_ch].reshape(att, n_ch)
@@ -696,7 +742,7 @@ class _LcChain(_Chain):
             inside = (tail > -2147483649.0) & (tail < 2147483648.0)      # (WORD32) of a float as x86 converts it: what does
             v = np.where(inside, np.trunc(np.where(inside, tail, 0.0)), -2147483648.0).astype(np.int64)   # not fit is INT_MIN
             v = np.clip(v + 0x8000, -(1 << 31), (1 << 31) - 1) >> 16   # round16
-            out[i].append(v.astype(np.int16))
+            out[i].append(out_map_apply_host(self.out_map, v.astype(np.int16)))   # the flushed samples take the map the frames took
 
 
 class _SbrBase(_Chain):
@@ -898,10 +944,10 @@ class _McEsbrChain(_EsbrChain):
         n, n_ch = self.n, self.n_ch
         elements, self.route, _ = MC_LAYOUT[n_ch]
         self.el_of_ch = np.repeat(np.arange(len(elements)), [2 if e == 1 else 1 for e in elements])
-        self.out_ch = n_ch
+        self.out_ch = out_ch = 2 if self.out_map is not None else n_ch   # (the downmix to stereo on the way out)
         self.out32, self.qadj = dz(self.nc, 1024, dtype=torch.int32), dz(self.nc, dtype=torch.int8)
-        self.pcm2 = [dz(n * 2048 * n_ch, dtype=torch.int16) for _ in range(2)]
-        self.pcm_h2 = [pinned(n * 2048 * n_ch, dtype=torch.int16) for _ in range(2)]
+        self.pcm2 = [dz(n * 2048 * out_ch, dtype=torch.int16) for _ in range(2)]
+        self.pcm_h2 = [pinned(n * 2048 * out_ch, dtype=torch.int16) for _ in range(2)]
 
     def send_up(self, step, slot, got):
         self.hdr_d2[slot].copy_(step.hdr, non_blocking=True)
@@ -925,8 +971,28 @@ class _McEsbrChain(_EsbrChain):
             self.trace(dict(state=state, hbe=self.hbe, ps_state=None, core=self.core, side=eside_d, header=hdr_d, frame=frm_d))
         ctx.esbr_sbr_process_batch(self.core, hdr_d, frm_d, eside_d, state, self.out_l, self.ws, status=self.status2[slot],
                                    hbe_state=self.hbe, hbe_max_synth_size=self.hbe_hint())
-        ctx.mc_pcm16_from_planes(self.out_l, self.pcm2[slot], self.route)
-        return (self.n, 2048, n_ch), 0, first
+        ctx.mc_pcm16_from_planes(self.out_l, self.pcm2[slot], self.route, out_map=self.out_map)
+        return (self.n, 2048, self.out_ch), 0, first
+
+
+def _pick_out_map(name, n_ch, sbr, channel_config):
+    """the OutMap decode_streams' out_map asks for on this kind of stream, None where the reference's flag is a no-op, ValueError
+    where the command line decoder refuses the combination"""
+    if name is None:
+        return None
+    if name not in ("downmix", "mono", "mono_dup", "dup"):
+        raise ValueError('out_map is None, "downmix", "mono", "mono_dup" or "dup"')
+    if name == "downmix":
+        if n_ch <= 2 or not channel_config:
+            raise ValueError("out_map=\"downmix\" on a stream of one or two channels is not supported (there is nothing to mix down)")
+        return make_out_map(name, channel_config)
+    if name in ("mono", "mono_dup"):
+        if sbr or n_ch > 2:
+            raise ValueError("out_map=\"%s\" on a stream with SBR or with more than two channels is not supported" % name)
+        if n_ch == 1 and name == "mono_dup":
+            raise ValueError("out_map=\"mono_dup\" on a mono stream is not supported")
+        return make_out_map(name) if n_ch == 2 else None
+    return make_out_map(name) if n_ch == 1 and not sbr else None    # "dup": a mono AAC-LC stream's channel twice, else a no-op
 
 
 class _Pipeline:
@@ -937,7 +1003,8 @@ class _Pipeline:
     later.  What runs between the two is the chain's business (_LcChain, _SbrChain or _EsbrChain, picked once in here), with
     the spectral tools in front of it when gpu_tools says so."""
 
-    def __init__(self, streams, ctx, device, threads, keep_pcm, overlap, esbr, trace, frames_per_parse, gpu_tools, mc_sbr=False):
+    def __init__(self, streams, ctx, device, threads, keep_pcm, overlap, esbr, trace, frames_per_parse, gpu_tools, mc_sbr=False,
+                 out_map=None, limiter=True):
         self.dev = dev = torch.device(device)
         alloc, lib = _Alloc(dev), load_host_library()
         self.own = ctx is None
@@ -954,6 +1021,11 @@ class _Pipeline:
             except ValueError:
                 bp.close()
                 raise
+        try:
+            out_map = _pick_out_map(out_map, bp.n_ch, bool(bp.sbr), bp.channel_config)
+        except ValueError:
+            bp.close()
+            raise
         # more than two channels: bitstream channel c of a stream goes up as row route[c] of its rows (the reference's output order);
         # with SBR the rows stay in bitstream order (the hand-off behind the SBR calls routes them)
         self.route = MC_LAYOUT[bp.channel_config][1] if bp.channel_config and not bp.sbr else None
@@ -961,7 +1033,7 @@ class _Pipeline:
         self.n, self.nc, self.keep_pcm, self.overlap = bp.n, bp.n * bp.n_ch, keep_pcm, overlap
         self.T = T = max(1, int(frames_per_parse))
         kind = _LcChain if not bp.sbr else _McEsbrChain if bp.mc_sbr else _EsbrChain if esbr else _SbrChain
-        self.chain = chain = kind(ctx, lib, dev, bp.n, bp.n_ch, bp.core_rate, alloc, trace)
+        self.chain = chain = kind(ctx, lib, dev, bp.n, bp.n_ch, bp.core_rate, alloc, trace, out_map, bool(limiter) or bool(bp.sbr))
         first_rows = (0,)
         if bp.channel_config:   # every element's first bitstream channel, where the routed upload puts it
             elements, route, _ = MC_LAYOUT[bp.channel_config]
@@ -1123,7 +1195,7 @@ class _Pipeline:
 
 
 def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True, timing=None, overlap=True, esbr=False,
-                   _trace=None, frames_per_parse=4, gpu_tools=False, mc_sbr=False):
+                   _trace=None, frames_per_parse=4, gpu_tools=False, mc_sbr=False, out_map=None, limiter=True):
     """Decodes N ADTS streams of the same kind (all AAC-LC mono or stereo, all AAC-LC of one channel_config 3 .. 6 -- 3.0 to
     5.1, output channels in the reference's order, MC_LAYOUT --, all HE-AAC stereo, or all HE-AAC / HE-AACv2 mono) in lock step: per step one frame of every stream is parsed on CPU threads into pinned staging arrays, copied to the GPU
     (spectra + window info, SBR / PS side info: nothing else crosses the bus on the way in), run through the GPU entry
@@ -1148,9 +1220,16 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     mc_sbr: take HE-AAC streams of channel_config 3 .. 6 (an SBR payload per channel element; one SBR decoder per element, as the
     reference keeps them; output channels in the reference's order at twice the core's rate, no limiter).  esbr=True only: with
     esbr=False, or with an output rate above 48 kHz (the down-sampled bank), such a stream is a ValueError; without mc_sbr an SBR
-    payload in a stream of more than two channels is a ValueError as before."""
+    payload in a stream of more than two channels is a ValueError as before.
+    out_map: the reference's output stage on the GPU, as an epilogue of the call that writes the PCM (only the mapped block comes down):
+    "downmix" (-downmix:1: 3 .. 6 channels -> stereo), "mono" (-dmix:1: a stereo AAC-LC stream -> mono; a no-op on a mono one),
+    "mono_dup" (-dmix:1 -tostereo:1: that mix in both channels), "dup" (-tostereo:1: a mono AAC-LC stream's channel twice; a no-op
+    on everything else).  What the command line decoder refuses is a ValueError: "downmix" on one or two channels, "mono" /
+    "mono_dup" with SBR or more than two channels, "mono_dup" on a mono stream.  Every sample is mapped, the limiter's flushed delay
+    line included.
+    limiter: False is -peak_limiter_off:1 (AAC-LC: ixheaacd_scale_adjust + round16 in the limiter's place; nothing changes with SBR)."""
     global torch
     import torch
     with _TorchCpuThreads():
         return _Pipeline(streams, ctx, device, threads, keep_pcm, overlap, esbr, _trace, frames_per_parse, bool(gpu_tools),
-                         bool(mc_sbr)).run(timing)
+                         bool(mc_sbr), out_map, limiter).run(timing)

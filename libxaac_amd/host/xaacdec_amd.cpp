@@ -8,6 +8,18 @@
  *   xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:<0|1>] [-copies:<N>] [-verify] [-threads:<T>] [-quiet]
  *   xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-esbr:<0|1>] [-threads:<T>] [-quiet]
  *   ... [-gpus:<G>] [-device:<k>] [-plan] [-gputools:<0|1>] [-mcsbr:<0|1>]
+ *   ... [-downmix:<0|1>] [-dmix:<0|1>] [-tostereo:<0|1>] [-peak_limiter_off:<0|1>]
+ *
+ * The reference's output stage flags, on the GPU (include/xaac_amd.h: xaac_out_map; the mapped calls store the mapped block only, and
+ * the device PCM buffers, the copy down, the pinned staging and -verify all have the mapped channel count):
+ *   -downmix:1           a stream of 3 .. 6 channels comes out in stereo (ixheaacd_dec_downmix_to_stereo); refused for one or two channels
+ *   -dmix:1              a stereo AAC-LC stream comes out mono ((l >> 1) + (r >> 1)), with -tostereo:1 that word twice; a no-op on a mono
+ *                        AAC-LC stream; refused with SBR, with more than two channels, with -downmix:1
+ *   -tostereo:1          a mono AAC-LC stream comes out with its channel twice; a no-op on everything else
+ *   -peak_limiter_off:1  AAC-LC: ixheaacd_scale_adjust + round16 in the limiter's place; a no-op with SBR (no limiter on that path)
+ * -tostereo:1, -peak_limiter_off:1 and the no-op cases write the reference's bytes.  -downmix:1 and -dmix:1 write a file that is right
+ * where the reference's is not: a 44-byte PCM header with the mapped channel count and every sample of the unflagged decode mixed --
+ * the reference's header keeps the stream's channel count over stereo data and its tail (the limiter's flushed delay line) is unmixed.
  *
  * -mcsbr:1 (default 0) takes HE-AAC streams of more than two channels (channel_config 3 .. 6 with SBR payloads): one SBR decoder per
  * channel element, as the reference keeps them; default flags (-esbr:1) only.  Without the flag such a stream is refused.
@@ -60,6 +72,11 @@
 
 namespace {
 
+/* a combination of flags and stream this decoder does not take: its own message, no output file */
+[[noreturn]] void reject(const char *why) {
+  fprintf(stderr, "xaacdec_amd: %s\n", why);
+  exit(2);
+}
 [[noreturn]] void die(const char *what, long code = 0) {
   fprintf(stderr, "xaacdec_amd: %s failed (%ld)\n", what, code);
   exit(2);
@@ -276,6 +293,8 @@ struct Job {
   int hq; /* -esbr_hq:1: the DFT harmonic transposer in the QMF one's place (Path A only) */
   int threads, verify, profile;
   int gputools; /* -gputools:1: parse at stage 1, the spectral tools run on the GPU in front of the IMDCT */
+  xaac_out_map map; /* -downmix:1 / -dmix:1 / -tostereo:1: what the PCM hand-off does to a sample's channels (out_ch is the mapped count) */
+  int lim_off;      /* -peak_limiter_off:1 on an AAC-LC stream */
   bool list_mode;
 };
 /* one device's share of the batch: streams [lo, lo + n) on HIP device `device`, decoded by one host thread */
@@ -531,22 +550,45 @@ class LcChain : public Chain {
     d_ws_ = E.mem.workspace(ws_bytes_);
     kept_.assign((size_t)N, 0);
     if (E.J.list_mode) lim_at_end_.resize((size_t)N);
+    mapped_ = E.J.map.kind != XAAC_OUT_MAP_NONE;
   }
   Wants wants() const override { return {false, false, false}; }
   StepOut run(const Staging &, int slot) override {
     const int N = E_.N, n_ch = E_.J.n_ch;
     xaac_imdct_batch ib = E_.imdct;
+    const bool planar = E_.imdct.ch_fac == 1 && n_ch > 1; /* more than two channels: the IMDCT writes [stream][channel][1024] */
+    const size_t bytes = (size_t)N * E_.J.per * E_.J.out_ch * 2;
+    if (E_.J.lim_off && !mapped_ && n_ch <= 2) { /* -peak_limiter_off:1: the IMDCT's own hand-off (XAAC_PCM_LC: scale_adjust + round16) */
+      ib.pcm16 = E_.d_pcm[slot], ib.pcm_mode = XAAC_PCM_LC;
+      XA(xaac_imdct_process_batch(E_.ctx, &ib));
+      return {E_.d_pcm[slot], bytes, false, false, 0};
+    }
     ib.out32 = d_out32_, ib.qshift_adj = d_qadj_;
     XA(xaac_imdct_process_batch(E_.ctx, &ib));
+    if (E_.J.lim_off) { /* ... for more channels, or with a map: a sample's channels meet in one lane behind the IMDCT */
+      xaac_scale_adjust_map_batch sb;
+      memset(&sb, 0, sizeof(sb));
+      sb.n_streams = N, sb.frame_len = 1024, sb.num_channels = n_ch, sb.planar = planar, sb.samples = d_out32_, sb.stride = 1024 * n_ch;
+      sb.qshift_adj = d_qadj_, sb.pcm16 = E_.d_pcm[slot], sb.map = E_.J.map;
+      XA(xaac_pcm16_scale_adjust_map_batch(E_.ctx, &sb));
+      return {E_.d_pcm[slot], bytes, false, false, 0};
+    }
     xaac_limiter_batch lb;
     memset(&lb, 0, sizeof(lb));
     lb.n_streams = N, lb.frame_len = 1024, lb.samples = d_out32_, lb.stride = 1024 * n_ch, lb.qshift_adj = d_qadj_, lb.state = d_lim_;
     lb.num_channels = n_ch, lb.pcm16 = E_.d_pcm[slot], lb.workspace = d_ws_, lb.workspace_bytes = ws_bytes_;
-    lb.planar = E_.imdct.ch_fac == 1 && n_ch > 1; /* more than two channels: the IMDCT writes [stream][channel][1024] */
-    XA(xaac_peak_limiter_process_batch(E_.ctx, &lb));
-    return {E_.d_pcm[slot], (size_t)N * E_.J.per * E_.J.out_ch * 2, false, false, 0};
+    lb.planar = planar;
+    if (mapped_) { /* the map is the limiter's epilogue: only the mapped block is stored */
+      xaac_limiter_map_batch mb;
+      mb.lim = lb, mb.map = E_.J.map;
+      XA(xaac_peak_limiter_process_map_batch(E_.ctx, &mb));
+    } else {
+      XA(xaac_peak_limiter_process_batch(E_.ctx, &lb));
+    }
+    return {E_.d_pcm[slot], bytes, false, false, 0};
   }
   void stream_ended(int i) override { /* the limiter state a stream leaves behind its last frame */
+    if (E_.J.lim_off) return;
     HIP(hipMemcpy(&lim_at_end_[(size_t)i], d_lim_ + i, sizeof(xaac_limiter_state), hipMemcpyDeviceToHost)); /* (waits for the step before) */
     kept_[(size_t)i] = 1;
   }
@@ -555,18 +597,30 @@ class LcChain : public Chain {
     /* the limiter's delay line holds the last attack_time_samples samples: api.c:2824-2866 */
     const int n_ch = E_.J.n_ch;
     static thread_local xaac_limiter_state l;
+    std::vector<int16_t> tail;
     for (size_t i = 0; i < pcms.size(); i++) {
+      if (E_.J.lim_off) { /* -peak_limiter_off:1: the reference flushes the delay line all the same, and nothing ever went into it */
+        pcms[i].insert(pcms[i].end(), (size_t)delay_ * E_.J.out_ch, (int16_t)0);
+        continue;
+      }
       if (kept_[i]) l = lim_at_end_[i];
       else HIP(hipMemcpy(&l, d_lim_ + i, sizeof(l), hipMemcpyDeviceToHost));
       const uint32_t att = l.attack_time_samples, at = l.delayed_input_index;
+      tail.clear();
       for (uint32_t k = 0; k < att; k++)
         for (int c = 0; c < n_ch; c++) {
           const float v = l.delayed_input[(size_t)((at + k) % att) * n_ch + c];
           const int64_t w = (v >= 2147483648.0f || v < -2147483648.0f || v != v) ? INT32_MIN : (int64_t)v; /* (WORD32)v as x86 has it */
           int64_t r = w + 0x8000;
           if (r > INT32_MAX) r = INT32_MAX;
-          pcms[i].push_back((int16_t)(r >> 16));
+          tail.push_back((int16_t)(r >> 16));
         }
+      /* the flushed samples take the map the frames took, on the host (the CPU twin of the mapped calls), in place: a mono
+         channel written twice needs the room of two */
+      tail.resize((size_t)att * (size_t)(n_ch > E_.J.out_ch ? n_ch : E_.J.out_ch));
+      const int32_t oc = xaac_out_map_apply_host(&E_.J.map, n_ch, tail.data(), (int64_t)att, tail.data());
+      if (oc != E_.J.out_ch) die("xaac_out_map_apply_host", oc);
+      pcms[i].insert(pcms[i].end(), tail.begin(), tail.begin() + (size_t)att * oc);
     }
   }
 
@@ -580,6 +634,7 @@ class LcChain : public Chain {
   int delay_;
   std::vector<xaac_limiter_state> lim_at_end_; /* -ilist: the limiter state a stream leaves behind its last frame */
   std::vector<char> kept_;
+  bool mapped_ = false;
 };
 
 /* -esbr:0, the fixed-point SBR tools: IMDCT -> low-power SBR for pairs, HQ SBR + parametric stereo for mono streams */
@@ -986,7 +1041,13 @@ class EsbrChain : public Chain {
       memset(&mb, 0, sizeof(mb));
       mb.n_streams = N, mb.n_ch = E_.J.n_ch, mb.stride = 2048, mb.planes = d_out_l_, mb.pcm = E_.d_pcm[slot];
       for (int c = 0; c < E_.J.n_ch; c++) mb.slot[c] = E_.J.slot[c];
-      XA(xaac_mc_pcm16_from_float_batch(E_.ctx, &mb));
+      if (E_.J.map.kind == XAAC_OUT_MAP_DOWNMIX_STEREO) { /* -downmix:1: a sample's channels become its stereo pair on the way out */
+        xaac_mc_pcm_out_map_batch xb;
+        xb.out = mb, xb.map = E_.J.map;
+        XA(xaac_mc_pcm16_from_float_map_batch(E_.ctx, &xb));
+      } else {
+        XA(xaac_mc_pcm16_from_float_batch(E_.ctx, &mb));
+      }
     } else {
       XA(xaac_esbr_pcm16_from_float_batch(E_.ctx, &ob));
     }
@@ -1335,8 +1396,21 @@ void decode_shard(const Job &J, Shard &S) {
 int main(int argc, char **argv) {
   std::string in, out, ilist, odir;
   int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0, gputools = 0, mcsbr = 0;
+  int downmix = 0, dmix = 0, tostereo = 0, lim_off = 0;
+  const struct {
+    const char *name;
+    int *value;
+  } out_flags[] = {{"-downmix:", &downmix}, {"-dmix:", &dmix}, {"-tostereo:", &tostereo}, {"-peak_limiter_off:", &lim_off}};
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
+    bool taken = false;
+    for (const auto &f : out_flags)
+      if (a.rfind(f.name, 0) == 0) {
+        const std::string v = a.substr(strlen(f.name));
+        if (v != "0" && v != "1") reject((std::string(f.name) + "0 or " + f.name + "1").c_str());
+        *f.value = v == "1", taken = true;
+      }
+    if (taken) continue;
     if (a.rfind("-ifile:", 0) == 0) in = a.substr(7);
     else if (a.rfind("-ofile:", 0) == 0) out = a.substr(7);
     else if (a.rfind("-ilist:", 0) == 0) ilist = a.substr(7);
@@ -1379,7 +1453,12 @@ int main(int argc, char **argv) {
   }
   if (inputs.empty() || (ilist.empty() && out.empty() && !plan) || copies < 1 || gpus < 1 || device0 < 0) {
     fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-gputools:0|1] [-mcsbr:0|1] [-quiet]\n"
-                    "  -mcsbr:1  decode HE-AAC streams of more than two channels (channel_config 3 .. 6, SBR per channel element; default flags only)\n");
+                    "       [-downmix:0|1] [-dmix:0|1] [-tostereo:0|1] [-peak_limiter_off:0|1]\n"
+                    "  -mcsbr:1  decode HE-AAC streams of more than two channels (channel_config 3 .. 6, SBR per channel element; default flags only)\n"
+                    "  -downmix:1  3 .. 6 channels come out in stereo (the reference's downmix matrix; a 44-byte stereo WAV header)\n"
+                    "  -dmix:1  a stereo AAC-LC stream comes out mono, with -tostereo:1 the mono mix in both channels\n"
+                    "  -tostereo:1  a mono AAC-LC stream comes out with its channel twice\n"
+                    "  -peak_limiter_off:1  AAC-LC without the peak limiter (scale adjust + round16)\n");
     return 1;
   }
   std::vector<std::vector<uint8_t>> datas(inputs.size());
@@ -1408,9 +1487,29 @@ int main(int argc, char **argv) {
     if (2 * f0.rate > 48000) die("-mcsbr:1 with a down-sampled bank (an output rate above 48 kHz) is not supported");
   }
 
+  /* the output stage flags: what this decoder does not take is refused here, before anything is opened or written */
+  if (downmix && dmix) reject("-downmix:1 together with -dmix:1 is not supported");
+  if (downmix && n_ch <= 2) reject("-downmix:1 on a stream of one or two channels is not supported (there is nothing to mix down)");
+  if (downmix && (n_ch > 6 || !f0.channel_config)) reject("-downmix:1 takes channel configurations 3 .. 6");
+  if (dmix && (sbr || n_ch > 2)) reject("-dmix:1 on a stream with SBR or with more than two channels is not supported");
+  if (dmix && tostereo && n_ch == 1) reject("-dmix:1 together with -tostereo:1 on a mono stream is not supported");
+
   if (!sbr) esbr = 0; /* AAC-LC streams decode the same either way */
-  /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC, and everything with more than two channels, as coded */
-  const int out_ch = sbr && !f0.channel_config ? 2 : n_ch;
+  xaac_out_map map;
+  memset(&map, 0, sizeof(map));
+  if (downmix) { /* the frame's channel elements and their slots (layout_of): SCE CPE [SCE | CPE [LFE]] */
+    static const int k_type[4][4] = {{0, 1}, {0, 1, 0}, {0, 1, 1}, {0, 1, 1, 3}}, k_slot[4][4] = {{2, 0}, {2, 0, 3}, {2, 0, 3}, {2, 0, 4, 3}};
+    map.kind = XAAC_OUT_MAP_DOWNMIX_STEREO, map.matrix = n_ch == 6, map.n_elements = n_ch == 3 ? 2 : (n_ch == 6 ? 4 : 3);
+    for (int k = 0; k < map.n_elements; k++) map.element_type[k] = k_type[n_ch - 3][k], map.element_slot[k] = k_slot[n_ch - 3][k];
+  } else if (dmix && n_ch == 2) {
+    map.kind = tostereo ? XAAC_OUT_MAP_MONO_MIX_DUP : XAAC_OUT_MAP_MONO_MIX;
+  } else if (tostereo && n_ch == 1 && !sbr) {
+    map.kind = XAAC_OUT_MAP_DUP_STEREO;
+  } /* (everything else is a no-op in the reference too) */
+  if (sbr) lim_off = 0; /* no limiter on the SBR paths: the flag changes nothing there */
+  /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC, and everything with more than two channels, as coded;
+     with a map, what the map leaves */
+  const int out_ch = map.kind == XAAC_OUT_MAP_MONO_MIX ? 1 : (map.kind != XAAC_OUT_MAP_NONE ? 2 : (sbr && !f0.channel_config ? 2 : n_ch));
   const int N = ilist.empty() ? copies : (int)datas.size(), rate = f0.rate, out_rate = sbr ? 2 * rate : rate, per = sbr ? 2048 : 1024;
 
   /* the split: contiguous stream ranges over the devices, as bench.py --gpus N splits over ranks (a shard without streams is
@@ -1424,7 +1523,10 @@ int main(int argc, char **argv) {
     shards[(size_t)r].device = device0 + r, shards[(size_t)r].lo = lo, shards[(size_t)r].n = hi - lo;
   }
   if (plan) { /* nothing below this line runs: no HIP call has been made */
-    printf("{\"streams\": %d, \"gpus\": %d, \"channels\": %d, \"sbr\": %d, \"esbr\": %d, \"shards\": [", N, gpus, n_ch, sbr, esbr);
+    static const char *const k_map[] = {"none", "downmix", "mono", "mono_dup", "dup"};
+    printf("{\"streams\": %d, \"gpus\": %d, \"channels\": %d, \"sbr\": %d, \"esbr\": %d, \"out_channels\": %d, \"out_map\": \"%s\", "
+           "\"limiter\": %d, \"wav_header\": \"%s\", \"shards\": [",
+           N, gpus, n_ch, sbr, esbr, out_ch, k_map[map.kind], !sbr && !lim_off, out_ch > 2 ? "extensible68" : "pcm44");
     for (int r = 0; r < gpus; r++)
       printf("%s{\"device\": %d, \"lo\": %d, \"n\": %d}", r ? ", " : "", shards[(size_t)r].device, shards[(size_t)r].lo, shards[(size_t)r].n);
     printf("]}\n");
@@ -1459,6 +1561,7 @@ int main(int argc, char **argv) {
       if (c >= J.first_ch[k]) J.el_of_ch[c] = k;
   }
   J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode, J.gputools = gputools;
+  J.map = map, J.lim_off = lim_off;
   const auto t_run = std::chrono::steady_clock::now();
   if (gpus == 1) {
     decode_shard(J, shards[0]);
