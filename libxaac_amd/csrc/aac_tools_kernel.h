@@ -29,6 +29,7 @@ typedef struct XaacAacToolsParams {
 extern "C" {
 #endif
 hipError_t xaac_launch_aac_tools(const XaacAacToolsParams *p, hipStream_t stream);
+hipError_t xaac_warm_aac_tools(void);
 #ifdef __cplusplus
 }
 #endif

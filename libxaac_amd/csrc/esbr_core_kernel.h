@@ -7,17 +7,32 @@
 
 #include "../../include/xaac_esbr.h"
 
+#define XAAC_ESBR_CORE_BLOCK 64                                 /* one wave per channel, no dynamic LDS: what xaac_esbr_sbr_process_batch reports of its chain */
 #define XAAC_ESBR_OUT_ROWS 42                                   /* 8 history + 32 + 2 rows a VARVAR frame can reach */
 #define XAAC_ESBR_L_ROWS 38                                     /* 32 regrouped rows + the 6 look-ahead rows of the PS hybrid filter */
 #define XAAC_ESBR_PH_ROWS 40                                    /* ph_vocod_qmf: 8 history rows + the transposer's 32 */
-#define XAAC_ESBR_WS_FLOATS (2 * 2048 + 2 * XAAC_ESBR_OUT_ROWS * 64 + 2 * XAAC_ESBR_L_ROWS * 64 + 2 * 2048 + 2 * XAAC_ESBR_PH_ROWS * 64 + 16 * 64) /* analysis rows, sbr_qmf_out, left rows, right rows, transposer rows, the PVC decoder's envelope */
+/* the chain's workspace, X(sub-buffer, floats per channel) in the order they lie: the size below and the pointers
+   xaac_esbr_sbr_process_batch hands out (xaac_abi.cpp) are both made from this list */
+#define XAAC_ESBR_WS_PARTS(X)                                                                                      \
+  X(ana_re, 2048) X(ana_im, 2048)                                       /* the frame's analysis rows */             \
+  X(out_re, XAAC_ESBR_OUT_ROWS * 64) X(out_im, XAAC_ESBR_OUT_ROWS * 64) /* sbr_qmf_out */                           \
+  X(syn_re, XAAC_ESBR_L_ROWS * 64) X(syn_im, XAAC_ESBR_L_ROWS * 64)     /* the left rows */                         \
+  X(r_re, 2048) X(r_im, 2048)                                           /* the right rows */                        \
+  X(ph_re, XAAC_ESBR_PH_ROWS * 64) X(ph_im, XAAC_ESBR_PH_ROWS * 64)     /* the transposer's rows */                 \
+  X(pvc_out, 16 * 64)                                                   /* the PVC decoder's envelope */
+#define XAAC_ESBR_WS_ADD(name, floats) +(floats)
+#define XAAC_ESBR_WS_FLOATS (0 XAAC_ESBR_WS_PARTS(XAAC_ESBR_WS_ADD))
 
 /* 4:1 SBR (64 slots, four to an envelope time slot; op_delay 12): the low-band matrix is a scratch of its own -- 14 history rows,
    the 16-channel bank's 64 rows (written in place by the bank), 2 rows of zeros -- and sbr_qmf_out grows likewise; no PS rows,
    no transposer rows */
 #define XAAC_ESBR_Q_ROWS_4_1 80
 #define XAAC_ESBR_OUT_ROWS_4_1 82
-#define XAAC_ESBR_WS_FLOATS_4_1 (2 * XAAC_ESBR_Q_ROWS_4_1 * 64 + 2 * XAAC_ESBR_OUT_ROWS_4_1 * 64 + 2 * 64 * 64 + 16 * 64)
+#define XAAC_ESBR_WS_PARTS_4_1(X)                                                     \
+  X(q_re, XAAC_ESBR_Q_ROWS_4_1 * 64) X(q_im, XAAC_ESBR_Q_ROWS_4_1 * 64)               \
+  X(out_re, XAAC_ESBR_OUT_ROWS_4_1 * 64) X(out_im, XAAC_ESBR_OUT_ROWS_4_1 * 64)       \
+  X(syn_re, 64 * 64) X(syn_im, 64 * 64) X(pvc_out, 16 * 64)
+#define XAAC_ESBR_WS_FLOATS_4_1 (0 XAAC_ESBR_WS_PARTS_4_1(XAAC_ESBR_WS_ADD))
 
 typedef struct XaacEsbrCoreParams {
   int32_t n_ch;
@@ -47,6 +62,7 @@ typedef struct XaacEsbrCoreParams {
 extern "C" {
 #endif
 hipError_t xaac_launch_esbr_core(const XaacEsbrCoreParams *p, hipStream_t stream);
+hipError_t xaac_warm_esbr_core(void);
 
 typedef struct XaacEsbrPsParams {
   int32_t n;
@@ -59,6 +75,7 @@ typedef struct XaacEsbrPsParams {
   int32_t *status;                /* -1 is written where the side info is outside the tool's tables */
 } XaacEsbrPsParams;
 hipError_t xaac_launch_esbr_ps(const XaacEsbrPsParams *p, hipStream_t stream);
+hipError_t xaac_warm_esbr_ps(void);
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,11 @@
 
 #include "../../include/xaac_amd.h"
 
+#define XAAC_ESBR_ANA_BLOCK 64    /* both analysis banks: one wave */
+#define XAAC_ESBR_SYN_BLOCK 128   /* the synthesis bank: two waves */
+#define XAAC_ESBR_SYN_DS_BLOCK 64 /* its down-sampled form: one wave, no dynamic LDS */
+/* what xaac_esbr_qmf_synthesis_batch has always reported as its block: the kernel runs XAAC_ESBR_SYN_BLOCK threads */
+#define XAAC_ESBR_SYN_REPORTED_BLOCK 64
 #define XAAC_ESBR_ANA_LDS (64 * 65 * 4)                        /* two channels' time-ordered history (2 x 1312 words), then the 64 x 65 exchange tile in its place */
 #define XAAC_ESBR_SYN_LDS (41 * 129 * 4)                       /* ring samples of one channel x (9 + 32) slots; the half-row tile fits */
 
@@ -59,6 +64,7 @@ hipError_t xaac_launch_esbr_pcm16_from_float(const XaacEsbrPcmOutParams *p, hipS
 hipError_t xaac_launch_esbr_analysis(const XaacEsbrAnaParams *p, hipStream_t stream);
 hipError_t xaac_launch_esbr_analysis_nb(const XaacEsbrAnaNbParams *p, hipStream_t stream);
 hipError_t xaac_launch_esbr_synthesis(const XaacEsbrSynParams *p, hipStream_t stream);
+hipError_t xaac_warm_esbr_qmf(void);
 hipError_t xaac_launch_esbr_synthesis_ds(const XaacEsbrSynParams *p, hipStream_t stream); /* 32 synthesis channels: out [n_ch][out_stride | 1024] */
 #ifdef __cplusplus
 }

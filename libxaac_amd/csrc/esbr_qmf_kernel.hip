@@ -46,7 +46,7 @@ __device__ __forceinline__ int win_after_frame(int w) {
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void xaac_esbr_analysis_kernel(XaacEsbrAnaParams p) {
+__global__ __launch_bounds__(XAAC_ESBR_ANA_BLOCK) void xaac_esbr_analysis_kernel(XaacEsbrAnaParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x;
   int32_t *hist = reinterpret_cast<int32_t *>(smem);                 /* [2][kHist] time-ordered, oldest first */
@@ -191,7 +191,7 @@ struct XeRingAt {        /* anal_filter_states_32 at slot s of this frame */
 }  // namespace
 
 template <int NB>
-__global__ __launch_bounds__(64) void xaac_esbr_analysis_nb_kernel(XaacEsbrAnaNbParams p) {
+__global__ __launch_bounds__(XAAC_ESBR_ANA_BLOCK) void xaac_esbr_analysis_nb_kernel(XaacEsbrAnaNbParams p) {
   constexpr int RS = 2 * NB + 1, CPW = NB == 24 ? 2 : 1, SL = 64 / CPW; /* tile row: NB real | NB imaginary words (+ 1: no bank conflicts); channel-frames a wave takes, lanes (slots) of each */
   __shared__ int32_t old_ring[CPW][10 * NB];
   __shared__ int32_t frame[CPW][(1024 / NB) * (NB + 1)];
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(64) void xaac_esbr_analysis_nb_kernel(XaacEsbrAnaNb
 #ifndef XE_SYN_MIN_WAVES
 #define XE_SYN_MIN_WAVES 2
 #endif
-__global__ __launch_bounds__(128, XE_SYN_MIN_WAVES) void xaac_esbr_synthesis_kernel(XaacEsbrSynParams p) {
+__global__ __launch_bounds__(XAAC_ESBR_SYN_BLOCK, XE_SYN_MIN_WAVES) void xaac_esbr_synthesis_kernel(XaacEsbrSynParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int RS = 65, VSLOTS = 41, VROW = 129, RING = 1280;
   static_assert(2 * 32 * RS <= VSLOTS * VROW, "the tiles fit where the ring samples go");
@@ -463,7 +463,7 @@ __global__ __launch_bounds__(256) void xaac_esbr_pcm16_from_float_kernel(XaacEsb
    :605-628; ixheaacd_esbr_qmfsyn32_winadd generic:1577): 32 samples a slot, the ring's first 640 words.  Lane = slot, two channel-frames
    a wave, as in the 24-channel analysis bank above and with its way of finding a ring block's words at a given slot: the slot's own 64
    new words, an earlier slot's of this frame, or the words the state holds.  Not a headline kernel: exact, short, untuned. */
-__global__ __launch_bounds__(64) void xaac_esbr_synthesis_ds_kernel(XaacEsbrSynParams p) {
+__global__ __launch_bounds__(XAAC_ESBR_SYN_DS_BLOCK) void xaac_esbr_synthesis_ds_kernel(XaacEsbrSynParams p) {
   constexpr int RS = 65, TS = 33;
   __shared__ int32_t old_ring[2][640];
   __shared__ int32_t blk[2][32 * RS]; /* slot k's 64 ring words */
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(64) void xaac_esbr_synthesis_ds_kernel(XaacEsbrSynP
 }
 
 extern "C" hipError_t xaac_launch_esbr_synthesis_ds(const XaacEsbrSynParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_esbr_synthesis_ds_kernel, dim3((p->n_ch + 1) / 2), dim3(64), 0, stream, *p);
+  hipLaunchKernelGGL(xaac_esbr_synthesis_ds_kernel, dim3((p->n_ch + 1) / 2), dim3(XAAC_ESBR_SYN_DS_BLOCK), 0, stream, *p);
   return hipGetLastError();
 }
 
@@ -563,18 +563,18 @@ extern "C" hipError_t xaac_launch_esbr_pcm16_from_float(const XaacEsbrPcmOutPara
 }
 
 extern "C" hipError_t xaac_launch_esbr_analysis(const XaacEsbrAnaParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_esbr_analysis_kernel, dim3((p->n_ch + 1) / 2), dim3(64), XAAC_ESBR_ANA_LDS, stream, *p);
+  hipLaunchKernelGGL(xaac_esbr_analysis_kernel, dim3((p->n_ch + 1) / 2), dim3(XAAC_ESBR_ANA_BLOCK), XAAC_ESBR_ANA_LDS, stream, *p);
   return hipGetLastError();
 }
 
 extern "C" hipError_t xaac_launch_esbr_analysis_nb(const XaacEsbrAnaNbParams *p, hipStream_t stream) {
-  if (p->nb == 24) hipLaunchKernelGGL(xaac_esbr_analysis_nb_kernel<24>, dim3((p->n_ch + 1) / 2), dim3(64), 0, stream, *p); /* two channel-frames a wave */
-  else hipLaunchKernelGGL(xaac_esbr_analysis_nb_kernel<16>, dim3(p->n_ch), dim3(64), 0, stream, *p);
+  if (p->nb == 24) hipLaunchKernelGGL(xaac_esbr_analysis_nb_kernel<24>, dim3((p->n_ch + 1) / 2), dim3(XAAC_ESBR_ANA_BLOCK), 0, stream, *p); /* two channel-frames a wave */
+  else hipLaunchKernelGGL(xaac_esbr_analysis_nb_kernel<16>, dim3(p->n_ch), dim3(XAAC_ESBR_ANA_BLOCK), 0, stream, *p);
   return hipGetLastError();
 }
 
 extern "C" hipError_t xaac_launch_esbr_synthesis(const XaacEsbrSynParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_esbr_synthesis_kernel, dim3((p->n_ch + 1) / 2), dim3(128), XAAC_ESBR_SYN_LDS, stream, *p);
+  hipLaunchKernelGGL(xaac_esbr_synthesis_kernel, dim3((p->n_ch + 1) / 2), dim3(XAAC_ESBR_SYN_BLOCK), XAAC_ESBR_SYN_LDS, stream, *p);
   return hipGetLastError();
 }
 

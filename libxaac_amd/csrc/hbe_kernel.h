@@ -62,6 +62,7 @@ typedef struct XaacHbePostParams {
   int32_t lds_synth_size;       /* as XaacHbeBanksParams: a channel the banks kernel refused for its size is left alone here too */
 } XaacHbePostParams;
 
+#define XAAC_HBE_DFT_THREADS 256
 #define XAAC_HBE_DFT_LDS (32 * 128 * 4) /* u of 32 columns */
 typedef struct XaacHbeDftParams {
   int32_t n_ch, no_bins;
@@ -111,6 +112,7 @@ hipError_t xaac_launch_hbe_dft_anal(const XaacHbeDftParams *p, hipStream_t strea
 hipError_t xaac_launch_hbe_dft_core(const XaacHbeDftCoreParams *p, hipStream_t stream);
 hipError_t xaac_launch_hbe_banks(const XaacHbeBanksParams *p, hipStream_t stream);
 hipError_t xaac_launch_hbe_post(const XaacHbePostParams *p, hipStream_t stream);
+hipError_t xaac_warm_hbe(void);
 #ifdef __cplusplus
 }
 #endif

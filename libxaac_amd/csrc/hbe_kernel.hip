@@ -345,7 +345,7 @@ __global__ __launch_bounds__(XAAC_HBE_POST_THREADS) void xaac_hbe_post_kernel(Xa
 /* The DFT transposer's analysis bank: 256 threads per channel; u of all columns into LDS (five window products each), then
    thread = (column, sub-band) runs the 2 L-term sums against the coefficient matrices (global, shared by the channels of
    a configuration), and the rows' cleared cells are written in the closed form of the reference's overlapping memsets. */
-__global__ __launch_bounds__(256) void xaac_hbe_dft_anal_kernel(XaacHbeDftParams p) {
+__global__ __launch_bounds__(XAAC_HBE_DFT_THREADS) void xaac_hbe_dft_anal_kernel(XaacHbeDftParams p) {
   extern __shared__ float lds[];
   float(*u)[128] = reinterpret_cast<float(*)[128]>(lds);
   const int ch = blockIdx.x, tid = threadIdx.x, nb = p.no_bins;
@@ -482,7 +482,7 @@ extern "C" hipError_t xaac_launch_hbe_dft_core(const XaacHbeDftCoreParams *p, hi
 }
 
 extern "C" hipError_t xaac_launch_hbe_dft_anal(const XaacHbeDftParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_hbe_dft_anal_kernel, dim3(p->n_ch), dim3(256), XAAC_HBE_DFT_LDS, stream, *p);
+  hipLaunchKernelGGL(xaac_hbe_dft_anal_kernel, dim3(p->n_ch), dim3(XAAC_HBE_DFT_THREADS), XAAC_HBE_DFT_LDS, stream, *p);
   return hipGetLastError();
 }
 

@@ -23,7 +23,7 @@ __device__ __forceinline__ int32_t wave_or(int32_t v) {
 }
 }  // namespace
 
-__global__ __launch_bounds__(64 * XAAC_I960_WAVES_PER_WG) void xaac_imdct960_kernel(xaac_imdct_batch p) {
+__global__ __launch_bounds__(XAAC_I960_BLOCK) void xaac_imdct960_kernel(xaac_imdct_batch p) {
   extern __shared__ __attribute__((aligned(16))) int32_t smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nl = 64;
   const int ch = blockIdx.x * XAAC_I960_WAVES_PER_WG + wave;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64 * XAAC_I960_WAVES_PER_WG) void xaac_imdct960_ker
 
 extern "C" hipError_t xaac_launch_imdct960(const xaac_imdct_batch *p, hipStream_t stream) {
   const int wgs = (p->n_ch + XAAC_I960_WAVES_PER_WG - 1) / XAAC_I960_WAVES_PER_WG;
-  hipLaunchKernelGGL(xaac_imdct960_kernel, dim3(wgs), dim3(64 * XAAC_I960_WAVES_PER_WG), XAAC_I960_LDS, stream, *p);
+  hipLaunchKernelGGL(xaac_imdct960_kernel, dim3(wgs), dim3(XAAC_I960_BLOCK), XAAC_I960_LDS, stream, *p);
   return hipGetLastError();
 }
 

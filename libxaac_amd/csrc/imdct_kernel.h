@@ -43,6 +43,7 @@ extern "C" {
 #endif
 hipError_t xaac_launch_imdct(const XaacImdctParams *p, int grid, hipStream_t stream);
 int xaac_imdct_blocks_per_cu(void);
+hipError_t xaac_warm_imdct(void);
 #ifdef __cplusplus
 }
 #endif

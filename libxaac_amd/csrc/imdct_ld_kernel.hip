@@ -52,7 +52,7 @@ __device__ __forceinline__ void eld_overlap_add_regs(const int32_t *out, const i
 }  // namespace
 
 template <int F, bool ELD>
-__global__ __launch_bounds__(64 * XAAC_LD_WAVES_PER_WG) void xaac_imdct_ld_kernel(xaac_imdct_ld_batch p) {
+__global__ __launch_bounds__(XAAC_LD_BLOCK) void xaac_imdct_ld_kernel(xaac_imdct_ld_batch p) {
   extern __shared__ __attribute__((aligned(16))) int32_t smem[];
   constexpr int NOV = ELD ? 3 * F : F / 2, PER_WAVE = 1024 + 512;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nl = 64;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * XAAC_LD_WAVES_PER_WG) void xaac_imdct_ld_kerne
 }
 
 extern "C" hipError_t xaac_launch_imdct_ld(const xaac_imdct_ld_batch *p, hipStream_t stream) {
-  const dim3 grid((p->n_ch + XAAC_LD_WAVES_PER_WG - 1) / XAAC_LD_WAVES_PER_WG), block(64 * XAAC_LD_WAVES_PER_WG);
+  const dim3 grid((p->n_ch + XAAC_LD_WAVES_PER_WG - 1) / XAAC_LD_WAVES_PER_WG), block(XAAC_LD_BLOCK);
   const size_t lds = XAAC_LD_LDS(p->frame_length, p->eld);
   if (p->frame_length == 512) {
     if (p->eld) hipLaunchKernelGGL((xaac_imdct_ld_kernel<512, true>), grid, block, lds, stream, *p);

@@ -7,6 +7,9 @@
 
 #include "../../include/xaac_amd.h"
 
+#define XAAC_LIM_BLOCK 64 /* one wave per stream (front, apply) or per 64 streams (gain) */
+#define XAAC_LIM_FRONT_LDS ((2 * (XAAC_LIM_MAX_ATTACK + 1024) + 64) * 4) /* the front kernel's static arrays: s_w, s_g, s_run */
+
 typedef struct XaacLimiterParams {
   int32_t n_streams, frame_len, num_channels;
   int32_t planar; /* samples: [channel][frame_len] per stream instead of [frame_len][channel] */
@@ -28,6 +31,7 @@ extern "C" {
 #endif
 hipError_t xaac_launch_limiter(const XaacLimiterParams *p, hipStream_t stream);
 hipError_t xaac_launch_limiter_map(const XaacLimiterParams *p, hipStream_t stream);
+hipError_t xaac_warm_limiter(void);
 #ifdef __cplusplus
 }
 #endif

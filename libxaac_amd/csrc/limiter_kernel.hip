@@ -271,10 +271,11 @@ __device__ __forceinline__ void apply_frame(const XaacLimiterParams &p, int s, i
 /* CT: channel count known at compile time (1, 2, and 3 .. 6 -- the multichannel configurations: the loads of a phase are then
    all in flight together), 0: any.  MAP: the output map on the PCM16 hand-off (CT != 0), 0: none */
 template <int CT, int MAP = 0>
-__global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParams p) {
+__global__ __launch_bounds__(XAAC_LIM_BLOCK) void xaac_limiter_front_kernel(XaacLimiterParams p) {
   __shared__ float s_w[kMaxW]; /* W: the state's window in time order, then the frame's magnitudes */
   __shared__ float s_g[kMaxW]; /* run suffix maxima, then window maxima; the walk's target gains */
   __shared__ float s_run[64];
+  static_assert(sizeof(s_w) + sizeof(s_g) + sizeof(s_run) == XAAC_LIM_FRONT_LDS, "limiter_kernel.h states this kernel's LDS");
   const int lane = threadIdx.x, s = blockIdx.x;
   xaac_limiter_state *st = p.state + s;
   const int32_t *x = p.samples + (int64_t)s * p.stride;
@@ -506,7 +507,8 @@ __global__ __launch_bounds__(64) void xaac_limiter_front_kernel(XaacLimiterParam
 }
 
 /* ---- step 5: lane = stream ---- */
-__global__ __launch_bounds__(64) void xaac_limiter_gain_kernel(XaacLimiterParams p) {
+static_assert(XAAC_LIM_BLOCK == 64, "the gain kernel's stream index is written for one wave per block");
+__global__ __launch_bounds__(XAAC_LIM_BLOCK) void xaac_limiter_gain_kernel(XaacLimiterParams p) {
   const int s = blockIdx.x * 64 + threadIdx.x;
   const bool mine = s < p.n_streams && p.ws_flag[2 * (s < p.n_streams ? s : 0)] == 0;
   if (!__ballot(mine)) return;
@@ -563,7 +565,7 @@ __global__ __launch_bounds__(64) void xaac_limiter_gain_kernel(XaacLimiterParams
 }
 
 template <int CT, int MAP = 0>
-__global__ __launch_bounds__(64) void xaac_limiter_apply_kernel(XaacLimiterParams p) {
+__global__ __launch_bounds__(XAAC_LIM_BLOCK) void xaac_limiter_apply_kernel(XaacLimiterParams p) {
   const int lane = threadIdx.x, s = blockIdx.x;
   if (p.ws_flag[2 * s] != 0) return; /* finished by the front kernel */
   const float *row = p.ws_gain + (int64_t)s * 1024;
@@ -571,36 +573,28 @@ __global__ __launch_bounds__(64) void xaac_limiter_apply_kernel(XaacLimiterParam
 }
 
 namespace {
+/* a frame's three launches, the front and the apply kernel at <CT, MAP> */
 template <int CT, int MAP>
-hipError_t launch_mapped(const XaacLimiterParams *p, hipStream_t stream) {
-  const dim3 grid(p->n_streams), block(64);
+hipError_t launch_frame(const XaacLimiterParams *p, hipStream_t stream) {
+  const dim3 grid(p->n_streams), block(XAAC_LIM_BLOCK);
   hipLaunchKernelGGL((xaac_limiter_front_kernel<CT, MAP>), grid, block, 0, stream, *p);
-  hipLaunchKernelGGL(xaac_limiter_gain_kernel, dim3((p->n_streams + 63) / 64), block, 0, stream, *p);
+  hipLaunchKernelGGL(xaac_limiter_gain_kernel, dim3((p->n_streams + XAAC_LIM_BLOCK - 1) / XAAC_LIM_BLOCK), block, 0, stream, *p);
   hipLaunchKernelGGL((xaac_limiter_apply_kernel<CT, MAP>), grid, block, 0, stream, *p);
   return hipGetLastError();
 }
 }  // namespace
 
-/* the limiter with an output map on its PCM16 hand-off: the map's channel count is the batch's (xaac_abi.cpp checks) */
+/* the limiter with an output map on its PCM16 hand-off: the map's channel count is the batch's (xaac_abi.cpp checks against the
+   same rows of out_map.h).  No map is no row of this launcher: a missing kernel is an error */
 extern "C" hipError_t xaac_launch_limiter_map(const XaacLimiterParams *p, hipStream_t stream) {
-  switch (p->map_kind) {
-    case XAAC_OUT_MAP_DOWNMIX_STEREO:
-      switch (p->num_channels) {
-        case 3: return launch_mapped<3, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-        case 4: return launch_mapped<4, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-        case 5: return launch_mapped<5, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-        case 6: return launch_mapped<6, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-      }
-      break;
-    case XAAC_OUT_MAP_MONO_MIX: if (p->num_channels == 2) return launch_mapped<2, XAAC_OUT_MAP_MONO_MIX>(p, stream); break;
-    case XAAC_OUT_MAP_MONO_MIX_DUP: if (p->num_channels == 2) return launch_mapped<2, XAAC_OUT_MAP_MONO_MIX_DUP>(p, stream); break;
-    case XAAC_OUT_MAP_DUP_STEREO: if (p->num_channels == 1) return launch_mapped<1, XAAC_OUT_MAP_DUP_STEREO>(p, stream); break;
-  }
-  return hipErrorInvalidValue; /* a missing kernel is an error */
+  hipError_t e = hipErrorInvalidValue;
+  xo_dispatch(p->map_kind, p->num_channels, [&](auto nch, auto map) {
+    if constexpr (decltype(map)::value != XAAC_OUT_MAP_NONE) e = launch_frame<decltype(nch)::value, decltype(map)::value>(p, stream);
+  });
+  return e;
 }
 
 extern "C" hipError_t xaac_launch_limiter(const XaacLimiterParams *p, hipStream_t stream) {
-  const dim3 grid(p->n_streams), block(64);
   /* 3 .. 6 channels from a planar block (what the multichannel decode chain hands over): the instantiations that hold all
      channels of a sample in one lane; every other shape of more than two channels walks them one at a time */
   /* (they store a sample's PCM16 words as 32-bit words where the count is even: a PCM buffer that is not 4-byte aligned keeps
@@ -608,25 +602,14 @@ extern "C" hipError_t xaac_launch_limiter(const XaacLimiterParams *p, hipStream_
   const bool pcm_fits = (p->num_channels & 1) || (reinterpret_cast<uintptr_t>(p->pcm16) & 3) == 0;
   const int ct = p->num_channels <= 2 ? p->num_channels : (p->planar && p->num_channels <= 6 && pcm_fits ? p->num_channels : 0);
   switch (ct) {
-    case 1: hipLaunchKernelGGL(xaac_limiter_front_kernel<1>, grid, block, 0, stream, *p); break;
-    case 2: hipLaunchKernelGGL(xaac_limiter_front_kernel<2>, grid, block, 0, stream, *p); break;
-    case 3: hipLaunchKernelGGL(xaac_limiter_front_kernel<3>, grid, block, 0, stream, *p); break;
-    case 4: hipLaunchKernelGGL(xaac_limiter_front_kernel<4>, grid, block, 0, stream, *p); break;
-    case 5: hipLaunchKernelGGL(xaac_limiter_front_kernel<5>, grid, block, 0, stream, *p); break;
-    case 6: hipLaunchKernelGGL(xaac_limiter_front_kernel<6>, grid, block, 0, stream, *p); break;
-    default: hipLaunchKernelGGL(xaac_limiter_front_kernel<0>, grid, block, 0, stream, *p); break;
+    case 1: return launch_frame<1, 0>(p, stream);
+    case 2: return launch_frame<2, 0>(p, stream);
+    case 3: return launch_frame<3, 0>(p, stream);
+    case 4: return launch_frame<4, 0>(p, stream);
+    case 5: return launch_frame<5, 0>(p, stream);
+    case 6: return launch_frame<6, 0>(p, stream);
   }
-  hipLaunchKernelGGL(xaac_limiter_gain_kernel, dim3((p->n_streams + 63) / 64), block, 0, stream, *p);
-  switch (ct) {
-    case 1: hipLaunchKernelGGL(xaac_limiter_apply_kernel<1>, grid, block, 0, stream, *p); break;
-    case 2: hipLaunchKernelGGL(xaac_limiter_apply_kernel<2>, grid, block, 0, stream, *p); break;
-    case 3: hipLaunchKernelGGL(xaac_limiter_apply_kernel<3>, grid, block, 0, stream, *p); break;
-    case 4: hipLaunchKernelGGL(xaac_limiter_apply_kernel<4>, grid, block, 0, stream, *p); break;
-    case 5: hipLaunchKernelGGL(xaac_limiter_apply_kernel<5>, grid, block, 0, stream, *p); break;
-    case 6: hipLaunchKernelGGL(xaac_limiter_apply_kernel<6>, grid, block, 0, stream, *p); break;
-    default: hipLaunchKernelGGL(xaac_limiter_apply_kernel<0>, grid, block, 0, stream, *p); break;
-  }
-  return hipGetLastError();
+  return launch_frame<0, 0>(p, stream);
 }
 
 /* xaac_warm_up (xaac_abi.cpp): asking for a kernel's attributes puts this translation unit's code object on the device */

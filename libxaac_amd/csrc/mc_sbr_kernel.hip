@@ -137,14 +137,14 @@ hipError_t launch_out_map(const XaacMcPcmOutParams *p, const int32_t (*coef)[6],
   for (int c = 0; c < 6; c++) m.src[c] = 0, m.coef[0][c] = coef[0][c], m.coef[1][c] = coef[1][c];
   for (int c = 0; c < p->n_ch; c++) m.src[p->slot[c]] = c;
   const dim3 grid((unsigned)(((size_t)p->n_streams * 1024 + 255) / 256)), block(256);
-  switch (p->n_ch) {
-    case 3: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<3, T>), grid, block, 0, stream, *p, m); break;
-    case 4: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<4, T>), grid, block, 0, stream, *p, m); break;
-    case 5: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<5, T>), grid, block, 0, stream, *p, m); break;
-    case 6: hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<6, T>), grid, block, 0, stream, *p, m); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  hipError_t e = hipErrorInvalidValue; /* no downmix row of out_map.h for this many channels: no kernel */
+  xo_dispatch(XAAC_OUT_MAP_DOWNMIX_STEREO, p->n_ch, [&](auto nch, auto map) {
+    if constexpr (decltype(map)::value == XAAC_OUT_MAP_DOWNMIX_STEREO) {
+      hipLaunchKernelGGL((xaac_mc_pcm_out_map_kernel<decltype(nch)::value, T>), grid, block, 0, stream, *p, m);
+      e = hipGetLastError();
+    }
+  });
+  return e;
 }
 }  // namespace
 

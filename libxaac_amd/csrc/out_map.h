@@ -16,6 +16,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/xaac_amd.h"
 #include "fx.h"
 
@@ -63,16 +65,36 @@ FX_HD int16_t xo_mono_mix(int16_t l, int16_t r) { return (int16_t)((l >> 1) + (r
 /* ixheaacd_scale_adjust (a wrapping multiply by 2^qshift_adj) and ixheaac_round16 behind it */
 FX_HD int16_t xo_scale_round16(int32_t x, int qshift_adj) { return fx_round16(fx_shlw(x, qshift_adj)); }
 
-/* channels a map leaves of `nch`; 0: the map does not take that many */
+/* The (map kind, channels in, channels out) rows the GPU has a kernel for -- the one list of them: xo_out_channels answers the
+   checks from it and xo_dispatch hands a row to the launchers as compile-time values, so a pair that passes a check has a kernel. */
+#define XO_MAP_ROWS(X)                                                                                                              \
+  X(XAAC_OUT_MAP_NONE, 1, 1) X(XAAC_OUT_MAP_NONE, 2, 2) X(XAAC_OUT_MAP_NONE, 3, 3)                                                  \
+  X(XAAC_OUT_MAP_NONE, 4, 4) X(XAAC_OUT_MAP_NONE, 5, 5) X(XAAC_OUT_MAP_NONE, 6, 6)                                                  \
+  X(XAAC_OUT_MAP_DOWNMIX_STEREO, 3, 2) X(XAAC_OUT_MAP_DOWNMIX_STEREO, 4, 2)                                                         \
+  X(XAAC_OUT_MAP_DOWNMIX_STEREO, 5, 2) X(XAAC_OUT_MAP_DOWNMIX_STEREO, 6, 2)                                                         \
+  X(XAAC_OUT_MAP_MONO_MIX, 2, 1) X(XAAC_OUT_MAP_MONO_MIX_DUP, 2, 2) X(XAAC_OUT_MAP_DUP_STEREO, 1, 2)
+
+/* channels a map leaves of `nch`; 0: the map does not take that many.  (No map leaves any count as it is: the host twin copies
+   the seven and eight channels there is no kernel for; the GPU entry points bound the count themselves.) */
 static inline int xo_out_channels(int kind, int nch) {
-  switch (kind) {
-    case XAAC_OUT_MAP_NONE: return nch;
-    case XAAC_OUT_MAP_DOWNMIX_STEREO: return nch >= 3 && nch <= 6 ? 2 : 0;
-    case XAAC_OUT_MAP_MONO_MIX: return nch == 2 ? 1 : 0;
-    case XAAC_OUT_MAP_MONO_MIX_DUP: return nch == 2 ? 2 : 0;
-    case XAAC_OUT_MAP_DUP_STEREO: return nch == 1 ? 2 : 0;
+#define XO_ROW(k, n, oc) \
+  if (kind == k && nch == n) return oc;
+  XO_MAP_ROWS(XO_ROW)
+#undef XO_ROW
+  return kind == XAAC_OUT_MAP_NONE ? nch : 0;
+}
+
+/* f(integral_constant<int, NCH>, integral_constant<int, MAP>) for the row of (kind, nch); false: there is no such row */
+template <class F>
+static inline bool xo_dispatch(int kind, int nch, F &&f) {
+#define XO_ROW(k, n, oc)                                                         \
+  if (kind == k && nch == n) {                                                   \
+    f(std::integral_constant<int, n>(), std::integral_constant<int, (int)k>());  \
+    return true;                                                                 \
   }
-  return 0;
+  XO_MAP_ROWS(XO_ROW)
+#undef XO_ROW
+  return false;
 }
 
 /* What the sums of a row can reach, over the table itself (the way xp_gsum_fits looks at its table): the largest |term| of a

@@ -5,6 +5,11 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#define XAAC_SCALE_ADJUST_BLOCK 256 /* one lane per (stream, sample); no LDS */
+static inline int64_t xaac_scale_adjust_grid(int32_t n_streams, int32_t frame_len) {
+  return ((int64_t)n_streams * frame_len + XAAC_SCALE_ADJUST_BLOCK - 1) / XAAC_SCALE_ADJUST_BLOCK;
+}
+
 typedef struct XaacScaleAdjustParams {
   int32_t n_streams, frame_len, num_channels;
   int32_t planar;          /* samples: [channel][frame_len] per stream instead of [frame_len][channel] */

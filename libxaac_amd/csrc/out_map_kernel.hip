@@ -13,8 +13,9 @@
 #include "out_map.h"
 #include "out_map_kernel.h"
 
+static_assert(XAAC_SCALE_ADJUST_BLOCK == 256, "the kernel's (stream, sample) index is written for blocks of 256 lanes");
 template <int NCH, int MAP>
-__global__ __launch_bounds__(256) void xaac_scale_adjust_map_kernel(XaacScaleAdjustParams p) {
+__global__ __launch_bounds__(XAAC_SCALE_ADJUST_BLOCK) void xaac_scale_adjust_map_kernel(XaacScaleAdjustParams p) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; /* (stream, sample) */
   const int L = p.frame_len;
   if (e >= (int64_t)p.n_streams * L) return;
@@ -59,42 +60,13 @@ __global__ __launch_bounds__(256) void xaac_scale_adjust_map_kernel(XaacScaleAdj
   }
 }
 
-namespace {
-template <int NCH, int MAP>
-hipError_t launch(const XaacScaleAdjustParams *p, hipStream_t stream) {
-  const int64_t n = (int64_t)p->n_streams * p->frame_len;
-  hipLaunchKernelGGL((xaac_scale_adjust_map_kernel<NCH, MAP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *p);
-  return hipGetLastError();
-}
-}  // namespace
-
-/* the map's channel count is the batch's (xaac_abi.cpp checks); a combination without a kernel is an error */
+/* the map's channel count is the batch's (xaac_abi.cpp checks against the same rows of out_map.h); a pair without a row is an error */
 extern "C" hipError_t xaac_launch_scale_adjust_map(const XaacScaleAdjustParams *p, hipStream_t stream) {
-  const int c = p->num_channels;
-  switch (p->map_kind) {
-    case XAAC_OUT_MAP_NONE:
-      switch (c) {
-        case 1: return launch<1, XAAC_OUT_MAP_NONE>(p, stream);
-        case 2: return launch<2, XAAC_OUT_MAP_NONE>(p, stream);
-        case 3: return launch<3, XAAC_OUT_MAP_NONE>(p, stream);
-        case 4: return launch<4, XAAC_OUT_MAP_NONE>(p, stream);
-        case 5: return launch<5, XAAC_OUT_MAP_NONE>(p, stream);
-        case 6: return launch<6, XAAC_OUT_MAP_NONE>(p, stream);
-      }
-      break;
-    case XAAC_OUT_MAP_DOWNMIX_STEREO:
-      switch (c) {
-        case 3: return launch<3, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-        case 4: return launch<4, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-        case 5: return launch<5, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-        case 6: return launch<6, XAAC_OUT_MAP_DOWNMIX_STEREO>(p, stream);
-      }
-      break;
-    case XAAC_OUT_MAP_MONO_MIX: if (c == 2) return launch<2, XAAC_OUT_MAP_MONO_MIX>(p, stream); break;
-    case XAAC_OUT_MAP_MONO_MIX_DUP: if (c == 2) return launch<2, XAAC_OUT_MAP_MONO_MIX_DUP>(p, stream); break;
-    case XAAC_OUT_MAP_DUP_STEREO: if (c == 1) return launch<1, XAAC_OUT_MAP_DUP_STEREO>(p, stream); break;
-  }
-  return hipErrorInvalidValue;
+  const bool found = xo_dispatch(p->map_kind, p->num_channels, [&](auto nch, auto map) {
+    hipLaunchKernelGGL((xaac_scale_adjust_map_kernel<decltype(nch)::value, decltype(map)::value>),
+                       dim3((unsigned)xaac_scale_adjust_grid(p->n_streams, p->frame_len)), dim3(XAAC_SCALE_ADJUST_BLOCK), 0, stream, *p);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 /* xaac_warm_up (xaac_abi.cpp): asking for a kernel's attributes puts this translation unit's code object on the device */

@@ -6,6 +6,9 @@
 
 #include "../../include/xaac_pvc.h"
 
+#define XAAC_PVC_BLOCK 64 /* one wave per channel */
+#define XAAC_PVC_LDS ((31 * 3 + 16 * 3 + 16 * 3 + 16 * 8) * 4 + (int32_t)sizeof(xaac_pvc_frame)) /* the kernel's static arrays: pvc.h's work space, the frame */
+
 typedef struct XaacPvcParams {
   int32_t n_ch;
   const xaac_pvc_frame *frame;
@@ -17,5 +20,6 @@ typedef struct XaacPvcParams {
 } XaacPvcParams;
 
 hipError_t xaac_launch_pvc(const XaacPvcParams *p, hipStream_t stream);
+extern "C" hipError_t xaac_warm_pvc(void);
 
 #endif

@@ -11,10 +11,12 @@
 #include "pvc.h"
 #include "pvc_kernel.h"
 
-__global__ __launch_bounds__(64) void xaac_pvc_kernel(XaacPvcParams p) {
+__global__ __launch_bounds__(XAAC_PVC_BLOCK) void xaac_pvc_kernel(XaacPvcParams p) {
   const int ch = blockIdx.x;
   __shared__ XpWork w;
   __shared__ xaac_pvc_frame f;
+  static_assert(sizeof(w) + sizeof(f) == XAAC_PVC_LDS, "pvc_kernel.h states this kernel's LDS");
+  static_assert(XAAC_PVC_BLOCK == 64, "the team below is one wave");
   { /* the frame's 40 bytes as ten words */
     const int32_t *src = reinterpret_cast<const int32_t *>(p.frame + ch);
     if (threadIdx.x < sizeof(xaac_pvc_frame) / 4) reinterpret_cast<int32_t *>(&f)[threadIdx.x] = src[threadIdx.x];
@@ -27,7 +29,7 @@ __global__ __launch_bounds__(64) void xaac_pvc_kernel(XaacPvcParams p) {
 }
 
 hipError_t xaac_launch_pvc(const XaacPvcParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_pvc_kernel, dim3(p->n_ch), dim3(64), 0, stream, *p);
+  hipLaunchKernelGGL(xaac_pvc_kernel, dim3(p->n_ch), dim3(XAAC_PVC_BLOCK), 0, stream, *p);
   return hipGetLastError();
 }
 

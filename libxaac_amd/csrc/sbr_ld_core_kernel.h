@@ -7,6 +7,8 @@
 
 #include "../../include/xaac_amd.h"
 
+#define XAAC_SBR_LD_CORE_BLOCK 64 /* one wave per channel, no dynamic LDS: what xaac_sbr_eld_process_batch reports of its chain */
+
 typedef struct XaacSbrLdCoreParams {
   int32_t n_ch, n_slots;
   const xaac_sbr_header *header;
@@ -21,6 +23,7 @@ typedef struct XaacSbrLdCoreParams {
 extern "C" {
 #endif
 hipError_t xaac_launch_sbr_ld_core(const XaacSbrLdCoreParams *p, hipStream_t stream);
+hipError_t xaac_warm_sbr_ld_core(void);
 #ifdef __cplusplus
 }
 #endif

@@ -41,7 +41,7 @@ struct XlLds {
 };
 }  // namespace
 
-__global__ __launch_bounds__(64) void xaac_sbr_ld_core_kernel(XaacSbrLdCoreParams p) {
+__global__ __launch_bounds__(XAAC_SBR_LD_CORE_BLOCK) void xaac_sbr_ld_core_kernel(XaacSbrLdCoreParams p) {
   __shared__ XlLds s;
   const int ch = blockIdx.x, lane = threadIdx.x, n = p.n_slots;
   xaac_sbr_eld_state *gst = p.state + ch;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(64) void xaac_sbr_ld_core_kernel(XaacSbrLdCoreParam
 }
 
 extern "C" hipError_t xaac_launch_sbr_ld_core(const XaacSbrLdCoreParams *p, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_sbr_ld_core_kernel, dim3(p->n_ch), dim3(64), 0, stream, *p);
+  hipLaunchKernelGGL(xaac_sbr_ld_core_kernel, dim3(p->n_ch), dim3(XAAC_SBR_LD_CORE_BLOCK), 0, stream, *p);
   return hipGetLastError();
 }
 

@@ -33,6 +33,7 @@ extern "C" {
 hipError_t xaac_launch_sbr_handover(const xaac_sbr_handover_batch *b, hipStream_t stream);
 hipError_t xaac_launch_sbr_apply_side(const xaac_sbr_apply_side_batch *b, hipStream_t stream);
 hipError_t xaac_launch_ps(const XaacPsParams *p, hipStream_t stream);
+hipError_t xaac_warm_sbr_ps(void);
 #ifdef __cplusplus
 }
 #endif

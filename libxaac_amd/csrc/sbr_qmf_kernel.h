@@ -20,6 +20,10 @@
 /* synthesis: max(row tile, ring-sample store) ; row tile 64 x (64|128)+1 words, store 2 x 41 x 128 int16 */
 #define XAAC_QMF_SYN_LDS_PER_WAVE_LP 21376 /* 2 channels x 41 slots x (128 + 2) ring samples, rounded up */
 #define XAAC_QMF_SYN_LDS_PER_WAVE_HQ (64 * 129 * 4)
+/* ... of a workgroup: what the launches ask for */
+#define XAAC_QMF_ANA_LDS (XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE)
+#define XAAC_QMF_SYN_LDS_LP (XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP)
+#define XAAC_QMF_SYN_LDS_HQ (XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ)
 
 /* state / qmf / scale are addressed with explicit per-channel strides so that the same kernels serve the
    stand-alone QMF entry points (tight arrays) and the fused SBR path (fields inside xaac_sbr_state, rows
@@ -61,6 +65,7 @@ typedef struct XaacQmfSynParams {
 /* HE-AACv2: both complex synthesis banks of a stream in one wave (channel 0 = left, state in xaac_sbr_state; channel
    1 = right, state in xaac_ps_state), output as interleaved L,R pairs.  scale[c] + 8 i: lb, ov_lb, hb, st_syn scales,
    lsb, usb, and [6] != 0 where the channel is not synthesised this frame (bank and output samples left alone). */
+#define XAAC_QMF_SYN_PAIR_BLOCK 128 /* a wave per half of the bands, one workgroup per stream */
 #define XAAC_QMF_SYN_PAIR_LDS (2 * 42 * 65 * 4) /* the 2 x 42 x 65 pair rows; the two 32 x 65-word half-row tiles (one per wave, one channel at a time) alias them */
 typedef struct XaacQmfSynPairParams {
   int32_t n;       /* streams */
@@ -80,6 +85,7 @@ extern "C" {
 #endif
 hipError_t xaac_launch_qmf_synthesis_pair(const XaacQmfSynPairParams *p, hipStream_t stream);
 hipError_t xaac_launch_qmf_analysis(const XaacQmfAnaParams *p, int grid, hipStream_t stream);
+#define XAAC_QMF_ELD_BLOCK 64 /* the low-delay banks: one wave, four channels */
 #define XAAC_QMF_ELD_LDS (4 * (288 + 512) * 2 + 64 * 65 * 4) /* four channels' time-ordered history + the exchange tile */
 /* the LD / ELD banks inside the low-delay SBR chain (xaac_sbr_eld_process_batch): the public batch + where the chain keeps
    things.  All optional: zero = the stand-alone entry points' tight arrays and batch-wide band limits. */
@@ -99,6 +105,7 @@ hipError_t xaac_launch_qmf_synthesis_eld_chain(const xaac_qmf_syn_eld_batch *p, 
 hipError_t xaac_launch_qmf_synthesis_eld(const xaac_qmf_syn_eld_batch *p, hipStream_t stream);
 hipError_t xaac_launch_qmf_synthesis(const XaacQmfSynParams *p, int grid, hipStream_t stream);
 int xaac_qmf_blocks_per_cu(int which);
+hipError_t xaac_warm_sbr_qmf(void);
 #ifdef __cplusplus
 }
 #endif

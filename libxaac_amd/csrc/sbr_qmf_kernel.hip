@@ -662,7 +662,7 @@ typedef short xq_short2 __attribute__((ext_vector_type(2)));
 #define XQ_STAGGER_FIRST 1536 /* six workgroups per CU: the ones that start together */
 #endif
 template <int NS = 32>
-__global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSynPairParams p) {
+__global__ __launch_bounds__(XAAC_QMF_SYN_PAIR_BLOCK) void xaac_qmf_synthesis_pair_kernel(XaacQmfSynPairParams p) {
   constexpr int NH = NS / 2; /* slots a wave window-adds */
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int RS = 65;          /* padded LDS row stride (dwords) of tiles and pair rows */
@@ -881,9 +881,9 @@ __global__ __launch_bounds__(128) void xaac_qmf_synthesis_pair_kernel(XaacQmfSyn
 
 extern "C" hipError_t xaac_launch_qmf_synthesis_pair(const XaacQmfSynPairParams *p, hipStream_t stream) {
   if (p->n_slots == 30) /* 960-sample cores (xaac_sbr_hq960_process_batch) */
-    hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel<30>, dim3(p->n), dim3(128), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
+    hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel<30>, dim3(p->n), dim3(XAAC_QMF_SYN_PAIR_BLOCK), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
   else
-    hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel<32>, dim3(p->n), dim3(128), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
+    hipLaunchKernelGGL(xaac_qmf_synthesis_pair_kernel<32>, dim3(p->n), dim3(XAAC_QMF_SYN_PAIR_BLOCK), XAAC_QMF_SYN_PAIR_LDS, stream, *p);
   return hipGetLastError();
 }
 
@@ -905,7 +905,7 @@ __device__ __forceinline__ int eld_phase(const xaac_qmf_ana_eld_state *st) { /* 
 }
 }  // namespace
 
-__global__ __launch_bounds__(64) void xaac_qmf_analysis_eld_kernel(xaac_qmf_ana_eld_batch p, XaacQmfEldChain cn) {
+__global__ __launch_bounds__(XAAC_QMF_ELD_BLOCK) void xaac_qmf_analysis_eld_kernel(xaac_qmf_ana_eld_batch p, XaacQmfEldChain cn) {
   const auto state_of = [&](int ch) {
     return reinterpret_cast<xaac_qmf_ana_eld_state *>(reinterpret_cast<char *>(p.state) +
                                                       (size_t)ch * (cn.state_stride ? cn.state_stride : (int)sizeof(xaac_qmf_ana_eld_state)));
@@ -1005,7 +1005,7 @@ __device__ __forceinline__ int eld_syn_phase(const xaac_qmf_syn_eld_state *st) {
 }
 }  // namespace
 
-__global__ __launch_bounds__(64) void xaac_qmf_synthesis_eld_kernel(xaac_qmf_syn_eld_batch p, XaacQmfEldChain cn) {
+__global__ __launch_bounds__(XAAC_QMF_ELD_BLOCK) void xaac_qmf_synthesis_eld_kernel(xaac_qmf_syn_eld_batch p, XaacQmfEldChain cn) {
   const auto state_of = [&](int ch) {
     return reinterpret_cast<xaac_qmf_syn_eld_state *>(reinterpret_cast<char *>(p.state) +
                                                       (size_t)ch * (cn.state_stride ? cn.state_stride : (int)sizeof(xaac_qmf_syn_eld_state)));
@@ -1096,7 +1096,7 @@ __global__ __launch_bounds__(64) void xaac_qmf_synthesis_eld_kernel(xaac_qmf_syn
 }
 
 extern "C" hipError_t xaac_launch_qmf_synthesis_eld_chain(const xaac_qmf_syn_eld_batch *p, const XaacQmfEldChain *c, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_qmf_synthesis_eld_kernel, dim3((p->n_ch + 3) / 4), dim3(64), XAAC_QMF_ELD_SYN_LDS, stream, *p, *c);
+  hipLaunchKernelGGL(xaac_qmf_synthesis_eld_kernel, dim3((p->n_ch + 3) / 4), dim3(XAAC_QMF_ELD_BLOCK), XAAC_QMF_ELD_SYN_LDS, stream, *p, *c);
   return hipGetLastError();
 }
 extern "C" hipError_t xaac_launch_qmf_synthesis_eld(const xaac_qmf_syn_eld_batch *p, hipStream_t stream) {
@@ -1105,7 +1105,7 @@ extern "C" hipError_t xaac_launch_qmf_synthesis_eld(const xaac_qmf_syn_eld_batch
 }
 
 extern "C" hipError_t xaac_launch_qmf_analysis_eld_chain(const xaac_qmf_ana_eld_batch *p, const XaacQmfEldChain *c, hipStream_t stream) {
-  hipLaunchKernelGGL(xaac_qmf_analysis_eld_kernel, dim3((p->n_ch + 3) / 4), dim3(64), XAAC_QMF_ELD_LDS, stream, *p, *c);
+  hipLaunchKernelGGL(xaac_qmf_analysis_eld_kernel, dim3((p->n_ch + 3) / 4), dim3(XAAC_QMF_ELD_BLOCK), XAAC_QMF_ELD_LDS, stream, *p, *c);
   return hipGetLastError();
 }
 extern "C" hipError_t xaac_launch_qmf_analysis_eld(const xaac_qmf_ana_eld_batch *p, hipStream_t stream) {
@@ -1117,14 +1117,14 @@ extern "C" hipError_t xaac_launch_qmf_analysis(const XaacQmfAnaParams *p, int gr
   if (p->n_slots == 30) { /* 960-sample cores (xaac_sbr_lp960_process_batch, xaac_sbr_hq960_process_batch) */
     if (p->low_pow)
       hipLaunchKernelGGL((xaac_qmf_analysis_kernel<true, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                         XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
+                         XAAC_QMF_ANA_LDS, stream, *p);
     else
       hipLaunchKernelGGL(xaac_qmf_analysis_hq_kernel<30>, dim3((p->n_ch + 1) / 2), dim3(128), 0, stream, *p);
     return hipGetLastError();
   }
   if (p->low_pow)
     hipLaunchKernelGGL(xaac_qmf_analysis_kernel<true>, dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE, stream, *p);
+                       XAAC_QMF_ANA_LDS, stream, *p);
   else /* two channels per workgroup, not persistent: `grid` (sized for the low-power kernel) does not apply */
     hipLaunchKernelGGL(xaac_qmf_analysis_hq_kernel<32>, dim3((p->n_ch + 1) / 2), dim3(128), 0, stream, *p);
   return hipGetLastError();
@@ -1135,24 +1135,24 @@ extern "C" hipError_t xaac_launch_qmf_synthesis(const XaacQmfSynParams *p, int g
     if (p->down_sample) return hipErrorInvalidValue;
     if (p->low_pow)
       hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, false, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                         XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);
+                         XAAC_QMF_SYN_LDS_LP, stream, *p);
     else
       hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<false, false, 30>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                         XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ, stream, *p);
+                         XAAC_QMF_SYN_LDS_HQ, stream, *p);
     return hipGetLastError();
   }
   if (p->low_pow && p->down_sample)
     hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, true>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);
+                       XAAC_QMF_SYN_LDS_LP, stream, *p);
   else if (p->low_pow)
     hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<true, false>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP, stream, *p);
+                       XAAC_QMF_SYN_LDS_LP, stream, *p);
   else if (p->down_sample)
     hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<false, true>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ, stream, *p);
+                       XAAC_QMF_SYN_LDS_HQ, stream, *p);
   else
     hipLaunchKernelGGL((xaac_qmf_synthesis_kernel<false, false>), dim3(grid), dim3(XAAC_QMF_BLOCK),
-                       XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ, stream, *p);
+                       XAAC_QMF_SYN_LDS_HQ, stream, *p);
   return hipGetLastError();
 }
 
@@ -1160,10 +1160,10 @@ extern "C" int xaac_qmf_blocks_per_cu(int which) {
   int n = 0;
   hipError_t e;
   switch (which) {
-    case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xaac_qmf_analysis_kernel<true>, XAAC_QMF_BLOCK, XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE); break;
-    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xaac_qmf_analysis_kernel<false>, XAAC_QMF_BLOCK, XAAC_QMF_WAVES * XAAC_QMF_ANA_LDS_PER_WAVE); break;
-    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (xaac_qmf_synthesis_kernel<true, false>), XAAC_QMF_BLOCK, XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_LP); break;
-    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (xaac_qmf_synthesis_kernel<false, false>), XAAC_QMF_BLOCK, XAAC_QMF_WAVES * XAAC_QMF_SYN_LDS_PER_WAVE_HQ); break;
+    case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xaac_qmf_analysis_kernel<true>, XAAC_QMF_BLOCK, XAAC_QMF_ANA_LDS); break;
+    case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xaac_qmf_analysis_kernel<false>, XAAC_QMF_BLOCK, XAAC_QMF_ANA_LDS); break;
+    case 2: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (xaac_qmf_synthesis_kernel<true, false>), XAAC_QMF_BLOCK, XAAC_QMF_SYN_LDS_LP); break;
+    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (xaac_qmf_synthesis_kernel<false, false>), XAAC_QMF_BLOCK, XAAC_QMF_SYN_LDS_HQ); break;
   }
   if (e != hipSuccess || n < 1) n = 1;
   return n;

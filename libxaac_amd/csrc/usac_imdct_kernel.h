@@ -8,6 +8,7 @@
 #include "../../include/xaac_amd.h"
 
 #define XAAC_USAC_WAVES_PER_WG 4
+#define XAAC_USAC_BLOCK (64 * XAAC_USAC_WAVES_PER_WG)
 #define XAAC_USAC_LDS (XAAC_USAC_WAVES_PER_WG * 2 * 1024 * 4)
 
 typedef struct XaacUsacImdctParams {
@@ -37,6 +38,7 @@ extern "C" {
 #endif
 hipError_t xaac_launch_usac_fac(const XaacUsacFacParams *p, hipStream_t stream);
 hipError_t xaac_launch_usac_imdct(const XaacUsacImdctParams *p, hipStream_t stream);
+hipError_t xaac_warm_usac_imdct(void);
 #ifdef __cplusplus
 }
 #endif

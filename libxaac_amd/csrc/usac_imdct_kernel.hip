@@ -265,7 +265,7 @@ __device__ __forceinline__ int frame(const XaacUsacImdctParams &p, int ch, int32
 #ifndef XU_MIN_WAVES
 #define XU_MIN_WAVES 1
 #endif
-__global__ __launch_bounds__(64 * XAAC_USAC_WAVES_PER_WG, XU_MIN_WAVES) void xaac_usac_imdct_kernel(XaacUsacImdctParams p) {
+__global__ __launch_bounds__(XAAC_USAC_BLOCK, XU_MIN_WAVES) void xaac_usac_imdct_kernel(XaacUsacImdctParams p) {
   extern __shared__ __attribute__((aligned(16))) int32_t smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ch = blockIdx.x * XAAC_USAC_WAVES_PER_WG + wave;
@@ -301,7 +301,7 @@ extern "C" hipError_t xaac_launch_usac_fac(const XaacUsacFacParams *p, hipStream
 
 extern "C" hipError_t xaac_launch_usac_imdct(const XaacUsacImdctParams *p, hipStream_t stream) {
   const int wgs = (p->n_ch + XAAC_USAC_WAVES_PER_WG - 1) / XAAC_USAC_WAVES_PER_WG;
-  hipLaunchKernelGGL(xaac_usac_imdct_kernel, dim3(wgs), dim3(64 * XAAC_USAC_WAVES_PER_WG), XAAC_USAC_LDS, stream, *p);
+  hipLaunchKernelGGL(xaac_usac_imdct_kernel, dim3(wgs), dim3(XAAC_USAC_BLOCK), XAAC_USAC_LDS, stream, *p);
   return hipGetLastError();
 }
 

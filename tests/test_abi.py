@@ -80,6 +80,30 @@ def test_version_string():
     assert b"gfx950" in libxaac_amd.load_library().xaac_version()
 
 
+# Workspace sizes are part of the ABI (callers cache them, and an entry point refuses one byte less): the values the library gave
+# before the layouts were stated once in xaac_abi.cpp, taken from that build for these counts.
+WS_COUNTS = (-1, 0, 1, 2, 3, 64, 255, 8192)
+WS_BYTES = {
+    ("xaac_sbr_lp_workspace_bytes",): (0, 384, 10640, 20896, 31152, 656768, 2615664, 84017536),
+    ("xaac_sbr_hq_workspace_bytes", 0): (0, 640, 21140, 41640, 62140, 1312640, 5228140, 167936640),
+    ("xaac_sbr_hq_workspace_bytes", 1): (0, 640, 37540, 74440, 111340, 2362240, 9410140, 302285440),
+    ("xaac_sbr_eld_workspace_bytes",): (0, 0, 8720, 16928, 25136, 525824, 2093552, 67240448),
+    ("xaac_esbr_workspace_bytes",): (0, 0, 98304, 196608, 294912, 6291456, 25067520, 805306368),
+    ("xaac_esbr_workspace_bytes_ratio", 0): (0, 0, 98304, 196608, 294912, 6291456, 25067520, 805306368),
+    ("xaac_esbr_workspace_bytes_ratio", 1): (0, 0, 98304, 196608, 294912, 6291456, 25067520, 805306368),
+    ("xaac_esbr_workspace_bytes_ratio", 2): (0, 0, 119808, 239616, 359424, 7667712, 30551040, 981467136),
+    ("xaac_peak_limiter_workspace_bytes",): (0, 256, 4360, 8464, 12568, 262912, 1046776, 33620224),
+}
+
+
+def test_workspace_sizes_are_the_published_ones():
+    lib = libxaac_amd.load_library()
+    for (name, *rest), want in sorted(WS_BYTES.items()):
+        fn = getattr(lib, name)
+        got = tuple(int(fn(n, *rest)) for n in WS_COUNTS)
+        assert got == want, (name, rest)
+
+
 def test_null_and_bad_arguments_are_fatal_codes():
     lib = libxaac_amd.load_library()
     assert lib.xaac_create(None, 0, None) & 0x80000000

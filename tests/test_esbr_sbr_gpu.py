@@ -64,6 +64,7 @@ def test_chain_vs_oracle(oracle):
             prev_modes[ch] = [f.sbr_invf_mode[i] for i in range(10)]
         pack = lambda xs: torch.from_numpy(np.stack([np.frombuffer(bytes(x), np.uint8) for x in xs])).to(dev)
         ctx.esbr_sbr_process_batch(torch.from_numpy(core).to(dev), pack(hs), pack(fs), pack(sds), st_g, out, ws, status)
+        assert ctx.last_launch() == {"grid": n, "block": 64, "lds_bytes": 0}  # (what the chain reports: its core launch)
         ctx.sync()
         o_g, s_g, rc_g = out.cpu().numpy(), st_g.cpu().numpy(), status.cpu().numpy()
         for ch in range(n):

@@ -168,6 +168,7 @@ def test_gpu_apply_matches_reference_and_oracle(oracle):
         pv_re = torch.full((n, 32, 64), 7.5, dtype=torch.float32, device=dev)
         pv_im = torch.full((n, 32, 64), 7.5, dtype=torch.float32, device=dev)
         ctx.hbe_apply_batch(torch.from_numpy(re).to(dev), torch.from_numpy(im).to(dev), state, pv_re, pv_im, status, pitch)
+        assert ctx.last_launch() == {"grid": n, "block": 256, "lds_bytes": 47580}  # the products launch
         ctx.sync()
         got, g_re, g_im = state.cpu().numpy(), pv_re.cpu().numpy(), pv_im.cpu().numpy()
         assert status.cpu().tolist() == [0] * (2 * nchain) + [-1, -1]
@@ -229,6 +230,7 @@ def test_gpu_dft_bank_matches_reference_chains():
         qr = torch.from_numpy(np.stack([i[1][0] for i in ins])).to(dev)
         qi = torch.from_numpy(np.stack([i[1][1] for i in ins])).to(dev)
         ctx.hbe_dft_anal_batch(t, cre, cim, state, qr, qi, cfg)
+        assert ctx.last_launch() == {"grid": n, "block": 256, "lds_bytes": 16384}
         ctx.sync()
         s, a, b = state.cpu().numpy(), qr.cpu().numpy(), qi.cpu().numpy()
         for c in range(n):

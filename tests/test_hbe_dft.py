@@ -197,6 +197,7 @@ def test_gpu_reproduces_the_committed_reference_chains_in_one_batch():
         ovs = torch.tensor([i[2] for i in ins], dtype=torch.int32, device=dev)
         pitch = torch.tensor([i[3] for i in ins], dtype=torch.int32, device=dev)
         ctx.hbe_dft_apply_batch(qre, qim, cfg_tab, coef_re, coef_im, state, pv_re, pv_im, status, pitch_in_bins=pitch, oversampling=ovs, cfg=cfg_idx)
+        assert ctx.last_launch() == {"grid": n, "block": 256, "lds_bytes": 44080}  # the transposer's core launch
         torch.cuda.synchronize()
         assert (status == 0).all()
         pr, pi = pv_re.cpu().numpy(), pv_im.cpu().numpy()

@@ -171,6 +171,7 @@ def test_host_buffer_entry_point(ctx, oracle):
     h_ovl, h_state = ovl.copy(), state.copy()
     out32 = np.zeros(n * 1024, np.int32); pcm = np.zeros(n * 1024, np.int16); q = np.zeros(n, np.int8)
     ctx.imdct_process_batch_host(spec, ics, h_ovl, h_state, out32, pcm, q)
+    assert ctx.last_launch() == {"grid": 33, "block": 256, "lds_bytes": 40448}  # 130 channel-frames, four waves a workgroup
     assert np.array_equal(out32.reshape(n, 1024), want["out32"])
     assert np.array_equal(pcm.reshape(n, 1024), want["pcm16"])
     assert np.array_equal(h_ovl, want["overlap"]) and np.array_equal(h_state, want["state"])

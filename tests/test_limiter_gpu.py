@@ -41,6 +41,7 @@ def run_gpu(ctx, torch, x, q, states, nch, frame_len, stride=None):
     status = torch.full((n,), 77, dtype=torch.int32, device="cuda")
     ws = torch.zeros(ctx.peak_limiter_workspace_bytes(n), dtype=torch.uint8, device="cuda")
     ctx.peak_limiter_process_batch(xs, qs, st, nch, ws, frame_len=frame_len, pcm16=pcm, stride=stride, status=status)
+    assert ctx.last_launch() == {"grid": n, "block": 64, "lds_bytes": 12288}  # a wave per stream; the front kernel's arrays
     ctx.sync()
     return xs.cpu().numpy(), pcm.cpu().numpy(), tensor_to_states(st, n), status.cpu().numpy()
 

@@ -75,6 +75,7 @@ def test_mapped_limiter_equals_the_twin_of_the_unmapped_call(ctx, n_ch, kind, pl
         ctx.peak_limiter_process_batch(a, qd, states[0], n_ch, ws, pcm16=plain, planar=planar)
         ctx.sync()
         ctx.peak_limiter_process_map_batch(b, qd, states[1], n_ch, ws, mapped[:n * 1024 * out_ch], m, planar=planar)
+        assert ctx.last_launch() == {"grid": n, "block": 64, "lds_bytes": 12288}
         ctx.sync()
         got = mapped.cpu().numpy()
         assert (got[n * 1024 * out_ch:] == 0x1234).all()
@@ -183,6 +184,7 @@ def test_limiter_off_hand_off_equals_scale_adjust_round16_and_the_twin(ctx, n_ch
             xd = torch.from_numpy(xs.reshape(-1).copy()).cuda()
             pcm = torch.full((n * L * out_ch + 64,), 0x1234, dtype=torch.int16, device="cuda")
             ctx.pcm16_scale_adjust_map_batch(xd, torch.from_numpy(q.reshape(-1).copy()).cuda(), n_ch, pcm[:n * L * out_ch], m, planar=planar)
+            assert ctx.last_launch() == {"grid": (n * L + 255) // 256, "block": 256, "lds_bytes": 0}  # a lane per (stream, sample)
             ctx.sync()
             got = pcm.cpu().numpy()
             assert (got[n * L * out_ch:] == 0x1234).all()

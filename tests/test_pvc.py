@@ -95,6 +95,7 @@ def _gpu_walk(chains, n_frames):
         out = torch.full((n, 16, 64), -7.0, dtype=torch.float32, device=dev)
         status = torch.full((n,), 5, dtype=torch.int32, device=dev)
         ctx.pvc_process_batch(frame, re, im, state, out, status)
+        assert ctx.last_launch() == {"grid": n, "block": 64, "lds_bytes": 1308}  # a wave per channel; 317 work floats + the 40-byte frame
         ctx.sync()
         o, s, rc = out.cpu().numpy(), state.cpu().numpy(), status.cpu().numpy()
         for k in range(n):

@@ -32,6 +32,7 @@ def test_analysis_chain(ctx, oracle, low_pow, n_ch, ch_fac):
         want, o_state = oracle_lib.qmf_analysis_batch(oracle, pcm, o_state, low_pow, 32, ss, ch_fac)
         qmf = torch.full((n_ch, 32, ss), 0x55555555, dtype=torch.int32, device="cuda")
         ctx.qmf_analysis_batch(torch.from_numpy(pcm).cuda(), t_state, qmf, low_pow, 32, ss, ch_fac)
+        assert ctx.last_launch() == {"grid": (n_ch + 1) // 2, "block": 64, "lds_bytes": 21920}  # (what the entry reports for both banks)
         torch.cuda.synchronize()
         got = qmf.cpu().numpy()
         if low_pow:
@@ -61,6 +62,7 @@ def test_synthesis_chain(ctx, oracle, low_pow, n_ch, ch_fac):
         t_qmf = torch.from_numpy(qmf).cuda()
         before = t_qmf.clone()
         ctx.qmf_synthesis_batch(t_qmf, torch.from_numpy(scale).cuda(), t_state, pcm, low_pow, lsb, usb, 6, ss, ch_fac)
+        assert ctx.last_launch() == {"grid": (n_ch + 1) // 2, "block": 64, "lds_bytes": 21376 if low_pow else 33024}
         torch.cuda.synchronize()
         assert torch.equal(t_qmf, before), "qmf input must not be modified"
         assert np.array_equal(pcm.cpu().numpy(), want), f

@@ -81,6 +81,7 @@ def test_gpu_walks_the_reference_chains(n_slots):
         hand = torch.zeros(m * n_slots * 128, dtype=torch.int32, device=dev)
         status = torch.full((m,), 7, dtype=torch.int32, device=dev)
         ctx.sbr_eld_process_batch(pin, g("header"), g("frame"), t_st, out, ws, n_slots, status=status, qmf_handed_on=hand)
+        assert ctx.last_launch() == {"grid": m, "block": 64, "lds_bytes": 0}  # (what the chain reports: its core launch)
         ctx.sync()
         assert np.array_equal(status.cpu().numpy(), CH["ret"][rows]), s
         o, hd, stn = out.cpu().numpy().reshape(m, -1), hand.cpu().numpy().reshape(m, -1), t_st.cpu().numpy()

@@ -33,6 +33,7 @@ def gpu_run(ctx, headers, frames, states, pcm_in, in_ch_fac=1, out_ch_fac=1):
     ws = torch.zeros(ctx.sbr_lp_workspace_bytes(n), dtype=torch.uint8, device="cuda")
     ctx.sbr_lp_process_batch(torch.from_numpy(np.ascontiguousarray(pcm_in)).cuda(), t_h, t_f, t_s, out, ws, status,
                              in_ch_fac, out_ch_fac)
+    assert ctx.last_launch() == {"grid": (n + 1) // 2, "block": 64, "lds_bytes": 21376}  # the synthesis bank (n stays small here)
     torch.cuda.synchronize()
     return out.cpu().numpy(), t_s.cpu().numpy(), status.cpu().numpy()
 

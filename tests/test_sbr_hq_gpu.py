@@ -35,6 +35,9 @@ def gpu_run(ctx, headers, frames, states, ps_frames, ps_states, pcm_in, max_band
     ws = torch.zeros(ctx.sbr_hq_workspace_bytes(n, with_ps), dtype=torch.uint8, device="cuda")
     ctx.sbr_hq_process_batch(torch.from_numpy(np.ascontiguousarray(pcm_in)).cuda(), t_h, t_f, t_s, out, ws, t_pf, t_ps,
                              status, max_band_hint=max_band_hint)
+    # the chain's last launch: the pair bank, a workgroup of two waves per stream | the HQ bank, a wave per two streams (n stays small)
+    assert ctx.last_launch() == ({"grid": n, "block": 128, "lds_bytes": 21840} if with_ps else
+                                 {"grid": (n + 1) // 2, "block": 64, "lds_bytes": 33024})
     torch.cuda.synchronize()
     return out.cpu().numpy(), t_s.cpu().numpy(), (t_ps.cpu().numpy() if with_ps else None), status.cpu().numpy()
 
