@@ -18,6 +18,7 @@ import os
 __all__ = [
     "ONLY_LONG_SEQUENCE", "LONG_START_SEQUENCE", "EIGHT_SHORT_SEQUENCE", "LONG_STOP_SEQUENCE",
     "PCM_LC", "PCM_SBR", "BAD_WINDOW_SEQ", "XaacError", "XaacContext", "load_library", "library_path",
+    "decode_mixed",
 ]
 
 # decoder/ixheaacd_cnst.h:100-103
@@ -1208,3 +1209,10 @@ class XaacContext:
         rc = self._lib.xaac_sbr_lp960_process_batch(self._h, ctypes.byref(b))
         if rc != 0:
             raise XaacError(rc, "xaac_sbr_lp960_process_batch")
+
+
+def decode_mixed(streams, **kwargs):
+    """libxaac_amd.decoder.decode_mixed: ADTS streams of several kinds in one call -> (PCM arrays, output rates), both in the
+    order of `streams`.  (The decoder module builds on this one, so it is imported by the first call.)"""
+    from . import decoder
+    return decoder.decode_mixed(streams, **kwargs)

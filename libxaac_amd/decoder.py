@@ -767,7 +767,7 @@ class _SbrBase(_Chain):
         self.frm_d2[slot].copy_(step.frm, non_blocking=True)
         if eside_d is not None:
             eside_d.copy_(step.eside, non_blocking=True)
-        if self.n_ch == 1 and (step.flags[got, F_PS] != 0).all():   # the PS frames, when every delivered frame has one
+        if self.n_ch == 1 and (step.flags[got, F_PS] != 0).any():   # the PS frames, when a delivered frame has one
             self.psf_d2[slot].copy_(step.psf, non_blocking=True)
 
 
@@ -808,15 +808,20 @@ class _SbrChain(_SbrBase):
             ctx.sbr_lp_process_batch(self.core16, hdr_d, frm_d, state, pcm, self.ws, status=status, in_ch_fac=2, out_ch_fac=2)
         else:
             with_ps = flags[got, F_PS] != 0
-            if with_ps.any() != with_ps.all():
-                raise NotImplementedError("a batch mixing PS and non-PS frames")
-            if with_ps.all():
+            if with_ps.any():
                 starts = np.nonzero(got & (flags[:, F_PS_START] != 0))[0]
                 if starts.size:
                     idx = torch.from_numpy(starts.astype(np.int32)).to(self.dev)
                     ctx.sbr_state_handover(HANDOVER_PS_START, idx, idx, state, self.ps_state)
                 ctx.sbr_hq_process_batch(self.core16, hdr_d, frm_d, state, pcm, self.ws, ps_frame=self.psf_d2[slot],
                                          ps_state=self.ps_state, status=status)
+                if not with_ps.all():
+                    # streams with and without parametric stereo in one step (HE-AAC beside HE-AACv2 mono streams): the PS launch
+                    # passes a stream without PS through as the mono frame it is and leaves its right samples alone (as the
+                    # native decoder runs such a step, host/xaacdec_amd.cpp: SbrChain::run_hq_ps): the left ones go there too
+                    rows = torch.from_numpy(np.nonzero(got & (flags[:, F_PS] == 0))[0]).to(self.dev)
+                    both = pcm.view(n, 2048, 2)
+                    both[rows, :, 1] = both[rows, :, 0]
             else:
                 ctx.sbr_hq_process_batch(self.core16, hdr_d, frm_d, state, self.pcm_mono, self.ws, status=status)
                 # mono duplicated to stereo (api.c:3639-3660)
@@ -921,13 +926,16 @@ class _EsbrChain(_SbrBase):
         if self.trace is not None:   # debugging: the device states in front of the chain call
             self.trace(dict(state=state, hbe=self.hbe, ps_state=self.ps_state, core=self.core, side=eside_d, header=hdr_d, frame=frm_d))
         with_ps = (flags[got, F_PS] != 0) if n_ch == 1 else np.zeros(1, bool)
-        if with_ps.any() != with_ps.all():
-            raise NotImplementedError("a batch mixing PS and non-PS frames")
-        ps = with_ps.all()      # float parametric stereo: the chain writes both channels
+        ps = with_ps.any()      # float parametric stereo: the chain writes both channels
         psf_d, ps_state, out_r = (self.psf_d2[slot], self.ps_state, self.out_r) if ps else (None, None, None)
         right, stride = (out_r, 2048) if ps else self.plain
         ctx.esbr_sbr_process_batch(self.core, hdr_d, frm_d, eside_d, state, out_l, self.ws, status=self.status2[slot], ps_frame=psf_d,
                                    ps_state=ps_state, out_r=out_r, hbe_state=self.hbe, hbe_max_synth_size=self.hbe_hint())
+        if ps and not with_ps.all():
+            # streams without PS in a PS step: the float PS launch skips them and leaves their rows of out_r alone
+            # (esbr_ps_kernel.hip); they are mono frames, the left channel twice (EsbrChain::run of the native decoder)
+            rows = torch.from_numpy(np.nonzero(got & (flags[:, F_PS] == 0))[0]).to(self.dev)
+            out_r[rows] = out_l[rows]
         ctx.esbr_pcm16_from_float(out_l, right, self.pcm2[slot], stride=stride)
         return (self.n, 2048, 2), 0, first      # the first frame's output is not written in this mode
 
@@ -1233,3 +1241,120 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     with _TorchCpuThreads():
         return _Pipeline(streams, ctx, device, threads, keep_pcm, overlap, esbr, _trace, frames_per_parse, bool(gpu_tools),
                          bool(mc_sbr), out_map, limiter).run(timing)
+
+
+def stream_kind(data):
+    """the kind of an ADTS stream, as the batch calls need it to be one for all their streams: (core sampling rate, channels, frame
+    0 carries an SBR payload, channel_config 3 .. 6 of a stream of several channel elements or else 0).  CPU only."""
+    data = bytes(data)
+    hdr = AdtsHeader()
+    rc = load_host_library().xaac_adts_parse_header(data[:16], min(16, len(data)), ctypes.byref(hdr))
+    if rc:
+        raise ParseError(rc, 0)
+    channels, n_elems, sbr, config = probe_first_frame(data)
+    return int(hdr.sampling_rate), int(channels), bool(sbr), int(config) if n_elems > 1 else 0
+
+
+def _default_parser_threads():
+    """the size the parser library's team takes when nobody names one (host/xaac_parse.cpp: batch_threads)"""
+    hw = os.cpu_count() or 1
+    return min(min(hw // 2, 48) if hw >= 4 else hw, 2 * usable_cores())
+
+
+# one group of decode_mixed: its kind (stream_kind), the places of its streams in the caller's list, its share of the parser threads
+MixedGroup = collections.namedtuple("MixedGroup", "kind index threads")
+
+
+def plan_mixed(streams, out_map=None, threads=0):
+    """What decode_mixed does before anything touches a GPU: probes every stream and sorts the list into groups of one kind, in the
+    order in which the list first names the kinds, every group's streams in list order.  -> [MixedGroup].
+    ValueError: a stream of channel_config 3 .. 6 beside another kind ("channel configurations", as decode_streams says it), or an
+    out_map that one of the groups refuses (_pick_out_map's message behind "stream <i>: ", i the first such stream of the list).
+    threads: the whole call's parser threads (0: the library's default), shared out over several groups in proportion to their
+    streams, one at least; a single group keeps the value as it is."""
+    if out_map is not None and out_map not in ("downmix", "mono", "mono_dup", "dup"):
+        _pick_out_map(out_map, 0, False, 0)    # (a name that is none of the maps: its own message, no stream's)
+    by_kind = {}
+    for i, d in enumerate(streams):
+        by_kind.setdefault(stream_kind(d), []).append(i)
+    if len(by_kind) > 1 and any(kind[3] for kind in by_kind):
+        raise ValueError("streams of different channel configurations in one batch")
+    for (_, n_ch, sbr, config), index in by_kind.items():    # (in the order of the groups' first streams)
+        try:
+            _pick_out_map(out_map, n_ch, sbr, config)
+        except ValueError as e:
+            raise ValueError("stream %d: %s" % (index[0], e)) from None
+    if len(by_kind) == 1:
+        return [MixedGroup(kind, index, int(threads)) for kind, index in by_kind.items()]
+    team = int(threads) if int(threads) > 0 else _default_parser_threads()
+    return [MixedGroup(kind, index, max(1, team * len(index) // len(streams))) for kind, index in by_kind.items()]
+
+
+def restore_list_order(groups, results, n):
+    """results[g][k] belongs to stream groups[g].index[k] of the caller's list -> the n results in list order"""
+    out = [None] * n
+    for g, per_stream in zip(groups, results):
+        if len(per_stream) != len(g.index):
+            raise ValueError("a group of %d streams with %d results" % (len(g.index), len(per_stream)))
+        for i, r in zip(g.index, per_stream):
+            out[i] = r
+    if any(r is None for r in out):
+        raise ValueError("the groups do not cover the list")
+    return out
+
+
+def decode_mixed(streams, device="cuda:0", serial=False, esbr=False, gpu_tools=False, out_map=None, limiter=True, threads=0,
+                 frames_per_parse=4, keep_pcm=True):
+    """Decodes ADTS streams of several kinds in one call: mono and stereo, any core sampling rate, AAC-LC beside HE-AAC and
+    HE-AACv2.  -> (list of int16 [samples, channels] arrays, list of output sampling rates), both in the order of `streams`.
+
+    The kind of a stream is (core sampling rate, channels, SBR payload in the first frame) -- what decode_streams wants to be
+    the same for all its streams.  Every stream is probed on the CPU (stream_kind) and the list sorted into groups of one kind
+    (plan_mixed); every group is decoded as decode_streams decodes it, by a pipeline of its own on its own torch.cuda.Stream with
+    its own XaacContext, driven by one Python thread per group, so that the groups' copies and kernels share the device side by
+    side.  The groups share nothing but the parser library's one team of threads: its calls queue, and `threads` (the whole
+    call's, 0: the library's default) is shared out over the groups in proportion to their streams.  serial=True runs the
+    same groups one after the other on the calling thread (the same PCM: to measure what side by side gains, or to find the
+    group an error belongs to).
+    esbr, gpu_tools, out_map, limiter, frames_per_parse, keep_pcm: as decode_streams takes them, for every group what they mean
+    for a list of that kind alone (AAC-LC groups decode the same with either esbr; "dup" doubles a mono AAC-LC group's channel
+    and is a no-op on the others).  An out_map that one group refuses is a ValueError that names the first such stream of the
+    list ("stream <i>: ..."), raised before any GPU work, and nothing is decoded.  A stream of channel_config 3 .. 6 is only
+    taken beside streams of its own kind (one group: decode_streams' path); beside another kind it is the ValueError "streams of
+    different channel configurations in one batch", also before any GPU work -- its flags (mc_sbr, "downmix") mean nothing
+    for the other kinds.  An SBR mono stream comes out in two channels, as decode_streams and the reference write it.
+    An error inside one group's pipeline is raised here once every group has ended (the first group's, in list order)."""
+    global torch
+    groups = plan_mixed(streams, out_map, threads)    # (the refusals: before torch is so much as imported)
+    import threading
+    import torch
+    dev = torch.device(device)
+    results, errors = [None] * len(groups), [None] * len(groups)
+
+    def run_group(k):
+        g = groups[k]
+        try:
+            own = torch.cuda.Stream(dev)
+            with torch.cuda.device(dev), torch.cuda.stream(own):   # (the pipeline's context launches on the thread's current stream)
+                results[k] = _Pipeline([streams[i] for i in g.index], None, dev, g.threads, keep_pcm, True, esbr, None,
+                                       frames_per_parse, bool(gpu_tools), False, out_map, limiter).run(None)
+                own.synchronize()
+        except BaseException as e:   # (handed to the caller's thread)
+            errors[k] = e
+
+    with _TorchCpuThreads():
+        if serial or len(groups) == 1:
+            for k in range(len(groups)):
+                run_group(k)
+        else:
+            team = [threading.Thread(target=run_group, args=(k,), name="decode_mixed-%d" % k) for k in range(len(groups))]
+            for t in team:
+                t.start()
+            for t in team:
+                t.join()
+    for e in errors:
+        if e is not None:
+            raise e
+    pcm = restore_list_order(groups, [r[0] for r in results], len(streams))
+    rates = restore_list_order(groups, [[r[1]] * len(g.index) for g, r in zip(groups, results)], len(streams))
+    return pcm, rates

@@ -6,7 +6,7 @@
  * stream's state resident in device memory.  No reference code, no Python, no torch: HIP runtime + the two libraries.
  *
  *   xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:<0|1>] [-copies:<N>] [-verify] [-threads:<T>] [-quiet]
- *   xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-esbr:<0|1>] [-threads:<T>] [-quiet]
+ *   xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-esbr:<0|1>] [-threads:<T>] [-serialgroups:<0|1>] [-quiet]
  *   ... [-gpus:<G>] [-device:<k>] [-plan] [-gputools:<0|1>] [-mcsbr:<0|1>]
  *   ... [-downmix:<0|1>] [-dmix:<0|1>] [-tostereo:<0|1>] [-peak_limiter_off:<0|1>]
  *
@@ -37,8 +37,16 @@
  *
  * -copies:N decodes N instances of the stream in one lock-step batch (the first one's PCM is written; with -verify all N are
  * compared with it word for word) and prints the end-to-end rate: the shape a serving host has, with one input here for brevity.
- * -ilist decodes different streams of one kind (sampling rate, channels, SBR / PS or not) in one batch, each to <odir>/<name>.wav;
- * a stream that ends drops out of the steps, the others go on.
+ * -ilist decodes different streams in one run, each to <odir>/<name>.wav.  The streams of one kind (core sampling rate, one or two
+ * channels, an SBR payload in the first frame or not) are a group, in list order: one lock-step batch with its own Job, in which a
+ * stream that ends drops out of the steps and the others go on.  A list of several kinds has several groups, and every (device,
+ * group) that has streams gets a host thread with its own HIP stream and context, as the shards of -gpus do: the groups run side by
+ * side and share only the parser library's team (-threads:T is divided over them in proportion to their streams).  Every flag
+ * means for a group what it means for a list of that kind alone; an output stage flag that one group refuses refuses the run, with
+ * the first such file's name, before a device is looked at.  Every file has its own group's channels, rate and header; the closing
+ * line's "groups" array (only there for several groups) has the groups in the order of their first files.  -serialgroups:1 runs
+ * the groups one after the other (the same files: to measure what side by side gains, or to find the group that fails).  A stream
+ * of more than two channels is only taken beside streams of its own kind: mixed with others the list is refused up front.
  *
  * The shape of a shard (decode_shard), the same as libxaac_amd/decoder.py has in Python (used by the tests for its ease of
  * inspection): ShardOwner hands out and releases what the shard allocates; ParseSide owns the parsers, the staging groups and
@@ -275,9 +283,11 @@ void write_wav(const std::string &path, const std::vector<int16_t> &pcm, int cha
   fclose(f);
 }
 
-/* what the command line fixes for every shard */
+/* what the command line fixes for every shard of one group: the streams of one kind (core sampling rate, channels, SBR or not) of
+   a list in list order, or the copies of the one input */
 struct Job {
-  std::vector<std::vector<uint8_t>> datas; /* -ilist: one per stream; else the one input */
+  std::vector<std::vector<uint8_t>> datas; /* -ilist: one per stream of the group; else the one input */
+  std::vector<int> index;                  /* -ilist: where each of them stands in the list (what the messages call it) */
   int n_ch, sbr, esbr, out_ch, rate, per;
   int channel_config; /* 3 .. 6: a stream of several channel elements (with sbr: -mcsbr:1, Path A only); 0: one element, the mono / stereo paths */
   int n_els;          /* channel elements of a frame: 1, or the configuration's 2 .. 4 */
@@ -427,7 +437,7 @@ class ParseSide {
              here (what it delivered so far is written), the batch goes on */
           if (!J_.list_mode) die("a frame does not parse", r);
           if (!broken_[(size_t)i])
-            fprintf(stderr, "xaacdec_amd: stream %d: a frame does not parse (%d) at byte %llu: the stream ends here\n", lo_ + i, r,
+            fprintf(stderr, "xaacdec_amd: stream %d: a frame does not parse (%d) at byte %llu: the stream ends here\n", J_.index[(size_t)(lo_ + i)], r,
                     (unsigned long long)pos_[(size_t)i]);
           broken_[(size_t)i] = 1;
           r = XAAC_PARSE_NEED_DATA;
@@ -1277,7 +1287,7 @@ class ShardDriver {
      in front of this frame, the batch goes on (its rows keep running; nothing more of them is written) */
   void refuse(size_t i, int row, const char *who) {
     if (!J_.list_mode) die((std::string("the ") + who + " refused a frame").c_str(), row);
-    fprintf(stderr, "xaacdec_amd: stream %zu: the %s refused a frame: the stream ends here\n", (size_t)S_.lo + i, who);
+    fprintf(stderr, "xaacdec_amd: stream %d: the %s refused a frame: the stream ends here\n", J_.index[(size_t)S_.lo + i], who);
     refused_[i] = 1;
   }
   void consume() { /* what a step leaves for the host once its copy down has arrived */
@@ -1391,12 +1401,114 @@ void decode_shard(const Job &J, Shard &S) {
   ShardDriver(J, S, *S.mem).run();
 }
 
+/* the flags that decide what a kind of stream goes through */
+struct Flags {
+  int esbr, hq, gputools, mcsbr, downmix, dmix, tostereo, lim_off;
+};
+
+/* One group of a run: the streams of one kind -- an -ilist of mono and stereo streams has as many groups as kinds, in the order in
+   which the list first names them; every other run has one -- with its Job, its shards over the devices and what its files' headers
+   say.  Groups share nothing but the parser library's team of threads. */
+struct Group {
+  FirstFrame kind;
+  Job J;
+  std::vector<Shard> shards;
+  uint32_t mask;
+  int out_rate;
+  long frames() const {
+    long f = 0;
+    for (const Shard &S : shards) f += S.frames;
+    return f;
+  }
+};
+
+/* What the flags mean for one kind of stream, as they mean it for a list of that kind alone: the part of the Job that follows
+   from the kind.  -> nullptr, or why this decoder does not take the output stage flags on that kind (nothing has been opened or
+   written yet; the caller says which file it was). */
+const char *fill_job(Job &J, const FirstFrame &f0, const Flags &F) {
+  const int n_ch = f0.n_ch, sbr = f0.sbr;
+  if (f0.channel_config && sbr) {
+    if (!F.mcsbr) die("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported");
+    if (F.hq) die("-mcsbr:1 with -esbr_hq:1 (the DFT transposer in a stream of more than two channels) is not supported");
+    if (!F.esbr) die("-mcsbr:1 with -esbr:0 (the fixed-point SBR tools in a stream of more than two channels) is not supported");
+    if (2 * f0.rate > 48000) die("-mcsbr:1 with a down-sampled bank (an output rate above 48 kHz) is not supported");
+  }
+  const int downmix = F.downmix, dmix = F.dmix, tostereo = F.tostereo;
+  if (downmix && dmix) return "-downmix:1 together with -dmix:1 is not supported";
+  if (downmix && n_ch <= 2) return "-downmix:1 on a stream of one or two channels is not supported (there is nothing to mix down)";
+  if (downmix && (n_ch > 6 || !f0.channel_config)) return "-downmix:1 takes channel configurations 3 .. 6";
+  if (dmix && (sbr || n_ch > 2)) return "-dmix:1 on a stream with SBR or with more than two channels is not supported";
+  if (dmix && tostereo && n_ch == 1) return "-dmix:1 together with -tostereo:1 on a mono stream is not supported";
+
+  xaac_out_map map;
+  memset(&map, 0, sizeof(map));
+  if (downmix) { /* the frame's channel elements and their slots (layout_of): SCE CPE [SCE | CPE [LFE]] */
+    static const int k_type[4][4] = {{0, 1}, {0, 1, 0}, {0, 1, 1}, {0, 1, 1, 3}}, k_slot[4][4] = {{2, 0}, {2, 0, 3}, {2, 0, 3}, {2, 0, 4, 3}};
+    map.kind = XAAC_OUT_MAP_DOWNMIX_STEREO, map.matrix = n_ch == 6, map.n_elements = n_ch == 3 ? 2 : (n_ch == 6 ? 4 : 3);
+    for (int k = 0; k < map.n_elements; k++) map.element_type[k] = k_type[n_ch - 3][k], map.element_slot[k] = k_slot[n_ch - 3][k];
+  } else if (dmix && n_ch == 2) {
+    map.kind = tostereo ? XAAC_OUT_MAP_MONO_MIX_DUP : XAAC_OUT_MAP_MONO_MIX;
+  } else if (tostereo && n_ch == 1 && !sbr) {
+    map.kind = XAAC_OUT_MAP_DUP_STEREO;
+  } /* (everything else is a no-op in the reference too) */
+  J.hq = F.hq, J.gputools = F.gputools;
+  J.n_ch = n_ch, J.sbr = sbr, J.rate = f0.rate, J.per = sbr ? 2048 : 1024;
+  J.esbr = sbr ? F.esbr : 0;       /* AAC-LC streams decode the same either way */
+  J.lim_off = sbr ? 0 : F.lim_off; /* no limiter on the SBR paths: the flag changes nothing there */
+  /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC, and everything with more than two channels, as coded;
+     with a map, what the map leaves */
+  J.out_ch = map.kind == XAAC_OUT_MAP_MONO_MIX ? 1 : (map.kind != XAAC_OUT_MAP_NONE ? 2 : (sbr && !f0.channel_config ? 2 : n_ch));
+  J.map = map;
+  J.channel_config = f0.channel_config;
+  memset(J.slot, 0, sizeof(J.slot));
+  J.n_els = 1, J.first_ch[0] = J.first_ch[1] = J.first_ch[2] = J.first_ch[3] = 0;
+  if (J.channel_config) { /* SCE CPE [SCE | CPE [LFE]] */
+    static const int k_first[4][4] = {{0, 1}, {0, 1, 3}, {0, 1, 3}, {0, 1, 3, 5}};
+    J.n_els = J.channel_config == 3 ? 2 : (J.channel_config == 6 ? 4 : 3);
+    for (int k = 0; k < 4; k++) J.first_ch[k] = k_first[J.channel_config - 3][k];
+  }
+  for (int c = 0; c < 8; c++) {
+    J.el_of_ch[c] = 0;
+    for (int k = 1; k < J.n_els; k++)
+      if (c >= J.first_ch[k]) J.el_of_ch[c] = k;
+  }
+  return nullptr;
+}
+
+/* the size the parser library's team takes when nobody names one (host/xaac_parse.cpp: batch_threads, less its look at a cgroup's
+   quota): what the groups of a mixed list share when -threads is not given -- one default for the run, not one per group */
+int default_parser_threads() {
+  const int hw = (int)std::thread::hardware_concurrency();
+  int t = hw >= 4 ? (hw / 2 > 48 ? 48 : hw / 2) : (hw > 0 ? hw : 1);
+  cpu_set_t set;
+  const int usable = sched_getaffinity(0, sizeof(set), &set) == 0 ? CPU_COUNT(&set) : 0;
+  if (usable > 0 && t > 2 * usable) t = 2 * usable;
+  return t;
+}
+
+const char *const k_map_name[] = {"none", "downmix", "mono", "mono_dup", "dup"};
+
+void print_shards(const std::vector<Shard> &shards, int group) { /* -plan: a group's split; group >= 0: with the group's number */
+  for (size_t r = 0; r < shards.size(); r++) {
+    printf("%s{\"device\": %d, ", r ? ", " : "", shards[r].device);
+    if (group >= 0) printf("\"group\": %d, ", group);
+    printf("\"lo\": %d, \"n\": %d}", shards[r].lo, shards[r].n);
+  }
+}
+/* -plan: what a group's streams come out as (the keys a run of one group has had all along) */
+void print_plan_kind(const Group &G) {
+  const Job &J = G.J;
+  printf("\"channels\": %d, \"sbr\": %d, \"esbr\": %d, \"out_channels\": %d, \"out_map\": \"%s\", \"limiter\": %d, \"wav_header\": \"%s\"", J.n_ch,
+         J.sbr, J.esbr, J.out_ch, k_map_name[J.map.kind], !J.sbr && !J.lim_off, J.out_ch > 2 ? "extensible68" : "pcm44");
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
   std::string in, out, ilist, odir;
   int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0, gputools = 0, mcsbr = 0;
-  int downmix = 0, dmix = 0, tostereo = 0, lim_off = 0;
+  int downmix = 0, dmix = 0, tostereo = 0, lim_off = 0, serialgroups = 0;
+  bool bad_flag = false;
   const struct {
     const char *name;
     int *value;
@@ -1421,6 +1533,9 @@ int main(int argc, char **argv) {
     else if (a.rfind("-device:", 0) == 0) device0 = atoi(a.c_str() + 8);
     else if (a == "-plan") plan = 1;
     else if (a == "-wrap_devices") wrap = 1; /* shard r on device (k + r) mod the node's count: the -gpus host path on a box with fewer devices */
+    else if (a == "-serialgroups:0") serialgroups = 0;
+    else if (a == "-serialgroups:1") serialgroups = 1; /* the groups of a mixed list one after the other (to measure what side by side gains) */
+    else if (a.rfind("-serialgroups", 0) == 0) bad_flag = true;
     else if (a == "-quiet") quiet = 1;
     else if (a == "-verify") verify = 1;
     else if (a == "-profile") profile = 1; /* synchronise behind every phase of a step and report the seconds spent in each */
@@ -1451,9 +1566,14 @@ int main(int argc, char **argv) {
   } else if (!in.empty()) {
     inputs.push_back(in);
   }
-  if (inputs.empty() || (ilist.empty() && out.empty() && !plan) || copies < 1 || gpus < 1 || device0 < 0) {
+  if (bad_flag || inputs.empty() || (ilist.empty() && out.empty() && !plan) || copies < 1 || gpus < 1 || device0 < 0) {
     fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-gputools:0|1] [-mcsbr:0|1] [-quiet]\n"
+                    "       xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-serialgroups:0|1] [the flags above but -copies]\n"
                     "       [-downmix:0|1] [-dmix:0|1] [-tostereo:0|1] [-peak_limiter_off:0|1]\n"
+                    "  -ilist  mono and stereo streams of any sampling rate, with SBR or without, in one list: the streams of one kind are one group,\n"
+                    "          the groups run side by side, every flag means for a group what it means for a list of that kind alone; a stream of\n"
+                    "          more than two channels only beside streams of its own kind (refused before anything is written)\n"
+                    "  -serialgroups:1  the groups of such a list one after the other on one thread (the same files)\n"
                     "  -mcsbr:1  decode HE-AAC streams of more than two channels (channel_config 3 .. 6, SBR per channel element; default flags only)\n"
                     "  -downmix:1  3 .. 6 channels come out in stereo (the reference's downmix matrix; a 44-byte stereo WAV header)\n"
                     "  -dmix:1  a stereo AAC-LC stream comes out mono, with -tostereo:1 the mono mix in both channels\n"
@@ -1473,141 +1593,183 @@ int main(int argc, char **argv) {
     fclose(f);
     datas[k].resize((size_t)n);
   }
-  const FirstFrame f0 = first_frame(datas[0], true);
-  for (size_t k = 1; k < datas.size(); k++) { /* -ilist: one kind of stream per batch */
-    const FirstFrame f = first_frame(datas[k], false);
-    if (f.rate != f0.rate || f.n_ch != f0.n_ch || f.sbr != f0.sbr || f.channel_config != f0.channel_config)
-      die("-ilist: streams of different kinds (sampling rate, channels, channel configuration, SBR) in one batch");
-  }
-  const int n_ch = f0.n_ch, sbr = f0.sbr;
-  if (f0.channel_config && sbr) {
-    if (!mcsbr) die("multichannel SBR (an SBR payload in a stream of more than two channels) is not supported");
-    if (hq) die("-mcsbr:1 with -esbr_hq:1 (the DFT transposer in a stream of more than two channels) is not supported");
-    if (!esbr) die("-mcsbr:1 with -esbr:0 (the fixed-point SBR tools in a stream of more than two channels) is not supported");
-    if (2 * f0.rate > 48000) die("-mcsbr:1 with a down-sampled bank (an output rate above 48 kHz) is not supported");
-  }
-
-  /* the output stage flags: what this decoder does not take is refused here, before anything is opened or written */
-  if (downmix && dmix) reject("-downmix:1 together with -dmix:1 is not supported");
-  if (downmix && n_ch <= 2) reject("-downmix:1 on a stream of one or two channels is not supported (there is nothing to mix down)");
-  if (downmix && (n_ch > 6 || !f0.channel_config)) reject("-downmix:1 takes channel configurations 3 .. 6");
-  if (dmix && (sbr || n_ch > 2)) reject("-dmix:1 on a stream with SBR or with more than two channels is not supported");
-  if (dmix && tostereo && n_ch == 1) reject("-dmix:1 together with -tostereo:1 on a mono stream is not supported");
-
-  if (!sbr) esbr = 0; /* AAC-LC streams decode the same either way */
-  xaac_out_map map;
-  memset(&map, 0, sizeof(map));
-  if (downmix) { /* the frame's channel elements and their slots (layout_of): SCE CPE [SCE | CPE [LFE]] */
-    static const int k_type[4][4] = {{0, 1}, {0, 1, 0}, {0, 1, 1}, {0, 1, 1, 3}}, k_slot[4][4] = {{2, 0}, {2, 0, 3}, {2, 0, 3}, {2, 0, 4, 3}};
-    map.kind = XAAC_OUT_MAP_DOWNMIX_STEREO, map.matrix = n_ch == 6, map.n_elements = n_ch == 3 ? 2 : (n_ch == 6 ? 4 : 3);
-    for (int k = 0; k < map.n_elements; k++) map.element_type[k] = k_type[n_ch - 3][k], map.element_slot[k] = k_slot[n_ch - 3][k];
-  } else if (dmix && n_ch == 2) {
-    map.kind = tostereo ? XAAC_OUT_MAP_MONO_MIX_DUP : XAAC_OUT_MAP_MONO_MIX;
-  } else if (tostereo && n_ch == 1 && !sbr) {
-    map.kind = XAAC_OUT_MAP_DUP_STEREO;
-  } /* (everything else is a no-op in the reference too) */
-  if (sbr) lim_off = 0; /* no limiter on the SBR paths: the flag changes nothing there */
-  /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC, and everything with more than two channels, as coded;
-     with a map, what the map leaves */
-  const int out_ch = map.kind == XAAC_OUT_MAP_MONO_MIX ? 1 : (map.kind != XAAC_OUT_MAP_NONE ? 2 : (sbr && !f0.channel_config ? 2 : n_ch));
-  const int N = ilist.empty() ? copies : (int)datas.size(), rate = f0.rate, out_rate = sbr ? 2 * rate : rate, per = sbr ? 2048 : 1024;
-
-  /* the split: contiguous stream ranges over the devices, as bench.py --gpus N splits over ranks (a shard without streams is
-     not started: -gpus larger than the batch uses as many devices as there are streams) */
+  /* the kinds of stream the run holds, in the order in which the list first names them, and which stream is of which */
   const bool list_mode = !ilist.empty();
-  if (gpus > N) gpus = N;
-  std::vector<Shard> shards((size_t)gpus);
-  for (int r = 0; r < gpus; r++) {
-    int lo, hi;
-    shard_range(N, r, gpus, &lo, &hi);
-    shards[(size_t)r].device = device0 + r, shards[(size_t)r].lo = lo, shards[(size_t)r].n = hi - lo;
+  std::vector<Group> groups;
+  std::vector<std::vector<int>> members;
+  bool several_elements = false;
+  for (size_t k = 0; k < datas.size(); k++) {
+    const FirstFrame f = first_frame(datas[k], k == 0);
+    several_elements = several_elements || f.channel_config != 0;
+    size_t g = 0;
+    for (; g < groups.size(); g++) {
+      const FirstFrame &o = groups[g].kind;
+      if (f.rate == o.rate && f.n_ch == o.n_ch && f.sbr == o.sbr && f.channel_config == o.channel_config) break;
+    }
+    if (g == groups.size()) {
+      groups.emplace_back();
+      groups.back().kind = f;
+      members.emplace_back();
+    }
+    members[g].push_back((int)k);
   }
+  /* a stream of several channel elements only beside streams of its own kind: its files have another header and its flags
+     (-mcsbr, -downmix) refuse every other kind, so such a list is refused as a whole, here, before anything is opened or written */
+  if (groups.size() > 1 && several_elements)
+    die("-ilist: streams of different kinds (sampling rate, channels, channel configuration, SBR) in one batch");
+  const bool mixed = groups.size() > 1;
+
+  /* one Job per group.  The output stage flags are looked at per group: what this decoder does not take on one of them is refused
+     here for the whole run, before a device is looked at or a file written (a mixed list: with the name of the first file it is
+     refused for -- the groups stand in the order of their first files) */
+  const Flags F = {esbr, hq, gputools, mcsbr, downmix, dmix, tostereo, lim_off};
+  const int total = list_mode ? (int)datas.size() : copies;
+  /* -threads:T is the whole run's: the groups of a mixed list take shares of it in proportion to their streams, one at least */
+  const int team_threads = threads > 0 ? threads : default_parser_threads();
+  int gpus_used = 0;
+  for (size_t g = 0; g < groups.size(); g++) {
+    Group &G = groups[g];
+    Job &J = G.J;
+    if (const char *why = fill_job(J, G.kind, F)) reject(mixed ? (inputs[(size_t)members[g][0]] + ": " + why).c_str() : why);
+    const int N = list_mode ? (int)members[g].size() : copies;
+    const int share = (int)((long)team_threads * N / total);
+    J.threads = mixed ? (share > 1 ? share : 1) : threads;
+    J.verify = verify, J.profile = profile, J.list_mode = list_mode;
+    if (list_mode) {
+      for (int k : members[g]) J.datas.push_back(std::move(datas[(size_t)k]));
+      J.index = members[g];
+    } else {
+      J.datas = std::move(datas);
+    }
+    G.mask = J.channel_config ? layout_of(J.channel_config, J.slot) : 0;
+    G.out_rate = J.sbr ? 2 * J.rate : J.rate;
+    /* the split: contiguous stream ranges over the devices, as bench.py --gpus N splits over ranks (a shard without streams is
+       not started: -gpus larger than a group uses as many devices as the group has streams) */
+    const int g_gpus = gpus > N ? N : gpus;
+    G.shards.resize((size_t)g_gpus);
+    for (int r = 0; r < g_gpus; r++) {
+      int lo, hi;
+      shard_range(N, r, g_gpus, &lo, &hi);
+      G.shards[(size_t)r].device = device0 + r, G.shards[(size_t)r].lo = lo, G.shards[(size_t)r].n = hi - lo;
+    }
+    gpus_used = g_gpus > gpus_used ? g_gpus : gpus_used;
+  }
+  gpus = gpus_used;
+  const Group &G0 = groups[0]; /* the first listed stream's group: what the run's own lines say of the kind of stream */
   if (plan) { /* nothing below this line runs: no HIP call has been made */
-    static const char *const k_map[] = {"none", "downmix", "mono", "mono_dup", "dup"};
-    printf("{\"streams\": %d, \"gpus\": %d, \"channels\": %d, \"sbr\": %d, \"esbr\": %d, \"out_channels\": %d, \"out_map\": \"%s\", "
-           "\"limiter\": %d, \"wav_header\": \"%s\", \"shards\": [",
-           N, gpus, n_ch, sbr, esbr, out_ch, k_map[map.kind], !sbr && !lim_off, out_ch > 2 ? "extensible68" : "pcm44");
-    for (int r = 0; r < gpus; r++)
-      printf("%s{\"device\": %d, \"lo\": %d, \"n\": %d}", r ? ", " : "", shards[(size_t)r].device, shards[(size_t)r].lo, shards[(size_t)r].n);
-    printf("]}\n");
+    printf("{\"streams\": %d, \"gpus\": %d, ", total, gpus);
+    print_plan_kind(G0);
+    printf(", \"shards\": [");
+    if (!mixed) print_shards(G0.shards, -1);
+    for (size_t g = 0; mixed && g < groups.size(); g++) {
+      if (g) printf(", ");
+      print_shards(groups[g].shards, (int)g); /* (lo counts within the group) */
+    }
+    printf("]");
+    if (mixed) { /* per group: what its files are, which list entries it holds and its own split */
+      printf(", \"groups\": [");
+      for (size_t g = 0; g < groups.size(); g++) {
+        const Group &G = groups[g];
+        printf("%s{\"rate\": %d, \"core_rate\": %d, \"streams\": %zu, \"threads\": %d, ", g ? ", " : "", G.out_rate, G.J.rate, members[g].size(), G.J.threads);
+        print_plan_kind(G);
+        printf(", \"list_index\": [");
+        for (size_t k = 0; k < members[g].size(); k++) printf("%s%d", k ? ", " : "", members[g][k]);
+        printf("], \"shards\": [");
+        print_shards(G.shards, -1);
+        printf("]}");
+      }
+      printf("], \"serialgroups\": %d", serialgroups);
+    }
+    printf("}\n");
     return 0;
   }
   {
     int have = 0;
     HIP(hipGetDeviceCount(&have));
-    if (wrap && have > 0)
-      for (Shard &S : shards) S.device %= have;
-    else if (device0 + gpus > have) {
+    if (wrap && have > 0) {
+      for (Group &G : groups)
+        for (Shard &S : G.shards) S.device %= have;
+    } else if (device0 + gpus > have) {
       fprintf(stderr, "xaacdec_amd: -device:%d -gpus:%d asks for devices %d..%d, the node has %d\n", device0, gpus, device0, device0 + gpus - 1, have);
       return 2;
     }
   }
-  Job J;
-  J.datas = std::move(datas);
-  J.hq = hq;
-  J.n_ch = n_ch, J.sbr = sbr, J.esbr = esbr, J.out_ch = out_ch, J.rate = rate, J.per = per;
-  J.channel_config = f0.channel_config;
-  memset(J.slot, 0, sizeof(J.slot));
-  const uint32_t mask = J.channel_config ? layout_of(J.channel_config, J.slot) : 0;
-  J.n_els = 1, J.first_ch[0] = J.first_ch[1] = J.first_ch[2] = J.first_ch[3] = 0;
-  if (J.channel_config) { /* SCE CPE [SCE | CPE [LFE]] */
-    static const int k_first[4][4] = {{0, 1}, {0, 1, 3}, {0, 1, 3}, {0, 1, 3, 5}};
-    J.n_els = J.channel_config == 3 ? 2 : (J.channel_config == 6 ? 4 : 3);
-    for (int k = 0; k < 4; k++) J.first_ch[k] = k_first[J.channel_config - 3][k];
-  }
-  for (int c = 0; c < 8; c++) {
-    J.el_of_ch[c] = 0;
-    for (int k = 1; k < J.n_els; k++)
-      if (c >= J.first_ch[k]) J.el_of_ch[c] = k;
-  }
-  J.threads = threads, J.verify = verify, J.profile = profile, J.list_mode = list_mode, J.gputools = gputools;
-  J.map = map, J.lim_off = lim_off;
-  const auto t_run = std::chrono::steady_clock::now();
-  if (gpus == 1) {
-    decode_shard(J, shards[0]);
-  } else {
+  /* every (group, device) that has streams: one host thread with its own HIP stream and context.  -serialgroups:1: the groups one
+     after the other (a group's shards side by side, as a run of that group alone has them) */
+  const auto run_side_by_side = [](const std::vector<std::pair<const Job *, Shard *>> &work) {
+    if (work.size() == 1) return decode_shard(*work[0].first, *work[0].second);
     std::vector<std::thread> team;
-    for (int r = 0; r < gpus; r++) team.emplace_back([&, r] { decode_shard(J, shards[(size_t)r]); });
+    for (const auto &w : work) team.emplace_back([w] { decode_shard(*w.first, *w.second); });
     for (auto &t : team) t.join();
+  };
+  const auto t_run = std::chrono::steady_clock::now();
+  {
+    std::vector<std::pair<const Job *, Shard *>> work;
+    for (Group &G : groups) {
+      for (Shard &S : G.shards) work.push_back({&G.J, &S});
+      if (serialgroups) run_side_by_side(work), work.clear();
+    }
+    if (!work.empty()) run_side_by_side(work);
   }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_run).count();
-  for (Shard &S : shards) S.mem.reset(); /* the shards are done: streams waited for, everything they allocated released */
+  for (Group &G : groups)
+    for (Shard &S : G.shards) S.mem.reset(); /* the shards are done: streams waited for, everything they allocated released */
   long frames = 0, mismatched = 0, first_frames = 0;
-  double parse_s = 0, steady = 0, phase_s[4] = {0, 0, 0, 0};
-  for (const Shard &S : shards) {
-    frames += S.frames, mismatched += S.mismatched, first_frames += S.first_frames;
-    parse_s = S.parse_s > parse_s ? S.parse_s : parse_s;
-    steady = S.steady > steady ? S.steady : steady;
-    for (int k = 0; k < 4; k++) phase_s[k] = S.phase_s[k] > phase_s[k] ? S.phase_s[k] : phase_s[k];
-    /* -verify: every shard's copies were compared with its first one; the shards' first ones with the first shard's */
-    if (verify && !list_mode && &S != &shards[0]) mismatched += S.pcms[0] != shards[0].pcms[0];
-  }
-  const std::vector<int16_t> &pcm = shards[0].pcms[0];
-  if (list_mode) {
-    for (const Shard &S : shards)
-      for (size_t i = 0; i < S.pcms.size(); i++) {
-        std::string base = inputs[(size_t)S.lo + i];
-        const size_t slash = base.find_last_of('/');
-        if (slash != std::string::npos) base = base.substr(slash + 1);
-        const size_t dot = base.find_last_of('.');
-        if (dot != std::string::npos) base = base.substr(0, dot);
-        write_wav(odir + "/" + base + ".wav", S.pcms[i], out_ch, out_rate, mask);
-      }
+  double parse_s = 0, steady = 0;
+  std::vector<std::vector<double>> phase_s(groups.size(), std::vector<double>(4, 0.0));
+  for (size_t g = 0; g < groups.size(); g++)
+    for (const Shard &S : groups[g].shards) {
+      frames += S.frames, mismatched += S.mismatched, first_frames += S.first_frames;
+      parse_s = S.parse_s > parse_s ? S.parse_s : parse_s;
+      steady = S.steady > steady ? S.steady : steady;
+      for (int k = 0; k < 4; k++) phase_s[g][(size_t)k] = S.phase_s[k] > phase_s[g][(size_t)k] ? S.phase_s[k] : phase_s[g][(size_t)k];
+      /* -verify: every shard's copies were compared with its first one; the shards' first ones with the first shard's */
+      if (verify && !list_mode && &S != &G0.shards[0]) mismatched += S.pcms[0] != G0.shards[0].pcms[0];
+    }
+  const std::vector<int16_t> &pcm = G0.shards[0].pcms[0];
+  if (list_mode) { /* every stream with its own group's channel count, output rate and kind of header */
+    for (const Group &G : groups)
+      for (const Shard &S : G.shards)
+        for (size_t i = 0; i < S.pcms.size(); i++) {
+          std::string base = inputs[(size_t)G.J.index[(size_t)S.lo + i]];
+          const size_t slash = base.find_last_of('/');
+          if (slash != std::string::npos) base = base.substr(slash + 1);
+          const size_t dot = base.find_last_of('.');
+          if (dot != std::string::npos) base = base.substr(0, dot);
+          write_wav(odir + "/" + base + ".wav", S.pcms[i], G.J.out_ch, G.out_rate, G.mask);
+        }
   } else {
-    write_wav(out, pcm, out_ch, out_rate, mask);
+    write_wav(out, pcm, G0.J.out_ch, G0.out_rate, G0.mask);
   }
-  if (!quiet && gpus > 1) { /* (the run's own line stays the last one) */
+  if (!quiet && gpus > 1) { /* (the run's own line stays the last one); a device's rate: all it decoded over the longest of its shards */
     printf("{\"per_gpu_frames_per_s\": [");
-    for (size_t r = 0; r < shards.size(); r++) printf("%s%.1f", r ? ", " : "", shards[r].wall > 0 ? shards[r].frames / shards[r].wall : 0.0);
+    for (int r = 0; r < gpus; r++) {
+      long f = 0;
+      double w = 0;
+      for (const Group &G : groups)
+        if ((size_t)r < G.shards.size()) f += G.shards[(size_t)r].frames, w = G.shards[(size_t)r].wall > w ? G.shards[(size_t)r].wall : w;
+      printf("%s%.1f", r ? ", " : "", w > 0 ? f / w : 0.0);
+    }
     printf("]}\n");
   }
-  if (!quiet)
+  if (!quiet) {
+    /* a mixed list: frames and streams are the run's, the kind of stream is the first listed stream's group's, the groups follow */
     printf("{\"frames\": %ld, \"streams\": %d, \"wall_s\": %.4f, \"parse_s\": %.4f, \"frames_per_s\": %.1f, "
            "\"frames_per_s_after_first_step\": %.1f, \"mismatched_copies\": %ld, \"samples\": %zu, \"rate\": %d, \"sbr\": %d, "
-           "\"channels\": %d, \"esbr\": %d, \"gpus\": %d}\n",
-           frames, N, wall, parse_s, frames / wall, frames > first_frames && steady > 0 ? (frames - first_frames) / steady : 0.0, mismatched,
-           pcm.size() / out_ch, out_rate, sbr, n_ch, esbr, gpus);
-  if (profile)
-    printf("{\"h2d_s\": %.4f, \"kernels_s\": %.4f, \"d2h_s\": %.4f, \"host_pcm_s\": %.4f}\n", phase_s[0], phase_s[1], phase_s[2], phase_s[3]);
+           "\"channels\": %d, \"esbr\": %d, \"gpus\": %d",
+           frames, total, wall, parse_s, frames / wall, frames > first_frames && steady > 0 ? (frames - first_frames) / steady : 0.0, mismatched,
+           pcm.size() / G0.J.out_ch, G0.out_rate, G0.J.sbr, G0.J.n_ch, G0.J.esbr, gpus);
+    for (size_t g = 0; mixed && g < groups.size(); g++) {
+      const Group &G = groups[g];
+      printf("%s{\"rate\": %d, \"channels\": %d, \"sbr\": %d, \"esbr\": %d, \"streams\": %zu, \"frames\": %ld}%s", g ? ", " : ", \"groups\": [", G.out_rate,
+             G.J.n_ch, G.J.sbr, G.J.esbr, G.J.index.size(), G.frames(), g + 1 == groups.size() ? "]" : "");
+    }
+    printf("}\n");
+  }
+  for (size_t g = 0; profile && g < groups.size(); g++) { /* a mixed list: a line per group, with the group's number */
+    printf("{");
+    if (mixed) printf("\"group\": %zu, ", g);
+    printf("\"h2d_s\": %.4f, \"kernels_s\": %.4f, \"d2h_s\": %.4f, \"host_pcm_s\": %.4f}\n", phase_s[g][0], phase_s[g][1], phase_s[g][2], phase_s[g][3]);
+  }
   return mismatched ? 3 : 0;
 }
