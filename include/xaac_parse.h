@@ -132,7 +132,9 @@ XAAC_API int32_t xaac_parse_core_tools_side_mc(xaac_parser *p, int32_t element, 
    more than one element (:2384-2387).  An element without payload is a frame whose SBR data is missing, as in the reference: the
    LFE's normal case, whose decoder therefore stays in the up-sampling state (side->apply 0).  side->frame[1] is in use for a
    pair.  xaac_parser_set_esbr applies to all elements (before the first of these calls); xaac_parse_esbr_side_mc /
-   xaac_parse_reset_pitch_mc are xaac_parse_esbr_side / xaac_parse_reset_pitch for one element. */
+   xaac_parse_reset_pitch_mc are xaac_parse_esbr_side / xaac_parse_reset_pitch for one element.
+   Element 0 here and the element of xaac_parse_sbr_side / _esbr_side / _reset_pitch are the same SBR front end: whichever side
+   info call comes first fixes its configuration, parametric stereo included, and calls of either family continue it. */
 XAAC_API int32_t xaac_parse_sbr_side_mc(xaac_parser *p, int32_t element, xaac_sbr_side *side);
 XAAC_API int32_t xaac_parse_esbr_side_mc(xaac_parser *p, int32_t element, int32_t channel, xaac_esbr_side *side);
 XAAC_API int32_t xaac_parse_reset_pitch_mc(xaac_parser *p, int32_t element, int32_t *pitch_in_bins);

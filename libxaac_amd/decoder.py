@@ -178,16 +178,12 @@ class StreamParser:
         if rc:
             raise ParseError(rc, 0)
         self.core_rate = hdr.sampling_rate
-        probe = ctypes.c_void_p()           # a look at frame 0 with a parser of its own: channels, SBR payload or not
-        self.lib.xaac_parser_create(ctypes.byref(probe))
-        rc = self.lib.xaac_parse_adts_frame(probe, self.buf, len(self.data), 1, ctypes.byref(self.core), ctypes.byref(self.used))
-        self.lib.xaac_parser_destroy(probe)
-        if rc:
-            raise ParseError(rc, 0)
-        self.n_ch = self.core.n_ch
+        self.n_ch, n_elems, sbr, _ = probe_first_frame(self.data)   # a look at frame 0: channels, SBR payload or not
+        if n_elems != 1:
+            raise ParseError(-3, 0)         # (several channel elements: parse_stream_mc)
         # the SBR tools run for the frames that carry an SBR payload (api.c:3369-3373: a stream at 24 kHz and below gets an SBR
         # decoder object by implicit signalling, api.c:2160, but without payloads it is never called: plain AAC-LC output)
-        self.sbr = bool(self.core.sbr_bytes > 0) if with_sbr is None else bool(with_sbr)
+        self.sbr = bool(sbr) if with_sbr is None else bool(with_sbr)
 
     def close(self):
         if self.h:

@@ -644,14 +644,8 @@ int xh_core_init(XhCoreState *st, int sr_index) {
   return 0;
 }
 
-int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stage) {
-  xaac_core_tools_state *tools = &st->tools;
-  int n = 0;
-  return xh_parse_raw_data_block_mc(st, br, &el, &tools, 1, &n, stage);
-}
-
-int xh_parse_raw_data_block_mc(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
-                               int *n_els, int stage) {
+int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
+                            int *n_els, int stage) {
   const size_t block_start = br->pos;
   int prev = XH_ID_END, have_channels = 0;
   XhElement *el = els[0]; /* the channel element parsed last: a FIL element behind it carries its SBR payload */

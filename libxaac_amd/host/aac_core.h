@@ -67,7 +67,12 @@ struct XhChannel {
 };
 #define XH_SPEC_WORDS (1024 + 2 * XH_SPEC_SLACK)
 
-/* what is constant between ADTS headers of one stream, and the little state that outlives a frame */
+/* what is constant between ADTS headers of one stream.  (The state that outlives a frame is the caller's, one per channel element:
+   the noise generator xaac_core_tools_state -- pns_seed = pstr_pns_rand_vec_data->current_seed, which starts at 0 and runs on from
+   frame to frame; pns_corr_seed = pstr_pns_corr_info->random_vector: the left channel's seed of a band whose noise the M/S flag
+   correlates; a right channel that substitutes noise in such a band where the left one does not finds the value an earlier frame
+   left, the reference keeps it in scratch memory that AAC-LC decoding does not reuse in between.  Only stage-2 parsing advances it:
+   behind a stage-1 parse the tools' caller keeps the state, xaac_core_tools_apply_host or the GPU's xaac_aac_tools_process_batch.) */
 struct XhCoreState {
   int sr_index;            /* 0 .. 11 */
   int16_t swb_long[52], swb_short[16];
@@ -75,13 +80,6 @@ struct XhCoreState {
   int num_swb_long, num_swb_short;
   int wide;                /* the stream has more than two channels (set by the caller behind xh_core_init): scale factors with
                               q_factor 34 and the 32-bit TNS variant (block.c:1263, channel.c:642, pns_js_thumb.c:328) */
-  xaac_core_tools_state tools; /* the noise generator: pns_seed = pstr_pns_rand_vec_data->current_seed (starts at 0, runs on
-                                  from frame to frame); pns_corr_seed = pstr_pns_corr_info->random_vector: the left channel's
-                                  seed of a band whose noise the M/S flag correlates; a right channel that substitutes noise
-                                  in such a band where the left one does not finds the value an earlier frame left (the
-                                  reference keeps it in scratch memory that AAC-LC decoding does not reuse in between).
-                                  Only stage-2 parsing advances it: behind a stage-1 parse the tools' caller keeps the state
-                                  (xaac_core_tools_apply_host, or the GPU's xaac_aac_tools_process_batch) */
 };
 
 struct XhElement {
@@ -104,19 +102,16 @@ int32_t xh_inverse_quant(int32_t magnitude, int *err);
 /* sr_index 0 .. 11; returns 0 or XH_ERR_UNSUPPORTED */
 int xh_core_init(XhCoreState *st, int sr_index);
 
-/* Parses one raw_data_block at the reader's position (up to and including ID_END and the byte alignment) into the line
-   buffers el->ch[c].spec_mem point to, dequantises,
-   applies the scale factors and the tools (M/S, intensity, PNS, TNS): el->ch[c].spec() are the lines the IMDCT takes.
+/* Parses one raw_data_block at the reader's position (up to and including ID_END and the byte alignment) of up to `cap` channel
+   elements (SCE / CPE / LFE in bitstream order; one more is XH_ERR_UNSUPPORTED): element k into els[k] and the line buffers
+   els[k]->ch[c].spec_mem point to, its noise generator tools[k] -- the reference keeps one core decoder instance, and so one
+   generator, per element (api.c:2433-2458) --; *n_els = how many the block held.  The SBR payload of a FIL element goes to the
+   channel element in front of it.  Dequantises, applies the scale factors and the tools (M/S, intensity, PNS, TNS):
+   el->ch[c].spec() are the lines the IMDCT takes.
    `stage`: 2 = everything; 1 = stop before the tools (spectra as at the entry of ixheaacd_channel_pair_process).
    Returns 0 or a negative XH_ERR_*. */
-int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *el, int stage);
-
-/* The same for a block of up to `cap` channel elements (SCE / CPE / LFE in bitstream order; one more is
-   XH_ERR_UNSUPPORTED): element k into els[k], its noise generator tools[k] -- the reference keeps one core decoder instance,
-   and so one generator, per element (api.c:2433-2458) --; *n_els = how many the block held.  The SBR payload of a FIL element
-   goes to the channel element in front of it. */
-int xh_parse_raw_data_block_mc(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
-                               int *n_els, int stage);
+int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
+                            int *n_els, int stage);
 
 /* What the tools read of the element parsed last, as the boundary struct of include/xaac_tools.h (ms_used and
    pns_correlated as the tools apply them).  Writes the bands below max_sfb, the filters n_filt counts and the scalar

@@ -6,6 +6,7 @@
 #include "../../include/xaac_parse.h"
 #include <stddef.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <functional>
@@ -41,44 +42,47 @@ static const int8_t k_config_elements[7][5] = {{0},
 static const int8_t k_config_channels[7] = {0, 1, 2, 3, 4, 5, 6};
 #define XP_MAX_ELEMENTS 4
 
-/* what a stream of more than one channel element needs beside the parser's first element: allocated by the first
-   multichannel call, so that a mono / stereo stream's parser stays as small as it was */
-struct XpMore {
-  XhElement el[XP_MAX_ELEMENTS - 1];
-  xaac_core_tools_state tools[XP_MAX_ELEMENTS - 1]; /* one noise generator per element, as the reference's core instances */
-  int have_sequence, sequence_n, sequence[XP_MAX_ELEMENTS]; /* the first frame's element ids: later frames must repeat them */
+/* What belongs to one channel element of a stream: the element as parsed last, its noise generator (the reference keeps one core
+   decoder instance, and so one generator, per element: api.c:2433-2458) and its SBR front end (one SBR decoder per element:
+   api.c:2389-2517), set up by the first side info call for the element. */
+struct XpSlot {
+  xaac_core_tools_state tools;
+  XhElement el;
+  int sbr_ready;
+  XsDecoder sbr;
 };
 
-/* ... and the SBR front ends of such a stream, one per channel element as the reference keeps one SBR decoder per element
-   (api.c:2389-2517): allocated by the first xaac_parse_sbr_side_mc call */
-struct XpSbrMc {
-  XsDecoder dec[XP_MAX_ELEMENTS];
-  int ready[XP_MAX_ELEMENTS];
+/* an ADTS frame with several raw data blocks (api.c:2909-2925): the blocks of the frame still to come, whether a 16-bit CRC
+   follows every block, and the bytes of the frame behind the last delivered block (ISO/IEC 13818-7 adts_frame():
+   raw_data_block() + crc_check per block when protection_absent == 0; headerdecode.c:356-362 reads the positions).
+   DELIBERATELY NOT THE REFERENCE'S BEHAVIOUR for protected multi-block frames: api.c:3760-3767 means to skip that word,
+   but its `adts` struct (api.c:2626, zero-initialised per call) is only filled by the call that reads a header, so in the
+   follow-up calls no_raw_data_blocks reads 0, the CRC is never skipped and blocks 2..N of a protected multi-block frame are
+   misparsed there.  This parser follows the syntax; parity with the reference is claimed (and tested against the real
+   decoder) for the unprotected layout only.
+   A step that fails behind a delivered block (sequence, channel count, SBR side info) leaves the stream's read position where it
+   was, so the caller puts back the copy it took before: the next call would otherwise read the ADTS header it is pointed at as
+   a raw data block. */
+struct XpBlocks {
+  int left, crc;
+  size_t frame_left;
 };
 
 struct xaac_parser {
   int sr_index;
   XhCoreState core;
-  XhElement el;
-  int sbr_ready, sampling_rate, esbr;
-  XsDecoder sbr;
-  /* an ADTS frame with several raw data blocks (api.c:2909-2925): the blocks of the frame still to come, the bytes of the
-     frame behind the last delivered block, and whether a 16-bit CRC follows every block (ISO/IEC 13818-7 adts_frame():
-     raw_data_block() + crc_check per block when protection_absent == 0; headerdecode.c:356-362 reads the positions).
-     DELIBERATELY NOT THE REFERENCE'S BEHAVIOUR for protected multi-block frames: api.c:3760-3767 means to skip that word,
-     but its `adts` struct (api.c:2626, zero-initialised per call) is only filled by the call that reads a header, so in the
-     follow-up calls no_raw_data_blocks reads 0, the CRC is never skipped and blocks 2..N of a protected multi-block frame are
-     misparsed there.  This parser follows the syntax; parity with the reference is claimed (and tested against the real
-     decoder) for the unprotected layout only. */
-  int blocks_left, block_crc;
-  size_t frame_left;
-  int frame_ok; /* the last parse_frame delivered an element: p->el is whole (xaac_parse_core_tools_side) */
+  /* The first element's slot is part of the parser; those of a stream with several elements are allocated by the first
+     multichannel call, so that a mono / stereo stream's parser stays as small as it was */
+  XpSlot first;
+  XpSlot *slot[XP_MAX_ELEMENTS]; /* slot[0] = &first; slot[1 ..]: one block, or null */
+  int sampling_rate, esbr;
+  XpBlocks blocks;
+  int frame_ok; /* the last parse_frame delivered its elements: they are whole (xaac_parse_core_tools_side) */
   int channel_config; /* of the ADTS header read last */
-  int n_els;    /* ... and how many (more than one: the others are in more->el) */
-  XpMore *more;
-  XpSbrMc *sbr_mc;
+  int n_els;    /* ... and how many elements its block held */
+  int8_t sequence_n, sequence[XP_MAX_ELEMENTS]; /* the multichannel calls' rule: the element ids of the first frame they saw (none: 0) */
 };
-static inline XhElement *element_of(xaac_parser *p, int k) { return k == 0 ? &p->el : &p->more->el[k - 1]; }
+static_assert(sizeof(xaac_parser) <= 14592 + 64, "a mono / stereo stream's parser has grown: it was 14592 bytes with one slot's members inline");
 
 /* A small persistent team for xaac_parse_batch_run.  Workers wait for the next call on a generation counter: a short spin
    (batches of a running decoder follow each other within microseconds), then asleep in the kernel on a futex -- a host
@@ -239,13 +243,13 @@ int32_t xaac_parser_create(xaac_parser **p) {
   if (!q) return XAAC_PARSE_ERR_UNSUPPORTED;
   memset(static_cast<void *>(q), 0, sizeof(*q));
   q->sr_index = -1;
+  q->slot[0] = &q->first;
   *p = q;
   return XAAC_PARSE_OK;
 }
 
 void xaac_parser_destroy(xaac_parser *p) {
-  if (p) delete p->more;
-  if (p) delete p->sbr_mc;
+  if (p) delete[] p->slot[1];
   delete p;
 }
 
@@ -292,27 +296,20 @@ static int32_t tools_of(const XhElement &el) {
   return tools;
 }
 
-/* the frame at data[0 .. n) into p->el */
+/* the frame at data[0 .. n) into the parser's slots */
 static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap);
-/* one raw data block of at most `cap` channel elements into p->el (and p->more->el) */
+/* one raw data block of at most `cap` channel elements (beyond one: the slots behind the first are there) */
 static int32_t parse_block(xaac_parser *p, XhBits *br, int32_t stage, int cap) {
   /* the frame's lines live in a buffer of the calling thread until the caller has copied them out (the entry points do,
      before they return): nothing of a stream outlives the frame there */
-  static thread_local int32_t lines[2][XH_SPEC_WORDS];
-  p->el.ch[0].spec_mem = lines[0], p->el.ch[1].spec_mem = lines[1];
-  if (cap <= 1) {
-    p->n_els = 1;
-    return xh_parse_raw_data_block(&p->core, br, &p->el, stage);
-  }
-  static thread_local int32_t lines_more[XP_MAX_ELEMENTS - 1][2][XH_SPEC_WORDS];
+  static thread_local int32_t lines[XP_MAX_ELEMENTS][2][XH_SPEC_WORDS];
   XhElement *els[XP_MAX_ELEMENTS];
   xaac_core_tools_state *tools[XP_MAX_ELEMENTS];
-  els[0] = &p->el, tools[0] = &p->core.tools;
-  for (int k = 1; k < XP_MAX_ELEMENTS; k++) {
-    els[k] = &p->more->el[k - 1], tools[k] = &p->more->tools[k - 1];
-    els[k]->ch[0].spec_mem = lines_more[k - 1][0], els[k]->ch[1].spec_mem = lines_more[k - 1][1];
+  for (int k = 0; k < cap; k++) {
+    els[k] = &p->slot[k]->el, tools[k] = &p->slot[k]->tools;
+    els[k]->ch[0].spec_mem = lines[k][0], els[k]->ch[1].spec_mem = lines[k][1];
   }
-  return xh_parse_raw_data_block_mc(&p->core, br, els, tools, cap < XP_MAX_ELEMENTS ? cap : XP_MAX_ELEMENTS, &p->n_els, stage);
+  return xh_parse_raw_data_block(&p->core, br, els, tools, cap, &p->n_els, stage);
 }
 static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap = 1) {
   p->frame_ok = 0;
@@ -321,21 +318,22 @@ static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_
   return r;
 }
 static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap) {
-  if (p->blocks_left > 0) {
+  XpBlocks &blocks = p->blocks;
+  if (blocks.left > 0) {
     /* the next raw data block of the ADTS frame the call before started (data points behind what that call consumed): the
        reference reads a header only when its block count has run out (api.c:2914) */
-    if (n < p->frame_left) return XAAC_PARSE_NEED_DATA;
-    XhBits br(data, p->frame_left);
+    if (n < blocks.frame_left) return XAAC_PARSE_NEED_DATA;
+    XhBits br(data, blocks.frame_left);
     const int32_t r = parse_block(p, &br, stage, cap);
     if (r) {
-      p->blocks_left = 0; /* (the rest of the frame goes with it: the caller looks for the next header) */
-      if (consumed) *consumed = p->frame_left;
+      blocks.left = 0; /* (the rest of the frame goes with it: the caller looks for the next header) */
+      if (consumed) *consumed = blocks.frame_left;
       return r;
     }
-    size_t used = br.pos / 8 + (p->block_crc ? 2 : 0);
-    p->blocks_left--;
-    if (p->blocks_left == 0 || used > p->frame_left) used = p->frame_left; /* the last block ends the frame */
-    p->frame_left -= used;
+    size_t used = br.pos / 8 + (blocks.crc ? 2 : 0);
+    blocks.left--;
+    if (blocks.left == 0 || used > blocks.frame_left) used = blocks.frame_left; /* the last block ends the frame */
+    blocks.frame_left -= used;
     if (consumed) *consumed = used;
     return XAAC_PARSE_OK;
   }
@@ -346,11 +344,8 @@ static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, 
   if (h.frame_bytes < h.header_bytes) return XAAC_PARSE_ERR_UNSUPPORTED;
   if (consumed) *consumed = (size_t)h.frame_bytes;
   if (p->sr_index != h.sr_index) {
-    const XhCoreState keep = p->core;
+    /* (a change of sampling rate in mid-stream: the slots' noise generators run on) */
     if (xh_core_init(&p->core, h.sr_index)) return XAAC_PARSE_ERR_HEADER;
-    if (p->sr_index >= 0) { /* a change of sampling rate in mid-stream: the noise generator runs on */
-      p->core.tools = keep.tools;
-    }
     p->sr_index = h.sr_index;
     p->sampling_rate = h.sampling_rate;
   }
@@ -364,33 +359,32 @@ static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, 
      and that block (+ its CRC in a protected frame); the calls that follow deliver the others, one each */
   size_t used = (size_t)h.header_bytes + br.pos / 8 + (h.protection_absent ? 0 : 2);
   if (used > (size_t)h.frame_bytes) used = (size_t)h.frame_bytes;
-  p->blocks_left = h.raw_blocks;
-  p->block_crc = h.protection_absent ? 0 : 1;
-  p->frame_left = (size_t)h.frame_bytes - used;
+  blocks.left = h.raw_blocks;
+  blocks.crc = h.protection_absent ? 0 : 1;
+  blocks.frame_left = (size_t)h.frame_bytes - used;
   if (consumed) *consumed = used;
   return XAAC_PARSE_OK;
 }
 
 /* the frame parse_frame delivered: its element sequence against the one of its channel_config (3 .. 6; every other
-   configuration: one element, as the single-element entry takes it) and against the stream's first frame */
+   configuration: one element, as the single-element entry takes it) and against the first frame the multichannel calls saw */
 static int32_t check_sequence(xaac_parser *p) {
   const int cc = p->channel_config;
   if (cc >= 3 && cc <= 6) {
     if (p->n_els != k_config_elements[cc][0]) return XAAC_PARSE_ERR_UNSUPPORTED;
     for (int k = 0; k < p->n_els; k++)
-      if (element_of(p, k)->id != k_config_elements[cc][1 + k]) return XAAC_PARSE_ERR_UNSUPPORTED;
+      if (p->slot[k]->el.id != k_config_elements[cc][1 + k]) return XAAC_PARSE_ERR_UNSUPPORTED;
   } else if (p->n_els != 1) {
     return XAAC_PARSE_ERR_UNSUPPORTED;
   }
-  XpMore *m = p->more;
-  if (!m->have_sequence) {
-    m->have_sequence = 1, m->sequence_n = p->n_els;
-    for (int k = 0; k < p->n_els; k++) m->sequence[k] = element_of(p, k)->id;
+  if (!p->sequence_n) {
+    p->sequence_n = (int8_t)p->n_els;
+    for (int k = 0; k < p->n_els; k++) p->sequence[k] = (int8_t)p->slot[k]->el.id;
     return XAAC_PARSE_OK;
   }
-  if (m->sequence_n != p->n_els) return XAAC_PARSE_ERR_UNSUPPORTED;
+  if (p->sequence_n != p->n_els) return XAAC_PARSE_ERR_UNSUPPORTED;
   for (int k = 0; k < p->n_els; k++)
-    if (m->sequence[k] != element_of(p, k)->id) return XAAC_PARSE_ERR_UNSUPPORTED;
+    if (p->sequence[k] != p->slot[k]->el.id) return XAAC_PARSE_ERR_UNSUPPORTED;
   return XAAC_PARSE_OK;
 }
 
@@ -401,7 +395,7 @@ static int32_t check_sequence(xaac_parser *p) {
 static bool stale_correlated_seed(xaac_parser *p) {
   if (p->n_els < 2) return false;
   for (int k = 0; k < p->n_els; k++) {
-    const XhElement &el = *element_of(p, k);
+    const XhElement &el = p->slot[k]->el;
     if (el.n_ch != 2 || !el.common_window || !(el.ch[0].pns_active || el.ch[1].pns_active)) continue;
     for (int g = 0; g < el.ch[0].ics.num_groups; g++)
       for (int sfb = 0; sfb < el.ch[0].ics.max_sfb; sfb++)
@@ -410,24 +404,21 @@ static bool stale_correlated_seed(xaac_parser *p) {
   return false;
 }
 
-/* parse_frame for the multichannel entry points: up to XP_MAX_ELEMENTS channel elements, the sequence checked.  A frame the
-   check refuses leaves the multi-block bookkeeping where it was, as a frame that did not parse */
+/* parse_frame for the multichannel entry points: up to XP_MAX_ELEMENTS channel elements (the first call allocates the slots
+   behind the first), the sequence checked.  A frame the check refuses is a frame that did not parse */
 static int32_t parse_frame_mc(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed) {
-  if (!p->more) {
-    p->more = new (std::nothrow) XpMore;
-    if (!p->more) return XAAC_PARSE_ERR_UNSUPPORTED;
-    memset(static_cast<void *>(p->more), 0, sizeof(*p->more));
+  if (!p->slot[1]) {
+    XpSlot *rest = new (std::nothrow) XpSlot[XP_MAX_ELEMENTS - 1];
+    if (!rest) return XAAC_PARSE_ERR_UNSUPPORTED;
+    memset(static_cast<void *>(rest), 0, (XP_MAX_ELEMENTS - 1) * sizeof(XpSlot));
+    for (int k = 1; k < XP_MAX_ELEMENTS; k++) p->slot[k] = rest + (k - 1);
   }
-  const int32_t keep_blocks = p->blocks_left, keep_crc = p->block_crc;
-  const size_t keep_left = p->frame_left;
+  const XpBlocks keep = p->blocks;
   int32_t r = parse_frame(p, data, n, stage, consumed, XP_MAX_ELEMENTS);
   if (r) return r;
   r = check_sequence(p);
   if (r == 0 && stale_correlated_seed(p)) r = XAAC_PARSE_ERR_UNSUPPORTED;
-  if (r) {
-    p->frame_ok = 0;
-    p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
-  }
+  if (r) p->frame_ok = 0, p->blocks = keep;
   return r;
 }
 
@@ -452,7 +443,7 @@ int32_t xaac_parse_adts_frame(xaac_parser *p, const uint8_t *data, size_t n, int
                               size_t *consumed) {
   const int32_t r = parse_frame(p, data, n, stage, consumed);
   if (r) return r;
-  fill_core_frame(p->el, out);
+  fill_core_frame(p->first.el, out);
   return XAAC_PARSE_OK;
 }
 
@@ -466,78 +457,69 @@ int32_t xaac_parse_adts_frame_mc(xaac_parser *p, const uint8_t *data, size_t n, 
     p->frame_ok = 0;
     return XAAC_PARSE_ERR_SYNTAX;
   }
-  for (int k = 0; k < p->n_els; k++) fill_core_frame(*element_of(p, k), elems + k);
+  for (int k = 0; k < p->n_els; k++) fill_core_frame(p->slot[k]->el, elems + k);
   *n_elems = p->n_els;
   return XAAC_PARSE_OK;
 }
 
-int32_t xaac_parse_sbr_side(xaac_parser *p, int32_t ps_enable, xaac_sbr_side *side) {
-  if (!p || !side || p->sr_index < 0 || p->el.n_ch < 1) return XAAC_PARSE_ERR_SYNTAX;
-  if (!p->sbr_ready) {
-    xs_init(&p->sbr, p->sampling_rate, p->el.n_ch, ps_enable && p->el.n_ch == 1, p->esbr);
-    p->sbr_ready = 1;
+/* One channel element's SBR payload through the element's own front end, which the first call sets up (ps_enable: parametric
+   stereo for a single channel; off in a frame of several elements, api.c:2384-2387).  An element without payload -- the LFE
+   always -- is a frame whose SBR data is missing */
+static int32_t sbr_side_of(xaac_parser *p, int element, int ps_enable, xaac_sbr_side *side) {
+  XpSlot *s = p->slot[element];
+  if (!s->sbr_ready) {
+    xs_init(&s->sbr, p->sampling_rate, s->el.n_ch, ps_enable && s->el.n_ch == 1, p->esbr);
+    s->sbr_ready = 1;
   }
   XsFrameResult r;
-  if (xs_decode_frame(&p->sbr, p->el.sbr, p->el.sbr_bytes, p->el.sbr_ext_type, &side->header, side->frame, &side->ps_frame, &r))
+  if (xs_decode_frame(&s->sbr, s->el.sbr, s->el.sbr_bytes, s->el.sbr_ext_type, &side->header, side->frame, &side->ps_frame, &r))
     return XAAC_PARSE_ERR_SYNTAX;
-  xs_frame_done(&p->sbr, &r); /* what the frame's ixheaacd_sbr_dec leaves for the next frame's delta decoding */
+  xs_frame_done(&s->sbr, &r); /* what the frame's ixheaacd_sbr_dec leaves for the next frame's delta decoding */
   side->apply = r.apply, side->reset = r.reset, side->reset_channels = r.reset_channels, side->upsampling = r.upsampling;
   side->stereo = r.stereo, side->ps = r.ps, side->ps_start = r.ps_start, side->frame_ok = r.frame_ok;
   return XAAC_PARSE_OK;
 }
+/* the element has a slot whose SBR front end a side info call has set up */
+static inline bool sbr_ready(const xaac_parser *p, int element) {
+  return element >= 0 && element < XP_MAX_ELEMENTS && p->slot[element] && p->slot[element]->sbr_ready;
+}
 
-/* one channel element's SBR payload through the element's own front end: parametric stereo is off in a frame of several elements
-   (api.c:2384-2387), an element without payload -- the LFE always -- is a frame whose SBR data is missing */
-static int32_t sbr_side_mc(xaac_parser *p, int element, xaac_sbr_side *side) {
-  if (!p->sbr_mc) {
-    p->sbr_mc = new (std::nothrow) XpSbrMc;
-    if (!p->sbr_mc) return XAAC_PARSE_ERR_UNSUPPORTED;
-    memset(static_cast<void *>(p->sbr_mc), 0, sizeof(*p->sbr_mc));
-  }
-  XhElement *el = element_of(p, element);
-  XsDecoder *d = &p->sbr_mc->dec[element];
-  if (!p->sbr_mc->ready[element]) {
-    xs_init(d, p->sampling_rate, el->n_ch, 0, p->esbr);
-    p->sbr_mc->ready[element] = 1;
-  }
-  XsFrameResult r;
-  if (xs_decode_frame(d, el->sbr, el->sbr_bytes, el->sbr_ext_type, &side->header, side->frame, &side->ps_frame, &r)) return XAAC_PARSE_ERR_SYNTAX;
-  xs_frame_done(d, &r);
-  side->apply = r.apply, side->reset = r.reset, side->reset_channels = r.reset_channels, side->upsampling = r.upsampling;
-  side->stereo = r.stereo, side->ps = r.ps, side->ps_start = r.ps_start, side->frame_ok = r.frame_ok;
-  return XAAC_PARSE_OK;
+int32_t xaac_parse_sbr_side(xaac_parser *p, int32_t ps_enable, xaac_sbr_side *side) {
+  if (!p || !side || p->sr_index < 0 || p->first.el.n_ch < 1) return XAAC_PARSE_ERR_SYNTAX;
+  return sbr_side_of(p, 0, ps_enable, side);
 }
 
 int32_t xaac_parse_sbr_side_mc(xaac_parser *p, int32_t element, xaac_sbr_side *side) {
-  if (!p || !side || p->sr_index < 0 || !p->frame_ok || !p->more || element < 0 || element >= p->n_els) return XAAC_PARSE_ERR_SYNTAX;
-  return sbr_side_mc(p, element, side);
+  if (!p || !side || p->sr_index < 0 || !p->frame_ok || !p->slot[1] || element < 0 || element >= p->n_els) return XAAC_PARSE_ERR_SYNTAX;
+  return sbr_side_of(p, element, 0, side);
 }
 
 int32_t xaac_parse_esbr_side_mc(xaac_parser *p, int32_t element, int32_t channel, xaac_esbr_side *side) {
-  if (!p || !side || !p->esbr || !p->sbr_mc || element < 0 || element >= XP_MAX_ELEMENTS || !p->sbr_mc->ready[element] || channel < 0 || channel > 1)
-    return XAAC_PARSE_ERR_SYNTAX;
-  xs_export_esbr_side(&p->sbr_mc->dec[element], channel, side);
+  if (!p || !side || !p->esbr || !sbr_ready(p, element) || channel < 0 || channel > 1) return XAAC_PARSE_ERR_SYNTAX;
+  xs_export_esbr_side(&p->slot[element]->sbr, channel, side);
   return XAAC_PARSE_OK;
 }
+
+int32_t xaac_parse_esbr_side(xaac_parser *p, int32_t channel, xaac_esbr_side *side) { return xaac_parse_esbr_side_mc(p, 0, channel, side); }
 
 int32_t xaac_parse_reset_pitch_mc(xaac_parser *p, int32_t element, int32_t *pitch_in_bins) {
-  if (!p || !pitch_in_bins || !p->sbr_mc || element < 0 || element >= XP_MAX_ELEMENTS || !p->sbr_mc->ready[element]) return XAAC_PARSE_ERR_SYNTAX;
-  *pitch_in_bins = p->sbr_mc->dec[element].reset_pitch;
+  if (!p || !pitch_in_bins || !sbr_ready(p, element)) return XAAC_PARSE_ERR_SYNTAX;
+  *pitch_in_bins = p->slot[element]->sbr.reset_pitch;
   return XAAC_PARSE_OK;
 }
 
-int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side) {
-  if (!p || !side || p->sr_index < 0 || p->el.n_ch < 1 || !p->frame_ok) return XAAC_PARSE_ERR_SYNTAX;
-  memset(side, 0, sizeof(*side));
-  xh_export_tools_side(&p->core, &p->el, side);
-  return XAAC_PARSE_OK;
-}
+int32_t xaac_parse_reset_pitch(xaac_parser *p, int32_t *pitch_in_bins) { return xaac_parse_reset_pitch_mc(p, 0, pitch_in_bins); }
 
 int32_t xaac_parse_core_tools_side_mc(xaac_parser *p, int32_t element, xaac_core_tools_side *side) {
   if (!p || !side || p->sr_index < 0 || !p->frame_ok || element < 0 || element >= p->n_els) return XAAC_PARSE_ERR_SYNTAX;
   memset(side, 0, sizeof(*side));
-  xh_export_tools_side(&p->core, element_of(p, element), side);
+  xh_export_tools_side(&p->core, &p->slot[element]->el, side);
   return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side) {
+  if (!p || p->first.el.n_ch < 1) return XAAC_PARSE_ERR_SYNTAX;
+  return xaac_parse_core_tools_side_mc(p, 0, side);
 }
 
 int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_tools_state *state, int32_t *spec) {
@@ -554,20 +536,10 @@ int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_t
 }
 
 int32_t xaac_parser_set_esbr(xaac_parser *p, int32_t esbr) {
-  if (!p || p->sbr_ready || p->sbr_mc || (esbr != 0 && esbr != 1)) return XAAC_PARSE_ERR_SYNTAX;
+  if (!p || (esbr != 0 && esbr != 1)) return XAAC_PARSE_ERR_SYNTAX;
+  for (int k = 0; k < XP_MAX_ELEMENTS; k++)
+    if (sbr_ready(p, k)) return XAAC_PARSE_ERR_SYNTAX; /* the reading is fixed by the first side info call */
   p->esbr = esbr;
-  return XAAC_PARSE_OK;
-}
-
-int32_t xaac_parse_esbr_side(xaac_parser *p, int32_t channel, xaac_esbr_side *side) {
-  if (!p || !side || !p->sbr_ready || !p->esbr || channel < 0 || channel > 1) return XAAC_PARSE_ERR_SYNTAX;
-  xs_export_esbr_side(&p->sbr, channel, side);
-  return XAAC_PARSE_OK;
-}
-
-int32_t xaac_parse_reset_pitch(xaac_parser *p, int32_t *pitch_in_bins) {
-  if (!p || !pitch_in_bins || !p->sbr_ready) return XAAC_PARSE_ERR_SYNTAX;
-  *pitch_in_bins = p->sbr.reset_pitch;
   return XAAC_PARSE_OK;
 }
 
@@ -588,141 +560,80 @@ struct BatchJob {
 };
 BatchJob g_job;
 
-/* frame t (of the call's b->frames) of stream i; the arrays of step t lie one step's array behind those of step t - 1 */
-int32_t parse_one_mc(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok);
+/* the topmost block of 16 lines with a non-zero word, looked for above block `top` only */
+inline int top_block(const int32_t *x, int top) {
+  int blk = 1024 / 16;
+  for (; blk > top; blk--) {
+    const int32_t *q = x + 16 * (blk - 1);
+    int32_t any = 0;
+    for (int k = 0; k < 16; k++) any |= q[k];
+    if (any) break;
+  }
+  return blk > top ? blk : top;
+}
+/* ... and the block the tools can reach: noise and intensity bands are zero until the tools have run; a TNS filter runs its order
+   (rounded up to four) lines even where that leaves the region */
+inline int tools_reach_block(const XhCoreState &core, const XhIcs &ics) {
+  const bool is_short = ics.window_sequence == XH_EIGHT_SHORT;
+  const int reach = (is_short ? 7 * 128 + core.swb_short[ics.max_sfb] : core.swb_long[ics.max_sfb]) + XT_SLACK;
+  return reach >= 1024 ? 64 : (reach + 15) / 16;
+}
+
+/* frame t (of the call's b->frames) of stream i; the arrays of step t lie one step's array behind those of step t - 1.  Every
+   channel element of the frame (one with channel_config 0), channels in bitstream order, the rows per element element-major */
 int32_t parse_one(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok) {
-  if (b->channel_config) return parse_one_mc(b, i, t, ok);
-  const int n_ch = b->n_ch;
+  const bool wide = b->channel_config != 0; /* channel_config 3 .. 6: the multichannel calls' frames, sequence rule included */
+  const int n_ch = b->n_ch, n_els = wide ? k_config_elements[b->channel_config][0] : 1;
   const size_t S = (size_t)b->n_streams * (size_t)t, SC = S * (size_t)n_ch; /* streams / channels in front of this step's rows */
+  const size_t row0 = SC + (size_t)i * n_ch;                               /* the stream's first channel row */
   xaac_parser *p = b->parser[i];
   size_t used = 0;
   const uint64_t at = b->pos ? (b->pos[i] < b->bytes[i] ? b->pos[i] : b->bytes[i]) : 0;
-  /* a step that fails behind a successful parse_frame (channel count, SBR side info) leaves the stream's read position where
-     it was, so the multi-block bookkeeping parse_frame has already moved on has to go back with it: the next call would
-     otherwise read the ADTS header it is pointed at as a raw data block */
-  const int32_t keep_blocks = p->blocks_left, keep_crc = p->block_crc;
-  const size_t keep_left = p->frame_left;
-  int32_t r = parse_frame(p, b->data[i] + at, (size_t)(b->bytes[i] - at), b->stage, &used);
+  const XpBlocks keep = p->blocks;
+  const uint8_t *data = b->data[i] + at;
+  int32_t r = wide ? parse_frame_mc(p, data, (size_t)(b->bytes[i] - at), b->stage, &used) : parse_frame(p, data, (size_t)(b->bytes[i] - at), b->stage, &used);
   const bool framed = r == 0;
-  if (r == 0 && p->el.n_ch != n_ch) r = XAAC_PARSE_ERR_UNSUPPORTED;
-  xaac_sbr_side *side = nullptr;
+  /* a stream whose rows would not fit the batch's: one element is told by its channel count, several by the configuration */
+  if (r == 0 && (wide ? p->channel_config != b->channel_config : p->first.el.n_ch != n_ch)) r = XAAC_PARSE_ERR_UNSUPPORTED;
+  /* every element's SBR side info: the rows per channel (a pair's channels get copies of the header), flags and reset pitch per
+     element */
   if (r == 0 && b->with_sbr) {
-    static thread_local xaac_sbr_side side_of_thread; /* copied into the batch's arrays below */
-    side = &side_of_thread;
-    r = xaac_parse_sbr_side(p, b->ps_enable, side);
+    static thread_local xaac_sbr_side side; /* copied into the batch's arrays */
+    const bool ps = !wide;                  /* parametric stereo and its ps_frame rows: a batch of one element per frame only */
+    size_t row = row0;
+    for (int k = 0; k < n_els; k++) {
+      XpSlot *s = p->slot[k];
+      r = sbr_side_of(p, k, ps && b->ps_enable, &side);
+      if (r) break;
+      const size_t e_row = (S + i) * (size_t)n_els + k;
+      for (int c = 0; c < s->el.n_ch; c++, row++) {
+        b->header[row] = side.header;
+        b->frame[row] = side.frame[c];
+        if (b->esbr_side && p->esbr) xs_export_esbr_side(&s->sbr, c, b->esbr_side + row);
+      }
+      int32_t *f = b->flags + e_row * 8;
+      f[0] = side.apply, f[1] = side.reset, f[2] = side.reset_channels, f[3] = side.upsampling;
+      f[4] = side.stereo, f[5] = side.ps, f[6] = side.ps_start, f[7] = side.frame_ok;
+      if (b->reset_pitch && side.reset) b->reset_pitch[e_row] = s->sbr.reset_pitch;
+      if (ps && b->ps_frame) b->ps_frame[S + i] = side.ps_frame;
+    }
   }
   b->status[S + i] = r;
   if (r) {
-    if (framed) p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
+    /* a refusal behind a delivered frame: the read position stays, so the block count goes back.  The multichannel calls' frame
+       then no longer counts as delivered; a single element's does (xaac_parse_core_tools_side still answers for it) */
+    if (framed) p->blocks = keep;
+    if (framed && wide) p->frame_ok = 0;
     return r;
   }
   (*ok)++;
   b->consumed[i] += used;
   if (b->pos) b->pos[i] = at + used;
-  if (b->tools) b->tools[S + i] = tools_of(p->el);
-  for (int c = 0; c < n_ch; c++) {
-    const size_t row = SC + (size_t)i * n_ch + c;
-    memcpy(b->spec + row * 1024, p->el.ch[c].spec(), 1024 * sizeof(int32_t));
-    b->ics[row * 2 + 0] = (uint8_t)p->el.ch[c].ics.window_sequence;
-    b->ics[row * 2 + 1] = (uint8_t)p->el.ch[c].ics.window_shape;
-    if (side) {
-      b->header[row] = side->header;
-      b->frame[row] = side->frame[c];
-    }
-  }
-  if (b->lines) {
-    int top = 0;
-    for (int c = 0; c < n_ch; c++) {
-      const int32_t *x = p->el.ch[c].spec();
-      int blk = 1024 / 16;
-      for (; blk > top; blk--) { /* the topmost block of 16 lines with a non-zero word */
-        const int32_t *q = x + 16 * (blk - 1);
-        int32_t any = 0;
-        for (int k = 0; k < 16; k++) any |= q[k];
-        if (any) break;
-      }
-      top = blk > top ? blk : top;
-    }
-    if (b->tools_side) { /* noise and intensity bands are zero until the tools have run; a TNS filter runs its order (rounded up
-                            to four) lines even where that leaves the region */
-      for (int c = 0; c < n_ch; c++) {
-        const XhIcs &ics = p->el.ch[c].ics;
-        const bool is_short = ics.window_sequence == XH_EIGHT_SHORT;
-        const int reach = (is_short ? 7 * 128 + p->core.swb_short[ics.max_sfb] : p->core.swb_long[ics.max_sfb]) + XT_SLACK;
-        const int blk = reach >= 1024 ? 64 : (reach + 15) / 16;
-        top = blk > top ? blk : top;
-      }
-    }
-    b->lines[S + i] = 16 * top;
-  }
-  if (b->tools_side) {
-    xaac_core_tools_side *side = b->tools_side + S + i;
-    memset(side, 0, sizeof(*side));
-    xh_export_tools_side(&p->core, &p->el, side);
-  }
-  if (side && b->reset_pitch && side->reset) b->reset_pitch[S + i] = p->sbr.reset_pitch;
-  if (side && b->esbr_side && p->esbr)
-    for (int c = 0; c < n_ch; c++) xs_export_esbr_side(&p->sbr, c, b->esbr_side + SC + (size_t)i * n_ch + c);
-  if (side) {
-    if (b->ps_frame) b->ps_frame[S + i] = side->ps_frame;
-    int32_t *f = b->flags + (S + i) * 8;
-    f[0] = side->apply, f[1] = side->reset, f[2] = side->reset_channels, f[3] = side->upsampling;
-    f[4] = side->stereo, f[5] = side->ps, f[6] = side->ps_start, f[7] = side->frame_ok;
-  }
-  return 0;
-}
-
-/* the same for a batch with channel_config 3 .. 6: every channel element of the frame, channels in bitstream order, the tools'
-   side rows element-major */
-int32_t parse_one_mc(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok) {
-  const int n_ch = b->n_ch, n_els = k_config_elements[b->channel_config][0];
-  const size_t S = (size_t)b->n_streams * (size_t)t, SC = S * (size_t)n_ch;
-  xaac_parser *p = b->parser[i];
-  size_t used = 0;
-  const uint64_t at = b->pos ? (b->pos[i] < b->bytes[i] ? b->pos[i] : b->bytes[i]) : 0;
-  const int32_t keep_blocks = p->blocks_left, keep_crc = p->block_crc;
-  const size_t keep_left = p->frame_left;
-  int32_t r = parse_frame_mc(p, b->data[i] + at, (size_t)(b->bytes[i] - at), b->stage, &used);
-  if (r == 0 && p->channel_config != b->channel_config) { /* (a stream of another configuration: its rows would not fit) */
-    r = XAAC_PARSE_ERR_UNSUPPORTED;
-    p->frame_ok = 0;
-    p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
-  }
-  /* mc_sbr: every element's SBR side info, the rows per channel (a pair's channels get copies of the header), flags and reset
-     pitch per element */
-  if (r == 0 && b->with_sbr) {
-    static thread_local xaac_sbr_side side; /* copied into the batch's arrays */
-    size_t ch_row = SC + (size_t)i * n_ch;
-    for (int k = 0; k < n_els && r == 0; k++) {
-      XhElement *el = element_of(p, k);
-      r = sbr_side_mc(p, k, &side);
-      if (r) break;
-      const size_t e_row = (S + i) * (size_t)n_els + k;
-      for (int c = 0; c < el->n_ch; c++, ch_row++) {
-        b->header[ch_row] = side.header;
-        b->frame[ch_row] = side.frame[c];
-        if (b->esbr_side && p->esbr) xs_export_esbr_side(&p->sbr_mc->dec[k], c, b->esbr_side + ch_row);
-      }
-      int32_t *f = b->flags + e_row * 8;
-      f[0] = side.apply, f[1] = side.reset, f[2] = side.reset_channels, f[3] = side.upsampling;
-      f[4] = side.stereo, f[5] = side.ps, f[6] = side.ps_start, f[7] = side.frame_ok;
-      if (b->reset_pitch && side.reset) b->reset_pitch[e_row] = p->sbr_mc->dec[k].reset_pitch;
-    }
-    if (r) {
-      p->frame_ok = 0;
-      p->blocks_left = keep_blocks, p->block_crc = keep_crc, p->frame_left = keep_left;
-    }
-  }
-  b->status[S + i] = r;
-  if (r) return r;
-  (*ok)++;
-  b->consumed[i] += used;
-  if (b->pos) b->pos[i] = at + used;
   int32_t tools = 0;
   int top = 0;
-  size_t row = SC + (size_t)i * n_ch;
+  size_t row = row0;
   for (int k = 0; k < n_els; k++) {
-    XhElement *el = element_of(p, k);
+    XhElement *el = &p->slot[k]->el;
     tools |= tools_of(*el);
     for (int c = 0; c < el->n_ch; c++, row++) {
       const int32_t *x = el->ch[c].spec();
@@ -730,21 +641,8 @@ int32_t parse_one_mc(const xaac_parse_batch *b, int i, int t, std::atomic<int> *
       b->ics[row * 2 + 0] = (uint8_t)el->ch[c].ics.window_sequence;
       b->ics[row * 2 + 1] = (uint8_t)el->ch[c].ics.window_shape;
       if (b->lines) {
-        int blk = 1024 / 16;
-        for (; blk > top; blk--) {
-          const int32_t *q = x + 16 * (blk - 1);
-          int32_t any = 0;
-          for (int j = 0; j < 16; j++) any |= q[j];
-          if (any) break;
-        }
-        top = blk > top ? blk : top;
-        if (b->tools_side) {
-          const XhIcs &ics = el->ch[c].ics;
-          const bool is_short = ics.window_sequence == XH_EIGHT_SHORT;
-          const int reach = (is_short ? 7 * 128 + p->core.swb_short[ics.max_sfb] : p->core.swb_long[ics.max_sfb]) + XT_SLACK;
-          const int reach_blk = reach >= 1024 ? 64 : (reach + 15) / 16;
-          top = reach_blk > top ? reach_blk : top;
-        }
+        top = top_block(x, top);
+        if (b->tools_side) top = std::max(top, tools_reach_block(p->core, el->ch[c].ics));
       }
     }
     if (b->tools_side) {

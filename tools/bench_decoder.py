@@ -47,9 +47,16 @@ def main():
     ap.add_argument("--copies", type=int, default=2048)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--overlap", type=int, default=1)
+    ap.add_argument("--parser-only", action="store_true", help="the host parser's figure alone: no GPU needed")
     a = ap.parse_args()
     from libxaac_amd import decoder
-    data = open(os.path.join(ROOT, "tests", "golden", "streams", a.stream + ".aac"), "rb").read()
+    golden = os.path.join(ROOT, "tests", "golden")
+    path = [p for p in (os.path.join(golden, d, a.stream + ".aac") for d in ("streams", "streams_wide")) if os.path.exists(p)][0]
+    data = open(path, "rb").read()
+    if a.parser_only:
+        print(json.dumps({"stream": a.stream, "copies": a.copies, "host_threads": a.threads or os.cpu_count(),
+                          "parser_only_frames_per_s": round(parser_only(decoder, data, a.copies, a.threads), 1)}))
+        return
     decoder.decode_streams([data] * 8)                           # warm up (library load, first launches)
     timing = {}
     t0 = time.perf_counter()
