@@ -16,10 +16,20 @@
  *   xs_energy_per_subband / xs_energy_per_sfb             ixheaacd_env_calc.c:1211 / :1298
  *   xs_subbandgain / xs_calc_subband_gains                ixheaacd_env_calc.c:1382 / :616
  *   xs_avggain / xs_noiselimiting / xs_alias_reduction    ixheaacd_env_calc.c:1454 / :229 / :78
- *   xs_erg_to_amplitude_lp                                ixheaacd_env_calc.c:423
- *   xs_harm_zerotwo_lp / xs_harm_onethree_lp              ixheaacd_env_calc.c:1564 / :1617
- *   xs_adapt_noise_gain / xs_calc_sbrenvelope             ixheaacd_env_calc.c:479 / :692
+ *   xs_erg_to_amplitude<HQ>                               ixheaacd_env_calc.c:423 (low-power) / :450 (HQ)
+ *   xs_adapt_noise_gain_lp / _hq / xs_calc_sbrenvelope    ixheaacd_env_calc.c:479 (with :1564 / :1617) / :692
  *   xs_sbr_core_lp                                        ixheaacd_sbr_dec.c:726-775, :1050-1245, :1283-1308
+ * The envelope adjuster runs in two lane arrangements (one envelope: band k on lane k; a pass of two envelopes, `_pk`:
+ * element c of envelope q on lane 32 q + c).  Its reference arithmetic is stated once, per element, and both call it:
+ *   xs_energy_shift / xs_energy_add / xs_energy_finish    ixheaacd_env_calc.c:1211 (head, step, finish)
+ *   xs_subband_gain_band                                  ixheaacd_env_calc.c:616 (one band around xs_subbandgain)
+ *   xs_lim_sum_operands / xs_lim_max_gain                 ixheaacd_env_calc.c:256-271 with :1454 (a limiter band's max gain)
+ *   xs_lim_limit_band / xs_lim_boost_operands             ixheaacd_env_calc.c:277-300, :318-364 (a band's gain limit, its addends)
+ *   xs_lim_boost_gain / xs_lim_boost_band                 ixheaacd_env_calc.c:366-388, :390-416 (the boost gain, applied)
+ *   xs_alias_run_bits / xs_alias_group_at                 ixheaacd_env_calc.c:78 (the groups of aliasing bands)
+ *   xs_alias_mix_band / xs_alias_compensation / xs_alias_compensate_band   ixheaacd_env_calc.c:78 (per band, per group)
+ *   xs_amplitude_band<HQ>                                 ixheaacd_env_calc.c:423 / :450 (one band)
+ *   xs_lp_band / xs_lp_slot                               ixheaacd_env_calc.c:479 with :1564 / :1617 (band constants, slot body)
  * Preconditions the reference's header parser guarantees (ixheaacd_freq_sca.c): band tables strictly
  * increasing, sub_band_end <= 64, at most 56 adjusted bands, patch destinations disjoint and above
  * the source range.
@@ -825,7 +835,37 @@ FX_HD void xs_map_sineflags(const XsCx &cx, const int16_t *tbl_hi, int nsf, cons
   }
 }
 
-/* env_calc.c:1211: energy estimate of band k over slots [s0,s1) (HQ: real and imaginary parts) */
+/* env_calc.c:1211, the arithmetic of one band's energy estimate in three steps; which slots are loaded when is the
+   caller's.  Head: the headroom of the band's samples -- from their maximum or from the OR of their magnitudes, which has
+   the maximum's leading bit, all the norm looks at -- gives the shift that brings them to 16 bits. */
+struct XsEnergyShift {
+  int pre, shr, shl; /* shift > 0 ? xs_sar(v, shift) : xs_shl(v, -shift) without the branch: one of the two counts is zero */
+};
+template <int HQ>
+FX_HD XsEnergyShift xs_energy_shift(int32_t mx) {
+  XsEnergyShift s;
+  s.pre = xs_pnorm32(mx) - (HQ ? 4 : 3);
+  const int shift = 16 - s.pre;
+  s.shr = shift > 0 ? shift & 31 : 0;
+  s.shl = shift > 0 ? 0 : (-shift) & 31;
+  return s;
+}
+/* step: one sample's (one part's) square onto the sum */
+FX_HD int32_t xs_energy_add(int32_t accu, int32_t v, const XsEnergyShift &s) {
+  const int16_t t = (int16_t)((int32_t)((uint32_t)v << s.shl) >> s.shr);
+  return fx_add(accu, (int32_t)t * t);
+}
+/* finish: the sum as a (mantissa, exponent) pair, divided by the number of slots */
+template <int HQ>
+FX_HD int32_t xs_energy_finish(int32_t accu, int pre, int16_t inv_width, int frame_exp2) {
+  if (accu == 0) return 0;
+  int shift = -xs_pnorm32(accu);
+  int16_t sum_m = (int16_t)xs_shr_dir_sat_limit(accu, 16 + shift);
+  sum_m = xs_mult16_shl_sat(sum_m, inv_width);
+  shift = shift - (pre << 1) + (HQ ? 0 : 1);
+  return xs_me(sum_m, (int16_t)(frame_exp2 + shift + 1));
+}
+/* energy estimate of band k over slots [s0,s1) (HQ: real and imaginary parts) */
 template <class Q>
 FX_HD int32_t xs_energy_of_subband(const Q &x, int s0, int s1, int k, int frame_exp2, int16_t inv_width) {
   const int n = s1 - s0;
@@ -839,26 +879,14 @@ FX_HD int32_t xs_energy_of_subband(const Q &x, int s0, int s1, int k, int frame_
       if (v > mx) mx = v;
     }
   }
-  int pre = xs_pnorm32(mx) - (Q::HQ ? 4 : 3);
+  const XsEnergyShift sh = xs_energy_shift<Q::HQ>(mx);
   int32_t accu = 0;
-  int shift = 16 - pre;
-  /* shift > 0 ? xs_sar(v, shift) : xs_shl(v, -shift) without the branch: one of the two counts is zero */
-  const int e_shr = shift > 0 ? shift & 31 : 0, e_shl = shift > 0 ? 0 : (-shift) & 31;
   XS_UNROLL4
   for (int l = 0; l < n; l++) {
-    int16_t t = (int16_t)((int32_t)((uint32_t)x(s0 + l, k) << e_shl) >> e_shr);
-    accu = fx_add(accu, (int32_t)t * t);
-    if (Q::HQ) {
-      t = (int16_t)((int32_t)((uint32_t)x.im(s0 + l, k) << e_shl) >> e_shr);
-      accu = fx_add(accu, (int32_t)t * t);
-    }
+    accu = xs_energy_add(accu, x(s0 + l, k), sh);
+    if (Q::HQ) accu = xs_energy_add(accu, x.im(s0 + l, k), sh);
   }
-  if (accu == 0) return 0;
-  shift = -xs_pnorm32(accu);
-  int16_t sum_m = (int16_t)xs_shr_dir_sat_limit(accu, 16 + shift);
-  sum_m = xs_mult16_shl_sat(sum_m, inv_width);
-  shift = shift - (pre << 1) + (Q::HQ ? 0 : 1);
-  return xs_me(sum_m, (int16_t)(frame_exp2 + shift + 1));
+  return xs_energy_finish<Q::HQ>(accu, sh.pre, inv_width, frame_exp2);
 }
 template <class Q>
 FX_HD void xs_energy_per_subband(const XsCx &cx, const Q &x, int s0, int s1, int b0, int b1, int frame_exp,
@@ -1035,6 +1063,20 @@ FX_HD XsLv xs_pick_env(const XsLv *v, int i) {
   return v[i];
 #endif
 }
+/* env_calc.c:616, one band around xs_subbandgain: the band's scale factor sf and noise-floor value nfl unpacked into
+   (mantissa, exponent) pairs, its energy estimate, whether its sfb carries a sine (`present`) and whether the sine is
+   mapped to this band in this envelope; results as packed pairs. */
+FX_HD void xs_subband_gain_band(int16_t sf, int16_t nfl, int32_t est, int present, int mapped, int noise_absc,
+                                int32_t &e_orig, int32_t &gain, int32_t &noise, int32_t &sine) {
+  const int16_t ref_e = (int16_t)((sf & 63) - 16), ref_m = (int16_t)(sf & 0xffc0);
+  const int16_t nm = (int16_t)(nfl & 0xffc0), ne = (int16_t)((nfl & 63) - 38);
+  int16_t g[2] = {0, 0}, nl[2] = {0, 0}, sn[2] = {0, 0};
+  xs_subbandgain(ref_m, nm, xs_m(est), xs_e(est), ne, ref_e, present, mapped, noise_absc, g, nl, sn);
+  e_orig = xs_me(ref_m, ref_e);
+  gain = xs_me(g[0], g[1]);
+  noise = xs_me(nl[0], nl[1]);
+  sine = xs_me(sn[0], sn[1]);
+}
 /* env_sf: the envelope's scale factors, element j = scale-factor band j */
 FX_HD void xs_calc_subband_gains(const XsCx &cx, const XsLv &env_sf, const int16_t *noise_floor, int env, int n_meta,
                                  int skip, XsEnv &v, int noise_absc) {
@@ -1045,18 +1087,8 @@ FX_HD void xs_calc_subband_gains(const XsCx &cx, const XsLv &env_sf, const int16
   const XsLv sfg = env_sf.gather(jv);
   XS_LANES(c, 0, n_meta) {
     const int meta = v.meta.own(c);
-    const int16_t sf = (int16_t)sfg.own(c);
-    const int16_t nfl = noise_floor[(meta >> 8) & 255];
-    const int present = (meta >> 16) & 1;
-    const int16_t ref_e = (int16_t)((sf & 63) - 16), ref_m = (int16_t)(sf & 0xffc0);
-    const int16_t nm = (int16_t)(nfl & 0xffc0), ne = (int16_t)((nfl & 63) - 38);
-    int16_t g[2] = {0, 0}, nl[2] = {0, 0}, sn[2] = {0, 0};
-    const int32_t est = v.est.own(c);
-    xs_subbandgain(ref_m, nm, xs_m(est), xs_e(est), ne, ref_e, present, env >= sm1.own(c), noise_absc, g, nl, sn);
-    v.e_orig.own(c) = xs_me(ref_m, ref_e);
-    v.gain.own(c) = xs_me(g[0], g[1]);
-    v.noise.own(c) = xs_me(nl[0], nl[1]);
-    v.sine.own(c) = xs_me(sn[0], sn[1]);
+    xs_subband_gain_band((int16_t)sfg.own(c), noise_floor[(meta >> 8) & 255], v.est.own(c), (meta >> 16) & 1,
+                         env >= sm1.own(c), noise_absc, v.e_orig.own(c), v.gain.own(c), v.noise.own(c), v.sine.own(c));
   }
 }
 
@@ -1131,6 +1163,126 @@ FX_HD XsLv xs_limiter_band_of(const XsCx &cx, const xaac_sbr_header *h, int skip
   return mine;
 }
 
+/* The limiter's arithmetic, per band and per limiter band; where a band's row of operands and a limiter band's row of
+   results lie is the caller's. */
+/* a band's operands of avggain's two sums over its limiter band (env_calc.c:1454, flag 0: the sum of e_orig and the sum
+   of est): the addends at the running maximum exponent and the exponent steps of both sums.  po / pe: the maximum exponent
+   of the limiter band's bands below this one. */
+FX_HD void xs_lim_sum_operands(int32_t e_orig, int32_t est, int32_t po, int32_t pe, int32_t *row) {
+  const int32_t eo = xs_e(e_orig), ee = xs_e(est);
+  const int Eo = eo > po ? eo : po, Ee = ee > pe ? ee : pe;
+  row[0] = fx_shr(xs_m(e_orig), Eo - eo);
+  row[1] = fx_shr(xs_m(est), Ee - ee);
+  row[2] = ((Eo - po) & 0xff) | (((Ee - pe) & 0xff) << 8); /* shr32 masks its count so */
+  row[3] = (Eo & 0xffff) | (int32_t)((uint32_t)Ee << 16);
+}
+/* the max gain of a limiter band, rows [b0,b1) of fb: the two sums as two-operation recursions, their quotient times the
+   limiter gain (env_calc.c:256-271).  res = {max gain (m, e), sum of e_orig (m, e)} */
+FX_HD void xs_lim_max_gain(const int32_t (*fb)[4], int b0, int b1, int16_t lim_m, int16_t lim_e, int16_t *res) {
+  int32_t som = 0, sem = 0, last = 0;
+  XS_UNROLL4
+  for (int k = b0; k < b1; k++) {
+    const int32_t d = fb[k][2];
+    som = fx_shr(som, d & 255) + fb[k][0];
+    sem = fx_shr(sem, d >> 8) + fb[k][1];
+    last = fb[k][3];
+  }
+  int32_t soe = (int16_t)last, see = last >> 16;
+  int nv = 16 - xs_pnorm32(som);
+  if (nv > 0) {
+    som >>= nv;
+    soe += nv;
+  }
+  nv = 16 - xs_pnorm32(sem);
+  if (nv > 0) {
+    sem >>= nv;
+    see += nv;
+  }
+  const int16_t so_m = (int16_t)som, so_e = (int16_t)soe;
+  int16_t mg_m;
+  int16_t mg_e = (int16_t)(xs_fix_mant_div(so_m, (int16_t)sem, &mg_m) + (so_e - (int16_t)see) + 1);
+  int32_t mt = xs_mult16x16_shl(mg_m, lim_m);
+  mg_e = (int16_t)(mg_e + lim_e);
+  int tv = fx_norm32(mt);
+  mg_e = (int16_t)(mg_e - tv);
+  mg_m = (int16_t)(xs_shl(mt, tv) >> 16);
+  if (mg_e >= 34) {
+    mg_m = 0x3000;
+    mg_e = 34;
+  }
+  res[0] = mg_m;
+  res[1] = mg_e;
+  res[2] = so_m;
+  res[3] = so_e;
+}
+/* the gain limit of a band; then what its limited gain, sine and noise deliver (env_calc.c:277-300, :318-364): up to two
+   addends, the first (a_m, a_e), the second b_me -- the sine if there is one, else the noise unless it is absent
+   (noise_absc) */
+FX_HD void xs_lim_limit_band(int16_t mg_m, int16_t mg_e, int32_t est, int32_t sn, int noise_absc, int32_t &gain,
+                             int32_t &noise, int32_t &a_m, int32_t &a_e, int32_t &b_me, int32_t &emax, int32_t &with_b) {
+  int16_t gm = xs_m(gain), ge = xs_e(gain);
+  if (ge > mg_e || (ge == mg_e && gm > mg_m)) {
+    int16_t na_m;
+    int na_e = xs_fix_mant_div(mg_m, gm, &na_m);
+    na_e += (mg_e - ge) + 1;
+    const int32_t nl = noise;
+    noise = xs_me((int16_t)(fx_shl_dir_sat_limit(xs_mult16x16_shl(xs_m(nl), na_m), (int16_t)na_e) >> 16), xs_e(nl));
+    gm = mg_m;
+    ge = mg_e;
+    gain = xs_me(gm, ge);
+  }
+  a_m = ((int32_t)gm * xs_m(est)) >> 15;
+  a_e = ge + xs_e(est);
+  b_me = xs_m(sn) != 0 ? sn : (noise_absc == 0 ? noise : 0);
+  const bool has_b = xs_m(sn) != 0 || noise_absc == 0;
+  emax = (has_b && xs_e(b_me) > a_e) ? xs_e(b_me) : a_e;
+  with_b = has_b ? 1 : 0;
+}
+/* ... and the addends as operands of the sum over the limiter band.  E0: the maximum exponent (emax) of the limiter band's
+   bands below this one. */
+FX_HD void xs_lim_boost_operands(int32_t a_m, int32_t a_e, int32_t b_me, int has_b, int E0, int32_t *row) {
+  const int E1 = a_e > E0 ? a_e : E0;
+  const int eb = xs_e(b_me);
+  const int E2 = (has_b && eb > E1) ? eb : E1;
+  row[0] = fx_shr(a_m, E1 - a_e);
+  row[1] = has_b ? fx_shr(xs_m(b_me), E2 - eb) : 0;
+  row[2] = ((E1 - E0) & 0xff) | (((E2 - E1) & 0xff) << 8);
+  row[3] = E2;
+}
+/* the boost gain of a limiter band, rows [b0,b1) of fb: the sum of e_orig (so) over the sum of what the bands deliver, at
+   most 1.584893192 (env_calc.c:366-388).  res = boost gain (m, e) */
+FX_HD void xs_lim_boost_gain(const int32_t (*fb)[4], int b0, int b1, int16_t so_m, int16_t so_e, int16_t *res) {
+  int32_t am = 0, ae = 0;
+  XS_UNROLL4
+  for (int k = b0; k < b1; k++) {
+    const int32_t d = fb[k][2];
+    am = fx_shr(am, d & 255) + fb[k][0];
+    am = fx_shr(am, d >> 8) + fb[k][1];
+    ae = fb[k][3];
+  }
+  int nv = 16 - fx_norm32(am);
+  if (nv > 0) {
+    am >>= nv;
+    ae += nv;
+  }
+  int16_t bg_m;
+  int bg_e = xs_fix_mant_div(so_m, (int16_t)am, &bg_m);
+  bg_e = (int16_t)(bg_e + (so_e - (int16_t)ae) + 1);
+  if (bg_e > 2 || (bg_e == 2 && bg_m > 0x5061)) {
+    bg_m = 0x5061;
+    bg_e = 2;
+  }
+  res[0] = bg_m;
+  res[1] = (int16_t)bg_e;
+}
+/* a band's gain, sine and noise times its limiter band's boost gain (env_calc.c:390-416) */
+FX_HD void xs_lim_boost_band(int16_t bg_m, int16_t bg_e, int32_t &gain, int32_t &sine, int32_t &noise) {
+  const int32_t g = gain, sn = sine, nl = noise;
+  gain = xs_me(xs_mult16_shl(xs_m(g), bg_m), (int16_t)(xs_e(g) + bg_e));
+  sine = xs_me(xs_mult16_shl(xs_m(sn), bg_m), (int16_t)(xs_e(sn) + bg_e));
+  noise = xs_me(xs_mult16_shl(xs_m(nl), bg_m), (int16_t)(xs_e(nl) + bg_e));
+}
+
 FX_HD void xs_noiselimiting(const XsCx &cx, const xaac_sbr_header *h, int skip, int n_bands, XsEnv &v, XsWork *w,
                             const int16_t *lim_tab, int noise_absc, const XsLv &band_of) {
   const int16_t lim_m = lim_tab[0], lim_e = lim_tab[1];
@@ -1138,8 +1290,7 @@ FX_HD void xs_noiselimiting(const XsCx &cx, const xaac_sbr_header *h, int skip, 
   XsLv mine;
   mine.fill(-1);
   XS_LANES(k, 0, n_bands) mine.own(k) = band_of.own(k);
-  /* env_calc.c:1454 (avggain, flag 0) per limiter band: sum of e_orig and sum of est -- addends and exponent steps of
-     both sums per band here, the two-operation recursions per limiter band below */
+  /* the operands of both sums per band here, the recursions per limiter band below */
   {
     XsLv eo, ee;
     eo.fill(0);
@@ -1149,59 +1300,17 @@ FX_HD void xs_noiselimiting(const XsCx &cx, const xaac_sbr_header *h, int skip, 
       ee.own(k) = xs_e(v.est.own(k));
     }
     const XsLv po = xs_seg_running_max(cx, mine, eo, n_bands), pe = xs_seg_running_max(cx, mine, ee, n_bands);
-    XS_LANES(k, 0, n_bands) {
-      const int Eo = eo.own(k) > po.own(k) ? eo.own(k) : po.own(k), Ee = ee.own(k) > pe.own(k) ? ee.own(k) : pe.own(k);
-      w->fold_b[k][0] = fx_shr(xs_m(v.e_orig.own(k)), Eo - eo.own(k));
-      w->fold_b[k][1] = fx_shr(xs_m(v.est.own(k)), Ee - ee.own(k));
-      w->fold_b[k][2] = ((Eo - po.own(k)) & 0xff) | (((Ee - pe.own(k)) & 0xff) << 8); /* shr32 masks its count so */
-      w->fold_b[k][3] = (Eo & 0xffff) | (int32_t)((uint32_t)Ee << 16);
-    }
+    XS_LANES(k, 0, n_bands) xs_lim_sum_operands(v.e_orig.own(k), v.est.own(k), po.own(k), pe.own(k), w->fold_b[k]);
   }
   cx.sync();
   XS_PAR(c, 0, nlf) {
     const int t_lo = h->freq_band_tbl_lim[c], t_hi = h->freq_band_tbl_lim[c + 1];
     const int b0 = t_lo > skip ? t_lo - skip : 0, b1 = t_hi > skip ? t_hi - skip : 0;
     if (b0 >= b1) continue;
-    int32_t som = 0, sem = 0, last = 0;
-    XS_UNROLL4
-    for (int k = b0; k < b1; k++) {
-      const int32_t d = w->fold_b[k][2];
-      som = fx_shr(som, d & 255) + w->fold_b[k][0];
-      sem = fx_shr(sem, d >> 8) + w->fold_b[k][1];
-      last = w->fold_b[k][3];
-    }
-    int32_t soe = (int16_t)last, see = last >> 16;
-    int nv = 16 - xs_pnorm32(som);
-    if (nv > 0) {
-      som >>= nv;
-      soe += nv;
-    }
-    nv = 16 - xs_pnorm32(sem);
-    if (nv > 0) {
-      sem >>= nv;
-      see += nv;
-    }
-    const int16_t so_m = (int16_t)som, so_e = (int16_t)soe;
-    int16_t mg_m;
-    int16_t mg_e = (int16_t)(xs_fix_mant_div(so_m, (int16_t)sem, &mg_m) + (so_e - (int16_t)see) + 1);
-    int32_t mt = xs_mult16x16_shl(mg_m, lim_m);
-    mg_e = (int16_t)(mg_e + lim_e);
-    int tv = fx_norm32(mt);
-    mg_e = (int16_t)(mg_e - tv);
-    mg_m = (int16_t)(xs_shl(mt, tv) >> 16);
-    if (mg_e >= 34) {
-      mg_m = 0x3000;
-      mg_e = 34;
-    }
-    w->res_a[c][0] = mg_m;
-    w->res_a[c][1] = mg_e;
-    w->res_a[c][2] = so_m;
-    w->res_a[c][3] = so_e;
+    xs_lim_max_gain(w->fold_b, b0, b1, lim_m, lim_e, w->res_a[c]);
   }
   cx.sync();
   XS_T(16);
-  /* the gain limit per band; then the sum of what the limited gains, sines and noise deliver (env_calc.c:330-390):
-     up to two addends per band, in band order */
   {
     XsLv a_m, a_e, b_me, emax, with_b;
     a_m.fill(0);
@@ -1212,40 +1321,13 @@ FX_HD void xs_noiselimiting(const XsCx &cx, const xaac_sbr_header *h, int skip, 
     XS_LANES(k, 0, n_bands) {
       const int c_of = mine.own(k);
       if (c_of < 0) continue;
-      const int16_t mg_m = w->res_a[c_of][0], mg_e = w->res_a[c_of][1];
-      int16_t gm = xs_m(v.gain.own(k)), ge = xs_e(v.gain.own(k));
-      if (ge > mg_e || (ge == mg_e && gm > mg_m)) {
-        int16_t na_m;
-        int na_e = xs_fix_mant_div(mg_m, gm, &na_m);
-        na_e += (mg_e - ge) + 1;
-        const int32_t nl = v.noise.own(k);
-        v.noise.own(k) =
-            xs_me((int16_t)(fx_shl_dir_sat_limit(xs_mult16x16_shl(xs_m(nl), na_m), (int16_t)na_e) >> 16), xs_e(nl));
-        gm = mg_m;
-        ge = mg_e;
-        v.gain.own(k) = xs_me(gm, ge);
-      }
-      a_m.own(k) = ((int32_t)gm * xs_m(v.est.own(k))) >> 15;
-      a_e.own(k) = ge + xs_e(v.est.own(k));
-      /* the second addend: the sine if there is one, else the noise unless it is absent (noise_absc) */
-      const int32_t sn = v.sine.own(k);
-      b_me.own(k) = xs_m(sn) != 0 ? sn : (noise_absc == 0 ? v.noise.own(k) : 0);
-      const bool has_b = xs_m(sn) != 0 || noise_absc == 0;
-      emax.own(k) = (has_b && xs_e(b_me.own(k)) > a_e.own(k)) ? xs_e(b_me.own(k)) : a_e.own(k);
-      with_b.own(k) = has_b ? 1 : 0;
+      xs_lim_limit_band(w->res_a[c_of][0], w->res_a[c_of][1], v.est.own(k), v.sine.own(k), noise_absc, v.gain.own(k),
+                        v.noise.own(k), a_m.own(k), a_e.own(k), b_me.own(k), emax.own(k), with_b.own(k));
     }
     const XsLv pm = xs_seg_running_max(cx, mine, emax, n_bands);
     XS_LANES(k, 0, n_bands) {
       if (mine.own(k) < 0) continue;
-      const int has_b = with_b.own(k);
-      const int E0 = pm.own(k);
-      const int E1 = a_e.own(k) > E0 ? a_e.own(k) : E0;
-      const int eb = xs_e(b_me.own(k));
-      const int E2 = (has_b && eb > E1) ? eb : E1;
-      w->fold_b[k][0] = fx_shr(a_m.own(k), E1 - a_e.own(k));
-      w->fold_b[k][1] = has_b ? fx_shr(xs_m(b_me.own(k)), E2 - eb) : 0;
-      w->fold_b[k][2] = ((E1 - E0) & 0xff) | (((E2 - E1) & 0xff) << 8);
-      w->fold_b[k][3] = E2;
+      xs_lim_boost_operands(a_m.own(k), a_e.own(k), b_me.own(k), with_b.own(k), pm.own(k), w->fold_b[k]);
     }
   }
   cx.sync();
@@ -1254,40 +1336,14 @@ FX_HD void xs_noiselimiting(const XsCx &cx, const xaac_sbr_header *h, int skip, 
     const int t_lo = h->freq_band_tbl_lim[c], t_hi = h->freq_band_tbl_lim[c + 1];
     const int b0 = t_lo > skip ? t_lo - skip : 0, b1 = t_hi > skip ? t_hi - skip : 0;
     if (b0 >= b1) continue;
-    const int16_t so_m = w->res_a[c][2], so_e = w->res_a[c][3];
-    int32_t am = 0, ae = 0;
-    XS_UNROLL4
-    for (int k = b0; k < b1; k++) {
-      const int32_t d = w->fold_b[k][2];
-      am = fx_shr(am, d & 255) + w->fold_b[k][0];
-      am = fx_shr(am, d >> 8) + w->fold_b[k][1];
-      ae = w->fold_b[k][3];
-    }
-    int nv = 16 - fx_norm32(am);
-    if (nv > 0) {
-      am >>= nv;
-      ae += nv;
-    }
-    int16_t bg_m;
-    int bg_e = xs_fix_mant_div(so_m, (int16_t)am, &bg_m);
-    bg_e = (int16_t)(bg_e + (so_e - (int16_t)ae) + 1);
-    if (bg_e > 2 || (bg_e == 2 && bg_m > 0x5061)) {
-      bg_m = 0x5061;
-      bg_e = 2;
-    }
-    w->res_b[c][0] = bg_m;
-    w->res_b[c][1] = (int16_t)bg_e;
+    xs_lim_boost_gain(w->fold_b, b0, b1, w->res_a[c][2], w->res_a[c][3], w->res_b[c]);
   }
   cx.sync();
   XS_T(18);
   XS_LANES(k, 0, n_bands) {
     const int c_of = mine.own(k);
     if (c_of < 0) continue;
-    const int16_t bg_m = w->res_b[c_of][0], bg_e = w->res_b[c_of][1];
-    const int32_t g = v.gain.own(k), sn = v.sine.own(k), nl = v.noise.own(k);
-    v.gain.own(k) = xs_me(xs_mult16_shl(xs_m(g), bg_m), (int16_t)(xs_e(g) + bg_e));
-    v.sine.own(k) = xs_me(xs_mult16_shl(xs_m(sn), bg_m), (int16_t)(xs_e(sn) + bg_e));
-    v.noise.own(k) = xs_me(xs_mult16_shl(xs_m(nl), bg_m), (int16_t)(xs_e(nl) + bg_e));
+    xs_lim_boost_band(w->res_b[c_of][0], w->res_b[c_of][1], v.gain.own(k), v.sine.own(k), v.noise.own(k));
   }
   cx.sync();
   XS_T(20);
@@ -1301,33 +1357,81 @@ FX_HD void xs_noiselimiting(const XsCx &cx, const xaac_sbr_header *h, int skip, 
    a multiple of four; its group ends four bands up when the next three bands are still in the run,
    else where the run stops.  Returns the mask of group-start bands; end.own(s) = end of the group
    that starts at s. */
+/* The two bits of band k (of nsb) that the masks are made of: 1 = the band is in a run, 2 = its alias_red is set. */
+FX_HD int32_t xs_alias_run_bits(int k, int nsb, int32_t deg1, int32_t alias_red) {
+  return ((k < nsb - 1 && deg1 != 0 && alias_red) ? 1 : 0) | (alias_red ? 2 : 0);
+}
+/* Whether position l of the masks starts a group, and where that group ends.  The bands of l's envelope are the
+   positions base .. base + nsb - 1 (one envelope: base = 0); a run does not reach below base. */
+FX_HD bool xs_alias_group_at(uint64_t in_run, uint64_t red, int l, int base, int nsb, int32_t &end) {
+  if (!((in_run >> l) & 1)) return false;
+  const uint64_t gaps_below = ~in_run & (xs_mask_upto(l) >> 1);
+  int run_start = gaps_below ? 64 - xs_clz64(gaps_below) : 0;
+  if (run_start < base) run_start = base;
+  if ((l - run_start) & 3) return false;
+  int e;
+  if (((in_run >> l) & 15) == 15) {
+    e = l + 4;
+  } else {
+    const int z = l + xs_ctz64(~(in_run >> l)); /* first position at or above l outside the run */
+    if (z - base >= nsb - 1)
+      e = base + nsb;
+    else
+      e = ((red >> z) & 1) ? z + 1 : z;
+  }
+  end = e;
+  return true;
+}
 FX_HD uint64_t xs_alias_groups(const XsCx &cx, const XsLv &deg1, const XsLv &alias_red, int nsb, XsLv &end) {
   XsLv f;
   f.fill(0);
-  XS_LANES(k, 0, 64)
-    f.own(k) = ((k < nsb - 1 && deg1.own(k) != 0 && alias_red.own(k)) ? 1 : 0) | (alias_red.own(k) ? 2 : 0);
+  XS_LANES(k, 0, 64) f.own(k) = xs_alias_run_bits(k, nsb, deg1.own(k), alias_red.own(k));
   const uint64_t in_run = xs_ballot(cx, f, 1, 64), red = xs_ballot(cx, f, 2, 64);
   XsLv st;
   st.fill(0);
-  XS_LANES(k, 0, 64) {
-    if (!((in_run >> k) & 1)) continue;
-    const uint64_t gaps_below = ~in_run & (xs_mask_upto(k) >> 1);
-    const int run_start = gaps_below ? 64 - xs_clz64(gaps_below) : 0;
-    if ((k - run_start) & 3) continue;
-    st.own(k) = 1;
-    int e;
-    if (((in_run >> k) & 15) == 15) {
-      e = k + 4;
-    } else {
-      const int z = k + xs_ctz64(~(in_run >> k)); /* first band at or above k outside the run */
-      if (z >= nsb - 1)
-        e = nsb;
-      else
-        e = ((red >> z) & 1) ? z + 1 : z;
-    }
-    end.own(k) = e;
-  }
+  XS_LANES(k, 0, 64) st.own(k) = xs_alias_group_at(in_run, red, k, 0, nsb, end.own(k)) ? 1 : 0;
   return xs_ballot(cx, st, 1, 64);
+}
+/* step 2, the arithmetic.  A band of a group: its gain mixed with the group's average gain gg by the larger of its own
+   and (below the last band) the next band's aliasing degree; row = what the mixed gain delivers, an addend of the group's
+   sum. */
+FX_HD void xs_alias_mix_band(int16_t deg, int16_t deg1, bool has_next, int16_t gg_m, int16_t gg_e, int32_t est,
+                             int32_t &gain, int32_t *row) {
+  int16_t alpha = deg;
+  if (has_next && deg1 > alpha) alpha = deg1;
+  int32_t gain_m = (int32_t)alpha * gg_m;
+  int16_t one_minus = (int16_t)(0x7fff - alpha);
+  int32_t tm = xs_m(gain), te = xs_e(gain);
+  tm = ((int32_t)one_minus * tm) >> 15;
+  int32_t d = gg_e - te;
+  if (d >= 0) {
+    te = gg_e;
+    tm = fx_shr(tm, d);
+    tm = (gain_m >> 15) + tm;
+  } else {
+    tm = fx_shr(gain_m, 15 - d) + tm;
+  }
+  gain = xs_me((int16_t)tm, (int16_t)te);
+  /* the reference multiplies the untruncated 32-bit tmp_gain_mant here (env_calc.c:182) */
+  row[0] = (int32_t)((uint32_t)tm * (uint32_t)(int32_t)xs_m(est)) >> 16;
+  row[1] = te + xs_e(est) + 1;
+}
+/* A group, rows [s,e) of fb: the energy amp it should deliver over the sum of what the mixed gains deliver */
+FX_HD void xs_alias_compensation(const int32_t (*fb)[4], int s, int e, int16_t amp_m, int16_t amp_e, int16_t &comp_m,
+                                 int16_t &comp_e) {
+  int32_t mod_m = 0, mod_e = 0;
+  for (int k = s; k < e; k++) xs_acc_me(&mod_m, &mod_e, fb[k][0], fb[k][1]);
+  int nv = 16 - xs_pnorm32(mod_m);
+  if (nv > 0) {
+    mod_m >>= nv;
+    mod_e += nv;
+  }
+  int ce = xs_fix_mant_div(amp_m, (int16_t)mod_m, &comp_m);
+  comp_e = (int16_t)(ce + amp_e - (int16_t)mod_e + 1 + 1);
+}
+/* ... which every band of the group takes into its gain */
+FX_HD int32_t xs_alias_compensate_band(int32_t g2, int16_t comp_m, int16_t comp_e) {
+  return xs_me((int16_t)(((int32_t)xs_m(g2) * comp_m) >> 16), (int16_t)(xs_e(g2) + comp_e));
 }
 /* step 2: equalise the gains inside each group (the lane of a group's first band does its sums) */
 FX_HD void xs_alias_reduction(const XsCx &cx, XsEnv &v, XsWork *w, uint64_t starts, const XsLv &end, int nsb) {
@@ -1356,57 +1460,26 @@ FX_HD void xs_alias_reduction(const XsCx &cx, XsEnv &v, XsWork *w, uint64_t star
     const int s = 63 - xs_clz64(below);
     if (k >= w->res_b[s][0]) continue;
     mine.own(k) = s;
-    const int16_t gg_m = w->res_a[s][2], gg_e = w->res_a[s][3];
-    int16_t alpha = (int16_t)v.deg.own(k);
-    if (k < nsb - 1 && (int16_t)v.deg1.own(k) > alpha) alpha = (int16_t)v.deg1.own(k);
-    int32_t gain_m = (int32_t)alpha * gg_m;
-    int16_t one_minus = (int16_t)(0x7fff - alpha);
-    int32_t tm = xs_m(v.gain.own(k)), te = xs_e(v.gain.own(k));
-    tm = ((int32_t)one_minus * tm) >> 15;
-    int32_t d = gg_e - te;
-    if (d >= 0) {
-      te = gg_e;
-      tm = fx_shr(tm, d);
-      tm = (gain_m >> 15) + tm;
-    } else {
-      tm = fx_shr(gain_m, 15 - d) + tm;
-    }
-    v.gain.own(k) = xs_me((int16_t)tm, (int16_t)te);
-    /* the reference multiplies the untruncated 32-bit tmp_gain_mant here (env_calc.c:182) */
-    w->fold_b[k][0] = (int32_t)((uint32_t)tm * (uint32_t)(int32_t)xs_m(v.est.own(k))) >> 16;
-    w->fold_b[k][1] = te + xs_e(v.est.own(k)) + 1;
+    xs_alias_mix_band((int16_t)v.deg.own(k), (int16_t)v.deg1.own(k), k < nsb - 1, w->res_a[s][2], w->res_a[s][3],
+                      v.est.own(k), v.gain.own(k), w->fold_b[k]);
   }
   cx.sync();
   XS_LANES(s, 0, nsb) {
     if (!((starts >> s) & 1)) continue;
-    int32_t mod_m = 0, mod_e = 0;
-    const int e = end.own(s);
-    for (int k = s; k < e; k++) xs_acc_me(&mod_m, &mod_e, w->fold_b[k][0], w->fold_b[k][1]);
-    int nv = 16 - xs_pnorm32(mod_m);
-    if (nv > 0) {
-      mod_m >>= nv;
-      mod_e += nv;
-    }
-    int16_t comp_m;
-    int comp_e = xs_fix_mant_div(w->res_a[s][0], (int16_t)mod_m, &comp_m);
-    comp_e = (int16_t)(comp_e + w->res_a[s][1] - (int16_t)mod_e + 1 + 1);
-    w->res_b[s][1] = comp_m;
-    w->res_a[s][3] = (int16_t)comp_e;
+    xs_alias_compensation(w->fold_b, s, end.own(s), w->res_a[s][0], w->res_a[s][1], w->res_b[s][1], w->res_a[s][3]);
   }
   cx.sync();
   XS_LANES(k, 0, nsb) {
     const int s = mine.own(k);
     if (s < 0) continue;
-    const int16_t comp_m = w->res_b[s][1], comp_e = w->res_a[s][3];
-    const int32_t g2 = v.gain.own(k);
-    v.gain.own(k) = xs_me((int16_t)(((int32_t)xs_m(g2) * comp_m) >> 16), (int16_t)(xs_e(g2) + comp_e));
+    v.gain.own(k) = xs_alias_compensate_band(v.gain.own(k), w->res_b[s][1], w->res_a[s][3]);
   }
   cx.sync();
 }
 
 /* ---- two envelopes side by side (HQ mode) ----------------------------------------------------------------------------
  * The gain mathematics of an envelope -- xs_subband_gain_meta, xs_calc_subband_gains, xs_noiselimiting,
- * xs_erg_to_amplitude_hq -- only reads the envelope's energy estimates and side info: nothing of it depends on the envelope
+ * xs_erg_to_amplitude -- only reads the envelope's energy estimates and side info: nothing of it depends on the envelope
  * before.  A frame's SBR range is at most 32 bands wide in every stream the reference's tables produce at 48 kHz and below
  * (26 - 27 bands in the bench's streams), so the chain above leaves more than half of the wave idle and runs once per
  * envelope, 2.9 times per frame in the bench's transient-heavy material.  Here element c of envelope q (q = 0, 1) of a pass
@@ -1451,25 +1524,14 @@ FX_HD int32_t xs_energy_element_pk(const Q &x, int first, int n, int k, int16_t 
     mx |= fx_abs_nrm(re[j]);
     if constexpr (Q::HQ) mx |= fx_abs_nrm(im[j]);
   }
-  const int pre = xs_pnorm32(mx) - (Q::HQ ? 4 : 3);
-  int shift = 16 - pre;
-  const int e_shr = shift > 0 ? shift & 31 : 0, e_shl = shift > 0 ? 0 : (-shift) & 31;
+  const XsEnergyShift sh = xs_energy_shift<Q::HQ>(mx);
   int32_t accu = 0;
   XS_UNROLL
   for (int j = 0; j < N; j++) {
-    int16_t t = (int16_t)((int32_t)((uint32_t)re[j] << e_shl) >> e_shr);
-    accu = fx_add(accu, (int32_t)t * t);
-    if constexpr (Q::HQ) {
-      t = (int16_t)((int32_t)((uint32_t)im[j] << e_shl) >> e_shr);
-      accu = fx_add(accu, (int32_t)t * t);
-    }
+    accu = xs_energy_add(accu, re[j], sh);
+    if constexpr (Q::HQ) accu = xs_energy_add(accu, im[j], sh);
   }
-  if (accu == 0) return 0;
-  shift = -xs_pnorm32(accu);
-  int16_t sum_m = (int16_t)xs_shr_dir_sat_limit(accu, 16 + shift);
-  sum_m = xs_mult16_shl_sat(sum_m, inv_width);
-  shift = shift - (pre << 1) + (Q::HQ ? 0 : 1);
-  return xs_me(sum_m, (int16_t)(frame_exp2 + shift + 1));
+  return xs_energy_finish<Q::HQ>(accu, sh.pre, inv_width, frame_exp2);
 }
 /* the same for any number of slots: two walks over the column part, eight slots' loads in flight at a time */
 template <class Q>
@@ -1491,9 +1553,7 @@ FX_HD int32_t xs_energy_element_long(const Q &x, int first, int n, int nmax, int
       if constexpr (Q::HQ) mx |= fx_abs_nrm(im[j]);
     }
   }
-  const int pre = xs_pnorm32(mx) - (Q::HQ ? 4 : 3);
-  int shift = 16 - pre;
-  const int e_shr = shift > 0 ? shift & 31 : 0, e_shl = shift > 0 ? 0 : (-shift) & 31;
+  const XsEnergyShift sh = xs_energy_shift<Q::HQ>(mx);
   int32_t accu = 0;
   for (int j0 = 0; j0 < nmax; j0 += 8) {
     int32_t re[8], im[8];
@@ -1509,20 +1569,11 @@ FX_HD int32_t xs_energy_element_long(const Q &x, int first, int n, int nmax, int
       if constexpr (Q::HQ) XS_KEEP(im[j]);
       re[j] = j0 + j < n ? re[j] : 0;
       im[j] = j0 + j < n ? im[j] : 0;
-      int16_t t = (int16_t)((int32_t)((uint32_t)re[j] << e_shl) >> e_shr);
-      accu = fx_add(accu, (int32_t)t * t);
-      if constexpr (Q::HQ) {
-        t = (int16_t)((int32_t)((uint32_t)im[j] << e_shl) >> e_shr);
-        accu = fx_add(accu, (int32_t)t * t);
-      }
+      accu = xs_energy_add(accu, re[j], sh);
+      if constexpr (Q::HQ) accu = xs_energy_add(accu, im[j], sh);
     }
   }
-  if (accu == 0) return 0;
-  shift = -xs_pnorm32(accu);
-  int16_t sum_m = (int16_t)xs_shr_dir_sat_limit(accu, 16 + shift);
-  sum_m = xs_mult16_shl_sat(sum_m, inv_width);
-  shift = shift - (pre << 1) + (Q::HQ ? 0 : 1);
-  return xs_me(sum_m, (int16_t)(frame_exp2 + shift + 1));
+  return xs_energy_finish<Q::HQ>(accu, sh.pre, inv_width, frame_exp2);
 }
 template <class Q>
 FX_HD void xs_energy_per_subband_pk(const XsCx &cx, const Q &x, const XsPass &ps, const int *s0, const int *s1, int b0,
@@ -1639,19 +1690,10 @@ FX_HD void xs_calc_subband_gains_pk(const XsCx &cx, const XsPass &ps, const XsLv
     const int q = l / XS_PK, c = l & (XS_PK - 1);
     if (q < ps.n && c < bands) {
       const int meta = v.meta.own(l);
-      const int16_t sf = (int16_t)(q ? gb.own(l) : ga.own(l));
-      const int16_t nfl = noise_floor_all[xs_qsel(q, ps.nf_off) + ((meta >> 8) & 255)];
-      const int present = (meta >> 16) & 1;
-      const int16_t ref_e = (int16_t)((sf & 63) - 16), ref_m = (int16_t)(sf & 0xffc0);
-      const int16_t nm = (int16_t)(nfl & 0xffc0), ne = (int16_t)((nfl & 63) - 38);
-      int16_t g[2] = {0, 0}, nl[2] = {0, 0}, sn[2] = {0, 0};
-      const int32_t est = v.est.own(l);
       const int mapped = c + skip < 64 ? (xs_qsel(q, ps.env) >= sm1.own(l)) : (xs_qsel(q, ps.env) >= 0);
-      xs_subbandgain(ref_m, nm, xs_m(est), xs_e(est), ne, ref_e, present, mapped, xs_qsel(q, ps.noise_absc), g, nl, sn);
-      v.e_orig.own(l) = xs_me(ref_m, ref_e);
-      v.gain.own(l) = xs_me(g[0], g[1]);
-      v.noise.own(l) = xs_me(nl[0], nl[1]);
-      v.sine.own(l) = xs_me(sn[0], sn[1]);
+      xs_subband_gain_band((int16_t)(q ? gb.own(l) : ga.own(l)), noise_floor_all[xs_qsel(q, ps.nf_off) + ((meta >> 8) & 255)],
+                           v.est.own(l), (meta >> 16) & 1, mapped, xs_qsel(q, ps.noise_absc), v.e_orig.own(l), v.gain.own(l),
+                           v.noise.own(l), v.sine.own(l));
     }
   }
 }
@@ -1685,13 +1727,7 @@ FX_HD void xs_noiselimiting_pk(const XsCx &cx, const xaac_sbr_header *h, const X
       ee.own(l) = xs_e(v.est.own(l));
     }
     const XsLv po = xs_seg_running_max(cx, key, eo, 64), pe = xs_seg_running_max(cx, key, ee, 64);
-    XS_LANES(l, 0, 64) {
-      const int Eo = eo.own(l) > po.own(l) ? eo.own(l) : po.own(l), Ee = ee.own(l) > pe.own(l) ? ee.own(l) : pe.own(l);
-      w->fold_b[l][0] = fx_shr(xs_m(v.e_orig.own(l)), Eo - eo.own(l));
-      w->fold_b[l][1] = fx_shr(xs_m(v.est.own(l)), Ee - ee.own(l));
-      w->fold_b[l][2] = ((Eo - po.own(l)) & 0xff) | (((Ee - pe.own(l)) & 0xff) << 8);
-      w->fold_b[l][3] = (Eo & 0xffff) | (int32_t)((uint32_t)Ee << 16);
-    }
+    XS_LANES(l, 0, 64) xs_lim_sum_operands(v.e_orig.own(l), v.est.own(l), po.own(l), pe.own(l), w->fold_b[l]);
   }
   cx.sync();
   XS_T(16);
@@ -1701,43 +1737,7 @@ FX_HD void xs_noiselimiting_pk(const XsCx &cx, const xaac_sbr_header *h, const X
       const int t_lo = h->freq_band_tbl_lim[c], t_hi = h->freq_band_tbl_lim[c + 1];
       int b0 = t_lo > skip ? t_lo - skip : 0, b1 = t_hi > skip ? t_hi - skip : 0;
       if (b1 > bands) b1 = bands; /* (the bands of the pass: xs_pack_frame_ok has checked that the table ends there) */
-      if (b0 < b1) {
-        int32_t som = 0, sem = 0, last = 0;
-        XS_UNROLL4
-        for (int k = b0; k < b1; k++) {
-          const int32_t d = w->fold_b[XS_PK * q + k][2];
-          som = fx_shr(som, d & 255) + w->fold_b[XS_PK * q + k][0];
-          sem = fx_shr(sem, d >> 8) + w->fold_b[XS_PK * q + k][1];
-          last = w->fold_b[XS_PK * q + k][3];
-        }
-        int32_t soe = (int16_t)last, see = last >> 16;
-        int nv = 16 - xs_pnorm32(som);
-        if (nv > 0) {
-          som >>= nv;
-          soe += nv;
-        }
-        nv = 16 - xs_pnorm32(sem);
-        if (nv > 0) {
-          sem >>= nv;
-          see += nv;
-        }
-        const int16_t so_m = (int16_t)som, so_e = (int16_t)soe;
-        int16_t mg_m;
-        int16_t mg_e = (int16_t)(xs_fix_mant_div(so_m, (int16_t)sem, &mg_m) + (so_e - (int16_t)see) + 1);
-        int32_t mt = xs_mult16x16_shl(mg_m, lim_m);
-        mg_e = (int16_t)(mg_e + lim_e);
-        int tv = fx_norm32(mt);
-        mg_e = (int16_t)(mg_e - tv);
-        mg_m = (int16_t)(xs_shl(mt, tv) >> 16);
-        if (mg_e >= 34) {
-          mg_m = 0x3000;
-          mg_e = 34;
-        }
-        w->res_a[r][0] = mg_m;
-        w->res_a[r][1] = mg_e;
-        w->res_a[r][2] = so_m;
-        w->res_a[r][3] = so_e;
-      }
+      if (b0 < b1) xs_lim_max_gain(w->fold_b + XS_PK * q, b0, b1, lim_m, lim_e, w->res_a[r]);
     }
   }
   cx.sync();
@@ -1752,40 +1752,15 @@ FX_HD void xs_noiselimiting_pk(const XsCx &cx, const xaac_sbr_header *h, const X
     XS_LANES(l, 0, 64) {
       const int c_of = mine.own(l);
       if (c_of < 0) continue;
-      const int q = l / XS_PK, noise_absc = xs_qsel(q, ps.noise_absc);
-      const int16_t mg_m = w->res_a[16 * q + c_of][0], mg_e = w->res_a[16 * q + c_of][1];
-      int16_t gm = xs_m(v.gain.own(l)), ge = xs_e(v.gain.own(l));
-      if (ge > mg_e || (ge == mg_e && gm > mg_m)) {
-        int16_t na_m;
-        int na_e = xs_fix_mant_div(mg_m, gm, &na_m);
-        na_e += (mg_e - ge) + 1;
-        const int32_t nl = v.noise.own(l);
-        v.noise.own(l) =
-            xs_me((int16_t)(fx_shl_dir_sat_limit(xs_mult16x16_shl(xs_m(nl), na_m), (int16_t)na_e) >> 16), xs_e(nl));
-        gm = mg_m;
-        ge = mg_e;
-        v.gain.own(l) = xs_me(gm, ge);
-      }
-      a_m.own(l) = ((int32_t)gm * xs_m(v.est.own(l))) >> 15;
-      a_e.own(l) = ge + xs_e(v.est.own(l));
-      const int32_t sn = v.sine.own(l);
-      b_me.own(l) = xs_m(sn) != 0 ? sn : (noise_absc == 0 ? v.noise.own(l) : 0);
-      const bool has_b = xs_m(sn) != 0 || noise_absc == 0;
-      emax.own(l) = (has_b && xs_e(b_me.own(l)) > a_e.own(l)) ? xs_e(b_me.own(l)) : a_e.own(l);
-      with_b.own(l) = has_b ? 1 : 0;
+      const int q = l / XS_PK;
+      xs_lim_limit_band(w->res_a[16 * q + c_of][0], w->res_a[16 * q + c_of][1], v.est.own(l), v.sine.own(l),
+                        xs_qsel(q, ps.noise_absc), v.gain.own(l), v.noise.own(l), a_m.own(l), a_e.own(l), b_me.own(l),
+                        emax.own(l), with_b.own(l));
     }
     const XsLv pm = xs_seg_running_max(cx, key, emax, 64);
     XS_LANES(l, 0, 64) {
       if (mine.own(l) < 0) continue;
-      const int has_b = with_b.own(l);
-      const int E0 = pm.own(l);
-      const int E1 = a_e.own(l) > E0 ? a_e.own(l) : E0;
-      const int eb = xs_e(b_me.own(l));
-      const int E2 = (has_b && eb > E1) ? eb : E1;
-      w->fold_b[l][0] = fx_shr(a_m.own(l), E1 - a_e.own(l));
-      w->fold_b[l][1] = has_b ? fx_shr(xs_m(b_me.own(l)), E2 - eb) : 0;
-      w->fold_b[l][2] = ((E1 - E0) & 0xff) | (((E2 - E1) & 0xff) << 8);
-      w->fold_b[l][3] = E2;
+      xs_lim_boost_operands(a_m.own(l), a_e.own(l), b_me.own(l), with_b.own(l), pm.own(l), w->fold_b[l]);
     }
   }
   cx.sync();
@@ -1796,31 +1771,7 @@ FX_HD void xs_noiselimiting_pk(const XsCx &cx, const xaac_sbr_header *h, const X
       const int t_lo = h->freq_band_tbl_lim[c], t_hi = h->freq_band_tbl_lim[c + 1];
       int b0 = t_lo > skip ? t_lo - skip : 0, b1 = t_hi > skip ? t_hi - skip : 0;
       if (b1 > bands) b1 = bands;
-      if (b0 < b1) {
-        const int16_t so_m = w->res_a[r][2], so_e = w->res_a[r][3];
-        int32_t am = 0, ae = 0;
-        XS_UNROLL4
-        for (int k = b0; k < b1; k++) {
-          const int32_t d = w->fold_b[XS_PK * q + k][2];
-          am = fx_shr(am, d & 255) + w->fold_b[XS_PK * q + k][0];
-          am = fx_shr(am, d >> 8) + w->fold_b[XS_PK * q + k][1];
-          ae = w->fold_b[XS_PK * q + k][3];
-        }
-        int nv = 16 - fx_norm32(am);
-        if (nv > 0) {
-          am >>= nv;
-          ae += nv;
-        }
-        int16_t bg_m;
-        int bg_e = xs_fix_mant_div(so_m, (int16_t)am, &bg_m);
-        bg_e = (int16_t)(bg_e + (so_e - (int16_t)ae) + 1);
-        if (bg_e > 2 || (bg_e == 2 && bg_m > 0x5061)) {
-          bg_m = 0x5061;
-          bg_e = 2;
-        }
-        w->res_b[r][0] = bg_m;
-        w->res_b[r][1] = (int16_t)bg_e;
-      }
+      if (b0 < b1) xs_lim_boost_gain(w->fold_b + XS_PK * q, b0, b1, w->res_a[r][2], w->res_a[r][3], w->res_b[r]);
     }
   }
   cx.sync();
@@ -1829,26 +1780,33 @@ FX_HD void xs_noiselimiting_pk(const XsCx &cx, const xaac_sbr_header *h, const X
     const int c_of = mine.own(l);
     if (c_of < 0) continue;
     const int q = l / XS_PK;
-    const int16_t bg_m = w->res_b[16 * q + c_of][0], bg_e = w->res_b[16 * q + c_of][1];
-    const int32_t g = v.gain.own(l), sn = v.sine.own(l), nl = v.noise.own(l);
-    v.gain.own(l) = xs_me(xs_mult16_shl(xs_m(g), bg_m), (int16_t)(xs_e(g) + bg_e));
-    v.sine.own(l) = xs_me(xs_mult16_shl(xs_m(sn), bg_m), (int16_t)(xs_e(sn) + bg_e));
-    v.noise.own(l) = xs_me(xs_mult16_shl(xs_m(nl), bg_m), (int16_t)(xs_e(nl) + bg_e));
+    xs_lim_boost_band(w->res_b[16 * q + c_of][0], w->res_b[16 * q + c_of][1], v.gain.own(l), v.sine.own(l), v.noise.own(l));
   }
   cx.sync();
   XS_T(20);
 }
 
-/* env_calc.c:423 */
-FX_HD void xs_erg_to_amplitude_lp(const XsCx &cx, int bands, int16_t noise_e, XsEnv &v) {
-  XS_LANES(k, 0, bands) {
-    int16_t sn[2] = {xs_m(v.sine.own(k)), xs_e(v.sine.own(k))};
-    int16_t g[2] = {xs_m(v.gain.own(k)), xs_e(v.gain.own(k))};
-    int16_t nl[2] = {xs_m(v.noise.own(k)), xs_e(v.noise.own(k))};
-    xs_mant_exp_sqrt(sn);
-    xs_mant_exp_sqrt(g);
-    xs_mant_exp_sqrt(nl);
-    int shift = (noise_e - nl[1]) - 4;
+/* env_calc.c:423 (low-power) / :450 (HQ), one band: the energies' square roots, the noise level brought to the envelope's
+   noise exponent.  The low-power branch takes its shift counts modulo 32 and shifts the sine level too; the HQ branch clamps
+   the noise shift to 31 and leaves the sine level alone. */
+template <int HQ>
+FX_HD void xs_amplitude_band(int noise_e, int32_t &sine, int32_t &gain, int32_t &noise) {
+  int16_t sn[2] = {xs_m(sine), xs_e(sine)};
+  int16_t g[2] = {xs_m(gain), xs_e(gain)};
+  int16_t nl[2] = {xs_m(noise), xs_e(noise)};
+  xs_mant_exp_sqrt(sn);
+  xs_mant_exp_sqrt(g);
+  xs_mant_exp_sqrt(nl);
+  int shift = (noise_e - nl[1]) - 4;
+  if (HQ) {
+    if (shift > 0) {
+      if (shift > 31) shift = 31;
+      nl[0] = (int16_t)(nl[0] >> shift);
+    } else {
+      if (shift < -31) shift = -31;
+      nl[0] = (int16_t)xs_shl(nl[0], -shift);
+    }
+  } else {
     if (shift > 0)
       nl[0] = (int16_t)xs_sar(nl[0], shift);
     else
@@ -1858,9 +1816,23 @@ FX_HD void xs_erg_to_amplitude_lp(const XsCx &cx, int bands, int16_t noise_e, Xs
       sn[0] = xs_shl16_sat(sn[0], (int16_t)shift);
     else
       sn[0] = (int16_t)xs_sar(sn[0], (int16_t)-shift);
-    v.sine.own(k) = xs_me(sn[0], sn[1]);
-    v.gain.own(k) = xs_me(g[0], g[1]);
-    v.noise.own(k) = xs_me(nl[0], nl[1]);
+  }
+  sine = xs_me(sn[0], sn[1]);
+  gain = xs_me(g[0], g[1]);
+  noise = xs_me(nl[0], nl[1]);
+}
+/* one envelope: band k on lane k */
+template <int HQ>
+FX_HD void xs_erg_to_amplitude(const XsCx &cx, int bands, int16_t noise_e, XsEnv &v) {
+  XS_LANES(k, 0, bands) xs_amplitude_band<HQ>(noise_e, v.sine.own(k), v.gain.own(k), v.noise.own(k));
+}
+/* a pass (see "two envelopes side by side"): element (q, c) on lane 32 q + c, the noise exponent a per-lane select */
+template <int HQ>
+FX_HD void xs_erg_to_amplitude_pk(const XsCx &cx, const XsPass &ps, int bands, XsEnv &v) {
+  XS_LANES(l, 0, 64) {
+    const int q = l / XS_PK, c = l & (XS_PK - 1);
+    if (q < ps.n && c < bands)
+      xs_amplitude_band<HQ>((int16_t)xs_qsel(q, ps.noise_e), v.sine.own(l), v.gain.own(l), v.noise.own(l));
   }
 }
 
@@ -1906,6 +1878,84 @@ FX_HD int16_t xs_noise_rescale(int16_t v, int diff) {
    spelled out per band, what is added to the gained sample is a per-envelope constant `term1` (its
    negative when the harmonic index is 3).  Shifts by 0 are the identity in both directions, which
    is why the reference's "> 0" / ">= 0" variants need no distinction. */
+/* What band k (of nsb, band 0 = QMF band sb_start) brings to every slot of an envelope.  sl / sl_prev / sl_next: the sine
+   levels of the band and its neighbours (0 outside the range), few_tones: at most 16 sines up to this band,
+   fi0: freq_inv for harmonic index 1 (index 3 negates it). */
+struct XsLpBand {
+  int16_t gm;
+  int32_t sine32, term1, edge1;
+  int edge_col, with_noise;
+  int shl_a, shr_a, shl_b, shr_b;
+};
+FX_HD XsLpBand xs_lp_band(int k, int nsb, int sb_start, int fi0, int32_t gain, int16_t sl, int16_t sl_prev, int16_t sl_next,
+                          int few_tones, int noise_absc, int input_e, int adj_e, int final_e) {
+  XsLpBand b;
+  const int nm1 = nsb - 1;
+  const int16_t ge = xs_e(gain);
+  b.gm = xs_m(gain);
+  b.with_noise = !noise_absc && sl == 0;
+  b.sine32 = xs_shl(sl, 16);
+  /* odd harmonic index: what band k adds to its own sample when the index is 1 */
+  if (k == 0) {
+    b.term1 = fx_mul32x16(XS_FACTOR, sl_next);
+    if (fi0 < 0) b.term1 = -b.term1;
+  } else if (k < nm1) {
+    const int32_t add = fx_mul32x16(XS_FACTOR, (int16_t)(sl_prev - sl_next));
+    b.term1 = few_tones ? (((k & 1) ? fi0 : -fi0) < 0 ? -add : add) : 0;
+  } else {
+    const int32_t tms = fx_mul32x16(XS_FACTOR, sl_prev);
+    b.term1 = few_tones ? (((nm1 & 1) ? fi0 : -fi0) > 0 ? tms : -tms) : 0;
+  }
+  /* ... and what the two edge bands add to the column outside the range (index 1; sign as above) */
+  b.edge1 = 0;
+  b.edge_col = -1;
+  if (k == 0) {
+    b.edge1 = fx_mul32x16(XS_FACTOR, sl); /* shifted by the slot's noise exponent in xs_lp_slot */
+    b.edge_col = sb_start - 1;
+  }
+  if (k == nm1 && nm1 > 0 && few_tones && k + sb_start < 62) {
+    const int32_t tm2 = fx_mul32x16(XS_FACTOR, sl);
+    b.edge1 = ((nm1 & 1) ? fi0 : -fi0) > 0 ? -tm2 : tm2;
+    b.edge_col = sb_start + k + 1;
+  }
+  /* the gain's shift of a slot, ge - (scale_change - 1) with one of two scale changes, as a (left, right) pair of counts of
+     which one is zero: lane constants, so that the slot loop has no branch on the lane's exponent (xs_shl / xs_sar take
+     their counts modulo 32) */
+  const int sh_a = ge - ((adj_e - input_e) - 1), sh_b = ge - ((final_e - input_e) - 1);
+  b.shl_a = sh_a > 0 ? (sh_a & 31) : 0;
+  b.shr_a = sh_a > 0 ? 0 : ((-sh_a) & 31);
+  b.shl_b = sh_b > 0 ? (sh_b & 31) : 0;
+  b.shr_b = sh_b > 0 ? 0 : ((-sh_b) & 31);
+  return b;
+}
+/* Slot l of band k: the gained sample plus noise (random value rp, level nl) or sine -- env_calc.c:1564 when the slot's
+   harmonic index hi is even, :1617 when it is odd (`odd` = hi & 1, as the caller has it).  ne: the slot's noise exponent. */
+template <class Q>
+FX_HD void xs_lp_slot(const Q &x, const XsLpBand &b, int l, int k, int sb_start, int fi0, int hi, int odd, int16_t rp,
+                      int16_t nl, int ne, int lb_scale) {
+  int32_t val = fx_mul32x16(x(l, sb_start + k), b.gm);
+  val = (int32_t)((uint32_t)val << (l < Q::NS ? b.shl_a : b.shl_b)) >> (l < Q::NS ? b.shr_a : b.shr_b);
+  const int32_t noisy = xs_mac16x16_shl_sat(val, rp, nl); /* (every lane: a select below, not a branch per lane) */
+  if (!odd) {
+    const int32_t toned = hi == 0 ? fx_add_sat(val, b.sine32) : fx_sub_sat(val, b.sine32);
+    val = b.with_noise ? noisy : toned;
+  } else {
+    val = b.with_noise ? noisy : val;
+    val = fx_add_sat(val, hi == 1 ? b.term1 : -b.term1);
+    if (b.edge_col >= 0) {
+      int32_t t = b.edge1;
+      const int neg = (hi == 1 ? fi0 : -fi0) < 0;
+      if (k == 0) { /* band 0's tail carries the noise exponent; freq_inv < 0 adds it, else subtracts */
+        const int16_t nexp = (int16_t)((ne - 16) - lb_scale);
+        t = nexp > 0 ? fx_shl(t, nexp) : fx_shr(t, -nexp);
+        x(l, b.edge_col) = neg ? fx_add_sat(x(l, b.edge_col), t) : fx_sub_sat(x(l, b.edge_col), t);
+      } else { /* edge1 holds the index-1 sign already */
+        x(l, b.edge_col) = hi == 1 ? fx_add_sat(x(l, b.edge_col), t) : fx_sub_sat(x(l, b.edge_col), t);
+      }
+    }
+  }
+  x(l, sb_start + k) = val;
+}
 template <class ST, class Q>
 FX_HD void xs_adapt_noise_gain_lp(const XsCx &cx, ST *st, XsEnv &v, const int16_t *rand_hi, int noise_e, int nsb,
                                   int skip, int s0, int s1, int input_e, int adj_e, int final_e, int sb_start,
@@ -1930,49 +1980,15 @@ FX_HD void xs_adapt_noise_gain_lp(const XsCx &cx, ST *st, XsEnv &v, const int16_
   const XsLv tone = xs_prefix_nonzero_m(cx, v.sine, nsb);
   const XsLv s_prev = v.sine.shifted(cx, -1), s_next = v.sine.shifted(cx, 1);
   XS_T(21);
-  const int nm1 = nsb - 1;
   int fi0 = !(sb_start & 1); /* freq_inv for harmonic index 1; index 3 negates it */
   fi0 = (fi0 << 1) - 1;
   XS_LANES(k, 0, nsb) {
-    const int16_t gm = xs_m(v.gain.own(k)), ge = xs_e(v.gain.own(k));
-    const int16_t sl = xs_m(v.sine.own(k)), sl_prev = xs_m(s_prev.own(k));
     const int16_t sl_next = (k + 1 < nsb) ? xs_m(s_next.own(k)) : (int16_t)0;
     int16_t nl = xs_m(v.noise.own(k));
-    const int with_noise = !noise_absc && sl == 0;
-    const int few_tones = tone.own(k) <= 16;
-    const int32_t sine32 = xs_shl(sl, 16);
-    /* odd harmonic index: what band k adds to its own sample when the index is 1 */
-    int32_t term1;
-    if (k == 0) {
-      term1 = fx_mul32x16(XS_FACTOR, sl_next);
-      if (fi0 < 0) term1 = -term1;
-    } else if (k < nm1) {
-      const int32_t add = fx_mul32x16(XS_FACTOR, (int16_t)(sl_prev - sl_next));
-      term1 = few_tones ? (((k & 1) ? fi0 : -fi0) < 0 ? -add : add) : 0;
-    } else {
-      const int32_t tms = fx_mul32x16(XS_FACTOR, sl_prev);
-      term1 = few_tones ? (((nm1 & 1) ? fi0 : -fi0) > 0 ? tms : -tms) : 0;
-    }
-    /* ... and what the two edge bands add to the column outside the range (index 1; sign as above) */
-    int32_t edge1 = 0;
-    int edge_col = -1;
-    if (k == 0) {
-      edge1 = fx_mul32x16(XS_FACTOR, sl); /* shifted by the slot's noise exponent below */
-      edge_col = sb_start - 1;
-    }
-    if (k == nm1 && nm1 > 0 && few_tones && k + sb_start < 62) {
-      const int32_t tm2 = fx_mul32x16(XS_FACTOR, sl);
-      edge1 = ((nm1 & 1) ? fi0 : -fi0) > 0 ? -tm2 : tm2;
-      edge_col = sb_start + k + 1;
-    }
+    const XsLpBand b = xs_lp_band(k, nsb, sb_start, fi0, v.gain.own(k), xs_m(v.sine.own(k)), xs_m(s_prev.own(k)), sl_next,
+                                  tone.own(k) <= 16, noise_absc, input_e, adj_e, final_e);
     int16_t fbn = st->filt_buf_noise_m[k];
     int ne = noise_e, fbe = fb_noise_e0, ph = ph0, harm = harm0;
-    /* the gain's shift of a slot, ge - (scale_change - 1) with one of two scale changes, as a (left, right) pair of counts of
-       which one is zero: lane constants, so that the slot loop has no branch on the lane's exponent (xs_shl / xs_sar take
-       their counts modulo 32) */
-    const int sh_a = ge - ((adj_e - input_e) - 1), sh_b = ge - ((final_e - input_e) - 1);
-    const int shl_a = sh_a > 0 ? (sh_a & 31) : 0, shr_a = sh_a > 0 ? 0 : ((-sh_a) & 31);
-    const int shl_b = sh_b > 0 ? (sh_b & 31) : 0, shr_b = sh_b > 0 ? 0 : ((-sh_b) & 31);
     for (int l = s0; l < s1; l++) {
       if (l == Q::NS && s0 < Q::NS) { /* (uniform) */
         const int diff = final_e - ne;
@@ -1986,28 +2002,7 @@ FX_HD void xs_adapt_noise_gain_lp(const XsCx &cx, ST *st, XsEnv &v, const int16_
       const int hi = harm;
       ph = (ph + nsb) & 511;
       harm = (harm + 1) & 3;
-      int32_t val = fx_mul32x16(x(l, sb_start + k), gm);
-      val = (int32_t)((uint32_t)val << (l < Q::NS ? shl_a : shl_b)) >> (l < Q::NS ? shr_a : shr_b);
-      const int32_t noisy = xs_mac16x16_shl_sat(val, rp, nl); /* (every lane: a select below, not a branch per lane) */
-      if (!(hi & 1)) {
-        const int32_t toned = hi == 0 ? fx_add_sat(val, sine32) : fx_sub_sat(val, sine32);
-        val = with_noise ? noisy : toned;
-      } else {
-        val = with_noise ? noisy : val;
-        val = fx_add_sat(val, hi == 1 ? term1 : -term1);
-        if (edge_col >= 0) {
-          int32_t t = edge1;
-          const int neg = (hi == 1 ? fi0 : -fi0) < 0;
-          if (k == 0) { /* band 0's tail carries the noise exponent; freq_inv < 0 adds it, else subtracts */
-            const int16_t nexp = (int16_t)((ne - 16) - lb_scale);
-            t = nexp > 0 ? fx_shl(t, nexp) : fx_shr(t, -nexp);
-            x(l, edge_col) = neg ? fx_add_sat(x(l, edge_col), t) : fx_sub_sat(x(l, edge_col), t);
-          } else { /* edge1 holds the index-1 sign already */
-            x(l, edge_col) = hi == 1 ? fx_add_sat(x(l, edge_col), t) : fx_sub_sat(x(l, edge_col), t);
-          }
-        }
-      }
-      x(l, sb_start + k) = val;
+      xs_lp_slot(x, b, l, k, sb_start, fi0, hi, hi & 1, rp, nl, ne, lb_scale);
     }
     st->filt_buf_noise_m[k] = fbn;
     v.noise.own(k) = xs_me(nl, xs_e(v.noise.own(k)));
@@ -2070,7 +2065,6 @@ FX_HD void xs_adapt_noise_gain_lp_split(const XsCx &cx, ST *st, const XsEnv &v, 
   const XsLv tone = xs_prefix_nonzero_m(cx, sine, nsb).gather(lo); /* (lanes 0 .. nsb - 1 hold the counts) */
   const XsLv s_prev = sine.shifted(cx, -1), s_next = sine.shifted(cx, 1);
   XS_T(21);
-  const int nm1 = nsb - 1;
   int fi0 = !(sb_start & 1); /* freq_inv for harmonic index 1; index 3 negates it */
   fi0 = (fi0 << 1) - 1;
   const int n = s1 > s0 ? s1 - s0 : 0;
@@ -2082,40 +2076,12 @@ FX_HD void xs_adapt_noise_gain_lp_split(const XsCx &cx, ST *st, const XsEnv &v, 
   XS_LANES(l, 0, 64) {
     const int h = l / XS_PK, k = l & (XS_PK - 1);
     if (k >= nsb) continue;
-    const int16_t gm = xs_m(gain.own(l)), ge = xs_e(gain.own(l));
-    const int16_t sl = xs_m(sine.own(l));
     const int16_t sl_prev = k > 0 ? xs_m(s_prev.own(l)) : (int16_t)0;
     const int16_t sl_next = (k + 1 < nsb) ? xs_m(s_next.own(l)) : (int16_t)0;
     const int16_t nl_a = xs_m(noise.own(l));
     const int16_t nl_b = k < bands ? xs_noise_rescale(nl_a, final_e - noise_e) : nl_a;
-    const int with_noise = !noise_absc && sl == 0;
-    const int few_tones = tone.own(l) <= 16;
-    const int32_t sine32 = xs_shl(sl, 16);
-    int32_t term1;
-    if (k == 0) {
-      term1 = fx_mul32x16(XS_FACTOR, sl_next);
-      if (fi0 < 0) term1 = -term1;
-    } else if (k < nm1) {
-      const int32_t add = fx_mul32x16(XS_FACTOR, (int16_t)(sl_prev - sl_next));
-      term1 = few_tones ? (((k & 1) ? fi0 : -fi0) < 0 ? -add : add) : 0;
-    } else {
-      const int32_t tms = fx_mul32x16(XS_FACTOR, sl_prev);
-      term1 = few_tones ? (((nm1 & 1) ? fi0 : -fi0) > 0 ? tms : -tms) : 0;
-    }
-    int32_t edge1 = 0;
-    int edge_col = -1;
-    if (k == 0) {
-      edge1 = fx_mul32x16(XS_FACTOR, sl);
-      edge_col = sb_start - 1;
-    }
-    if (k == nm1 && nm1 > 0 && few_tones && k + sb_start < 62) {
-      const int32_t tm2 = fx_mul32x16(XS_FACTOR, sl);
-      edge1 = ((nm1 & 1) ? fi0 : -fi0) > 0 ? -tm2 : tm2;
-      edge_col = sb_start + k + 1;
-    }
-    const int sh_a = ge - ((adj_e - input_e) - 1), sh_b = ge - ((final_e - input_e) - 1);
-    const int shl_a = sh_a > 0 ? (sh_a & 31) : 0, shr_a = sh_a > 0 ? 0 : ((-sh_a) & 31);
-    const int shl_b = sh_b > 0 ? (sh_b & 31) : 0, shr_b = sh_b > 0 ? 0 : ((-sh_b) & 31);
+    const XsLpBand b = xs_lp_band(k, nsb, sb_start, fi0, gain.own(l), xs_m(sine.own(l)), sl_prev, sl_next, tone.own(l) <= 16,
+                                  noise_absc, input_e, adj_e, final_e);
     /* half h walks the slots from s0 + h n_half on; n_half is even, so a step's harmonic index is even on both halves or odd
        on both: which of the two bodies (env_calc.c:1564 / :1617) a step runs is a scalar branch, not both under masks */
     const int first = s0 + h * n_half;
@@ -2126,29 +2092,7 @@ FX_HD void xs_adapt_noise_gain_lp_split(const XsCx &cx, ST *st, const XsEnv &v, 
       const int16_t nl = late ? nl_b : nl_a;
       const int ph = (ph0 + j * nsb) & 511, hi = (harm0 + j) & 3;
       const int16_t rp = rand_hi[ph + 1 + k];
-      int32_t val = fx_mul32x16(x(sl_i, sb_start + k), gm);
-      val = (int32_t)((uint32_t)val << (sl_i < Q::NS ? shl_a : shl_b)) >> (sl_i < Q::NS ? shr_a : shr_b);
-      const int32_t noisy = xs_mac16x16_shl_sat(val, rp, nl);
-      if (!((harm0 + u) & 1)) { /* (uniform) */
-        const int32_t toned = hi == 0 ? fx_add_sat(val, sine32) : fx_sub_sat(val, sine32);
-        val = with_noise ? noisy : toned;
-      } else {
-        val = with_noise ? noisy : val;
-        val = fx_add_sat(val, hi == 1 ? term1 : -term1);
-        if (edge_col >= 0) {
-          int32_t t = edge1;
-          const int neg = (hi == 1 ? fi0 : -fi0) < 0;
-          if (k == 0) {
-            const int ne = late ? final_e : noise_e;
-            const int16_t nexp = (int16_t)((ne - 16) - lb_scale);
-            t = nexp > 0 ? fx_shl(t, nexp) : fx_shr(t, -nexp);
-            x(sl_i, edge_col) = neg ? fx_add_sat(x(sl_i, edge_col), t) : fx_sub_sat(x(sl_i, edge_col), t);
-          } else {
-            x(sl_i, edge_col) = hi == 1 ? fx_add_sat(x(sl_i, edge_col), t) : fx_sub_sat(x(sl_i, edge_col), t);
-          }
-        }
-      }
-      x(sl_i, sb_start + k) = val;
+      xs_lp_slot(x, b, sl_i, k, sb_start, fi0, hi, (harm0 + u) & 1 /* (uniform) */, rp, nl, late ? final_e : noise_e, lb_scale);
     }
     /* what the walk leaves: the noise filter buffer rescaled at the first slot and where the exponent changes, the noise
        level of the last slot */
@@ -2177,65 +2121,14 @@ FX_HD void xs_adapt_noise_gain_lp_split(const XsCx &cx, ST *st, const XsEnv &v, 
   cx.sync();
 }
 
-/* ---- HQ (complex) mode -------------------------------------------------------------------------- */
-/* env_calc.c:450 */
-FX_HD void xs_erg_to_amplitude_hq(const XsCx &cx, int bands, int16_t noise_e, XsEnv &v) {
-  XS_LANES(k, 0, bands) {
-    int16_t sn[2] = {xs_m(v.sine.own(k)), xs_e(v.sine.own(k))};
-    int16_t g[2] = {xs_m(v.gain.own(k)), xs_e(v.gain.own(k))};
-    int16_t nl[2] = {xs_m(v.noise.own(k)), xs_e(v.noise.own(k))};
-    xs_mant_exp_sqrt(sn);
-    xs_mant_exp_sqrt(g);
-    xs_mant_exp_sqrt(nl);
-    int shift = (noise_e - nl[1]) - 4;
-    if (shift > 0) {
-      if (shift > 31) shift = 31;
-      nl[0] = (int16_t)(nl[0] >> shift);
-    } else {
-      if (shift < -31) shift = -31;
-      nl[0] = (int16_t)xs_shl(nl[0], -shift);
-    }
-    v.sine.own(k) = xs_me(sn[0], sn[1]);
-    v.gain.own(k) = xs_me(g[0], g[1]);
-    v.noise.own(k) = xs_me(nl[0], nl[1]);
-  }
-}
-
-/* xs_erg_to_amplitude_hq for a pass (see "two envelopes side by side") */
-FX_HD void xs_erg_to_amplitude_hq_pk(const XsCx &cx, const XsPass &ps, int bands, XsEnv &v) {
-  XS_LANES(l, 0, 64) {
-    const int q = l / XS_PK, c = l & (XS_PK - 1);
-    if (q < ps.n && c < bands) {
-      const int noise_e = (int16_t)xs_qsel(q, ps.noise_e);
-      int16_t sn[2] = {xs_m(v.sine.own(l)), xs_e(v.sine.own(l))};
-      int16_t g[2] = {xs_m(v.gain.own(l)), xs_e(v.gain.own(l))};
-      int16_t nl[2] = {xs_m(v.noise.own(l)), xs_e(v.noise.own(l))};
-      xs_mant_exp_sqrt(sn);
-      xs_mant_exp_sqrt(g);
-      xs_mant_exp_sqrt(nl);
-      int shift = (noise_e - nl[1]) - 4;
-      if (shift > 0) {
-        if (shift > 31) shift = 31;
-        nl[0] = (int16_t)(nl[0] >> shift);
-      } else {
-        if (shift < -31) shift = -31;
-        nl[0] = (int16_t)xs_shl(nl[0], -shift);
-      }
-      v.sine.own(l) = xs_me(sn[0], sn[1]);
-      v.gain.own(l) = xs_me(g[0], g[1]);
-      v.noise.own(l) = xs_me(nl[0], nl[1]);
-    }
-  }
-}
-
 /* ---- two envelopes side by side, low-power mode ------------------------------------------------------------------------
  * The same arrangement for the low-power chain (env_calc.c:692 with low_pow_flag): the energies (real matrix), the gain
- * mathematics and the limiter are the functions above; the alias reduction (env_calc.c:78) and the amplitude conversion
- * (env_calc.c:423) follow here on the same lanes -- element k of envelope q on lane 32 q + k -- and the slots of the two
- * envelopes are then adjusted one after the other by xs_adapt_noise_gain_lp on the envelope's half of the vectors.  Taken
- * for regular frames (xs_pack_frame_ok) whose adjusted range starts at sub_band_start (the reference indexes its gain
- * arrays from max_qmf_subband_aac and the aliasing degrees from sub_band_start with one counter; with the two apart the
- * one-envelope chain restates what that does). */
+ * mathematics, the limiter and the amplitude conversion (xs_erg_to_amplitude_pk<0>) are the functions above; the alias
+ * reduction (env_calc.c:78) follows here on the same lanes -- element k of envelope q on lane 32 q + k -- and the slots of
+ * the two envelopes are then adjusted one after the other by xs_adapt_noise_gain_lp_split.  Taken for regular frames
+ * (xs_pack_frame_ok) whose adjusted range starts at sub_band_start (the reference indexes its gain arrays from
+ * max_qmf_subband_aac and the aliasing degrees from sub_band_start with one counter; with the two apart the one-envelope
+ * chain restates what that does). */
 
 /* xs_alias_groups for a pass.  deg1p: element (q, k) = deg1[k].  A run cannot leave its half: the last band of an envelope
    (k = nsb - 1 <= 31) is never in a run. */
@@ -2245,32 +2138,12 @@ FX_HD uint64_t xs_alias_groups_pk(const XsCx &cx, const XsPass &ps, const XsLv &
   f.fill(0);
   XS_LANES(l, 0, 64) {
     const int q = l / XS_PK, k = l & (XS_PK - 1);
-    if (q < ps.n && k < nsb)
-      f.own(l) = ((k < nsb - 1 && deg1p.own(l) != 0 && alias_red.own(l)) ? 1 : 0) | (alias_red.own(l) ? 2 : 0);
+    if (q < ps.n && k < nsb) f.own(l) = xs_alias_run_bits(k, nsb, deg1p.own(l), alias_red.own(l));
   }
   const uint64_t in_run = xs_ballot(cx, f, 1, 64), red = xs_ballot(cx, f, 2, 64);
   XsLv st;
   st.fill(0);
-  XS_LANES(l, 0, 64) {
-    if (!((in_run >> l) & 1)) continue;
-    const int base = l & ~(XS_PK - 1);
-    const uint64_t gaps_below = ~in_run & (xs_mask_upto(l) >> 1);
-    int run_start = gaps_below ? 64 - xs_clz64(gaps_below) : 0;
-    if (run_start < base) run_start = base;
-    if ((l - run_start) & 3) continue;
-    st.own(l) = 1;
-    int e;
-    if (((in_run >> l) & 15) == 15) {
-      e = l + 4;
-    } else {
-      const int z = l + xs_ctz64(~(in_run >> l)); /* first lane at or above l outside the run */
-      if (z - base >= nsb - 1)
-        e = base + nsb;
-      else
-        e = ((red >> z) & 1) ? z + 1 : z;
-    }
-    end.own(l) = e;
-  }
+  XS_LANES(l, 0, 64) st.own(l) = xs_alias_group_at(in_run, red, l, l & ~(XS_PK - 1), nsb, end.own(l)) ? 1 : 0;
   return xs_ballot(cx, st, 1, 64);
 }
 /* xs_alias_reduction for a pass: groups, sums and results by lane number (a group's lanes are neighbours in its half) */
@@ -2303,81 +2176,22 @@ FX_HD void xs_alias_reduction_pk(const XsCx &cx, const XsPass &ps, XsEnv &v, con
     const int s = 63 - xs_clz64(below);
     if (l >= w->res_b[s][0]) continue; /* (a group of the other half ends below this half: never taken for it) */
     mine.own(l) = s;
-    const int16_t gg_m = w->res_a[s][2], gg_e = w->res_a[s][3];
-    int16_t alpha = (int16_t)degp.own(l);
-    if (k < nsb - 1 && (int16_t)deg1p.own(l) > alpha) alpha = (int16_t)deg1p.own(l);
-    int32_t gain_m = (int32_t)alpha * gg_m;
-    int16_t one_minus = (int16_t)(0x7fff - alpha);
-    int32_t tm = xs_m(v.gain.own(l)), te = xs_e(v.gain.own(l));
-    tm = ((int32_t)one_minus * tm) >> 15;
-    int32_t d = gg_e - te;
-    if (d >= 0) {
-      te = gg_e;
-      tm = fx_shr(tm, d);
-      tm = (gain_m >> 15) + tm;
-    } else {
-      tm = fx_shr(gain_m, 15 - d) + tm;
-    }
-    v.gain.own(l) = xs_me((int16_t)tm, (int16_t)te);
-    w->fold_b[l][0] = (int32_t)((uint32_t)tm * (uint32_t)(int32_t)xs_m(v.est.own(l))) >> 16;
-    w->fold_b[l][1] = te + xs_e(v.est.own(l)) + 1;
+    xs_alias_mix_band((int16_t)degp.own(l), (int16_t)deg1p.own(l), k < nsb - 1, w->res_a[s][2], w->res_a[s][3],
+                      v.est.own(l), v.gain.own(l), w->fold_b[l]);
   }
   cx.sync();
   XS_LANES(s, 0, 64) {
     if (!((starts >> s) & 1)) continue;
-    int32_t mod_m = 0, mod_e = 0;
-    const int e = end.own(s);
-    for (int k = s; k < e; k++) xs_acc_me(&mod_m, &mod_e, w->fold_b[k][0], w->fold_b[k][1]);
-    int nv = 16 - xs_pnorm32(mod_m);
-    if (nv > 0) {
-      mod_m >>= nv;
-      mod_e += nv;
-    }
-    int16_t comp_m;
-    int comp_e = xs_fix_mant_div(w->res_a[s][0], (int16_t)mod_m, &comp_m);
-    comp_e = (int16_t)(comp_e + w->res_a[s][1] - (int16_t)mod_e + 1 + 1);
-    w->res_b[s][1] = comp_m;
-    w->res_a[s][3] = (int16_t)comp_e;
+    xs_alias_compensation(w->fold_b, s, end.own(s), w->res_a[s][0], w->res_a[s][1], w->res_b[s][1], w->res_a[s][3]);
   }
   cx.sync();
   XS_LANES(l, 0, 64) {
     const int s = mine.own(l);
     if (s < 0) continue;
-    const int16_t comp_m = w->res_b[s][1], comp_e = w->res_a[s][3];
-    const int32_t g2 = v.gain.own(l);
-    v.gain.own(l) = xs_me((int16_t)(((int32_t)xs_m(g2) * comp_m) >> 16), (int16_t)(xs_e(g2) + comp_e));
+    v.gain.own(l) = xs_alias_compensate_band(v.gain.own(l), w->res_b[s][1], w->res_a[s][3]);
   }
   cx.sync();
 }
-/* xs_erg_to_amplitude_lp for a pass */
-FX_HD void xs_erg_to_amplitude_lp_pk(const XsCx &cx, const XsPass &ps, int bands, XsEnv &v) {
-  XS_LANES(l, 0, 64) {
-    const int q = l / XS_PK, c = l & (XS_PK - 1);
-    if (q < ps.n && c < bands) {
-      const int noise_e = (int16_t)xs_qsel(q, ps.noise_e);
-      int16_t sn[2] = {xs_m(v.sine.own(l)), xs_e(v.sine.own(l))};
-      int16_t g[2] = {xs_m(v.gain.own(l)), xs_e(v.gain.own(l))};
-      int16_t nl[2] = {xs_m(v.noise.own(l)), xs_e(v.noise.own(l))};
-      xs_mant_exp_sqrt(sn);
-      xs_mant_exp_sqrt(g);
-      xs_mant_exp_sqrt(nl);
-      int shift = (noise_e - nl[1]) - 4;
-      if (shift > 0)
-        nl[0] = (int16_t)xs_sar(nl[0], shift);
-      else
-        nl[0] = (int16_t)xs_shl(nl[0], -shift);
-      shift = sn[1] - noise_e;
-      if (shift > 0)
-        sn[0] = xs_shl16_sat(sn[0], (int16_t)shift);
-      else
-        sn[0] = (int16_t)xs_sar(sn[0], (int16_t)-shift);
-      v.sine.own(l) = xs_me(sn[0], sn[1]);
-      v.gain.own(l) = xs_me(g[0], g[1]);
-      v.noise.own(l) = xs_me(nl[0], nl[1]);
-    }
-  }
-}
-
 /* the regular frame the two-envelope chain is written for: energies per QMF band (interpol_freq), both frequency tables
    spanning exactly the SBR range of at most 32 bands, the limiter table inside it.  Every frame the reference's own tables
    (ixheaacd_freq_sca.c) describe at these widths passes; anything else runs the one-envelope chain. */
@@ -2392,6 +2206,7 @@ FX_HD bool xs_pack_frame_ok(const XsCx &cx, const xaac_sbr_header *h) {
   return cx.wave_or(bad) == 0;
 }
 
+/* ---- HQ (complex) mode -------------------------------------------------------------------------- */
 /* N slots of one band inside a segment of constant scale (xs_adapt_noise_gain_hq, step 2): the per-slot body of
    ixheaacd_harm_idx_zerotwo / _onethree with the gain, noise level and sine levels of the segment.  ph / harm
    advance by N slots. */
@@ -3178,7 +2993,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
       xs_noiselimiting_pk(cx, h, ps, skip, bands, v, w, lim_tab, lim_of);
       XS_T(7);
       if constexpr (Q::HQ) {
-        xs_erg_to_amplitude_hq_pk(cx, ps, bands, v);
+        xs_erg_to_amplitude_pk<1>(cx, ps, bands, v);
         XS_T(28);
         /* the envelopes' slots, one envelope after the other */
         for (int q = 0; q < ps.n; q++) {
@@ -3196,7 +3011,7 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
         XS_T(23);
         xs_alias_reduction_pk(cx, ps, v, degp, deg1p, w, grp_starts, grp_end, nsb);
         XS_T(8);
-        xs_erg_to_amplitude_lp_pk(cx, ps, bands, v);
+        xs_erg_to_amplitude_pk<0>(cx, ps, bands, v);
         XS_T(9);
         /* the envelopes' slots, one envelope after the other, every second slot on each half of the wave */
         for (int q = 0; q < ps.n; q++)
@@ -3247,12 +3062,12 @@ FX_HD int xs_calc_sbrenvelope(const XsCx &cx, const xaac_sbr_header *h, const xa
       XS_T(23);
       xs_alias_reduction(cx, v, w, grp_starts, grp_end, nsb);
       XS_T(8);
-      xs_erg_to_amplitude_lp(cx, nsb - skip, noise_e, v);
+      xs_erg_to_amplitude<0>(cx, nsb - skip, noise_e, v);
       XS_T(9);
       xs_adapt_noise_gain_lp(cx, st, v, rand_hi, noise_e, nsb, skip, s0, s1, input_e, adj_e, final_e, max_sb,
                              (int16_t)(15 - lb_scale), noise_absc, x);
     } else {
-      xs_erg_to_amplitude_hq(cx, nsb - skip, noise_e, v);
+      xs_erg_to_amplitude<1>(cx, nsb - skip, noise_e, v);
       xs_adapt_noise_gain_hq(cx, adj, v, 0, noise_e, nsb, skip, s0, s1, input_e, adj_e, final_e, max_sb, noise_absc,
                              smooth_length, x);
     }
