@@ -132,8 +132,19 @@ __global__ __launch_bounds__(XAAC_ESBR_CORE_BLOCK, USF4 ? 2 : 3) void xaac_esbr_
       ore[64 * r + lane] = apply ? hist_re[r] : 0.0f;
       oim[64 * r + lane] = apply ? hist_im[r] : 0.0f;
     }
-    /* rows 32.. become the next frame's history: cleared, the stages fill what they reach */
-    for (int i = ((!apply || rc) ? HIST : SLOTS) * 64 + lane; i < OUT_ROWS * 64; i += 64) {
+    /* rows 32.. become the next frame's history: the reference moves them down to row 0 and leaves them standing where they
+       were (sbr_dec.c:848-856), so they start out as the history once more and the stages overwrite what they reach -- a frame
+       that begins behind the previous one's end (a gap no conforming stream has; the reference's eSBR parser lets it through,
+       env_dec.c:744-769) plays the rows in between.  Cleared for a frame without SBR processing or a refused one. */
+    const bool keep = apply && !rc;
+    if (keep) {
+#pragma unroll
+      for (int r = 0; r < HIST; r++) {
+        ore[64 * (SLOTS + r) + lane] = hist_re[r];
+        oim[64 * (SLOTS + r) + lane] = hist_im[r];
+      }
+    }
+    for (int i = (keep ? SLOTS + HIST : HIST) * 64 + lane; i < OUT_ROWS * 64; i += 64) {
       ore[i] = 0.0f;
       oim[i] = 0.0f;
     }

@@ -161,6 +161,14 @@ static int esbr_frame(const float *core, int ratio, int ds, const xaac_sbr_heade
     memcpy(ore + 8, st->ph_re, sizeof(float) * 6 * 64);
     memcpy(oim + 8, st->ph_im, sizeof(float) * 6 * 64);
   }
+  /* sbr_dec.c:848-856 moves the rows from num_time_slots on down to row 0 and leaves them standing where they were: what this
+     frame does not write there (it ends before them, or is refused) is the next frame's history again -- a frame that starts
+     behind the previous one's end (a gap no conforming stream has, but the reference's eSBR parser lets through:
+     env_dec.c:744-769) plays those rows.  (A refused frame leaves zeros there, like the kernel.) */
+  if (f->apply_processing && !xe_side_info_bad(h, f, sd)) {
+    memcpy(ore + slots, ore, sizeof(float) * hist * 64);
+    memcpy(oim + slots, oim, sizeof(float) * hist * 64);
+  }
   if (nb == 32) xo_esbr_analysis(core, st->ana.ring, &st->ana.pos, &st->ana.win_off, &qre[ana_row][0], &qim[ana_row][0]);
   else xo_esbr_analysis_nb(core, nb, slots, st->ana.ring, &st->ana.pos, &st->ana.win_off, &qre[ana_row][0], &qim[ana_row][0]);
   bool have_ph = false;

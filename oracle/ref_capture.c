@@ -10,6 +10,7 @@
  * that INTEGRATION.md describes.  No reference code is copied: it only reads the reference's
  * own structs through the reference's own headers.
  */
+#include <math.h>
 #include "ref_convert.h"
 #include "ixheaacd_audioobjtypes.h"
 
@@ -203,6 +204,51 @@ static WORD32 esbr_chain_call(ia_sbr_dec_struct *d, WORD16 *time_data, ia_sbr_he
         }
     }
   }
+  /* $XAAC_ESBR_CHAIN_GRIDS (tools/make_golden_esbr_chains.py grids; 2:1 frames of 16 time slots without PVC): the frame's
+     envelope grid is replaced by a legal fuzzed one, the two kinds of tests/sbr_grid_cases.py: legal_grid_frame in turn --
+     kind 0: 0 = b0 < .. < b_n = 16, kind 1: first border 0..3, last border 16..19 (no bitstream ends a frame before time
+     slot 16, env_extr.c: the trailing border is num_time_slots plus 0..3; the whole-frame boundary of xaac_esbr.h refuses
+     such a frame) -- 1..5 envelopes, a freq_res per
+     envelope, the noise borders (one noise envelope for one envelope, else two, split at border (n + 1) / 2), transient_env
+     in -1..n, and envelope / noise-floor values as the parser's dequantisers make them from indices in their legal ranges
+     (env_dec.c:52-72, coupled channels :586-627, index ranges :298 and :364-370) */
+  if (seed && apply && getenv("XAAC_ESBR_CHAIN_GRIDS") && slots == 32 && h->num_time_slots == 16 && f->sbr_mode != PVC_SBR) {
+    const ia_freq_band_data_struct *fb = h->pstr_freq_band_data;
+    ia_frame_info_struct *fi = &f->str_frame_info_details;
+    const int kind = (steps[c] + c) & 1, nenv = 1 + (int)rnd(5);
+    const int lo = kind ? (int)rnd(4) : 0, hi = kind ? 16 + (int)rnd(4) : 16;
+    const int amp_res = f->amp_res ? 1 : 0, coupled = f->coupling_mode != COUPLING_OFF, right = (int)rnd(2);
+    const double a = amp_res ? 1.0 : 0.5, pan = amp_res ? 12.0 : 24.0;
+    int bord[MAX_ENVELOPES + 1], e, n_sf = 0, n_nf;
+    bord[0] = lo;
+    for (e = 1; e < nenv; e++) { /* strictly rising borders inside lo..hi */
+      const int b0 = bord[e - 1] + 1, b1 = hi - 1 - (nenv - 1 - e);
+      bord[e] = b0 + (int)rnd((uint32_t)(b1 - b0 + 1));
+    }
+    bord[nenv] = hi;
+    memset(fi->border_vec, 0, sizeof(fi->border_vec));
+    for (e = 0; e <= nenv; e++) fi->border_vec[e] = (WORD16)bord[e];
+    for (e = 0; e < MAX_ENVELOPES; e++) fi->freq_res[e] = (WORD16)rnd(2);
+    fi->num_env = (WORD16)nenv;
+    fi->num_noise_env = (WORD16)(nenv == 1 ? 1 : 2);
+    fi->noise_border_vec[0] = (WORD16)bord[0];
+    fi->noise_border_vec[1] = (WORD16)(nenv > 1 ? bord[(nenv + 1) / 2] : bord[nenv]);
+    fi->noise_border_vec[2] = (WORD16)bord[nenv];
+    fi->transient_env = (WORD16)((int)rnd((uint32_t)(nenv + 2)) - 1);
+    for (e = 0; e < nenv; e++) n_sf += fb->num_sf_bands[fi->freq_res[e]];
+    n_nf = fi->num_noise_env * fb->num_nf_bands;
+    f->num_env_sfac = (WORD16)n_sf;
+    for (i = 0; i < n_sf && i < MAX_NUM_ENVELOPE_VALUES; i++) {
+      const double l = (double)rnd((uint32_t)((SBR_ENV_SF_MAX_VAL_1_5 >> amp_res) + 1)), r = (double)rnd((uint32_t)(2 * pan + 1));
+      if (!coupled) f->flt_env_sf_arr[i] = (FLOAT32)(pow(2, l * a) * 64);
+      else f->flt_env_sf_arr[i] = (FLOAT32)(64 * (pow(2, l * a + 1) / (1 + pow(2, (right ? r - pan : pan - r) * a))));
+    }
+    for (i = 0; i < n_nf && i < MAX_NUM_NOISE_VALUES; i++) {
+      const double l = (double)rnd(MAX_NOISE_FLOOR_FAC_VAL + 1), r = (double)rnd(25);
+      if (!coupled) f->flt_noise_floor[i] = (FLOAT32)pow(2.0, NOISE_FLOOR_OFFSET - l);
+      else f->flt_noise_floor[i] = (FLOAT32)(pow(2, NOISE_FLOOR_OFFSET - l + 1) / (1 + pow(2, right ? r - 12.0 : 12.0 - r)));
+    }
+  }
   if (getenv("XAAC_ESBR_CHAIN_CORE_FILE")) { /* debugging aid: the stream's own core samples stay and are written out, call by call */
     static FILE *fc;
     if (!fc) fc = fopen(getenv("XAAC_ESBR_CHAIN_CORE_FILE"), "wb");
@@ -243,7 +289,14 @@ static WORD32 esbr_chain_call(ia_sbr_dec_struct *d, WORD16 *time_data, ia_sbr_he
   to_esbr_state(d, h, f, &est);
   if (h->hbe_flag && d->p_hbe_txposer) to_hbe_state(d->p_hbe_txposer, &hbs);
   else memset(&hbs, 0, sizeof(hbs));
+  const int end_border = f->str_frame_info_details.border_vec[f->str_frame_info_details.num_env]; /* of the grid the call ran on */
   if (seed && apply) {
+    if (getenv("XAAC_ESBR_CHAIN_GRIDS")) { /* the parser's own grid and values back (the branch's memory of the grid, str_frame_info_prev, stays) */
+      f->str_frame_info_details = f_keep.str_frame_info_details;
+      f->num_env_sfac = f_keep.num_env_sfac;
+      memcpy(f->flt_env_sf_arr, f_keep.flt_env_sf_arr, sizeof(f->flt_env_sf_arr));
+      memcpy(f->flt_noise_floor, f_keep.flt_noise_floor, sizeof(f->flt_noise_floor));
+    }
     h->limiter_gains = h_keep.limiter_gains;
     h->interpol_freq = h_keep.interpol_freq;
     h->smoothing_mode = h_keep.smoothing_mode;
@@ -271,9 +324,8 @@ static WORD32 esbr_chain_call(ia_sbr_dec_struct *d, WORD16 *time_data, ia_sbr_he
        frame-by-frame implementation that rebuilds the matrix from its eight carried rows has zeros there. */
     static xaac_esbr_state canon;
     const int kx = h->pstr_freq_band_data->sub_band_start;
-    const int nenv = f->str_frame_info_details.num_env;
     const int hist = slots == 64 ? XAAC_ESBR_OUT_HIST_ROWS_4_1 : XAAC_ESBR_OUT_HIST_ROWS;
-    int keep = apply ? 2 + (slots / 16) * f->str_frame_info_details.border_vec[nenv] - slots : hist, r, k;
+    int keep = apply ? 2 + (slots / 16) * end_border - slots : hist, r, k;
     canon = est;
     for (r = 0; r < hist; r++)
       for (k = 0; k < 64; k++)

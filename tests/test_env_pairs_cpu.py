@@ -17,6 +17,7 @@ import zlib
 import numpy as np
 
 import sbr_capture as cap
+from sbr_grid_cases import legal_grid_frame, set_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -82,37 +83,14 @@ def test_reference_made_chains(oracle):
 
 
 def _fuzz_frame(rng, h, f, wild):
-    """frame side info inside what xs_side_info_bad lets through"""
+    """frame side info inside what xs_side_info_bad lets through: wild 0 (a parser's grid, 0 = b0 < .. < b_n = 16) and
+    wild 1 (variable frames: first border 0..3, last 13..19) are the legal grids of tests/sbr_grid_cases.py, which
+    reference-made chains pin too (tests/test_sbr_grid_chains.py); wild 2 no bitstream can say, so it lives here alone"""
+    if wild < 2:
+        return legal_grid_frame(rng, h, f, wild)
     n_env = int(rng.integers(1, 6))
-    if wild == 0:      # a parser's grid: 0 = b0 < .. < b_n = 16
-        inner = sorted(rng.choice(np.arange(1, 16), n_env - 1, replace=False).tolist())
-        borders = [0] + inner + [16]
-    elif wild == 1:    # variable frames: first border 0..3, last 13..19
-        lo, hi = int(rng.integers(0, 4)), int(rng.integers(13, 20))
-        inner = sorted(rng.choice(np.arange(lo + 1, hi), n_env - 1, replace=False).tolist())
-        borders = [lo] + inner + [hi]
-    else:              # anything in 0..19: unsorted, repeated (empty envelopes), envelopes wholly behind slot 32
-        borders = rng.integers(0, 20, n_env + 1).tolist()
-    f.num_env = n_env
-    for e in range(9):
-        f.border_vec[e] = int(borders[e]) if e < len(borders) else 0
-    for e in range(8):
-        f.freq_res[e] = int(rng.integers(0, 2))
-    f.num_noise_env = 1 if n_env == 1 else 2
-    f.noise_border_vec[0] = f.border_vec[0]
-    f.noise_border_vec[1] = f.border_vec[(n_env + 1) // 2] if n_env > 1 else f.border_vec[n_env]
-    f.noise_border_vec[2] = f.border_vec[n_env]
-    f.transient_env = int(rng.integers(-1, n_env + 1))
-    for i in range(h.num_if_bands):
-        f.sbr_invf_mode[i] = int(rng.integers(0, 4))
-    nsf = h.num_sf_bands[1]
-    for i in range(nsf):
-        f.add_harmonics[i] = int(rng.integers(0, 5) == 0)
-    vals = np.frombuffer(f, dtype=np.uint8)  # noqa: F841  (keeps the ctypes buffer alive for the int16 views below)
-    for i in range(len(f.int_env_sf_arr)):
-        f.int_env_sf_arr[i] = int((int(rng.integers(0, 512)) << 6) | int(rng.integers(0, 40)))
-    for i in range(len(f.int_noise_floor)):
-        f.int_noise_floor[i] = int((int(rng.integers(0, 512)) << 6) | int(rng.integers(20, 50)))
+    # anything in 0..19: unsorted, repeated (empty envelopes), envelopes wholly behind slot 32
+    set_grid(rng, h, f, n_env, rng.integers(0, 20, n_env + 1).tolist())
 
 
 def test_fuzzed_chains(oracle):

@@ -8,7 +8,10 @@ states after the call; the float core input is regenerated here (counter-based i
   * CPU: the oracle's whole-frame function walks every chain (its own state carried) and must reproduce every CRC;
   * GPU (-m gpu): xaac_esbr_sbr_process_batch walks all chains as one batch with the three states resident on the device:
     the device builds of the float HF generator, envelope adjuster, float PS and transposer-in-chain meet reference data
-    directly (the float words, not +-1 LSB), not via the oracle."""
+    directly (the float words, not +-1 LSB), not via the oracle.
+tests/golden/esbr_grid_chains.npz ("grids"): 468 such calls in 36 chains over the four HE-AAC streams with every processed
+frame's envelope grid replaced, in the reference's live decoder, by a legal fuzzed one (tests/sbr_grid_cases.py; frames that
+start behind the previous frame's end among them: the rows of sbr_qmf_out in between are the reference's standing history)."""
 import ctypes
 import os
 import sys
@@ -25,7 +28,10 @@ PF = ctypes.POINTER(ctypes.c_float)
 FIXTURES = {"aac": np.load(os.path.join(ROOT, "tests", "golden", "esbr_chains.npz")),
             # the same chains for USAC channels (tools/make_golden_esbr_chains.py usac: stereo 2:1 eSBR with codec_x_delay 0, with the
             # harmonic transposer, a switched FD / LPD core's and a PVC stream's ORIG_SBR frames; 1482 calls in 78 chains)
-            "usac": np.load(os.path.join(ROOT, "tests", "golden", "esbr_usac_chains.npz"))}
+            "usac": np.load(os.path.join(ROOT, "tests", "golden", "esbr_usac_chains.npz")),
+            # the four HE-AAC streams again with every processed frame's envelope grid a legal fuzzed one
+            # (tools/make_golden_esbr_chains.py grids; tests/sbr_grid_cases.py says which grids)
+            "grids": np.load(os.path.join(ROOT, "tests", "golden", "esbr_grid_chains.npz"))}
 CH = FIXTURES["aac"]
 NO_X_DELAY, USAC = 8, 4     # include/xaac_esbr.h: bits of xaac_esbr_side::harmonic_sbr
 
@@ -93,7 +99,23 @@ def test_usac_fixture_is_what_it_says():
     assert (mode == 2).sum() > 150 and (mode == 1).sum() > 1000 and (mode == 0).sum() > 0      # PVC_SBR, ORIG_SBR, UNKNOWN_SBR frames
 
 
-@pytest.mark.parametrize("which", ["aac", "usac"])
+def test_grid_fixture_is_what_it_says():
+    """the coverage conditions of tests/golden/sbr_grid_chains.npz as far as they apply here: 1-5 envelopes, freq_res that changes
+    inside a frame and at the noise border, first borders 0 and above, last borders at and (20 times) above 16 (none below: no
+    bitstream ends a frame before slot 16, and xe_side_info_bad refuses one), every transient_env position, frames with and
+    without harmonics, no error return"""
+    import sbr_capture as cap
+    from sbr_grid_cases import grid_coverage_gaps
+    G = FIXTURES["grids"]
+    frames = [cap.Frame.from_buffer_copy(np.ascontiguousarray(G["frame"][r]).tobytes()) for r in np.nonzero(G["apply"])[0]]
+    assert len(frames) >= 300 and (G["chain_ps"] != 0).sum() >= 2
+    assert grid_coverage_gaps(frames, rets=G["ret"], min_late=20, early_end=False) == []
+    for f in frames:
+        b = [f.border_vec[e] for e in range(f.num_env + 1)]
+        assert all(x < y for x, y in zip(b, b[1:])) and 0 <= b[0] <= 3 and 16 <= b[-1] <= 19, b
+
+
+@pytest.mark.parametrize("which", ["aac", "usac", "grids"])
 def test_oracle_walks_the_reference_chains(oracle, which):
     CH = FIXTURES[which]
     fn = oracle.lib.xo_esbr_sbr_frame_pvc
@@ -126,7 +148,7 @@ def test_oracle_walks_the_reference_chains(oracle, which):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", ["aac", "usac"])
+@pytest.mark.parametrize("which", ["aac", "usac", "grids"])
 def test_gpu_walks_the_reference_chains(which):
     import torch
     import libxaac_amd

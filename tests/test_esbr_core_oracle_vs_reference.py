@@ -14,6 +14,7 @@ import pytest
 
 import sbr_capture as c
 from esbr_structs import EsbrSide, EsbrState, new_state
+from sbr_grid_cases import legal_grid_frame
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PF = ctypes.POINTER(ctypes.c_float)
@@ -70,9 +71,12 @@ def bind_h(lib, name):
     return fn
 
 
-def run_chain(oracle, reference, recs, seed, xover_extra=0, tes=False, n_frames=40, harmonic=False):
+def run_chain(oracle, reference, recs, seed, xover_extra=0, tes=False, n_frames=40, harmonic=False, grids=False):
     """harmonic: the HF generator's harmonic branch (sbr_patching_mode 0: the input is the transposer's rows, here random
-    ones) on most frames, LPP patching on the others, so that the limiter bands are remade at every change"""
+    ones) on most frames, LPP patching on the others, so that the limiter bands are remade at every change
+    grids: every frame's envelope grid is a fuzzed legal one instead of the captured stream's (tests/sbr_grid_cases.py:
+    1-5 envelopes, borders off 0 and 16, freq_res that changes inside the frame, every transient_env position), kind 0 and
+    kind 1 in turn"""
     if harmonic:
         ref_h, orc_h = bind_h(reference.lib, "ref_esbr_hf_env_h"), bind_h(oracle.lib, "xo_esbr_hf_env_h")
     ref_fn, orc_fn = bind(reference.lib, "ref_esbr_hf_env"), bind(oracle.lib, "xo_esbr_hf_env")
@@ -94,6 +98,8 @@ def run_chain(oracle, reference, recs, seed, xover_extra=0, tes=False, n_frames=
         if rng.integers(0, 3) == 0:
             for i in range(h.num_sf_bands[1]):
                 f.add_harmonics[i] = int(rng.integers(0, 5) == 0)
+        if grids:
+            legal_grid_frame(rng, h, f, n % 2)
         sd = make_side(rng, h, f, prev_modes, n, xover_extra, tes)
         tables = bytes(h)[12:]                        # a new header comes with a reset (the parser raises reset_flag)
         if prev_tables != tables:
@@ -166,3 +172,24 @@ def test_hf_env_chain_with_harmonic_patching(oracle, reference, recs, seed):
 @pytest.mark.parametrize("seed", range(3))
 def test_hf_env_chain_with_inter_tes(oracle, reference, recs, seed):
     run_chain(oracle, reference, recs, 300 + seed, tes=True)
+
+
+# ---- the same chains on fuzzed legal envelope grids (the captured streams' own grids above) -------------------------------
+@pytest.mark.parametrize("seed", range(3))
+def test_hf_env_chain_on_fuzzed_grids(oracle, reference, recs, seed):
+    run_chain(oracle, reference, recs, 500 + seed, grids=True)
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_hf_env_chain_on_fuzzed_grids_with_xover_offset(oracle, reference, recs, seed):
+    run_chain(oracle, reference, recs, 600 + seed, xover_extra=1 + seed, grids=True)
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_hf_env_chain_on_fuzzed_grids_with_harmonic_patching(oracle, reference, recs, seed):
+    run_chain(oracle, reference, recs, 700 + seed, harmonic=True, tes=seed == 1, grids=True)
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_hf_env_chain_on_fuzzed_grids_with_inter_tes(oracle, reference, recs, seed):
+    run_chain(oracle, reference, recs, 800 + seed, tes=True, grids=True)

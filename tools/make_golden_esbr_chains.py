@@ -36,6 +36,14 @@ USAC_STREAMS = ("u21", "u21harm", "u21sw", "m21swpvc", "m21tdpvc")
 # PVC frames (the reference encoder makes no harmonic SBR at these ratios); "chain_ratio" says which (xaac_esbr.h: XAAC_ESBR_RATIO_*)
 RATIO_STREAMS = ("u83", "m83swpvc", "u41", "m41swpvc", "m41tdpvc")
 USAC_PASSES = 6
+# `python tools/make_golden_esbr_chains.py grids` -> tests/golden/esbr_grid_chains.npz: the four HE-AAC streams again, every
+# processed frame's envelope grid replaced by a legal fuzzed one ($XAAC_ESBR_CHAIN_GRIDS, oracle/ref_capture.c: the two kinds of
+# tests/sbr_grid_cases.py -- the variable frames' last border 16..19 here: a bitstream cannot end a frame before slot 16, and the
+# whole-frame boundary refuses that -- with freq_res, noise borders, transient_env and dequantised envelope / noise-floor values) on top of the
+# fuzz above; every pass is fuzzed.  The reference's live decoder runs under a time limit: if it hangs or dies on a grid, the
+# generator stops with a message and writes nothing.  The coverage of sbr_grid_cases.grid_coverage_gaps is asserted before writing.
+GRID_PASSES = 2
+RUN_TIME_LIMIT = 120       # seconds for one decoder run (they take about one)
 
 
 def chain_core(run, chain, step):
@@ -80,23 +88,29 @@ def parse(path, run, z, pvc=False):
     return recs
 
 
-def main(usac=False, ratios=False):
+def main(usac=False, ratios=False, grids=False):
     usac = usac or ratios
     z = sizes()
     cap = os.path.join(ROOT, "oracle", "_ref", "xaacdec_capture")
     recs = []
     run = 0
-    for p in range(USAC_PASSES if usac else PASSES):
+    for p in range(GRID_PASSES if grids else USAC_PASSES if usac else PASSES):
         for s in (RATIO_STREAMS if ratios else USAC_STREAMS if usac else STREAMS):
             tmp = "/tmp/xaac_esbr_chain_%d.bin" % run
             env = dict(os.environ, XAAC_ESBR_CHAIN_FILE=tmp, XAAC_ESBR_CHAIN_SEED=str(0 if p == 0 else 100 * p + run),
                        XAAC_ESBR_CHAIN_RUN=str(run))
             if usac:
                 env["XAAC_ESBR_CHAIN_PVC"] = "1"
+            if grids:      # (runs 1000 and up: core inputs and seeds of their own)
+                env.update(XAAC_ESBR_CHAIN_GRIDS="1", XAAC_ESBR_CHAIN_SEED=str(7000 + 100 * p + run), XAAC_ESBR_CHAIN_RUN=str(1000 + run))
             src = os.path.join(ROOT, "tests", "golden", "streams_usac" if usac else "streams", s + ".aac")
             args = ["-ifile:" + src, "-ofile:/tmp/xaac_esbr_chain.wav"] + (["-mp4:1", "-imeta:" + src[:-4] + ".txt"] if usac else [])
-            subprocess.run([cap] + args, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
-            recs += parse(tmp, run, z, pvc=usac)
+            try:
+                subprocess.run([cap] + args, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True,
+                               timeout=RUN_TIME_LIMIT if grids else None)
+            except (subprocess.TimeoutExpired, subprocess.CalledProcessError) as e:
+                sys.exit("%s, pass %d: the reference decoder did not get through (%s) -- nothing written" % (s, p, e))
+            recs += parse(tmp, 1000 + run if grids else run, z, pvc=usac)
             os.remove(tmp)
             run += 1
     chains = sorted({(r["run"], r["chain"]) for r in recs})
@@ -131,7 +145,15 @@ def main(usac=False, ratios=False):
             d["hbs0"][i] = u8(r["hbs0"], 0)
             if r["eps"]:
                 d["eps0"][i] = u8(r["eps0"], 0)
-    dst = os.path.join(ROOT, "tests", "golden", "esbr_ratio_chains.npz" if ratios else "esbr_usac_chains.npz" if usac else "esbr_chains.npz")
+    dst = os.path.join(ROOT, "tests", "golden", "esbr_grid_chains.npz" if grids else "esbr_ratio_chains.npz" if ratios else
+                       "esbr_usac_chains.npz" if usac else "esbr_chains.npz")
+    if grids:
+        import sbr_capture as c
+        from sbr_grid_cases import grid_coverage_gaps
+        fr = [c.Frame.from_buffer_copy(r["fr"]) for r in recs if r["apply"]]
+        gaps = grid_coverage_gaps(fr, rets=d["ret"], early_end=False)
+        if gaps:
+            sys.exit("the grid chains miss their coverage: %s -- nothing written" % "; ".join(gaps))
     np.savez_compressed(dst, **d)
     from esbr_structs import EsbrSide
     harm = sum(1 for r in recs if r["apply"] and np.frombuffer(r["sd"], np.int16)[EsbrSide.harmonic_sbr.offset // 2] != 0)
@@ -141,4 +163,5 @@ def main(usac=False, ratios=False):
 
 
 if __name__ == "__main__":
-    main(usac=len(sys.argv) > 1 and sys.argv[1] == "usac", ratios=len(sys.argv) > 1 and sys.argv[1] == "ratios")
+    main(usac=len(sys.argv) > 1 and sys.argv[1] == "usac", ratios=len(sys.argv) > 1 and sys.argv[1] == "ratios",
+         grids=len(sys.argv) > 1 and sys.argv[1] == "grids")
