@@ -537,7 +537,8 @@ typedef struct xaac_ctx xaac_ctx;
  * of xaac_imdct_process_batch.  In: the spectra as they stand at the entry of ixheaacd_channel_pair_process (what the host
  * parser's stage 1 delivers), the side info of xaac_tools.h (xaac_parse_core_tools_side) and the stream's noise generator
  * state.  Out: the spectra ixheaacd_imdct_process receives, in place, and the state moved on.  1024-line frames, at most
- * two channels, no LTP / prediction.  The CPU twin with the same arithmetic is xaac_core_tools_apply_host (xaac_parse.h). */
+ * two channels, no LTP / prediction.  The CPU twin with the same arithmetic is xaac_core_tools_apply_host (xaac_parse.h).
+ * Dynamic range control, which the reference applies between these tools and the IMDCT, is xaac_drc_apply_batch (xaac_drc.h). */
 typedef struct xaac_aac_tools_batch {
   int32_t n;                        /* channel elements, >= 0 */
   int32_t spec_stride;              /* int32 words from one element's spectra to the next one's: a multiple of 4, >= 1024; an

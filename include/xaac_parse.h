@@ -9,6 +9,7 @@
  *   ixheaacd_check_for_sbr_payload      decoder/ixheaacd_aacpluscheck.c:59
  *   ixheaacd_sbr_read_sce / _cpe        decoder/ixheaacd_env_extr.c, ixheaacd_dec_sbrdata decoder/ixheaacd_env_dec.c
  *   ixheaacd_read_ps_data / ixheaacd_decode_ps_data   decoder/ixheaacd_ps_bitdec.c
+ *   ixheaacd_dec_drc_read_element / ixheaacd_drc_map_channels   decoder/ixheaacd_drc_freq_dec.c:771, :484 (xaac_parse_drc_config)
  * No reference code runs in the process.  CPU only: no GPU or torch dependency.
  */
 #ifndef XAAC_PARSE_H
@@ -17,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "xaac_drc.h"
 #include "xaac_esbr.h"
 #include "xaac_sbr.h"
 #include "xaac_tools.h"
@@ -157,6 +159,25 @@ XAAC_API int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side
    state are then left as they were (XAAC_TOOLS_REFUSED); XAAC_PARSE_ERR_SYNTAX for a NULL argument. */
 XAAC_API int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_tools_state *state, int32_t *spec);
 
+/* ---- dynamic range control (include/xaac_drc.h) ---------------------------------------------------------------------------
+ * Switches the stream's DRC decoding on, as any of the reference's -drc_cut_fac / -drc_boost_fac / -drc_target_level does
+ * (api.c:1913-1946): from the next frame on, the dynamic_range_info of FIL elements (extension type 11) is read as
+ * ixheaacd_drc_element_read reads it (drc_freq_dec.c:580-672; up to MAX_BS_ELEMENT elements a frame are kept, :771-798) and mapped
+ * onto the channels of the frame's channel element (ixheaacd_drc_map_channels, :484-528).  The state starts as
+ * ixheaacd_drc_dec_create leaves it, with prog_ref_level = the target level; a frame without an element keeps what the frame
+ * before had.  A frame in which two elements cover one channel does not parse (XAAC_PARSE_ERR_SYNTAX: the reference's
+ * IA_XHEAAC_DEC_EXE_FATAL_INVALID_DRC_DATA).  Mono and stereo streams; in a stream of more than two channels the elements are
+ * skipped as without this call.  A second call starts the state anew.  XAAC_PARSE_ERR_UNSUPPORTED for a value outside
+ * xaac_drc_config's ranges.  Without this call a parser reads nothing of such an element, as before. */
+XAAC_API int32_t xaac_parse_drc_config(xaac_parser *p, const xaac_drc_config *cfg);
+/* The DRC rows of the frame xaac_parse_adts_frame decoded last: side[0 .. n_ch), one per channel of its channel element, with the
+   gain factors of libxaac_amd/csrc/drc.h (drc_freq_dec.c:930-1006).  XAAC_PARSE_ERR_SYNTAX without xaac_parse_drc_config or
+   without a delivered frame, XAAC_PARSE_ERR_UNSUPPORTED for a stream of more than two channels. */
+XAAC_API int32_t xaac_parse_drc_side(xaac_parser *p, xaac_drc_side *side);
+/* The CPU twin of xaac_drc_apply_batch for one row: spec[1024] in place.  Returns 0, or XAAC_DRC_REFUSED for side info outside
+   the struct's capacity (the lines are then left as they were); XAAC_PARSE_ERR_SYNTAX for a NULL argument. */
+XAAC_API int32_t xaac_drc_apply_host(const xaac_drc_side *side, int32_t *spec);
+
 /* The reference's default interpretation of the SBR payload (-esbr:1, "Path A": decoder/ixheaacd_sbrdecoder.c:479-493 the
    payload runs one frame late; the ENHSBR extension element with patching mode / pitch, env_extr.c:595-714; scale factors
    and noise floors handed to the float tools, env_dec.c:52-72, :586-626) instead of the -esbr:0 one.  To be chosen before
@@ -236,6 +257,10 @@ typedef struct xaac_parse_batch {
                                  channels of a pair with copies of the pair's header; flags is [frames][n_streams][n_elems][8] and
                                  reset_pitch [frames][n_streams][n_elems], one row per channel ELEMENT (n_elems = 2, 3, 3, 4); ps_frame
                                  is not written.  The LFE's rows say apply 0 (its SBR data is always missing) */
+  xaac_drc_side *drc_side;    /* optional (appended with dynamic range control), out: [frames][n_streams][n_ch], one row beside every
+                                 row of spec -- xaac_parse_drc_side of every delivered frame, as xaac_drc_apply_batch takes them.  A
+                                 parser without xaac_parse_drc_config, and every stream of a channel_config 3 .. 6 batch, gets
+                                 identity rows */
 } xaac_parse_batch;
 
 /* returns the number of streams whose status is XAAC_PARSE_OK, or a negative XAAC_PARSE_ERR_* for a bad descriptor */

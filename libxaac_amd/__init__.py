@@ -354,6 +354,25 @@ class _AacToolsBatch(ctypes.Structure):
 CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES = 1652, 516   # include/xaac_tools.h
 
 
+class _DrcBatch(ctypes.Structure):
+    # struct xaac_drc_batch (include/xaac_drc.h)
+    _fields_ = [("n", ctypes.c_int32), ("spec_stride", ctypes.c_int32), ("spec", ctypes.c_void_p), ("side", ctypes.c_void_p),
+                ("status", ctypes.c_void_p)]
+
+
+class DrcSide(ctypes.Structure):
+    # struct xaac_drc_side: one channel-frame's bands and Q25 gain factors
+    _fields_ = [("n_bands", ctypes.c_int32), ("end", ctypes.c_int32 * 16), ("fac", ctypes.c_int32 * 16)]
+
+
+class DrcConfig(ctypes.Structure):
+    # struct xaac_drc_config
+    _fields_ = [("cut", ctypes.c_int32), ("boost", ctypes.c_int32), ("target_level", ctypes.c_int32)]
+
+
+DRC_SIDE_WORDS, DRC_ONE = 33, 1 << 25   # int32 words of xaac_drc_side; XAAC_DRC_ONE
+
+
 def load_library():
     """dlopen the product library; loud failure when it has not been built."""
     global _lib
@@ -592,6 +611,23 @@ class XaacContext:
         rc = self._lib.xaac_aac_tools_process_batch(self._h, ctypes.byref(b))
         if rc != 0:
             raise XaacError(rc, "xaac_aac_tools_process_batch")
+
+    def drc_apply_batch(self, spec, side, status=None, spec_stride=1024):
+        """MPEG-4 dynamic range control in the spectral domain (ixheaacd_drc_apply without SBR) on device tensors (asynchronous),
+        in front of imdct_process_batch: spec int32, row i's 1024 lines at word i * spec_stride, in / out; side
+        int32[N, DRC_SIDE_WORDS] (xaac_drc_side rows: xaac_parse_drc_side); optional status int32[N]: 0, or -1 for a row whose
+        side info is outside the struct's capacity (left untouched)."""
+        n, stride = side.shape[0], int(spec_stride)
+        if n and spec.numel() < (n - 1) * stride + 1024:
+            raise ValueError("spec is shorter than %d rows at a stride of %d words" % (n, stride))
+        b = _DrcBatch()
+        b.n, b.spec_stride = n, stride
+        b.spec = _ptr(spec, "int32", device_ok=True)
+        b.side = _ptr(side, "int32", n * DRC_SIDE_WORDS, device_ok=True)
+        b.status = _ptr(status, "int32", n, allow_none=True, device_ok=True)
+        rc = self._lib.xaac_drc_apply_batch(self._h, ctypes.byref(b))
+        if rc != 0:
+            raise XaacError(rc, "xaac_drc_apply_batch")
 
     def imdct960_process_batch(self, spec, ics, overlap, state, out32=None, pcm16=None, qshift_adj=None, ch_fac=1,
                                pcm_mode=PCM_LC, status=None):

@@ -32,6 +32,7 @@
 #include "mc_sbr_kernel.h"
 #include "out_map.h"
 #include "out_map_kernel.h"
+#include "drc_kernel.h"
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -467,7 +468,7 @@ int32_t xaac_warm_up(xaac_ctx *c) {
   hipError_t (*const hooks[])(void) = {xaac_warm_imdct,     xaac_warm_sbr_qmf,   xaac_warm_sbr_core, xaac_warm_sbr_ps,     xaac_warm_limiter,
                                        xaac_warm_esbr_qmf,  xaac_warm_esbr_core, xaac_warm_esbr_ps,  xaac_warm_hbe,        xaac_warm_usac_imdct,
                                        xaac_warm_imdct960,  xaac_warm_imdct_ld,  xaac_warm_pvc,      xaac_warm_sbr_ld_core,
-                                       xaac_warm_aac_tools, xaac_warm_mc_sbr,    xaac_warm_out_map};
+                                       xaac_warm_aac_tools, xaac_warm_mc_sbr,    xaac_warm_out_map,  xaac_warm_drc};
   for (auto h : hooks) XAAC_TRY(h());
   return XAAC_OK;
 }
@@ -1027,6 +1028,18 @@ int32_t xaac_pcm16_scale_adjust_map_batch(xaac_ctx *c, const xaac_scale_adjust_m
   p.samples = b->samples; p.stride = b->stride; p.qshift_adj = b->qshift_adj; p.pcm16 = b->pcm16; p.map_kind = b->map.kind;
   return run(c, (int32_t)xaac_scale_adjust_grid(b->n_streams, b->frame_len), XAAC_SCALE_ADJUST_BLOCK, 0,
              [&] { return xaac_launch_scale_adjust_map(&p, c->stream); });
+}
+
+/* ixheaacd_drc_apply's spectral branch on n channel-frame rows; what a row's side info has to satisfy is the kernel's (drc.h) */
+int32_t xaac_drc_apply_batch(xaac_ctx *c, const xaac_drc_batch *b) {
+  if (!c || !b) return XAAC_FATAL_NULL_ARG;
+  if (b->n < 0 || b->spec_stride < 1024 || (b->spec_stride & 3)) return XAAC_FATAL_BAD_ARG;
+  if (b->n == 0) return XAAC_OK;
+  if (!b->spec || !b->side) return XAAC_FATAL_NULL_ARG;
+  if ((uintptr_t)b->spec & 15u) return XAAC_FATAL_BAD_ARG;
+  XaacDrcParams p = {};
+  p.n = b->n; p.spec_stride = b->spec_stride; p.spec = b->spec; p.side = b->side; p.status = b->status;
+  return run(c, xaac_drc_grid(b->n), XAAC_DRC_BLOCK, XAAC_DRC_LDS_BYTES, [&] { return xaac_launch_drc(&p, c->stream); });
 }
 
 int32_t xaac_last_launch(xaac_ctx *c, int32_t *grid, int32_t *block, int32_t *lds_bytes) {

@@ -77,6 +77,7 @@ class CoreToolsState(ctypes.Structure):
     _fields_ = [("pns_seed", ctypes.c_int32), ("pns_corr_seed", ctypes.c_int32 * 128)]
 
 
+from . import DRC_SIDE_WORDS, DrcConfig  # noqa: E402  (include/xaac_drc.h)
 from . import CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES  # noqa: E402  (tests/test_aac_tools_cpu.py pins them to the header)
 
 
@@ -125,6 +126,11 @@ def load_host_library():
         lib.xaac_out_map_apply_host.restype = ctypes.c_int32
         lib.xaac_out_map_row_bound.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
         lib.xaac_out_map_row_bound.restype = ctypes.c_int32
+        lib.xaac_parse_drc_config.argtypes = [ctypes.c_void_p, ctypes.POINTER(DrcConfig)]
+        lib.xaac_parse_drc_side.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.xaac_drc_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        for fn in ("xaac_parse_drc_config", "xaac_parse_drc_side", "xaac_drc_apply_host"):
+            getattr(lib, fn).restype = ctypes.c_int32
         _host = lib
     return _host
 
@@ -141,6 +147,49 @@ def out_map_apply_host(m, pcm):
     if oc <= 0:
         raise ValueError("the output map does not take %d channels" % n_ch)
     return out.reshape(-1)[:samples * oc].reshape(samples, oc).copy()
+
+
+def drc_config(drc):
+    """decode_streams' drc argument -> the DrcConfig the parsers take (xaac_drc_config), or None for None.  drc: a dict of
+    cut=, boost= (0 .. 1: -drc_cut_fac, -drc_boost_fac) and target_level= (0 .. 127: -drc_target_level), any of them left out
+    keeps the reference's 1, 1 and 108 (api.c:477-481).  The reference keeps (WORD32)(factor * 100) of a float (api.c:629-653).  ValueError for
+    anything else: a value out of range, heavy_comp (-drc_heavy_comp:1: DVB ancillary data, not supported), an unknown key."""
+    if drc is None:
+        return None
+    if not isinstance(drc, dict):
+        raise ValueError("drc is None or a dict of cut=, boost=, target_level=")
+    unknown = set(drc) - {"cut", "boost", "target_level", "heavy_comp"}
+    if unknown:
+        raise ValueError("drc: unknown key %s" % sorted(unknown)[0])
+    if drc.get("heavy_comp"):
+        raise ValueError("drc heavy_comp (-drc_heavy_comp:1, DVB ancillary data) is not supported")
+    cfg = DrcConfig(100, 100, 108)
+    for key in ("cut", "boost"):
+        v = np.float32(drc.get(key, 1.0))
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("drc %s is outside 0 .. 1" % key)
+        setattr(cfg, key, int(v * np.float32(100)))
+    level = drc.get("target_level", 108)
+    if int(level) != level or not 0 <= level <= 127:
+        raise ValueError("drc target_level is outside 0 .. 127")
+    cfg.target_level = int(level)
+    return cfg
+
+
+def _refuse_drc(n_ch, sbr, channel_config):
+    """what dynamic range control does not cover, as decode_streams and the command line decoder refuse it"""
+    if sbr:
+        raise ValueError("drc on a stream with SBR (the QMF-domain branch of dynamic range control) is not supported")
+    if channel_config:
+        raise ValueError("drc on a stream of more than two channels is not supported")
+
+
+def drc_apply_host(side, spec):
+    """xaac_drc_apply_host, the CPU twin of xaac_drc_apply_batch: side int32[DRC_SIDE_WORDS] (one xaac_drc_side), spec int32[1024]
+    in place -> the call's return value (0, or -1 for a row it refuses)"""
+    side = np.ascontiguousarray(side, np.int32)
+    assert side.size == DRC_SIDE_WORDS and spec.dtype == np.int32 and spec.size == 1024 and spec.flags["C_CONTIGUOUS"]
+    return int(load_host_library().xaac_drc_apply_host(side.ctypes.data, spec.ctypes.data))
 
 
 def out_map_row_bound(matrix):
@@ -160,7 +209,7 @@ class StreamParser:
     while it initialises -- ixheaacd_dec_init, api.c:2097 -- and again as the first output frame; every state is set up
     afresh in between, api.c:2141-2170, so nothing of the first pass shows and one pass is all that is needed here.)"""
 
-    def __init__(self, data, with_sbr=None, stage=2, esbr=False):
+    def __init__(self, data, with_sbr=None, stage=2, esbr=False, drc=None):
         self.lib = load_host_library()
         self.esbr = bool(esbr)     # the reference's default -esbr:1 reading of the SBR payload (xaac_parser_set_esbr)
         self.data = bytes(data)
@@ -170,6 +219,9 @@ class StreamParser:
             raise RuntimeError("xaac_parser_create failed")
         if self.esbr and self.lib.xaac_parser_set_esbr(self.h, 1):
             raise RuntimeError("xaac_parser_set_esbr failed")
+        self.drc = drc_config(drc)   # dynamic range control on (xaac_parse_drc_config): drc_side() answers for every frame
+        if self.drc is not None and self.lib.xaac_parse_drc_config(self.h, ctypes.byref(self.drc)):
+            raise RuntimeError("xaac_parse_drc_config failed")
         self.pos, self.frame_no, self.stage = 0, 0, stage
         self.core, self.side, self.used = CoreFrame(), SbrSide(), ctypes.c_size_t()
         self.esbr_side = [(ctypes.c_uint8 * ESBR_SIDE_BYTES)(), (ctypes.c_uint8 * ESBR_SIDE_BYTES)()]
@@ -218,6 +270,14 @@ class StreamParser:
                         raise ParseError(-2, self.frame_no)
         self.frame_no += 1
         return True
+
+    def drc_side(self):
+        """the xaac_drc_side rows of the frame next() delivered last: int32[n_ch, DRC_SIDE_WORDS]"""
+        side = np.zeros((self.core.n_ch, DRC_SIDE_WORDS), np.int32)
+        rc = self.lib.xaac_parse_drc_side(self.h, side.ctypes.data)
+        if rc:
+            raise ParseError(rc, self.frame_no - 1)
+        return side
 
 
 def parse_stream(data, stage=2, esbr=False):
@@ -311,7 +371,7 @@ class _ParseBatch(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("parser", "data", "bytes", "spec", "ics", "header", "frame", "ps_frame", "flags",
                                                "tools", "consumed", "status", "esbr_side", "reset_pitch", "pos")] + \
                [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p), ("tools_side", ctypes.c_void_p),
-                ("channel_config", ctypes.c_int32), ("mc_sbr", ctypes.c_int32)]
+                ("channel_config", ctypes.c_int32), ("mc_sbr", ctypes.c_int32), ("drc_side", ctypes.c_void_p)]
 
 
 F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(8)
@@ -409,7 +469,7 @@ class BatchParser:
     """N ADTS streams of one kind through the host front end in lock step: xaac_parse_batch_run parses one frame of every
     stream on a team of CPU threads, straight into the (pinned) staging arrays handed to step()."""
 
-    def __init__(self, streams, threads=0, stage=2, esbr=False, mc_sbr=False):
+    def __init__(self, streams, threads=0, stage=2, esbr=False, mc_sbr=False, drc=None):
         self.lib = load_host_library()
         self.lib.xaac_parse_batch_run.argtypes = [ctypes.c_void_p]       # (the original layout's symbols: no pos / frames / lines)
         self.lib.xaac_parse_batch_start.argtypes = [ctypes.c_void_p]
@@ -431,6 +491,8 @@ class BatchParser:
                 raise RuntimeError("xaac_parser_create failed")
             if self.esbr:
                 self.lib.xaac_parser_set_esbr(h, 1)
+            if drc is not None and self.lib.xaac_parse_drc_config(h, ctypes.byref(drc)):   # (a DrcConfig: drc_config())
+                raise RuntimeError("xaac_parse_drc_config failed")
             self.parsers[i] = h
         self.threads, self.stage = int(threads), int(stage)
         self.consumed, self.status = np.zeros(n, np.uint64), np.zeros(n, np.int32)
@@ -467,7 +529,7 @@ class BatchParser:
                 self.parsers[i] = None
 
     def _descriptor(self, spec, ics, hdr, frm, psf, flags, with_sbr, eside=None, status=None, reset_pitch=None, frames=1, lines=None,
-                    tools_side=None):
+                    tools_side=None, drc_side=None):
         # data / bytes are the whole streams and stay as they are; the library moves self.pos (xaac_parse_batch::pos), so a
         # call costs this thread the filling of the descriptor and nothing per stream
         b = _ParseBatch()
@@ -485,6 +547,7 @@ class BatchParser:
         b.tools_side = ptr(tools_side)   # uint8[frames, n, CORE_TOOLS_SIDE_BYTES]: the tools' side info of a stage-1 parse
         b.channel_config = self.channel_config   # (with it: tools_side is uint8[frames, n_elems, n, ...], element-major)
         b.mc_sbr = int(self.mc_sbr)
+        b.drc_side = ptr(drc_side)       # int32[frames, n * n_ch, DRC_SIDE_WORDS]: a row beside every row of spec
         return b
 
     def _advance(self, ok, status=None):
@@ -501,14 +564,14 @@ class BatchParser:
                 raise ParseError(int(status[i]), int(self.frames[i]))
         return good
 
-    def step(self, spec, ics, hdr=None, frm=None, psf=None, flags=None, eside=None, tools_side=None):
+    def step(self, spec, ics, hdr=None, frm=None, psf=None, flags=None, eside=None, tools_side=None, drc_side=None):
         """parses the next frame of every stream into the staging arrays; -> bool[n]: which streams delivered a frame
         (the others are at their end: their rows are left as they were)"""
-        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, tools_side=tools_side)
+        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, tools_side=tools_side, drc_side=drc_side)
         return self._advance(self.lib.xaac_parse_batch_run_sized(ctypes.byref(b), ctypes.sizeof(b)))
 
     def start_step(self, spec, ics, hdr=None, frm=None, psf=None, flags=None, eside=None, status=None, reset_pitch=None, frames=1,
-                   lines=None, tools_side=None):
+                   lines=None, tools_side=None, drc_side=None):
         """step() in two halves (xaac_parse_batch_start / _wait): the library's worker team parses while the caller does
         something else; the staging arrays are the team's until wait_step() returns.  status / reset_pitch: the caller's own
         int32[n] arrays for this step's results (a caller that starts the next step before it has looked at this one's).
@@ -516,7 +579,7 @@ class BatchParser:
         a leading dimension T (status / reset_pitch int32[T, n]); finish_step is then called per step t with status[t].
         lines: int32[T, n] out, xaac_parse_batch::lines."""
         self._status_in_flight = status
-        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, status, reset_pitch, frames, lines, tools_side)
+        b = self._descriptor(spec, ics, hdr, frm, psf, flags, self.sbr, eside, status, reset_pitch, frames, lines, tools_side, drc_side)
         rc = self.lib.xaac_parse_batch_start_sized(ctypes.byref(b), ctypes.sizeof(b))
         if rc:
             raise RuntimeError("xaac_parse_batch_start: %d" % rc)
@@ -558,7 +621,7 @@ def _hip_runtime():
 
 
 # what the pipeline and the chains see of one step of a staging set: which streams delivered a frame, and that step's rows
-_Step = collections.namedtuple("_Step", "sent got spec ics hdr frm psf eside flags flags_pin tside reset_pitch lines")
+_Step = collections.namedtuple("_Step", "sent got spec ics hdr frm psf eside flags flags_pin tside reset_pitch lines dside")
 
 
 class _Alloc:
@@ -582,12 +645,13 @@ class Staging:
     side info the chain wants beside the spectra and window info (of "hdr", "frm", "psf", "flags", "eside"); tools: the spectral
     tools' side rows too"""
 
-    def __init__(self, bp, pinned, T, arrays=(), tools=False):
+    def __init__(self, bp, pinned, T, arrays=(), tools=False, drc=False):
         n, nc = bp.n, bp.n * bp.n_ch
         want = lambda name, *shape: pinned(T, *shape) if name in arrays else None
         self.bp, self.T = bp, T
         self.spec, self.ics = pinned(T, nc, 1024, dtype=torch.int32), pinned(T, nc, 2)
         self.tside = pinned(T, n * bp.n_elems, CORE_TOOLS_SIDE_BYTES) if tools else None   # element-major within a step
+        self.dside = pinned(T, nc, DRC_SIDE_WORDS, dtype=torch.int32) if drc else None      # a row per channel, beside the spectra
         self.hdr, self.frm = want("hdr", nc, SBR_HEADER_BYTES), want("frm", nc, SBR_FRAME_BYTES)
         self.psf, self.eside = want("psf", n, PS_FRAME_BYTES), want("eside", nc, ESBR_SIDE_BYTES)
         self.flags = self.flags_pin = None
@@ -606,7 +670,8 @@ class Staging:
         if self.sent_once:
             self.sent[self.T - 1].synchronize()   # (the set's last copies up: long over when its turn comes again)
         self.bp.start_step(self.spec, self.ics, self.hdr, self.frm, self.psf, self.flags, self.eside, status=self.status,
-                           reset_pitch=self.reset_pitch, frames=self.T, lines=self.lines, tools_side=self.tside)
+                           reset_pitch=self.reset_pitch, frames=self.T, lines=self.lines, tools_side=self.tside,
+                           drc_side=self.dside)
         return self
 
     def end(self):      # back from the team; the results are looked at in finish(), once the next set is on its way
@@ -615,7 +680,7 @@ class Staging:
 
     def finish(self):
         rows = (self.spec, self.ics, self.hdr, self.frm, self.psf, self.eside, self.flags, self.flags_pin, self.tside,
-                self.reset_pitch, self.lines)
+                self.reset_pitch, self.lines, self.dside)
         self.steps = [_Step(self.sent[t], self.bp.finish_step(None, self.status[t]), *(a if a is None else a[t] for a in rows))
                       for t in range(self.T)]
         return self
@@ -646,6 +711,21 @@ class _ToolsStage:
 
     def refused(self, slot, got):   # a delivered frame's element the kernel did not take
         return int(self.status_h2[slot].numpy().reshape(len(self.first_rows), self.n)[:, got].min(initial=0)) < 0
+
+
+class _DrcStage:
+    """drc: dynamic range control on the spectra in front of the AAC-LC chain's IMDCT (behind the spectral tools where they run on
+    the GPU) -- the side rows the parser made beside the spectra, in two device sets like them"""
+
+    def __init__(self, ctx, nc, dz):
+        self.ctx = ctx
+        self.side_d2 = [dz(nc, DRC_SIDE_WORDS, dtype=torch.int32) for _ in range(2)]
+
+    def send_up(self, step, slot):
+        self.side_d2[slot].copy_(step.dside, non_blocking=True)
+
+    def run(self, spec_d, slot):   # in place (ended streams' rows run idle on the rows their last frame left)
+        self.ctx.drc_apply_batch(spec_d, self.side_d2[slot])
 
 
 class _Chain:
@@ -1008,14 +1088,14 @@ class _Pipeline:
     the spectral tools in front of it when gpu_tools says so."""
 
     def __init__(self, streams, ctx, device, threads, keep_pcm, overlap, esbr, trace, frames_per_parse, gpu_tools, mc_sbr=False,
-                 out_map=None, limiter=True):
+                 out_map=None, limiter=True, drc=None):
         self.dev = dev = torch.device(device)
         alloc, lib = _Alloc(dev), load_host_library()
         self.own = ctx is None
         if self.own:   # the context launches on torch's current stream, so that its kernels and torch's copies stay in order
             ctx = XaacContext(dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
         self.ctx = ctx
-        self.bp = bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2, mc_sbr=mc_sbr)
+        self.bp = bp = BatchParser(streams, threads=threads, esbr=esbr, stage=1 if gpu_tools else 2, mc_sbr=mc_sbr, drc=drc)
         if bp.mc_sbr:   # what per-element SBR does not cover
             try:
                 if not esbr:
@@ -1027,6 +1107,8 @@ class _Pipeline:
                 raise
         try:
             out_map = _pick_out_map(out_map, bp.n_ch, bool(bp.sbr), bp.channel_config)
+            if drc is not None:
+                _refuse_drc(bp.n_ch, bool(bp.sbr), bp.channel_config)
         except ValueError:
             bp.close()
             raise
@@ -1044,11 +1126,12 @@ class _Pipeline:
             starts = np.concatenate([[0], np.cumsum([2 if e == 1 else 1 for e in elements])[:-1]])
             first_rows = tuple(route[int(c)] if self.route else int(c) for c in starts)
         self.tools = _ToolsStage(ctx, bp.n, alloc.dz, alloc.pinned, bp.n_ch, first_rows) if gpu_tools else None
+        self.drc = _DrcStage(ctx, bp.n * bp.n_ch, alloc.dz) if drc is not None else None
         # two sets of device input arrays: step k + 1 is copied up (its own stream) while step k's kernels read theirs
         self.spec_d2 = [alloc.dz(self.nc, 1024, dtype=torch.int32) for _ in range(2)]
         self.ics_d2 = [alloc.dz(self.nc, 2) for _ in range(2)]
         self.lines_held = [0, 0]   # per device input set: the leading spectral lines that may be non-zero there
-        self.sets = [Staging(bp, alloc.pinned, T, chain.host_arrays, bool(gpu_tools)) for _ in range(3 if overlap else 1)]
+        self.sets = [Staging(bp, alloc.pinned, T, chain.host_arrays, bool(gpu_tools), drc is not None) for _ in range(3 if overlap else 1)]
         self.main_stream, self.down, self.up = torch.cuda.current_stream(dev), torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         self.done = [torch.cuda.Event(), torch.cuda.Event()]
         self.computed = [torch.cuda.Event(), torch.cuda.Event()]
@@ -1128,6 +1211,8 @@ class _Pipeline:
                 self.ics_d2[slot].copy_(cur.ics, non_blocking=True)
             if self.tools is not None:
                 self.tools.send_up(cur, slot)
+            if self.drc is not None:
+                self.drc.send_up(cur, slot)
             self.chain.send_up(cur, slot, got)
             cur.sent.record(up)
 
@@ -1169,6 +1254,8 @@ class _Pipeline:
             spec_d = self.spec_d2[slot]
             if tools is not None:
                 tools.run(spec_d, slot)
+            if self.drc is not None:
+                self.drc.run(spec_d, slot)
             shape, cut, drop = chain.run(cur, slot, got, first, spec_d, self.ics_d2[slot])
             self.hand_down(slot, got, shape, cut, drop)
             self.t_gpu += time.perf_counter() - t0
@@ -1199,7 +1286,7 @@ class _Pipeline:
 
 
 def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True, timing=None, overlap=True, esbr=False,
-                   _trace=None, frames_per_parse=4, gpu_tools=False, mc_sbr=False, out_map=None, limiter=True):
+                   _trace=None, frames_per_parse=4, gpu_tools=False, mc_sbr=False, out_map=None, limiter=True, drc=None):
     """Decodes N ADTS streams of the same kind (all AAC-LC mono or stereo, all AAC-LC of one channel_config 3 .. 6 -- 3.0 to
     5.1, output channels in the reference's order, MC_LAYOUT --, all HE-AAC stereo, or all HE-AAC / HE-AACv2 mono) in lock step: per step one frame of every stream is parsed on CPU threads into pinned staging arrays, copied to the GPU
     (spectra + window info, SBR / PS side info: nothing else crosses the bus on the way in), run through the GPU entry
@@ -1231,12 +1318,20 @@ def decode_streams(streams, ctx=None, device="cuda:0", threads=0, keep_pcm=True,
     on everything else).  What the command line decoder refuses is a ValueError: "downmix" on one or two channels, "mono" /
     "mono_dup" with SBR or more than two channels, "mono_dup" on a mono stream.  Every sample is mapped, the limiter's flushed delay
     line included.
-    limiter: False is -peak_limiter_off:1 (AAC-LC: ixheaacd_scale_adjust + round16 in the limiter's place; nothing changes with SBR)."""
+    limiter: False is -peak_limiter_off:1 (AAC-LC: ixheaacd_scale_adjust + round16 in the limiter's place; nothing changes with SBR).
+    drc: None, or a dict of cut=, boost= (0 .. 1) and target_level= (0 .. 127) -- the reference's -drc_cut_fac, -drc_boost_fac and
+    -drc_target_level (drc_config()): MPEG-4 dynamic range control and level normalisation from the dynamic_range_info of the
+    streams' fill elements, on the GPU in front of the IMDCT (xaac_drc_apply_batch; the limiter runs behind as before).  AAC-LC
+    mono and stereo streams; with SBR or more than two channels, heavy_comp or a value out of range it is a ValueError."""
     global torch
+    drc = drc_config(drc)
+    if drc is not None and len(streams):   # (refused before anything touches a GPU; the pipeline checks the batch it builds again)
+        _, n_ch, sbr, config = stream_kind(streams[0])
+        _refuse_drc(n_ch, sbr, config)
     import torch
     with _TorchCpuThreads():
         return _Pipeline(streams, ctx, device, threads, keep_pcm, overlap, esbr, _trace, frames_per_parse, bool(gpu_tools),
-                         bool(mc_sbr), out_map, limiter).run(timing)
+                         bool(mc_sbr), out_map, limiter, drc).run(timing)
 
 
 def stream_kind(data):
@@ -1261,7 +1356,7 @@ def _default_parser_threads():
 MixedGroup = collections.namedtuple("MixedGroup", "kind index threads")
 
 
-def plan_mixed(streams, out_map=None, threads=0):
+def plan_mixed(streams, out_map=None, threads=0, drc=None):
     """What decode_mixed does before anything touches a GPU: probes every stream and sorts the list into groups of one kind, in the
     order in which the list first names the kinds, every group's streams in list order.  -> [MixedGroup].
     ValueError: a stream of channel_config 3 .. 6 beside another kind ("channel configurations", as decode_streams says it), or an
@@ -1270,6 +1365,7 @@ def plan_mixed(streams, out_map=None, threads=0):
     streams, one at least; a single group keeps the value as it is."""
     if out_map is not None and out_map not in ("downmix", "mono", "mono_dup", "dup"):
         _pick_out_map(out_map, 0, False, 0)    # (a name that is none of the maps: its own message, no stream's)
+    drc = drc_config(drc)                      # (a value out of range: its own message too)
     by_kind = {}
     for i, d in enumerate(streams):
         by_kind.setdefault(stream_kind(d), []).append(i)
@@ -1278,6 +1374,8 @@ def plan_mixed(streams, out_map=None, threads=0):
     for (_, n_ch, sbr, config), index in by_kind.items():    # (in the order of the groups' first streams)
         try:
             _pick_out_map(out_map, n_ch, sbr, config)
+            if drc is not None:
+                _refuse_drc(n_ch, sbr, config)
         except ValueError as e:
             raise ValueError("stream %d: %s" % (index[0], e)) from None
     if len(by_kind) == 1:
@@ -1300,7 +1398,7 @@ def restore_list_order(groups, results, n):
 
 
 def decode_mixed(streams, device="cuda:0", serial=False, esbr=False, gpu_tools=False, out_map=None, limiter=True, threads=0,
-                 frames_per_parse=4, keep_pcm=True):
+                 frames_per_parse=4, keep_pcm=True, drc=None):
     """Decodes ADTS streams of several kinds in one call: mono and stereo, any core sampling rate, AAC-LC beside HE-AAC and
     HE-AACv2.  -> (list of int16 [samples, channels] arrays, list of output sampling rates), both in the order of `streams`.
 
@@ -1315,13 +1413,15 @@ def decode_mixed(streams, device="cuda:0", serial=False, esbr=False, gpu_tools=F
     esbr, gpu_tools, out_map, limiter, frames_per_parse, keep_pcm: as decode_streams takes them, for every group what they mean
     for a list of that kind alone (AAC-LC groups decode the same with either esbr; "dup" doubles a mono AAC-LC group's channel
     and is a no-op on the others).  An out_map that one group refuses is a ValueError that names the first such stream of the
-    list ("stream <i>: ..."), raised before any GPU work, and nothing is decoded.  A stream of channel_config 3 .. 6 is only
+    list ("stream <i>: ..."), raised before any GPU work, and nothing is decoded.  drc (decode_streams' dict) acts on the AAC-LC
+    groups; a list with an SBR stream or one of more than two channels is refused the same way.  A stream of channel_config 3 .. 6 is only
     taken beside streams of its own kind (one group: decode_streams' path); beside another kind it is the ValueError "streams of
     different channel configurations in one batch", also before any GPU work -- its flags (mc_sbr, "downmix") mean nothing
     for the other kinds.  An SBR mono stream comes out in two channels, as decode_streams and the reference write it.
     An error inside one group's pipeline is raised here once every group has ended (the first group's, in list order)."""
     global torch
-    groups = plan_mixed(streams, out_map, threads)    # (the refusals: before torch is so much as imported)
+    groups = plan_mixed(streams, out_map, threads, drc)    # (the refusals: before torch is so much as imported)
+    drc = drc_config(drc)
     import threading
     import torch
     dev = torch.device(device)
@@ -1333,7 +1433,7 @@ def decode_mixed(streams, device="cuda:0", serial=False, esbr=False, gpu_tools=F
             own = torch.cuda.Stream(dev)
             with torch.cuda.device(dev), torch.cuda.stream(own):   # (the pipeline's context launches on the thread's current stream)
                 results[k] = _Pipeline([streams[i] for i in g.index], None, dev, g.threads, keep_pcm, True, esbr, None,
-                                       frames_per_parse, bool(gpu_tools), False, out_map, limiter).run(None)
+                                       frames_per_parse, bool(gpu_tools), False, out_map, limiter, drc).run(None)
                 own.synchronize()
         except BaseException as e:   # (handed to the caller's thread)
             errors[k] = e

@@ -569,7 +569,82 @@ int skip_pce(XhBits *br) { /* program_config_element: read over it (ISO/IEC 1449
   return br->overrun ? XH_ERR_BITS : 0;
 }
 
+/* ixheaacd_drc_excluded_channels + ixheaacd_drc_element_read (drc_freq_dec.c:580-672), in the reference's bit order; returns the
+   bytes the element took, extension type included */
+int read_drc_element(XhBits *br, XhDrcElement *e) {
+  int nbyte = 1;
+  e->num_bands = 1;
+  if (br->get1()) { /* pce_tag_present: pce_instance_tag, drc_tag_reserved_bits */
+    br->get(8);
+    nbyte++;
+  }
+  memset(e->channel_on, 1, sizeof(e->channel_on));
+  if (br->get1()) { /* excluded_chns_present: masks in groups of seven, each followed by "one more group" */
+    int first = 0;
+    do {
+      for (int ch = first; ch < first + 7; ch++) {
+        const int excluded = br->get1();
+        if (ch < XH_DRC_MAX_CHANNELS) e->channel_on[ch] = (uint8_t)!excluded;
+      }
+      nbyte++;
+      first += 7;
+    } while (br->get1() && !br->overrun);
+  }
+  if (br->get1()) { /* drc_bands_present */
+    e->num_bands = (uint8_t)(1 + br->get(4)); /* drc_band_incr */
+    br->get(4);                               /* drc_interpolation_scheme: read by the QMF-domain branch only */
+    nbyte++;
+    for (int k = 0; k < e->num_bands; k++, nbyte++) e->band_top[k] = (uint8_t)br->get(8);
+  } else {
+    e->band_top[0] = 1024 / 4 - 1;
+  }
+  e->prog_ref_level_present = (uint8_t)br->get1();
+  if (e->prog_ref_level_present) {
+    e->prog_ref_level = (uint8_t)br->get(7);
+    br->get1(); /* prog_ref_level_reserved_bits */
+    nbyte++;
+  }
+  for (int k = 0; k < e->num_bands; k++, nbyte++) {
+    const int sign = br->get1();
+    const int v = (int)br->get(7);
+    e->dyn_rng[k] = (int8_t)(sign ? -v : v);
+  }
+  return nbyte;
+}
+
+/* ixheaacd_drc_map_channels + ixheaacd_copy_drc_data (drc_freq_dec.c:460-528) for a frame of 1024 lines; a channel that two of
+   the frame's elements cover is IA_XHEAAC_DEC_EXE_FATAL_INVALID_DRC_DATA there: the frame does not parse */
+int drc_map_channels(XhDrc *d, int num_channels) {
+  if (d->num_elements > 1)
+    for (int ch = 0; ch < num_channels; ch++) {
+      int on = 0;
+      for (int e = 0; e < d->num_elements; e++) on += d->el[e].channel_on[ch] != 0;
+      if (on > 1) return XH_ERR_SYNTAX;
+    }
+  for (int e = 0; e < d->num_elements; e++) {
+    const XhDrcElement &bs = d->el[e];
+    if (bs.prog_ref_level_present) d->prog_ref_level = bs.prog_ref_level;
+    for (int ch = 0; ch < num_channels; ch++) {
+      if (!bs.channel_on[ch]) continue;
+      XhDrcChannel &c = d->ch[ch];
+      c.n_bands = bs.num_bands;
+      for (int k = 0; k < bs.num_bands; k++) {
+        c.n_mdct_bands[k] = (int16_t)(bs.num_bands == 1 ? 1024 : (bs.band_top[k] + 1) * 4);
+        c.drc_fac[k] = bs.dyn_rng[k];
+      }
+    }
+  }
+  return 0;
+}
+
 }  // namespace
+
+void xh_drc_init(XhDrc *d, int cut, int boost, int target_level) {
+  memset(d, 0, sizeof(*d));
+  d->cut = cut, d->boost = boost;
+  d->target_ref_level = d->prog_ref_level = target_level;
+  for (int ch = 0; ch < 2; ch++) d->ch[ch].n_bands = 1, d->ch[ch].n_mdct_bands[0] = 1024;
+}
 
 void xh_export_tools_side(const XhCoreState *st, XhElement *el, xaac_core_tools_side *side) {
   derive_pns_correlation(el);
@@ -655,6 +730,7 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, 
     els[k]->sbr_ext_type = 0;
   }
   *n_els = 0;
+  if (st->drc) st->drc->num_elements = 0;
   for (;;) {
     if (br->left() < 3) return XH_ERR_BITS;
     const int id = (int)br->get(3);
@@ -740,6 +816,11 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, 
               br->skip(32);
             }
             for (; i < count; i++) el->sbr[i] = (uint8_t)br->get(8);
+          } else if (type == 11 && st->drc) { /* EXT_DYNAMIC_RANGE, aacpluscheck.c:185-187: the element's bytes come off the
+                                                 count, and nothing is done with what is left of it */
+            XhDrc *d = st->drc;
+            XhDrcElement dropped;
+            read_drc_element(br, d->num_elements < XH_DRC_MAX_ELEMENTS ? &d->el[d->num_elements++] : &dropped);
           } else {
             br->get(4);
             br->skip(8 * (size_t)(count - 1));
@@ -755,5 +836,7 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, 
   }
   br->skip((8 - ((br->pos - block_start) & 7)) & 7);
   if (br->overrun) return XH_ERR_BITS;
-  return have_channels ? 0 : XH_ERR_SYNTAX;
+  if (!have_channels) return XH_ERR_SYNTAX;
+  /* aacdecoder.c:927-929: the frame's elements onto the channels of its channel element, in front of the IMDCT */
+  return st->drc ? drc_map_channels(st->drc, els[0]->n_ch) : 0;
 }

@@ -5,7 +5,8 @@
  * CPU code: the bitstream syntax is serial; everything behind this seam runs on the GPU.
  * Scope: AAC-LC objects (AOT 2; 5 / 29 through the SBR payload), 1024-line frames, one SCE or CPE per raw_data_block, or the
  * SCE / CPE / LFE sequence of channel_config 3 .. 6 (with the reference's q_factor / TNS variants for more than two
- * channels: XhCoreState::wide); no CCE, no LTP, no gain control, no DRC payload handling (read and ignored), no error concealment.
+ * channels: XhCoreState::wide); no CCE, no LTP, no gain control, no error concealment.  dynamic_range_info is read and mapped to
+ * the channels where the caller keeps a DRC state (XhCoreState::drc: mono and stereo streams), and skipped otherwise.
  */
 #ifndef XAAC_HOST_AAC_CORE_H
 #define XAAC_HOST_AAC_CORE_H
@@ -80,7 +81,37 @@ struct XhCoreState {
   int num_swb_long, num_swb_short;
   int wide;                /* the stream has more than two channels (set by the caller behind xh_core_init): scale factors with
                               q_factor 34 and the 32-bit TNS variant (block.c:1263, channel.c:642, pns_js_thumb.c:328) */
+  struct XhDrc *drc;       /* the stream's dynamic range control state, or null: dynamic_range_info is then skipped unread (set by
+                              the caller behind xh_core_init, like `wide`) */
 };
+
+/* ---- dynamic range control: what ia_drc_dec_struct keeps for the spectral-domain branch (decoder/ixheaacd_drc_data_struct.h) ---- */
+#define XH_DRC_MAX_ELEMENTS 10 /* MAX_BS_ELEMENT: dynamic_range_info elements kept per frame; further ones are read and dropped */
+#define XH_DRC_MAX_CHANNELS 8  /* MAX_AUDIO_CHANNELS: the channels an element's exclusion mask speaks of */
+#define XH_DRC_MAX_BANDS 16    /* MAX_DRC_BANDS */
+
+struct XhDrcElement { /* ixheaac_drc_bs_data_struct: one dynamic_range_info as read (drc_freq_dec.c:609-672) */
+  uint8_t channel_on[XH_DRC_MAX_CHANNELS];
+  uint8_t prog_ref_level_present, prog_ref_level, num_bands;
+  uint8_t band_top[XH_DRC_MAX_BANDS];
+  int8_t dyn_rng[XH_DRC_MAX_BANDS]; /* sign and 7 bits */
+};
+
+struct XhDrcChannel { /* ixheaac_drc_data_struct, by the channel's index inside the element; outlives the frame */
+  int n_bands;
+  int16_t n_mdct_bands[XH_DRC_MAX_BANDS], drc_fac[XH_DRC_MAX_BANDS];
+};
+
+struct XhDrc {
+  int cut, boost, target_ref_level; /* 0 .. 100, 0 .. 100, 0 .. 127 (api.c:1918-1923) */
+  int prog_ref_level;               /* starts as the target level (api.c:1924) */
+  int num_elements;                 /* of the frame in work (api.c:3055 clears it per frame) */
+  XhDrcElement el[XH_DRC_MAX_ELEMENTS];
+  XhDrcChannel ch[2];
+};
+
+/* ixheaacd_drc_dec_create (drc_freq_dec.c:530-578) + api.c:1918-1925 */
+void xh_drc_init(XhDrc *d, int cut, int boost, int target_level);
 
 struct XhElement {
   int id;                   /* XH_ID_SCE / XH_ID_CPE */

@@ -25,6 +25,7 @@
 #include <unistd.h>
 
 #include "../csrc/aac_tools.h"
+#include "../csrc/drc.h"
 #include "aac_core.h"
 #include "sbr_side.h"
 
@@ -81,6 +82,7 @@ struct xaac_parser {
   int channel_config; /* of the ADTS header read last */
   int n_els;    /* ... and how many elements its block held */
   int8_t sequence_n, sequence[XP_MAX_ELEMENTS]; /* the multichannel calls' rule: the element ids of the first frame they saw (none: 0) */
+  XhDrc *drc;   /* dynamic range control: allocated by xaac_parse_drc_config, so a parser without it stays as small as it was */
 };
 static_assert(sizeof(xaac_parser) <= 14592 + 64, "a mono / stereo stream's parser has grown: it was 14592 bytes with one slot's members inline");
 
@@ -250,6 +252,7 @@ int32_t xaac_parser_create(xaac_parser **p) {
 
 void xaac_parser_destroy(xaac_parser *p) {
   if (p) delete[] p->slot[1];
+  if (p) delete p->drc;
   delete p;
 }
 
@@ -309,6 +312,7 @@ static int32_t parse_block(xaac_parser *p, XhBits *br, int32_t stage, int cap) {
     els[k] = &p->slot[k]->el, tools[k] = &p->slot[k]->tools;
     els[k]->ch[0].spec_mem = lines[k][0], els[k]->ch[1].spec_mem = lines[k][1];
   }
+  p->core.drc = p->core.wide ? nullptr : p->drc; /* (a stream of more than two channels: the elements are skipped as before) */
   return xh_parse_raw_data_block(&p->core, br, els, tools, cap, &p->n_els, stage);
 }
 static int32_t parse_frame(xaac_parser *p, const uint8_t *data, size_t n, int32_t stage, size_t *consumed, int cap = 1) {
@@ -535,6 +539,47 @@ int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_t
   return XAAC_PARSE_OK;
 }
 
+int32_t xaac_parse_drc_config(xaac_parser *p, const xaac_drc_config *cfg) {
+  if (!p || !cfg) return XAAC_PARSE_ERR_SYNTAX;
+  if (cfg->cut < 0 || cfg->cut > 100 || cfg->boost < 0 || cfg->boost > 100 || cfg->target_level < 0 || cfg->target_level > 127)
+    return XAAC_PARSE_ERR_UNSUPPORTED;
+  if (!p->drc && !(p->drc = new (std::nothrow) XhDrc)) return XAAC_PARSE_ERR_UNSUPPORTED;
+  xh_drc_init(p->drc, cfg->cut, cfg->boost, cfg->target_level);
+  return XAAC_PARSE_OK;
+}
+
+/* one row per channel of the element parsed last: the channel's bands as ixheaacd_drc_apply walks them, with the factors of drc.h */
+static void drc_side_rows(const XhDrc *d, int n_ch, xaac_drc_side *side) {
+  const int32_t norm = xd_norm(d->target_ref_level, d->prog_ref_level);
+  for (int c = 0; c < n_ch; c++) {
+    const XhDrcChannel &ch = d->ch[c];
+    memset(&side[c], 0, sizeof(side[c]));
+    side[c].n_bands = ch.n_bands;
+    for (int k = 0; k < ch.n_bands; k++) {
+      side[c].end[k] = ch.n_mdct_bands[k];
+      side[c].fac[k] = xd_band_fac(ch.drc_fac[k], d->cut, d->boost, norm);
+    }
+  }
+}
+static void drc_side_identity(xaac_drc_side *side) {
+  memset(side, 0, sizeof(*side));
+  side->n_bands = 1, side->end[0] = 1024, side->fac[0] = XAAC_DRC_ONE;
+}
+
+int32_t xaac_parse_drc_side(xaac_parser *p, xaac_drc_side *side) {
+  if (!p || !side || !p->drc || p->sr_index < 0 || !p->frame_ok) return XAAC_PARSE_ERR_SYNTAX;
+  if (p->core.wide || p->n_els != 1) return XAAC_PARSE_ERR_UNSUPPORTED;
+  drc_side_rows(p->drc, p->first.el.n_ch, side);
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_drc_apply_host(const xaac_drc_side *side, int32_t *spec) {
+  if (!side || !spec) return XAAC_PARSE_ERR_SYNTAX;
+  if (!xd_side_ok(side)) return XAAC_DRC_REFUSED;
+  if (!xd_side_identity(side)) xd_apply_row(side, spec);
+  return XAAC_PARSE_OK;
+}
+
 int32_t xaac_parser_set_esbr(xaac_parser *p, int32_t esbr) {
   if (!p || (esbr != 0 && esbr != 1)) return XAAC_PARSE_ERR_SYNTAX;
   for (int k = 0; k < XP_MAX_ELEMENTS; k++)
@@ -650,6 +695,11 @@ int32_t parse_one(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok)
       memset(side, 0, sizeof(*side));
       xh_export_tools_side(&p->core, el, side);
     }
+  }
+  if (b->drc_side) { /* beside the spectra, row for row; a parser without DRC state gives the identity */
+    if (p->drc && !wide) drc_side_rows(p->drc, n_ch, b->drc_side + row0);
+    else
+      for (int c = 0; c < n_ch; c++) drc_side_identity(b->drc_side + row0 + c);
   }
   if (b->tools) b->tools[S + i] = tools;
   if (b->lines) b->lines[S + i] = 16 * top;

@@ -9,6 +9,13 @@
  *   xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-esbr:<0|1>] [-threads:<T>] [-serialgroups:<0|1>] [-quiet]
  *   ... [-gpus:<G>] [-device:<k>] [-plan] [-gputools:<0|1>] [-mcsbr:<0|1>]
  *   ... [-downmix:<0|1>] [-dmix:<0|1>] [-tostereo:<0|1>] [-peak_limiter_off:<0|1>]
+ *   ... [-drc_cut_fac:<0..1>] [-drc_boost_fac:<0..1>] [-drc_target_level:<0..127>]
+ * Any of the three -drc_* flags switches MPEG-4 dynamic range control on, as in the reference (api.c:1927-1946): the
+ * dynamic_range_info of an AAC-LC stream's fill elements is decoded by the front end, its gain factors go up beside the spectra and
+ * xaac_drc_apply_batch multiplies them in front of the IMDCT (behind the -gputools:1 stage); the limiter runs behind as before.
+ * Flags not given keep the reference's cut 1, boost 1, target level 108.  In a mixed list they act on the AAC-LC groups.  Refused
+ * before a device is looked at or a file written: with an SBR stream in the list, with more than two channels, -drc_heavy_comp:1,
+ * values out of range.
  *
  * The reference's output stage flags, on the GPU (include/xaac_amd.h: xaac_out_map; the mapped calls store the mapped block only, and
  * the device PCM buffers, the copy down, the pinned staging and -verify all have the mapped channel count):
@@ -239,6 +246,7 @@ struct Staging { /* what one step's parse leaves for the GPU */
   xaac_ps_frame *ps;
   xaac_esbr_side *eside;
   xaac_core_tools_side *tside; /* -gputools:1: the side info of the M/S, intensity, PNS and TNS tools */
+  xaac_drc_side *dside;        /* -drc_*: a row of band ends and gain factors beside every row of spec */
   const int32_t *flags, *status, *reset_pitch; /* the step's rows of its group's vectors: [N][8], [N], [N] */
   int delivered;
   int lines; /* leading spectral lines that may be non-zero in a delivered row (xaac_parse_batch::lines, rounded up to 64) */
@@ -305,6 +313,8 @@ struct Job {
   int gputools; /* -gputools:1: parse at stage 1, the spectral tools run on the GPU in front of the IMDCT */
   xaac_out_map map; /* -downmix:1 / -dmix:1 / -tostereo:1: what the PCM hand-off does to a sample's channels (out_ch is the mapped count) */
   int lim_off;      /* -peak_limiter_off:1 on an AAC-LC stream */
+  int drc;          /* a -drc_* flag on an AAC-LC stream: dynamic range control in front of the IMDCT, with ... */
+  xaac_drc_config drc_cfg;
   bool list_mode;
 };
 /* one device's share of the batch: streams [lo, lo + n) on HIP device `device`, decoded by one host thread */
@@ -345,6 +355,7 @@ class ParseSide {
     for (auto &p : parser_) {
       p = mem.parser();
       if (w.esbr) XA(xaac_parser_set_esbr(p, 1));
+      if (J.drc) XA(xaac_parse_drc_config(p, &J.drc_cfg));
     }
     for (int g = 0; g < 3; g++) {
       int32_t *spec = mem.pinned<int32_t>((size_t)T * NC * 1024);
@@ -355,6 +366,7 @@ class ParseSide {
       xaac_esbr_side *eside = w.esbr ? mem.pinned<xaac_esbr_side>((size_t)T * NC) : nullptr;
       const int NE = J.n_els; /* the tools' side rows: one per channel element, element-major within a step */
       xaac_core_tools_side *tside = J.gputools ? mem.pinned<xaac_core_tools_side>((size_t)T * N * NE) : nullptr;
+      xaac_drc_side *dside = J.drc ? mem.pinned<xaac_drc_side>((size_t)T * NC) : nullptr;
       StagingGroup &G = grp_[g];
       const int NF = J.channel_config && J.sbr ? NE : 1; /* flag rows of a stream: one, or one per channel element (mc_sbr) */
       G.flags.assign((size_t)T * N * NF * 8, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N * NF, 0);
@@ -365,6 +377,7 @@ class ParseSide {
         s.header = header ? header + (size_t)t * NC : nullptr, s.frame = frame ? frame + (size_t)t * NC : nullptr;
         s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
         s.tside = tside ? tside + (size_t)t * N * NE : nullptr;
+        s.dside = dside ? dside + (size_t)t * NC : nullptr;
         s.flags = &G.flags[(size_t)t * N * NF * 8], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N * NF];
         s.delivered = 0, s.lines = 1024;
       }
@@ -425,6 +438,7 @@ class ParseSide {
     b.spec = s0.spec, b.ics = s0.ics, b.header = s0.header, b.frame = s0.frame, b.ps_frame = s0.ps;
     b.flags = G.flags.data(), b.consumed = G.consumed.data(), b.status = G.status.data(), b.esbr_side = s0.eside;
     b.reset_pitch = G.reset_pitch.data(), b.lines = G.lines.data(), b.tools_side = s0.tside;
+    b.drc_side = s0.dside;
     const int ok = xaac_parse_batch_run(&b);
     if (ok < 0) die("xaac_parse_batch_run", ok);
     for (int t = 0; t < T; t++) {
@@ -561,10 +575,18 @@ class LcChain : public Chain {
     kept_.assign((size_t)N, 0);
     if (E.J.list_mode) lim_at_end_.resize((size_t)N);
     mapped_ = E.J.map.kind != XAAC_OUT_MAP_NONE;
+    d_dside_ = E.J.drc ? E.mem.dev<xaac_drc_side>((size_t)E.NC) : nullptr;
   }
   Wants wants() const override { return {false, false, false}; }
-  StepOut run(const Staging &, int slot) override {
+  StepOut run(const Staging &s, int slot) override {
     const int N = E_.N, n_ch = E_.J.n_ch;
+    if (E_.J.drc) { /* ixheaacd_drc_apply in front of ixheaacd_imdct_process (aacdecoder.c:981-992): the step's rows, then the launch */
+      HIP(hipMemcpyAsync(d_dside_, s.dside, (size_t)E_.NC * sizeof(xaac_drc_side), hipMemcpyHostToDevice, E_.stream));
+      xaac_drc_batch db;
+      memset(&db, 0, sizeof(db));
+      db.n = E_.NC, db.spec_stride = 1024, db.spec = E_.d_spec, db.side = d_dside_;
+      XA(xaac_drc_apply_batch(E_.ctx, &db));
+    }
     xaac_imdct_batch ib = E_.imdct;
     const bool planar = E_.imdct.ch_fac == 1 && n_ch > 1; /* more than two channels: the IMDCT writes [stream][channel][1024] */
     const size_t bytes = (size_t)N * E_.J.per * E_.J.out_ch * 2;
@@ -639,6 +661,7 @@ class LcChain : public Chain {
   int32_t *d_out32_;
   int8_t *d_qadj_;
   xaac_limiter_state *d_lim_;
+  xaac_drc_side *d_dside_; /* -drc_*: the step's rows on the device */
   void *d_ws_;
   uint64_t ws_bytes_;
   int delay_;
@@ -1404,6 +1427,8 @@ void decode_shard(const Job &J, Shard &S) {
 /* the flags that decide what a kind of stream goes through */
 struct Flags {
   int esbr, hq, gputools, mcsbr, downmix, dmix, tostereo, lim_off;
+  int drc; /* any -drc_* flag was given */
+  xaac_drc_config drc_cfg;
 };
 
 /* One group of a run: the streams of one kind -- an -ilist of mono and stereo streams has as many groups as kinds, in the order in
@@ -1439,6 +1464,8 @@ const char *fill_job(Job &J, const FirstFrame &f0, const Flags &F) {
   if (downmix && (n_ch > 6 || !f0.channel_config)) return "-downmix:1 takes channel configurations 3 .. 6";
   if (dmix && (sbr || n_ch > 2)) return "-dmix:1 on a stream with SBR or with more than two channels is not supported";
   if (dmix && tostereo && n_ch == 1) return "-dmix:1 together with -tostereo:1 on a mono stream is not supported";
+  if (F.drc && sbr) return "a -drc_* flag on a stream with SBR (the QMF-domain branch of dynamic range control) is not supported";
+  if (F.drc && (f0.channel_config || n_ch > 2)) return "a -drc_* flag on a stream of more than two channels is not supported";
 
   xaac_out_map map;
   memset(&map, 0, sizeof(map));
@@ -1455,6 +1482,7 @@ const char *fill_job(Job &J, const FirstFrame &f0, const Flags &F) {
   J.n_ch = n_ch, J.sbr = sbr, J.rate = f0.rate, J.per = sbr ? 2048 : 1024;
   J.esbr = sbr ? F.esbr : 0;       /* AAC-LC streams decode the same either way */
   J.lim_off = sbr ? 0 : F.lim_off; /* no limiter on the SBR paths: the flag changes nothing there */
+  J.drc = F.drc, J.drc_cfg = F.drc_cfg;
   /* SBR streams come out in stereo (PS, or the mono column twice); AAC-LC, and everything with more than two channels, as coded;
      with a map, what the map leaves */
   J.out_ch = map.kind == XAAC_OUT_MAP_MONO_MIX ? 1 : (map.kind != XAAC_OUT_MAP_NONE ? 2 : (sbr && !f0.channel_config ? 2 : n_ch));
@@ -1500,6 +1528,7 @@ void print_plan_kind(const Group &G) {
   const Job &J = G.J;
   printf("\"channels\": %d, \"sbr\": %d, \"esbr\": %d, \"out_channels\": %d, \"out_map\": \"%s\", \"limiter\": %d, \"wav_header\": \"%s\"", J.n_ch,
          J.sbr, J.esbr, J.out_ch, k_map_name[J.map.kind], !J.sbr && !J.lim_off, J.out_ch > 2 ? "extensible68" : "pcm44");
+  if (J.drc) printf(", \"drc\": {\"cut\": %d, \"boost\": %d, \"target_level\": %d}", J.drc_cfg.cut, J.drc_cfg.boost, J.drc_cfg.target_level);
 }
 
 }  // namespace
@@ -1509,6 +1538,8 @@ int main(int argc, char **argv) {
   int copies = 1, threads = 0, quiet = 0, verify = 0, profile = 0, esbr = 1, gpus = 1, device0 = 0, plan = 0, wrap = 0, hq = 0, gputools = 0, mcsbr = 0;
   int downmix = 0, dmix = 0, tostereo = 0, lim_off = 0, serialgroups = 0;
   bool bad_flag = false;
+  int drc = 0;
+  xaac_drc_config drc_cfg = {100, 100, 108}; /* what the reference keeps for the flags not given (api.c:477-481) */
   const struct {
     const char *name;
     int *value;
@@ -1523,6 +1554,26 @@ int main(int argc, char **argv) {
         *f.value = v == "1", taken = true;
       }
     if (taken) continue;
+    /* the reference's -drc_* flags (test/decoder/ixheaacd_main.c:507-538, api.c:629-673): each of them switches DRC on */
+    if (a.rfind("-drc_cut_fac:", 0) == 0 || a.rfind("-drc_boost_fac:", 0) == 0) {
+      const bool cut = a[5] == 'c';
+      const float v = (float)atof(a.c_str() + (cut ? 13 : 15));
+      if (!(v >= 0 && v <= 1)) reject(cut ? "-drc_cut_fac takes 0 .. 1" : "-drc_boost_fac takes 0 .. 1");
+      (cut ? drc_cfg.cut : drc_cfg.boost) = (int32_t)(v * 100);
+      drc = 1;
+      continue;
+    }
+    if (a.rfind("-drc_target_level:", 0) == 0) {
+      const long v = strtol(a.c_str() + 18, nullptr, 10);
+      if (v < 0 || v > 127) reject("-drc_target_level takes 0 .. 127");
+      drc_cfg.target_level = (int32_t)v, drc = 1;
+      continue;
+    }
+    if (a.rfind("-drc_heavy_comp:", 0) == 0) {
+      if (a != "-drc_heavy_comp:0") reject("-drc_heavy_comp:1 (heavy compression from DVB ancillary data) is not supported");
+      drc = 1;
+      continue;
+    }
     if (a.rfind("-ifile:", 0) == 0) in = a.substr(7);
     else if (a.rfind("-ofile:", 0) == 0) out = a.substr(7);
     else if (a.rfind("-ilist:", 0) == 0) ilist = a.substr(7);
@@ -1570,6 +1621,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "usage: xaacdec_amd -ifile:<in.aac> -ofile:<out.wav> [-esbr:0|1] [-esbr_hq:0|1] [-copies:N] [-threads:T] [-gpus:G] [-device:k] [-plan] [-gputools:0|1] [-mcsbr:0|1] [-quiet]\n"
                     "       xaacdec_amd -ilist:<file with one input path per line> -odir:<directory> [-serialgroups:0|1] [the flags above but -copies]\n"
                     "       [-downmix:0|1] [-dmix:0|1] [-tostereo:0|1] [-peak_limiter_off:0|1]\n"
+                    "       [-drc_cut_fac:0..1] [-drc_boost_fac:0..1] [-drc_target_level:0..127]\n"
                     "  -ilist  mono and stereo streams of any sampling rate, with SBR or without, in one list: the streams of one kind are one group,\n"
                     "          the groups run side by side, every flag means for a group what it means for a list of that kind alone; a stream of\n"
                     "          more than two channels only beside streams of its own kind (refused before anything is written)\n"
@@ -1578,7 +1630,9 @@ int main(int argc, char **argv) {
                     "  -downmix:1  3 .. 6 channels come out in stereo (the reference's downmix matrix; a 44-byte stereo WAV header)\n"
                     "  -dmix:1  a stereo AAC-LC stream comes out mono, with -tostereo:1 the mono mix in both channels\n"
                     "  -tostereo:1  a mono AAC-LC stream comes out with its channel twice\n"
-                    "  -peak_limiter_off:1  AAC-LC without the peak limiter (scale adjust + round16)\n");
+                    "  -peak_limiter_off:1  AAC-LC without the peak limiter (scale adjust + round16)\n"
+                    "  -drc_cut_fac / -drc_boost_fac / -drc_target_level  MPEG-4 dynamic range control and level normalisation on AAC-LC mono\n"
+                    "          and stereo streams (any of them switches it on; refused with SBR or more than two channels)\n");
     return 1;
   }
   std::vector<std::vector<uint8_t>> datas(inputs.size());
@@ -1622,7 +1676,7 @@ int main(int argc, char **argv) {
   /* one Job per group.  The output stage flags are looked at per group: what this decoder does not take on one of them is refused
      here for the whole run, before a device is looked at or a file written (a mixed list: with the name of the first file it is
      refused for -- the groups stand in the order of their first files) */
-  const Flags F = {esbr, hq, gputools, mcsbr, downmix, dmix, tostereo, lim_off};
+  const Flags F = {esbr, hq, gputools, mcsbr, downmix, dmix, tostereo, lim_off, drc, drc_cfg};
   const int total = list_mode ? (int)datas.size() : copies;
   /* -threads:T is the whole run's: the groups of a mixed list take shares of it in proportion to their streams, one at least */
   const int team_threads = threads > 0 ? threads : default_parser_threads();
