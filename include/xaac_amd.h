@@ -545,7 +545,7 @@ typedef struct xaac_aac_tools_batch {
                                        element whose side row has n_ch = 2 needs >= 2048 and is refused (status -1) below that */
   int32_t *spec;                    /* in / out, 16-byte aligned: element i's channel c at spec + i * spec_stride + 1024 * c */
   const xaac_core_tools_side *side; /* [n] */
-  xaac_core_tools_state *state;     /* [n] in / out: zero for a new stream */
+  xaac_core_tools_state *state;     /* [n] in / out: a new stream's from xaac_parse_core_tools_state */
   int32_t *status;                  /* optional [n]: 0, or -1 for side info outside the struct's capacity or the syntax (channel
                                        count, sampling frequency index, max_sfb beyond the band table, window grouping, code
                                        book 12 or > 15, TNS filter count / order > 12 / coefficient index) or a pair behind a stride

@@ -150,9 +150,19 @@ XAAC_API int32_t xaac_parse_sbr_side(xaac_parser *p, int32_t ps_enable, xaac_sbr
 /* The side info of the M/S, intensity, PNS and TNS tools for the frame xaac_parse_adts_frame decoded last (include/xaac_tools.h):
    with the spectra of a stage-1 parse, what xaac_core_tools_apply_host below or the GPU's xaac_aac_tools_process_batch
    (xaac_amd.h) turn into the spectra of a stage-2 parse.  A stage-1 parse leaves the parser's own noise generator where it
-   was: the caller keeps an xaac_core_tools_state per stream (zero for a new one).  XAAC_PARSE_ERR_SYNTAX where the last
-   xaac_parse_adts_frame of this parser did not deliver a frame. */
+   was: the caller keeps an xaac_core_tools_state per stream, which starts as xaac_parse_core_tools_state below says.
+   XAAC_PARSE_ERR_SYNTAX where the last xaac_parse_adts_frame of this parser did not deliver a frame. */
 XAAC_API int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side);
+/* The noise generator of the parser's stream (of channel element `element`: _mc).  A new stream's is not all zero: the reference
+   decodes the first frame twice, once while it initialises (ixheaacd_dec_init, api.c:2097) and again as the first output frame,
+   and the seeds of correlated noise bands (pstr_pns_corr_info->random_vector: scratch memory, aacdecoder.c:153-186) outlive the
+   first pass while current_seed starts at 0 again.  So pns_corr_seed starts as one pass of the tools over the first frame from
+   a zero state leaves it, pns_seed at 0.  The first frame a parser reads sets its own generators up that way, at either stage.
+   A stage-1 parser never advances them: at any time behind its first frame this call gives the state the tools' caller starts
+   from, in front of that first frame's tools.  (A stage-2 parser's answer is its generator behind the frame parsed last.)
+   XAAC_PARSE_ERR_SYNTAX before the first frame has parsed, or for an element the parser has no slot for. */
+XAAC_API int32_t xaac_parse_core_tools_state(xaac_parser *p, xaac_core_tools_state *state);
+XAAC_API int32_t xaac_parse_core_tools_state_mc(xaac_parser *p, int32_t element, xaac_core_tools_state *state);
 /* The tool half of ixheaacd_channel_pair_process on the CPU, with the arithmetic the stage-2 parse runs (the twin of the
    GPU kernel: libxaac_amd/csrc/aac_tools.h).  spec: [2][1024] (an SCE uses the first row), in place.  Returns 0, or -1 for
    side info outside the struct's capacity or the syntax (max_sfb beyond the band table, TNS order > 12, ...): spectra and

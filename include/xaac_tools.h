@@ -55,7 +55,10 @@ typedef struct xaac_core_tools_side {
   xaac_core_tools_channel ch[2];
 } xaac_core_tools_side;
 
-/* what outlives a frame, per stream: zero for a new stream */
+/* what outlives a frame, per stream.  A new stream: pns_seed 0, pns_corr_seed as one pass of the tools over the stream's first
+   frame from an all-zero state leaves it -- the reference decodes that frame twice (ixheaacd_dec_init, api.c:2097, then as the
+   first output frame) and random_vector, scratch memory (aacdecoder.c:153-186), outlives the first pass while current_seed is
+   set up afresh.  xaac_parse.h: xaac_parse_core_tools_state fills one for a parser's stream */
 typedef struct xaac_core_tools_state {
   int32_t pns_seed;                        /* pstr_pns_rand_vec_data->current_seed */
   int32_t pns_corr_seed[XAAC_TOOLS_BANDS]; /* pstr_pns_corr_info->random_vector */

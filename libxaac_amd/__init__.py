@@ -594,7 +594,7 @@ class XaacContext:
         """The AAC spectral tools (M/S, intensity, PNS, TNS: the tool half of ixheaacd_channel_pair_process) on device tensors
         (asynchronous), in front of imdct_process_batch: spec int32[N, 2, 1024] (or [N, 1024] for mono elements) as the host
         parser's stage 1 delivers it, in / out; side uint8[N, CORE_TOOLS_SIDE_BYTES] (xaac_parse_core_tools_side); state
-        uint8[N, CORE_TOOLS_STATE_BYTES] in / out (zero for a new stream); optional status int32[N]: 0, or -1 for side info
+        uint8[N, CORE_TOOLS_STATE_BYTES] in / out (a new stream's: xaac_parse_core_tools_state); optional status int32[N]: 0, or -1 for side info
         the tools refuse (that element is left untouched).  first_row: the element's first channel is row first_row of the
         spec_stride / 1024 rows every stream has in spec (streams of several channel elements: one call per element index)."""
         n = side.shape[0]

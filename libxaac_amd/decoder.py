@@ -73,7 +73,7 @@ class CoreToolsSide(ctypes.Structure):
 
 
 class CoreToolsState(ctypes.Structure):
-    # struct xaac_core_tools_state: the noise generator of one stream (zero for a new one)
+    # struct xaac_core_tools_state: the noise generator of one stream (a new one's: xaac_parse_core_tools_state)
     _fields_ = [("pns_seed", ctypes.c_int32), ("pns_corr_seed", ctypes.c_int32 * 128)]
 
 
@@ -111,6 +111,10 @@ def load_host_library():
         lib.xaac_parser_set_esbr.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         lib.xaac_parse_core_tools_side.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         lib.xaac_parse_core_tools_side.restype = ctypes.c_int32
+        lib.xaac_parse_core_tools_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        lib.xaac_parse_core_tools_state.restype = ctypes.c_int32
+        lib.xaac_parse_core_tools_state_mc.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        lib.xaac_parse_core_tools_state_mc.restype = ctypes.c_int32
         lib.xaac_core_tools_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.xaac_core_tools_apply_host.restype = ctypes.c_int32
         lib.xaac_parse_esbr_side.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
@@ -207,7 +211,8 @@ class ParseError(RuntimeError):
 class StreamParser:
     """One ADTS stream through the host front end, frame by frame.  (The reference decodes the first frame twice, once
     while it initialises -- ixheaacd_dec_init, api.c:2097 -- and again as the first output frame; every state is set up
-    afresh in between, api.c:2141-2170, so nothing of the first pass shows and one pass is all that is needed here.)"""
+    afresh in between, api.c:2141-2170, but for the seeds of correlated noise bands, which lie in scratch memory: the parser
+    starts its noise generator from them (xaac_parse_core_tools_state), so one pass is all that is needed here.)"""
 
     def __init__(self, data, with_sbr=None, stage=2, esbr=False, drc=None):
         self.lib = load_host_library()
@@ -528,6 +533,16 @@ class BatchParser:
                 self.lib.xaac_parser_destroy(self.parsers[i])
                 self.parsers[i] = None
 
+    def tools_states(self):
+        """uint8[n_elems, n, CORE_TOOLS_STATE_BYTES], element-major like the tools' side rows: what every stream's noise generators
+        start from (xaac_parse_core_tools_state_mc), for the caller of a stage-1 parse, once the first step has been parsed.  A
+        stream that delivered no frame keeps zeros"""
+        out = np.zeros((self.n_elems, self.n, CORE_TOOLS_STATE_BYTES), np.uint8)
+        for i in range(self.n):
+            for k in range(self.n_elems):
+                self.lib.xaac_parse_core_tools_state_mc(self.parsers[i], k, out[k, i].ctypes.data)
+        return out
+
     def _descriptor(self, spec, ics, hdr, frm, psf, flags, with_sbr, eside=None, status=None, reset_pitch=None, frames=1, lines=None,
                     tools_side=None, drc_side=None):
         # data / bytes are the whole streams and stay as they are; the library moves self.pos (xaac_parse_batch::pos), so a
@@ -698,6 +713,9 @@ class _ToolsStage:
         self.state = dz(rows, CORE_TOOLS_STATE_BYTES)
         self.status2 = [dz(rows, dtype=torch.int32) for _ in range(2)]
         self.status_h2 = [pinned(rows, dtype=torch.int32) for _ in range(2)]
+
+    def begin(self, bp):   # behind the first parsed step, in front of the first run: the streams' generators as they start
+        self.state.copy_(torch.from_numpy(bp.tools_states().reshape(self.state.shape)))
 
     def send_up(self, step, slot):
         self.side_d2[slot].copy_(step.tside, non_blocking=True)
@@ -1253,6 +1271,8 @@ class _Pipeline:
             main_stream.wait_event(cur.sent)
             spec_d = self.spec_d2[slot]
             if tools is not None:
+                if first:
+                    tools.begin(self.bp)
                 tools.run(spec_d, slot)
             if self.drc is not None:
                 self.drc.run(spec_d, slot)

@@ -719,6 +719,13 @@ int xh_core_init(XhCoreState *st, int sr_index) {
   return 0;
 }
 
+void xh_tools_state_begin(const xaac_core_tools_side *first, xaac_core_tools_state *state) {
+  static thread_local int32_t lines[1024]; /* the noise itself: thrown away (the seeds do not depend on the spectra) */
+  memset(state, 0, sizeof(*state));
+  for (int c = 0; c < first->n_ch; c++) xt_pns_host(first, c, lines, state);
+  state->pns_seed = 0;
+}
+
 int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
                             int *n_els, int stage) {
   const size_t block_start = br->pos;
@@ -775,8 +782,12 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, 
           const int e = read_channel_stream(st, br, el, c);
           if (e) return e;
         }
+        static thread_local xaac_core_tools_side side; /* only the bands below max_sfb are written and read */
+        if (!st->tools_born) { /* the stream's first frame: the generator as the reference's initialisation pass leaves it */
+          xh_export_tools_side(st, el, &side);
+          xh_tools_state_begin(&side, tool_state);
+        }
         if (stage >= 2) { /* channel.c:602-692 */
-          static thread_local xaac_core_tools_side side; /* only the bands below max_sfb are written and read */
           /* (a single channel without noise substitution and TNS has no tool to run: most frames of a mono stream; in a
              stream of more than two channels the three extra bits still have to come off) */
           if (el->n_ch == 2 || el->ch[0].pns_active || el->ch[0].tns.present || st->wide) {
@@ -837,6 +848,7 @@ int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, 
   br->skip((8 - ((br->pos - block_start) & 7)) & 7);
   if (br->overrun) return XH_ERR_BITS;
   if (!have_channels) return XH_ERR_SYNTAX;
+  st->tools_born = 1; /* (a first frame that did not parse: the next one starts the generators afresh) */
   /* aacdecoder.c:927-929: the frame's elements onto the channels of its channel element, in front of the IMDCT */
   return st->drc ? drc_map_channels(st->drc, els[0]->n_ch) : 0;
 }

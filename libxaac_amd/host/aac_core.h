@@ -72,8 +72,12 @@ struct XhChannel {
    the noise generator xaac_core_tools_state -- pns_seed = pstr_pns_rand_vec_data->current_seed, which starts at 0 and runs on from
    frame to frame; pns_corr_seed = pstr_pns_corr_info->random_vector: the left channel's seed of a band whose noise the M/S flag
    correlates; a right channel that substitutes noise in such a band where the left one does not finds the value an earlier frame
-   left, the reference keeps it in scratch memory that AAC-LC decoding does not reuse in between.  Only stage-2 parsing advances it:
-   behind a stage-1 parse the tools' caller keeps the state, xaac_core_tools_apply_host or the GPU's xaac_aac_tools_process_batch.) */
+   left, the reference keeps it in scratch memory that AAC-LC decoding does not reuse in between -- nor between its initialisation
+   pass over the first frame (ixheaacd_dec_init, api.c:2097) and the first output frame: a new stream's pns_corr_seed is what the
+   tools leave behind one pass over its first frame from zero, while current_seed is set back to 0 (xh_tools_state_begin; the
+   first block a parser reads sets its elements' generators up that way, whatever the stage).  Only stage-2 parsing advances it:
+   behind a stage-1 parse the tools' caller keeps the state, xaac_core_tools_apply_host or the GPU's xaac_aac_tools_process_batch,
+   and starts from the parser's, xaac_parse_core_tools_state.) */
 struct XhCoreState {
   int sr_index;            /* 0 .. 11 */
   int16_t swb_long[52], swb_short[16];
@@ -83,6 +87,8 @@ struct XhCoreState {
                               q_factor 34 and the 32-bit TNS variant (block.c:1263, channel.c:642, pns_js_thumb.c:328) */
   struct XhDrc *drc;       /* the stream's dynamic range control state, or null: dynamic_range_info is then skipped unread (set by
                               the caller behind xh_core_init, like `wide`) */
+  int tools_born;          /* a block of the stream has parsed: its elements' noise generators have been set up
+                              (xh_tools_state_begin; the caller carries it over xh_core_init, like `wide`) */
 };
 
 /* ---- dynamic range control: what ia_drc_dec_struct keeps for the spectral-domain branch (decoder/ixheaacd_drc_data_struct.h) ---- */
@@ -143,6 +149,13 @@ int xh_core_init(XhCoreState *st, int sr_index);
    Returns 0 or a negative XH_ERR_*. */
 int xh_parse_raw_data_block(XhCoreState *st, XhBits *br, XhElement *const *els, xaac_core_tools_state *const *tools, int cap,
                             int *n_els, int stage);
+
+/* A new stream's noise generator, from the tools' side info of its first frame: the seeds of the correlated noise bands as one
+   pass of the tools over that frame from a zero state leaves them, pns_seed 0.  The reference decodes the first frame twice -- while
+   it initialises (ixheaacd_dec_init, api.c:2097) and again as the first output frame --; pstr_pns_corr_info->random_vector lies in
+   scratch memory (aacdecoder.c:153-186) that outlives the first pass, current_seed belongs to the decoder instance that is set up
+   afresh in between. */
+void xh_tools_state_begin(const xaac_core_tools_side *first, xaac_core_tools_state *state);
 
 /* What the tools read of the element parsed last, as the boundary struct of include/xaac_tools.h (ms_used and
    pns_correlated as the tools apply them).  Writes the bands below max_sfb, the filters n_filt counts and the scalar

@@ -349,7 +349,9 @@ static int32_t parse_frame_inner(xaac_parser *p, const uint8_t *data, size_t n, 
   if (consumed) *consumed = (size_t)h.frame_bytes;
   if (p->sr_index != h.sr_index) {
     /* (a change of sampling rate in mid-stream: the slots' noise generators run on) */
+    const int born = p->core.tools_born;
     if (xh_core_init(&p->core, h.sr_index)) return XAAC_PARSE_ERR_HEADER;
+    p->core.tools_born = born;
     p->sr_index = h.sr_index;
     p->sampling_rate = h.sampling_rate;
   }
@@ -525,6 +527,14 @@ int32_t xaac_parse_core_tools_side(xaac_parser *p, xaac_core_tools_side *side) {
   if (!p || p->first.el.n_ch < 1) return XAAC_PARSE_ERR_SYNTAX;
   return xaac_parse_core_tools_side_mc(p, 0, side);
 }
+
+int32_t xaac_parse_core_tools_state_mc(xaac_parser *p, int32_t element, xaac_core_tools_state *state) {
+  if (!p || !state || !p->core.tools_born || element < 0 || element >= XP_MAX_ELEMENTS || !p->slot[element]) return XAAC_PARSE_ERR_SYNTAX;
+  *state = p->slot[element]->tools;
+  return XAAC_PARSE_OK;
+}
+
+int32_t xaac_parse_core_tools_state(xaac_parser *p, xaac_core_tools_state *state) { return xaac_parse_core_tools_state_mc(p, 0, state); }
 
 int32_t xaac_core_tools_apply_host(const xaac_core_tools_side *side, xaac_core_tools_state *state, int32_t *spec) {
   if (!side || !state || !spec) return XAAC_PARSE_ERR_SYNTAX;

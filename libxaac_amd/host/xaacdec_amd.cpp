@@ -409,6 +409,7 @@ class ParseSide {
     worker_.join();
   }
   const Staging &step(int which) const { return st_[which]; }
+  xaac_parser *const *parsers() const { return parser_.data(); }
 
  private:
   void work() {
@@ -519,14 +520,24 @@ class Chain {
   virtual void finish(std::vector<std::vector<int16_t>> &) {} /* what the chain still holds of every stream's output */
 };
 
-/* -gputools:1: the tools' side rows, the streams' noise generators (zero for a new stream), the kernel's status words; the
-   driver runs this in front of whichever chain */
+/* -gputools:1: the tools' side rows, the streams' noise generators (begin() gives them what a new stream's start from), the
+   kernel's status words; the driver runs this in front of whichever chain */
 class ToolsStage {
  public:
   explicit ToolsStage(const Env &E) : E_(E), rows_((size_t)E.N * E.J.n_els) {
     d_side_ = E.mem.dev<xaac_core_tools_side>(rows_), d_state_ = E.mem.dev<xaac_core_tools_state>(rows_);
     HIP(hipMemset(d_state_, 0, rows_ * sizeof(xaac_core_tools_state)));
     for (int k = 0; k < 2; k++) d_status_[k] = E.mem.dev<int32_t>(rows_), h_status_[k] = E.mem.pinned<int32_t>(rows_);
+  }
+  /* behind the parse of the streams' first frames, in front of the first run: every element's generator as its stage-1 parser
+     says a new stream's starts (xaac_parse_core_tools_state_mc; a stream without a first frame keeps zeros) */
+  void begin(xaac_parser *const *parser) {
+    std::vector<xaac_core_tools_state> h(rows_);
+    memset(static_cast<void *>(h.data()), 0, rows_ * sizeof(xaac_core_tools_state));
+    for (int k = 0; k < E_.J.n_els; k++)
+      for (int i = 0; i < E_.N; i++) xaac_parse_core_tools_state_mc(parser[i], k, &h[(size_t)k * E_.N + i]);
+    HIP(hipMemcpyAsync(d_state_, h.data(), rows_ * sizeof(xaac_core_tools_state), hipMemcpyHostToDevice, E_.stream));
+    HIP(hipStreamSynchronize(E_.stream));
   }
   void send_up(const Staging &s) {
     HIP(hipMemcpyAsync(d_side_, s.tside, rows_ * sizeof(xaac_core_tools_side), hipMemcpyHostToDevice, E_.stream));
@@ -1228,6 +1239,7 @@ class ShardDriver {
       const Staging &s = parse_->step(which);
       if (s.delivered == 0) break;
       if (s.delivered != N_) note_ended(s);
+      if (first && tools_) tools_->begin(parse_->parsers());
       if (step % T == 0) parse_->start(); /* the next group's frames are parsed while the GPU works on this one's */
       t_phase_ = std::chrono::steady_clock::now();
       if (J_.routed_up()) send_up_routed(s, which);

@@ -69,9 +69,10 @@ def stream_files(tmp):
     return out
 
 
-def reference_spectra(path, tmp, n_ch):
+def reference_spectra(path, tmp, n_ch, record=2):
     """the reference's spectra as ixheaacd_imdct_process receives them: [frames][n_ch][1024] (XAAC_SPEC_DUMP type-2 records of
-    oracle/ref_capture.c, the first frame's initialisation pass dropped)"""
+    oracle/ref_capture.c, the first frame's initialisation pass dropped); record=1: its type-1 records, the spectra in front of
+    the tools"""
     need("xaacdec_capture")
     spec = os.path.join(tmp, "spec_%s.bin" % os.path.basename(path))
     if os.path.exists(spec):
@@ -79,7 +80,7 @@ def reference_spectra(path, tmp, n_ch):
     subprocess.run([os.path.join(REF, "xaacdec_capture"), "-ifile:" + path, "-ofile:" + spec + ".wav", "-esbr:0"],
                    env=dict(os.environ, XAAC_SPEC_DUMP=spec), check=True, capture_output=True, timeout=600)
     raw = np.fromfile(spec, dtype=np.int32).reshape(-1, 1030)
-    t2 = raw[raw[:, 0] == 2][n_ch:, 6:]
+    t2 = raw[raw[:, 0] == record][n_ch:, 6:]
     return t2.reshape(-1, n_ch, 1024)
 
 
@@ -202,3 +203,116 @@ def random_element(rng):
             spec[c, lo:lo + 32] = rng.integers(-(1 << mag), 1 << mag, 32, dtype=np.int64).astype(np.int32)
     state = rng.integers(-2 ** 31, 2 ** 31, 129, dtype=np.int64).astype(np.int32).view(np.uint8).copy()
     return np.frombuffer(bytes(side), np.uint8).copy(), spec, state
+
+
+# ---- the generator-made streams of tests/golden/streams_synth ----------------------------------------------------------------
+SYNTH = os.path.join(ROOT, "tests", "golden", "streams_synth")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+UNSUPPORTED = -3
+_synth_cache = {}
+
+
+def synth_rows():
+    """tools/make_synth_streams.py: synth_set() -- (name, seed, sampling frequency index, frames, level, kind, avoid); kind: 1 mono,
+    2 stereo, ADTS channel_configuration 3 / 6"""
+    import make_synth_streams
+    return make_synth_streams.synth_set()
+
+
+def synth_path(name):
+    return os.path.join(SYNTH, name + ".aac")
+
+
+def synth_channels(kind):
+    return {1: 1, 2: 2, 3: 3, 6: 6}[kind]
+
+
+def new_states(data):
+    """what the noise generators of a new stream start from, one per channel element: xaac_parse_core_tools_state_mc of a
+    stage-1 parser behind the first frame"""
+    lib = decoder.load_host_library()
+    p = ctypes.c_void_p()
+    assert lib.xaac_parser_create(ctypes.byref(p)) == 0
+    try:
+        state = np.zeros(decoder.CORE_TOOLS_STATE_BYTES, np.uint8)
+        assert lib.xaac_parse_core_tools_state_mc(p, 0, state.ctypes.data) == -2       # no frame yet
+        elems, n, used = (decoder.CoreFrame * decoder.MC_MAX_ELEMENTS)(), ctypes.c_int32(), ctypes.c_size_t()
+        rc = lib.xaac_parse_adts_frame_mc(p, data, len(data), 1, elems, decoder.MC_MAX_ELEMENTS, ctypes.byref(n), ctypes.byref(used))
+        assert rc == 0, rc
+        out = []
+        for k in range(n.value):
+            assert lib.xaac_parse_core_tools_state_mc(p, k, state.ctypes.data) == 0
+            out.append(state.copy())
+        return out
+    finally:
+        lib.xaac_parser_destroy(p)
+
+
+def element_rows(ids):
+    """[(first channel row, channels)] of a frame's channel elements, bitstream order"""
+    rows, at = [], 0
+    for e in ids:
+        rows.append((at, 2 if e == 1 else 1))
+        at += rows[-1][1]
+    return rows
+
+
+def twin_walk(before, states):
+    """stage-1 frames of decoder.parse_stream_mc through xaac_core_tools_apply_host, every element from its own state ->
+    ([frames] int32[channels, 1024], the final states)"""
+    states = [s.copy() for s in states]
+    out = []
+    for s1, _, _, ids, sides in before:
+        got = s1.copy()
+        for k, (row, n) in enumerate(element_rows(ids)):
+            spec = np.zeros((2, 1024), np.int32)
+            spec[:n] = s1[row:row + n]
+            rc, spec, states[k] = apply_host(spec, np.frombuffer(sides[k], np.uint8), states[k])
+            assert rc == 0
+            got[row:row + n] = spec[:n]
+        out.append(got)
+    return out, states
+
+
+def synth_walk(name, data=None):
+    """(stage-1 frames, stage-2 frames) of decoder.parse_stream_mc -- which takes streams of one element too --, once per run"""
+    if data is not None:
+        return decoder.parse_stream_mc(data, stage=1), decoder.parse_stream_mc(data, stage=2)
+    if name not in _synth_cache:
+        data = open(synth_path(name), "rb").read()
+        _synth_cache[name] = (decoder.parse_stream_mc(data, stage=1), decoder.parse_stream_mc(data, stage=2))
+    return _synth_cache[name]
+
+
+def right_only_bands(side_bytes):
+    """the bands of an element where the right channel substitutes noise under a set ms_used bit and the left one does not: their
+    noise starts from the seed the band's last correlated left-channel noise left"""
+    s = decoder.CoreToolsSide.from_buffer_copy(side_bytes)
+    if s.n_ch != 2 or not s.common_window:
+        return []
+    return [b for b in range(128) if s.pns_correlated[b] and s.ch[1].pns_used[b] and not s.ch[0].pns_used[b]]
+
+
+def coverage(tools, side_bytes):
+    """which of the tools an element of a frame shows, from its XAAC_TOOL_* bits and side info -> set of names"""
+    s = decoder.CoreToolsSide.from_buffer_copy(side_bytes)
+    got = set()
+    for c in range(s.n_ch):
+        ch = s.ch[c]
+        if not ch.tns_present:
+            continue
+        short = ch.window_sequence == 2
+        orders = [ch.tns[w if short else f].order for w in range(8 if short else 1) for f in range(min(ch.n_filt[w], 1 if short else 3))]
+        if any(o > 0 for o in orders):
+            got.add("tns_short" if short else "tns_long")
+        if any(o >= 8 for o in orders):
+            got.add("tns_order8")
+    if tools & decoder.TOOL_MS:
+        got.add("ms")
+    if tools & decoder.TOOL_INTENSITY:
+        got.add("intensity")
+    if tools & decoder.TOOL_PNS:
+        got.add("pns")
+        if s.n_ch == 2 and s.common_window and any(s.pns_correlated[b] and (s.ch[0].pns_used[b] or s.ch[1].pns_used[b]) for b in range(128)):
+            got.add("pns_corr")
+    return got
