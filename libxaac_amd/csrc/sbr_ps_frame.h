@@ -18,8 +18,8 @@
  *      group sums of the upper bins               a running sum over the band lanes per slot, then lane = (slot, group):
  *                                                 the addends are >= 0, so the saturating sum is min(MAX, exact sum)
  *                                                 whatever the order (xp_gsum_*)
- *   P4 transient detector                         lane = bin, loop over slots (the recursion), then the 640 ratios
- *                                                 (one division each) lane-parallel
+ *   P4 transient detector                         lane = bin (peak decay) | 32 + bin (energy), loop over slots (the
+ *                                                 recursion), then the 640 ratios (one division each) lane-parallel
  *   P5 all-pass chains                            lane = chain (30), loop over slots (the recursion)
  *   P6 rotation in the hybrid domain + its sums   lane = (slot, re | im), loop over the ten sub-bands
  *   P7 delays, rotation, output scaling           lane = QMF band, loop over slots (coalesced row reads / writes)
@@ -66,8 +66,10 @@ struct XpFrameWork {
     uint32_t gscan[32][8];   /* P3: per slot the running sum of the group addends at the last band of groups 0..5; column 6:
                                 the other lanes' stores */
     int32_t peak[32][20];    /* P4: transient peak difference */
-    uint32_t dl[32][13];     /* P5/P7: rounded samples of QMF bands 23..34 (the 14-slot delay looks 14 slots back); column
-                                12 takes the other lanes' stores, so that the store needs no predicate */
+    uint32_t dl[14 + 32][13]; /* P5/P7: the 14-slot delay lines of QMF bands 23..34, unrolled over the frame: row l holds what
+                                slot l reads (rows 0..13: the state's ring in slot order), slot l writes row l + 14 -- the
+                                band's rounded sample, or what it read if the band is not active.  Column 12 takes the other
+                                lanes' stores, so that the store needs no predicate */
   };
   int32_t hyb_l[32][20];     /* left hybrid sub-band samples of every slot: re 0..9 | im 10..19 */
   union {
@@ -78,6 +80,7 @@ struct XpFrameWork {
   uint32_t seg_hd[XP_MAX_SEG][4][24]; /* per segment and group: H11, H12, H21, H22 before the segment's first slot (high
                                           half) and their per-slot increments (low half): a border reloads four words */
 };
+static_assert(sizeof(XpFrameWork::dl) <= sizeof(XpFrameWork::peak), "the unrolled 14-slot lines fit the scratch union as it was");
 template <bool B>
 struct XpBool {
   static constexpr bool value = B;
@@ -111,6 +114,15 @@ FX_HD uint32_t xp_load_pair(const int16_t *p) {
   return *reinterpret_cast<const xp_u32_alias *>(p);
 #else
   return xp_pack16(p[0], p[1]);
+#endif
+}
+FX_HD void xp_store_pair(int16_t *p, uint32_t v) { /* ... and the store that goes with it */
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef uint32_t __attribute__((may_alias)) xp_u32_alias;
+  *reinterpret_cast<xp_u32_alias *>(p) = v;
+#else
+  p[0] = xp_lo16(v);
+  p[1] = xp_hi16(v);
 #endif
 }
 /* a complex 16-bit rotation factor (re, im) as the two pairs the products of xp_allpass take: (re, -im) gives the real
@@ -203,6 +215,38 @@ FX_HD int32_t xp_adj_word(int32_t v, int shift) {
   return (int32_t)((uint32_t)v << shl) >> shr;
 }
 
+/* floor(u * 2^15 / v) for u < 2^16 and 2^14 <= v < 2^16 without an integer division.  u * 2^15 (sixteen significant bits)
+   and v are exact as floats; with a reciprocal r good to one unit in the last place (the host's division is, and so is
+   v_rcp_f32) and the product rounded once, the product is off by less than 2^17 * 2^-22 = 2^-5 and its integer part is the
+   quotient or a neighbour of it; the remainder says which.  (The compiler's 32-bit division: two dozen instructions behind
+   a predicate; this: a dozen, no branch.)  r is a parameter so that a test can hand in the neighbours of 1 / v too. */
+FX_HD uint32_t xp_quot15_rcp(uint32_t u, uint32_t v, float r) {
+  const uint32_t n = u << 15;
+  uint32_t q = (uint32_t)((float)n * r);
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int32_t rem = (int32_t)(n - __umul24(q, v)); /* q < 2^18, v < 2^16 */
+#else
+  const int32_t rem = (int32_t)(n - q * v);
+#endif
+  q += rem >= (int32_t)v ? 1u : 0u;
+  q -= rem < 0 ? 1u : 0u;
+  return q;
+}
+FX_HD uint32_t xp_quot15(uint32_t u, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return xp_quot15_rcp(u, v, __builtin_amdgcn_rcpf((float)v));
+#else
+  return xp_quot15_rcp(u, v, 1.0f / (float)v);
+#endif
+}
+/* xp_divide16_pos (sbr_ps.h, ps_dec.c:212) where the frame calls it: 0 <= op1 < op2, so that the normalised heads are
+   u <= v with v in [2^14, 2^15) -- the same word for every such pair (tests/test_ps_prep_cpu.py; u = 0 gives 0 by itself) */
+FX_HD int32_t xp_divide16_norm(int32_t op1, int32_t op2) {
+  const int nrm = fx_norm32(op2);
+  const uint32_t u = (uint32_t)xs_shl(op1, nrm) >> 16, v = (uint32_t)xs_shl(op2, nrm) >> 16;
+  return (int32_t)(xp_quot15(u, v) & 0xffffu);
+}
+
 /* ps_dec.c:470-519: the eight transient-detector bins that live in the hybrid domain */
 FX_HD int32_t xp_bin_power_hyb(const XpTables *T, int bin, const int32_t *re, const int32_t *im) {
   if (bin < 2) {
@@ -226,6 +270,10 @@ FX_HD int32_t xp_bin_power_hyb(const XpTables *T, int bin, const int32_t *re, co
    sbr_core.h: xs_prefix_max with + for max); on the host it is the running sum of the band loop. */
 /* the band's addend: its power in its group's scale if a group reads it, else nothing */
 FX_HD uint32_t xp_gsum_addend(int32_t pw, int group_shift, bool counts) { return counts ? (uint32_t)(pw >> group_shift) : 0u; }
+/* the same with "does not count" folded into the shift: a power is >= 0 (xp_power: two products of a word and its own high
+   half), so a count of 31 leaves nothing of it -- the slot's predicate and select become a choice between two lane constants */
+FX_HD int xp_gsum_shift(int group_shift, bool counts) { return counts ? group_shift : 31; }
+FX_HD uint32_t xp_gsum_addend_sh(int32_t pw, int shift) { return (uint32_t)(pw >> shift); }
 /* S of this band: `run` carries the sum over the bands before it where bands are walked one after the other (the host) */
 FX_HD uint32_t xp_gsum_scan(const XsCx &cx, uint32_t a, uint32_t &run) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -264,6 +312,64 @@ FX_HD bool xp_gsum_fits(const XpTables *T) {
     if ((uint64_t)(b1 - b0) * (uint64_t)(0x7fffffff >> shift) >= ((uint64_t)1 << 32)) return false;
   }
   return true;
+}
+
+/* P4, the transient detector of a whole frame (ps_dec.c:547-590; sbr_ps.h: xp_decorrelation has it per slot): peak decay
+   against smoothed energy, per bin.  In: w->binpw[l][bin], the bin powers of the NS slots; out: w->ratio[l][bin] and the
+   three carried values of every bin.  Two lanes per bin: lane `bin` carries the peak decay and its smoothed difference,
+   lane 32 + bin the smoothed energy.  Both smoothings are acc = acc * 0.75 + (t >> 2) with their own t, so the step is
+   issued once for the two (as one lane per bin it was three recursions one after the other in every step). */
+template <int NS, class PS>
+FX_HD void xp_transient_frame(const XsCx &cx, PS *ps, XpFrameWork *w) {
+  XS_PAR(i, 0, 32 + 20) {
+    const int bin = i & 31;
+    const bool en = i >= 32;
+    if (bin >= 20) continue;
+    int32_t pd = ps->peak_decay_diff[bin], acc = en ? ps->energy_prev[bin] : ps->peak_decay_diff_prev[bin];
+    int32_t *out = en ? &w->binpw[0][bin] : &w->peak[0][bin]; /* (rows of 20 words both) */
+    int32_t pin[NS]; /* the bin's NS powers first: the recursion below then waits for no LDS load */
+    XP_UNROLL
+    for (int l = 0; l < NS; l++) pin[l] = w->binpw[l][bin];
+    cx.sync(); /* both lanes of a bin have read its powers before the energy overwrites them */
+    XP_UNROLL
+    for (int l = 0; l < NS; l++) {
+      int32_t pw = fx_shl(pin[l], 1);
+      if (pw < 0) pw = 0;
+      pd = fx_mul32x16_shl(pd, 0x620a);
+      if (pw > pd) pd = pw;
+      const int32_t t = en ? pw : fx_sub_sat(pd, pw);
+      acc = fx_add_sat(fx_mul32x16_shl(acc, 0x6000), t >> 2);
+      out[20 * l] = en ? acc : fx_add_sat(acc, acc >> 1);
+    }
+    if (en) {
+      ps->energy_prev[bin] = acc;
+    } else {
+      ps->peak_decay_diff[bin] = pd;
+      ps->peak_decay_diff_prev[bin] = acc;
+    }
+  }
+  cx.sync();
+#if defined(__HIP_DEVICE_COMPILE__)
+  { /* the 640 (energy, peak) pairs of all ten trips are read before any lane stores a ratio: entry i lands inside word
+       i / 2 of the energies, and ten trips of their own were ten LDS round trips with a pair of fences each.  (Rows 30 and
+       31 of a 30-slot frame hold older words; their ratios are not read.) */
+    int32_t pk[10], nrg[10];
+    XP_UNROLL
+    for (int t = 0; t < 10; t++) {
+      pk[t] = (&w->peak[0][0])[64 * t + cx.lane];
+      nrg[t] = (&w->binpw[0][0])[64 * t + cx.lane];
+    }
+    cx.sync();
+    XP_UNROLL
+    for (int t = 0; t < 10; t++)
+      (&w->ratio[0][0])[64 * t + cx.lane] = pk[t] <= nrg[t] ? (int16_t)0x7fff : (int16_t)xp_divide16_norm(nrg[t], pk[t]);
+  }
+#else
+  for (int i = 0; i < 20 * NS; i++) { /* in order: entry i / 2 has been consumed */
+    const int32_t pk = (&w->peak[0][0])[i], nrg = (&w->binpw[0][0])[i];
+    (&w->ratio[0][0])[i] = pk <= nrg ? (int16_t)0x7fff : (int16_t)xp_divide16_norm(nrg, pk);
+  }
+#endif
 }
 
 /* One frame of NS slots (32, or 30).  xl: the stream's QMF matrix, slot 0 at xl (rows of 64 re | 64 im; rows 0..NS + 5
@@ -415,14 +521,18 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         for (int g = 0; g < 6; g++) gcol = sb == T->borders_group[17 + g] - 1 ? g : gcol;
         int32_t *dst = own_bin ? &w->binpw[8 * c][sb + 5] : reinterpret_cast<int32_t *>(&w->gscan[8 * c][gcol]);
         const int dstride = own_bin ? 20 : 8;
+        /* lane constants of the slot body: the band's scale shift in the overlap slots and behind them, and the group
+           shift under the old band limit and under the new one (which slot takes which is a fact of the unrolled loop
+           for the first, one uniform compare for the second) */
+        const int sh_ov = sb < lsb ? ov_lb_shift : (sb < usb ? hb_shift : 0), sh_lb = sb < lsb ? lb_shift : (sb < usb ? hb_shift : 0);
+        const int gsh_old = xp_gsum_shift(gsh, sb >= 9 && sb < usb_prev), gsh_new = xp_gsum_shift(gsh, sb >= 9 && sb < usb);
         XP_UNROLL
         for (int ls = 0; ls < 8; ls++) {
           const int l = 8 * c + ls;
-          const int usb_l = l >= clear_slot ? usb : usb_prev;
-          const int sh = sb < lsb ? (l < 6 ? ov_lb_shift : lb_shift) : (sb < usb ? hb_shift : 0);
+          const int sh = l < 6 ? sh_ov : sh_lb;
           const int32_t re = xp_adj_word(rre[ls], sh), im = xp_adj_word(rim[ls], sh);
           const int32_t pw = xp_power(re, im);
-          const uint32_t s = xp_gsum_scan(cx, xp_gsum_addend(pw, gsh, sb >= 9 && sb < usb_l), run[ls]);
+          const uint32_t s = xp_gsum_scan(cx, xp_gsum_addend_sh(pw, l >= clear_slot ? gsh_new : gsh_old), run[ls]);
           dst[ls * dstride] = own_bin ? pw : (int32_t)s;
         }
       }
@@ -444,43 +554,8 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
   cx.sync();
   XP_T(4);
 
-  /* ---- P4: transient detector (ps_dec.c:547-590): peak decay against smoothed energy, per bin */
-  XS_PAR(bin, 0, 20) {
-    int32_t pd = ps->peak_decay_diff[bin], pdp = ps->peak_decay_diff_prev[bin], nrg = ps->energy_prev[bin];
-    int32_t pin[NS]; /* the bin's NS powers first: the recursion below then waits for no LDS load */
-    XP_UNROLL
-    for (int l = 0; l < NS; l++) pin[l] = w->binpw[l][bin];
-    XP_UNROLL
-    for (int l = 0; l < NS; l++) {
-      int32_t pw = fx_shl(pin[l], 1);
-      if (pw < 0) pw = 0;
-      pd = fx_mul32x16_shl(pd, 0x620a);
-      if (pw > pd) pd = pw;
-      pdp = fx_add_sat(fx_mul32x16_shl(pdp, 0x6000), fx_sub_sat(pd, pw) >> 2);
-      nrg = fx_add_sat(fx_mul32x16_shl(nrg, 0x6000), pw >> 2);
-      w->binpw[l][bin] = nrg;
-      w->peak[l][bin] = fx_add_sat(pdp, pdp >> 1);
-    }
-    ps->peak_decay_diff[bin] = pd;
-    ps->peak_decay_diff_prev[bin] = pdp;
-    ps->energy_prev[bin] = nrg;
-  }
-  cx.sync();
-  for (int i0 = 0; i0 < 20 * NS; i0 += 64) { /* every lane reads its (energy, peak) pair before any lane stores a ratio */
-    int16_t q = 0;
-    XS_PAR(i, i0, (20 * NS) % 64 == 0 || i0 + 64 < 20 * NS ? i0 + 64 : 20 * NS) {
-      const int32_t pk = (&w->peak[0][0])[i], nrg = (&w->binpw[0][0])[i];
-      q = pk <= nrg ? (int16_t)0x7fff : (int16_t)xp_divide16_pos(nrg, pk);
-#if !defined(__HIP_DEVICE_COMPILE__)
-      (&w->ratio[0][0])[i] = q; /* sequential: entry i / 2 has been consumed */
-#endif
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-    cx.sync();
-    (&w->ratio[0][0])[i0 + cx.lane] = q;
-    cx.sync();
-#endif
-  }
+  /* ---- P4: transient detector */
+  xp_transient_frame<NS>(cx, ps, w);
   cx.sync();
   XP_T(5);
 
@@ -491,7 +566,7 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
      line and three links of 3, 4 and 5 slots) are loaded oldest-first into registers, shifted by renaming in the
      unrolled loop, and stored back at the end: no LDS traffic inside the recursion.
      Delays, rotation, output (ps_dec.c:602-648, :893-945, generic:1610): the 14-slot delay reads the lane's own
-     registers of slot l - 14, the 1-slot delay and the interpolated coefficients of the band's group stay in
+     column of dl 14 rows back, the 1-slot delay and the interpolated coefficients of the band's group stay in
      registers too.  Bands 0..2 are written by P6. */
   {
     const int idx0 = cx.uni(ps->idx), idx_long0 = cx.uni(ps->idx_long);
@@ -500,9 +575,20 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
     const int clear_hi = usb < 23 ? usb : 23;
     const int p14_0 = idx_long0 % 14;
     const int cs_right = common_shift < 0 ? (-common_shift > 31 ? 31 : -common_shift) : 0;
-    uint32_t events = seg_mask | (1u << 6) | (1u << 14); /* bit l: slot l sets lane state of the walk again (see there) */
+    uint32_t events = seg_mask | (1u << 6); /* bit l: slot l sets lane state of the walk again (see there) */
     if (clear_slot < NS) events |= 1u << clear_slot;
-    if (clear_slot + 14 < NS) events |= 1u << (clear_slot + 14);
+    /* The 14-slot ring of the state, laid out in the order the slots read it: rows 0..13 of dl (four lanes per row, three
+       bands each).  From there on the line is a plain look-back of 14 rows -- a slot whose band is not active hands what
+       it read on to row l + 14, as the ring keeps an entry nobody overwrites -- and no slot reads the state. */
+    static_assert(sizeof(ps->ld[0]) == 24 * sizeof(int16_t), "rows of the 14-slot ring: 24 int16, whole words");
+    static_assert(offsetof(PS, ld) % 4 == 0 && alignof(PS) % 4 == 0, "the 14-slot ring starts on a word of a word-aligned state");
+    XS_PAR(i, 0, 4 * 14) {
+      const int r = i >> 2, j0 = 3 * (i & 3);
+      const int pos = p14_0 + r >= 14 ? p14_0 + r - 14 : p14_0 + r;
+      XP_UNROLL
+      for (int k = 0; k < 3; k++) w->dl[r][j0 + k] = xp_load_pair(&ps->ld[pos][2 * (j0 + k)]);
+    }
+    cx.sync();
     XS_PAR(sb, 0, 64) {
       /* -- the lane's chain, if it has one */
       const int qmf_chain = sb >= 3 && sb < 23, hyb_chain = sb >= 32 && sb < 42, chain = qmf_chain || hyb_chain;
@@ -571,19 +657,14 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
          `events` (one uniform bit test per slot; worked out in every slot these were three dozen instructions of it):
            shl / shr     the shift counts in force                           (slot 6)
            active        the band lies below the slot's band limit           (clear_slot)
-           fed14         the slot 14 back put the band's sample into the 14-slot line  (slots 14 and clear_slot + 14)
            h.. / d..     the coefficient words                               (the borders)
          and the three links' lines of newly active bands are cleared at clear_slot. */
       int shl = shl_ov, shr = shr_ov;
-      bool active = sb < usb_prev, fed14 = false;
-      const int ldj = is_d14 ? 2 * (sb - 23) : 0, dlj = is_d14 ? sb - 23 : 12, apj = hyb_chain ? csb : 10;
-      int ld_at = 24 * p14_0; /* the slot's row of the 14-slot ring (as an offset into ps->ld): a counter that wraps */
-      const int16_t *const ld_lane = &ps->ld[0][ldj];
-      static_assert(sizeof(ps->ld[0]) == 24 * sizeof(int16_t), "rows of the 14-slot ring: 24 int16, whole words");
-      static_assert(offsetof(PS, ld) % 4 == 0 && alignof(PS) % 4 == 0, "the 14-slot ring starts on a word of a word-aligned state");
+      bool active = sb < usb_prev;
+      const int dlj = is_d14 ? sb - 23 : 12, apj = hyb_chain ? csb : 10;
       int16_t tr_nx = w->ratio[0][bin_sb];
       int32_t hre_nx = w->hyb_l[0][csb], him_nx = w->hyb_l[0][10 + csb];
-      uint32_t ld_nx = xp_load_pair(ld_lane + ld_at); /* (ldj is even and the rows are whole words) */
+      uint32_t o14_nx = w->dl[0][dlj]; /* (a lane without a 14-slot line reads the spare column and does not use it) */
       int32_t nre[4], nim[4];
       XP_UNROLL
       for (int j = 0; j < 4; j++) {
@@ -615,14 +696,13 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
             if (NS % 4 != 0 && l >= NS) break; /* (30 slots: the last pass has two) */
             const int16_t tr = tr_nx;
             const int32_t hre = hre_nx, him = him_nx;
-            const uint32_t ld_cur = ld_nx; /* what the state held at the slot's ring position */
+            const uint32_t o14 = o14_nx; /* what the 14-slot line holds at this slot */
             {
               const int ln = l + 1 < NS ? l + 1 : NS - 1;
-              ld_at = ld_at + 24 == 14 * 24 ? 0 : ld_at + 24;
               tr_nx = w->ratio[ln][bin_sb];
               hre_nx = w->hyb_l[ln][csb];
               him_nx = w->hyb_l[ln][10 + csb];
-              ld_nx = xp_load_pair(ld_lane + ld_at); /* (after the last slot: a row of the ring, not used) */
+              o14_nx = w->dl[l + 1][dlj]; /* written 13 slots ago (after the last slot: row NS, not used) */
             }
             if ((events4 >> j) & 1u) { /* (uniform) */
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -631,7 +711,6 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
               shl = l < 6 ? shl_ov : shl_lb;
               shr = l < 6 ? shr_ov : shr_lb;
               active = sb < (l >= clear_slot ? usb : usb_prev);
-              fed14 = l >= 14 && sb < (l - 14 >= clear_slot ? usb : usb_prev);
               if (l == clear_slot) { /* the three links' lines of the bands that just became active */
                 const int c = qmf_chain && sb >= clear_lo && sb < clear_hi;
                 XP_UNROLL
@@ -664,15 +743,13 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
             h12 += d12;
             h21 += d21;
             h22 += d22;
-            /* the decorrelated sample of the band: all-pass output, or the input of 14 slots / 1 slot ago.  The 14-slot
-               line holds what slot l - 14 put in if that slot ran with the band active, else what the state held.
-               (Both candidates are read by every lane -- a lane without a delay line reads entries it does not use -- and
-               the value is a select: no predicated region inside the walk.) */
-            const uint32_t o14_new = w->dl[l >= 14 ? l - 14 : 0][dlj];
-            const uint32_t o14 = fed14 ? o14_new : ld_cur;
-            const uint32_t o = is_ap ? o_chain : (is_d14 ? o14 : prev);
-            w->dl[l][dlj] = q; /* lanes without a 14-slot line write the spare column */
-            prev = active ? q : prev;
+            /* the decorrelated sample of the band: all-pass output, or the input of 14 slots / 1 slot ago (the line's
+               word came in a slot ahead, read by every lane: no predicated region and no wait inside the walk).  Either
+               line takes the band's sample if the band is active and keeps what it held if not: one select for both. */
+            const uint32_t held = is_d14 ? o14 : prev;
+            const uint32_t o = is_ap ? o_chain : held;
+            prev = active ? q : held;
+            w->dl[l + 14][dlj] = prev; /* lanes without a 14-slot line write the spare column */
             int32_t re = re0, im = im0;
             int32_t r_re = xp_m16x16_shl_pre(xp_lo16(o), 2 * tr), r_im = xp_m16x16_shl_pre(xp_hi16(o), 2 * tr);
             xp_rotate_w(&re, &r_re, h11, h12, h21, h22);
@@ -732,17 +809,16 @@ FX_HD int xp_ps_frame(const XsCx &cx, const XpTables *T, PS *ps, const xaac_ps_f
         ps->sd[2 * (sb - 35)] = xp_lo16(prev);
         ps->sd[2 * (sb - 35) + 1] = xp_hi16(prev);
       }
-      if (is_d14) { /* each position of the 14-slot ring ends up with the input of the last slot that wrote it */
-        for (int l = (clear_slot == 0 || usb == usb_prev) ? NS - 14 : 0; l < NS; l++) {
-          const int pos = (idx_long0 + l) % 14;
-          if (sb < (l >= clear_slot ? usb : usb_prev)) {
-            ps->ld[pos][ldj] = xp_lo16(w->dl[l][dlj]);
-            ps->ld[pos][ldj + 1] = xp_hi16(w->dl[l][dlj]);
-          }
-        }
-      }
     }
     cx.sync();
+    /* the 14-slot ring as the slot loop leaves it: what the frame's last 14 slots wrote or handed on (rows NS..NS + 13),
+       back at their ring positions */
+    XS_PAR(i, 0, 4 * 14) {
+      const int r = i >> 2, j0 = 3 * (i & 3), p0 = (idx_long0 + NS) % 14;
+      const int pos = p0 + r >= 14 ? p0 + r - 14 : p0 + r;
+      XP_UNROLL
+      for (int k = 0; k < 3; k++) xp_store_pair(&ps->ld[pos][2 * (j0 + k)], w->dl[NS + r][j0 + k]);
+    }
     XS_ONE {
       ps->idx = (int16_t)idx0; /* NS (even) slots later the 2-slot line is in the same phase */
       ps->idx_ser[0] = (int16_t)((is0 + NS) % 3);

@@ -33,6 +33,10 @@ __shared__ long long xp_prof_acc[16];
       xp_prof_last = t_;                          \
     }                                             \
   } while (0)
+#elif defined(XP_PHASE_MARKS)
+/* counting aid (tools/loop_instr_count.py --phases on the device-only assembly): a comment line at every phase border; never
+   part of the product build */
+#define XP_T(i) asm volatile("; XP_PHASE " #i)
 #else
 #define XP_T(i)
 #endif
@@ -257,6 +261,8 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     xp_wave_sync();
 #ifdef XS_PROFILE
     if (threadIdx.x == 0) xp_prof_last = clock64();
+#elif defined(XP_PHASE_MARKS)
+    XP_T(0);
 #endif
     const int ps_scale =
         xp_ps_frame<NSL>(cx, tabs, &s.ps, &s.pf, &s.w, gx, gr, lb_scale, ov_lb_scale, hb_scale, st_syn, lsb, usb, ps_scale_done);

@@ -8,6 +8,11 @@ The kernel is the first function whose (mangled) name contains the given string.
 back to it; per loop the script prints the number of VALU (v_*), SALU (s_*), LDS (ds_*) and global (global_* / flat_* /
 buffer_* / scratch_*) instructions between the two -- inner loops included, each instruction counted once, whatever the
 control flow in between -- and the N most frequent opcodes.  Loops with fewer than --min instructions are left out.
+
+  python tools/loop_instr_count.py ps_marks.s xaac_ps_kernelILi32 --phases [--min 20]
+
+With --phases the kernel is cut at the "; XP_PHASE n" comment lines a -DXP_PHASE_MARKS build of sbr_ps_kernel.hip leaves at its
+phase borders: per region the same four counts and the loops that lie inside it (profiles/ps_prep_instr.txt).
 """
 import argparse
 import collections
@@ -43,10 +48,16 @@ def main():
     ap.add_argument("kernel")
     ap.add_argument("--min", type=int, default=100, help="smallest loop to print (instructions)")
     ap.add_argument("--hist", type=int, default=24, help="opcodes in the histogram")
+    ap.add_argument("--phases", action="store_true", help="counts per region between the '; XP_PHASE n' markers of a "
+                    "-DXP_PHASE_MARKS build (sbr_ps_kernel.hip), with the loops that lie inside each region")
     a = ap.parse_args()
     body = kernel_body(open(a.asm).read().split("\n"), a.kernel)
     instrs, labels = [], {}  # (opcode, branch target or None); label -> index of the next instruction
+    marks = []               # (index of the next instruction, phase number) of every "; XP_PHASE n" marker
     for ln in body:
+        m = re.search(r"XP_PHASE (\d+)", ln)
+        if m:
+            marks.append((len(instrs), int(m.group(1))))
         s = ln.split(";")[0].strip()
         m = re.match(r"^(\.L[\w.$]+):", s)
         if m:
@@ -60,6 +71,18 @@ def main():
     total = collections.Counter(classify(op) for op, _ in instrs)
     print("%s: %d instructions  " % (a.kernel, len(instrs)) + "  ".join("%s %d" % (c, total[c]) for c, _ in CLASSES))
     loops = sorted({(labels[t], i) for i, (_, t) in enumerate(instrs) if t in labels and labels[t] <= i})
+    if a.phases:
+        # regions in the order of the code: from one marker to the next (the compiler may lay a phase's cold blocks out
+        # behind the kernel's last marker: they count where they stand)
+        edges = [(0, "start")] + [(i, "after mark %d" % n) for i, n in marks] + [(len(instrs), None)]
+        for (b, name), (e, _) in zip(edges, edges[1:]):
+            cnt = collections.Counter(classify(op) for op, _ in instrs[b:e])
+            print("\nregion %-14s %5d..%-5d (%4d)  " % (name, b, e - 1, e - b) + "  ".join("%s %d" % (c, cnt[c]) for c, _ in CLASSES))
+            for lb, le in loops:
+                if b <= lb and le < e and le - lb + 1 >= a.min:
+                    lc = collections.Counter(classify(op) for op, _ in instrs[lb:le + 1])
+                    print("    loop %5d..%-5d (%4d)  " % (lb, le, le - lb + 1) + "  ".join("%s %d" % (c, lc[c]) for c, _ in CLASSES))
+        return
     for b, e in loops:
         if e - b + 1 < a.min:
             continue
