@@ -64,15 +64,16 @@ static void ana_winadd(const int16_t *i1, const int16_t *i2, const int16_t *q1, 
   }
 }
 
-/* One frame: 32 slots of 32 new samples.  qmf: slot s at qmf + s*slot_stride; LP writes 32 reals,
-   HQ writes 32 reals at +0 and 32 imaginaries at +64.  usb = analysis bank's usb (HQ rotation count). */
-void xo_qmf_analysis(const int16_t *pcm, int stride, xo_qmf_ana_state *st, int low_pow, int usb, int32_t *qmf,
-                     int slot_stride) {
+/* One frame: n_slots (32, or 30 for a 960-line core) slots of 32 new samples.  qmf: slot s at qmf + s*slot_stride; LP
+   writes 32 reals, HQ writes 32 reals at +0 and 32 imaginaries at +64.  usb = analysis bank's usb (HQ rotation count).
+   The ring walk is literal, so wr and phase come out where the reference leaves them after n_slots steps. */
+void xo_qmf_analysis_ns(const int16_t *pcm, int stride, xo_qmf_ana_state *st, int low_pow, int usb, int32_t *qmf,
+                        int slot_stride, int n_slots) {
   const int16_t *c = xaac_qmf_qmf_c;
   int f1 = st->phase, f2 = st->phase + 64; /* offsets into qmf_c (int16 units) */
   int wr = st->wr;
   int fp1 = 0, fp2 = 32;
-  for (int s = 0; s < 32; s++) {
+  for (int s = 0; s < n_slots; s++) {
     int32_t z[64], t[128], sb[128];
     for (int k = 0; k < 32; k++) st->ring[wr + 31 - k] = pcm[stride * (32 * s + k)];
     ana_winadd(st->ring + fp1, st->ring + fp2, c + f1, c + f2, z);
@@ -97,6 +98,10 @@ void xo_qmf_analysis(const int16_t *pcm, int stride, xo_qmf_ana_state *st, int l
   }
   st->phase = (int16_t)f1;
   st->wr = (int16_t)wr;
+}
+void xo_qmf_analysis(const int16_t *pcm, int stride, xo_qmf_ana_state *st, int low_pow, int usb, int32_t *qmf,
+                     int slot_stride) {
+  xo_qmf_analysis_ns(pcm, stride, st, low_pow, usb, qmf, slot_stride, 32);
 }
 
 /* ---- synthesis bank --------------------------------------------------------------- */
@@ -262,18 +267,18 @@ void xo_qmf_synthesis_slot(const int32_t *x, xo_qmf_syn_state *st, int slot, int
   xo_qmf_synthesis_slot_n(x, st, slot, low_pow, out_scale, pcm, stride, 0);
 }
 
-/* One frame: 32 slots -> 2048 (ds: 1024) PCM16 at `stride`.  qmf rows as for analysis (64 reals, +64 imaginaries in
-   HQ); they are NOT modified here (the reference scales and transforms them in place).
+/* One frame: n_slots (32 or 30) slots -> 64 n_slots (ds: 32 n_slots) PCM16 at `stride`.  qmf rows as for analysis (64
+   reals, +64 imaginaries in HQ); they are NOT modified here (the reference scales and transforms them in place).
    sf = {lb_scale, ov_lb_scale, hb_scale, st_syn_scale}; no PS (active = 0). */
-void xo_qmf_synthesis_n(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,
-                        xo_qmf_syn_state *st, int low_pow, int16_t *pcm, int stride, int ds) {
+void xo_qmf_synthesis_ns(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,
+                         xo_qmf_syn_state *st, int low_pow, int16_t *pcm, int stride, int ds, int n_slots) {
   const int lb_scale = sf[0], ov_lb_scale = sf[1], hb_scale = sf[2], st_syn = sf[3];
   const int bias = low_pow ? 4 : 8; /* qmf_dec.c:906-933 */
   const int ov_lb_shift = (st_syn - ov_lb_scale) - bias, lb_shift = (st_syn - lb_scale) - bias,
             hb_shift = (st_syn - hb_scale) - bias;
   const int out_scale = low_pow ? -(st_syn - 1) : -(st_syn - 3);
   const int L = ds ? 32 : 64;
-  for (int s = 0; s < 32; s++) {
+  for (int s = 0; s < n_slots; s++) {
     int32_t x[128];
     const int32_t *row = qmf + (size_t)s * slot_stride;
     const int nparts = low_pow ? 1 : 2;
@@ -288,6 +293,10 @@ void xo_qmf_synthesis_n(const int32_t *qmf, int slot_stride, const int16_t *sf, 
       }
     xo_qmf_synthesis_slot_n(x, st, s, low_pow, out_scale, pcm + (size_t)stride * L * s, stride, ds);
   }
+}
+void xo_qmf_synthesis_n(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,
+                        xo_qmf_syn_state *st, int low_pow, int16_t *pcm, int stride, int ds) {
+  xo_qmf_synthesis_ns(qmf, slot_stride, sf, lsb, usb, split, st, low_pow, pcm, stride, ds, 32);
 }
 void xo_qmf_synthesis(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,
                       xo_qmf_syn_state *st, int low_pow, int16_t *pcm, int stride) {

@@ -30,11 +30,15 @@ void xo_synth_hq_slot(int32_t *s, int16_t *b, int shift);
 void xo_qmf_ana_init(xo_qmf_ana_state *st);
 void xo_qmf_analysis(const int16_t *pcm, int stride, xo_qmf_ana_state *st, int low_pow, int usb, int32_t *qmf,
                      int slot_stride);
+void xo_qmf_analysis_ns(const int16_t *pcm, int stride, xo_qmf_ana_state *st, int low_pow, int usb, int32_t *qmf,
+                        int slot_stride, int n_slots);
 void xo_qmf_syn_init(xo_qmf_syn_state *st);
 void xo_qmf_synthesis_slot_n(const int32_t *x, xo_qmf_syn_state *st, int slot, int low_pow, int out_scale, int16_t *pcm,
                              int stride, int ds);
 void xo_qmf_synthesis_n(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,
                         xo_qmf_syn_state *st, int low_pow, int16_t *pcm, int stride, int ds);
+void xo_qmf_synthesis_ns(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,
+                         xo_qmf_syn_state *st, int low_pow, int16_t *pcm, int stride, int ds, int n_slots);
 void xo_qmf_synthesis_slot(const int32_t *x, xo_qmf_syn_state *st, int slot, int low_pow, int out_scale, int16_t *pcm,
                            int stride);
 void xo_qmf_synthesis(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split,

@@ -9,7 +9,9 @@
  *
  * Parity status: PINNED on captured frames -- tests/test_sbr_oracle_vs_capture.py replays records
  * that oracle/ref_capture.c wrote while the compiled reference decoded real HE-AAC streams
- * (inputs + state before -> PCM + state after must match word for word).
+ * (inputs + state before -> PCM + state after must match word for word).  The 30-slot decoders of the 960-sample cores
+ * (xo_sbr_dec_lp960 / xo_sbr_dec_hq960, the same bodies at NS = 30): tests/test_sbr960_oracle_vs_reference.py, on every call
+ * the reference makes while it decodes 960-line HE-AAC and HE-AACv2 streams.
  */
 #include <stdint.h>
 #include <string.h>
@@ -47,26 +49,29 @@ static thread_local int g_ds = 0;
    instead of the slot loop below -- tests/test_ps_frame_cpu.py checks the two against each other on the host */
 static thread_local int g_ps_phased = 0;
 
-extern "C" int xo_sbr_dec_lp(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,
-                             const int16_t *pcm_in, int in_stride, int16_t *pcm_out, int out_stride) {
-  XO_MATRIX int32_t buf[40 * 64];
-  XsQmf x = {buf};
+/* NS: QMF slots of a frame, 32 (1024-sample cores) or 30 (the 960-sample cores of DAB+ / DRM: pcm_in 960 samples, pcm_out
+   1920).  Every slot count below follows it; at NS = 32 the body is what it was when 32 was written out. */
+template <int NS>
+static int sbr_dec_lp_t(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st, const int16_t *pcm_in,
+                        int in_stride, int16_t *pcm_out, int out_stride) {
+  XO_MATRIX int32_t buf[(NS + 8) * 64];
+  XsQmfT<0, 64, 0, NS> x = {buf};
   const XsCx cx = {0, 1}; /* sequential execution of the shared core */
   XsWork w;
   memset(buf, 0, sizeof(buf));
   /* sbr_dec.c:753: the six overlap slots */
   for (int l = 0; l < 6; l++)
     for (int k = 0; k < 64; k++) x(l, k) = st->overlap[64 * l + k];
-  if (xs_side_info_bad(cx, h, f, st)) return -1; /* refused before anything is touched, like sbr_dec.c:733-748 */
+  if (xs_side_info_bad(cx, h, f, st, 0, NS)) return -1; /* refused before anything is touched, like sbr_dec.c:733-748 */
   st->lb_scale = 0;
   if (f->apply_processing) xs_rescale_x_overlap(cx, h, f, st, x);
-  /* sbr_dec.c:1025: analysis bank into slots 6..37 */
+  /* sbr_dec.c:1025: analysis bank into slots 6..NS+5 */
   {
     xo_qmf_ana_state a;
     memcpy(a.ring, st->ana_ring, sizeof(a.ring));
     a.wr = st->ana_wr;
     a.phase = st->ana_phase;
-    xo_qmf_analysis(pcm_in, in_stride, &a, 1, st->codec_usb, &x(6, 0), 64);
+    xo_qmf_analysis_ns(pcm_in, in_stride, &a, 1, st->codec_usb, &x(6, 0), 64, NS);
     memcpy(st->ana_ring, a.ring, sizeof(a.ring));
     st->ana_wr = a.wr;
     st->ana_phase = a.phase;
@@ -75,23 +80,65 @@ extern "C" int xo_sbr_dec_lp(const xaac_sbr_header *h, const xaac_sbr_frame *f, 
   }
   int save_lb_scale = 0;
   if (xs_sbr_core(cx, h, f, f->int_env_sf_arr, f->int_noise_floor, st, x, &w, rand_hi_table(), &save_lb_scale)) return -1;
-  /* sbr_dec.c:1273: synthesis bank over slots 0..31 */
+  /* sbr_dec.c:1273: synthesis bank over slots 0..NS-1 */
   {
     xo_qmf_syn_state s;
     memcpy(s.ring, st->syn_ring, sizeof(s.ring));
     s.drc_offset = st->syn_drc_offset;
     s.phase = st->syn_phase;
     const int16_t sf[4] = {st->lb_scale, st->ov_lb_scale, st->hb_scale, st->st_syn_scale};
-    xo_qmf_synthesis_n(&x(0, 0), 64, sf, st->syn_lsb, st->syn_usb, 6, &s, 1, pcm_out, out_stride, g_ds);
+    xo_qmf_synthesis_ns(&x(0, 0), 64, sf, st->syn_lsb, st->syn_usb, 6, &s, 1, pcm_out, out_stride, g_ds, NS);
     memcpy(st->syn_ring, s.ring, sizeof(s.ring));
     st->syn_drc_offset = s.drc_offset;
     st->syn_phase = s.phase;
   }
   /* sbr_dec.c:1283-1308 */
   for (int l = 0; l < 6; l++)
-    for (int k = 0; k < 64; k++) st->overlap[64 * l + k] = x(32 + l, k);
+    for (int k = 0; k < 64; k++) st->overlap[64 * l + k] = x(NS + l, k);
   st->ov_lb_scale = (int16_t)save_lb_scale;
   return 0;
+}
+extern "C" int xo_sbr_dec_lp(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,
+                             const int16_t *pcm_in, int in_stride, int16_t *pcm_out, int out_stride) {
+  return sbr_dec_lp_t<32>(h, f, st, pcm_in, in_stride, pcm_out, out_stride);
+}
+/* the 960-sample cores: 15 time slots, 30 QMF slots; pcm_in 960 samples at in_stride, pcm_out 1920 */
+extern "C" int xo_sbr_dec_lp960(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,
+                                const int16_t *pcm_in, int in_stride, int16_t *pcm_out, int out_stride) {
+  return sbr_dec_lp_t<30>(h, f, st, pcm_in, in_stride, pcm_out, out_stride);
+}
+
+/* Mutation check of the 30-slot fuzz cases (tools/sbr960_mutation_check.py, profiles/sbr960_fuzz_coverage.txt): the oracle
+   alone, never the product, built with one comparison constant of the slot loop changed, to see which tests notice.
+   XO_MUT_HYB_DELAY: the hybrid delay shift starts at NS - 4;  XO_MUT_PS_CLAMP: PS borders are clamped into 0..NS + 2. */
+#ifdef XO_MUT_HYB_DELAY
+#define XO_HYB_DELAY_SLOTS 4
+#else
+#define XO_HYB_DELAY_SLOTS 6
+#endif
+#ifdef XO_MUT_PS_CLAMP
+#define XO_PS_CLAMP_EXTRA 2
+#else
+#define XO_PS_CLAMP_EXTRA 0
+#endif
+
+#if defined(XO_MUTATION_ID) && !defined(XS_NO_ENV_PAIRS)
+extern "C" const char *xo_mutation_id() { return XO_MUTATION_ID; } /* which mutant a test run has loaded; absent from the real oracle */
+#endif
+
+/* xp_frame_sanitize (sbr_ps.h) keeps PS borders in 0..32, what the parser can say for a 1024-sample core; for a 960-sample
+   core it ends a PS grid at max_num_columns = 30 (ps_bitdec.c:106, :243-249), and the 30-slot boundary holds borders to
+   0..NS the same way (sbr_ps_kernel.hip: xp_frame_sanitize_regs).  At NS = 32 nothing is left to do. */
+template <int NS>
+static int ps_borders_into_frame(xaac_ps_frame *pf) {
+  int bad = 0;
+  if (NS + XO_PS_CLAMP_EXTRA < 32)
+    for (int i = 0; i < XAAC_PS_MAX_ENV + 2; i++)
+      if (pf->border_position[i] > NS + XO_PS_CLAMP_EXTRA) {
+        pf->border_position[i] = (int16_t)(NS + XO_PS_CLAMP_EXTRA);
+        bad = 1;
+      }
+  return bad;
 }
 
 static inline int32_t adj_word(int32_t v, int shift) { /* env_calc.c:1099 on one word */
@@ -104,18 +151,19 @@ static inline int32_t adj_word(int32_t v, int shift) { /* env_calc.c:1099 on one
 /* One frame of ixheaacd_sbr_dec in HQ (complex) mode: low_pow_flag = 0, i.e. HE-AAC mono and, with
    pf / ps given and channel_mode = PS_STEREO, HE-AACv2 (sbr_dec.c:1246-1281: the left synthesis bank
    runs the parametric-stereo tool slot by slot, the right one consumes what it leaves in the matrix).
-   pcm_out: left at [n * out_stride], right at [n * out_stride + 1]. */
-extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,
-                             const xaac_ps_frame *pf, xaac_ps_state *ps, const int16_t *pcm_in, int in_stride,
-                             int16_t *pcm_out, int out_stride) {
-  XO_MATRIX int32_t buf[41 * 128];
-  XsQmfHq x = {buf};
+   pcm_out: left at [n * out_stride], right at [n * out_stride + 1].
+   NS as in sbr_dec_lp_t; the frame-at-once PS arrangement (g_ps_phased) exists at 32 slots only. */
+template <int NS>
+static int sbr_dec_hq_t(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st, const xaac_ps_frame *pf,
+                        xaac_ps_state *ps, const int16_t *pcm_in, int in_stride, int16_t *pcm_out, int out_stride) {
+  XO_MATRIX int32_t buf[(NS + 9) * 128];
+  XsQmfT<1, 64, 0, NS> x = {buf};
   const XsCx cx = {0, 1};
   XsWork w;
   memset(buf, 0, sizeof(buf));
   /* sbr_dec.c:753: twelve half-rows = six complex overlap slots */
   memcpy(&x(0, 0), st->overlap, sizeof(int32_t) * 12 * 64);
-  if (xs_side_info_bad(cx, h, f, st)) return -1; /* refused before anything is touched, like sbr_dec.c:733-748 */
+  if (xs_side_info_bad(cx, h, f, st, 0, NS)) return -1; /* refused before anything is touched, like sbr_dec.c:733-748 */
   st->lb_scale = 0;
   if (f->apply_processing) xs_rescale_x_overlap(cx, h, f, st, x);
   {
@@ -123,7 +171,7 @@ extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, 
     memcpy(a.ring, st->ana_ring, sizeof(a.ring));
     a.wr = st->ana_wr;
     a.phase = st->ana_phase;
-    xo_qmf_analysis(pcm_in, in_stride, &a, 0, st->codec_usb, &x(6, 0), 128);
+    xo_qmf_analysis_ns(pcm_in, in_stride, &a, 0, st->codec_usb, &x(6, 0), 128, NS);
     memcpy(st->ana_ring, a.ring, sizeof(a.ring));
     st->ana_wr = a.wr;
     st->ana_phase = a.phase;
@@ -138,7 +186,7 @@ extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, 
   s.phase = st->syn_phase;
   int ps_clamped = 0;
   xaac_ps_frame pf_clean;
-  if (f->apply_processing && h->channel_mode == 3 && pf && ps && g_ps_phased) {
+  if (NS == 32 && f->apply_processing && h->channel_mode == 3 && pf && ps && g_ps_phased) {
     pf_clean = *pf;
     ps_clamped = xp_frame_sanitize(cx, &pf_clean);
     static thread_local XpFrameWork wk;
@@ -163,20 +211,21 @@ extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, 
   } else if (f->apply_processing && h->channel_mode == 3 && pf && ps) {
     pf_clean = *pf;
     ps_clamped = xp_frame_sanitize(cx, &pf_clean);
+    ps_clamped |= ps_borders_into_frame<NS>(&pf_clean);
     pf = &pf_clean;
     const int ps_scale = xp_init_ps_scale(cx, ps, st->lb_scale, st->ov_lb_scale, st->hb_scale);
     st->ps_scale = (int16_t)ps_scale;
     const int lsb = st->syn_lsb, usb = st->syn_usb, st_syn = st->st_syn_scale;
     const int ov_lb_shift = ps_scale - st->ov_lb_scale, lb_shift = ps_scale - st->lb_scale,
               hb_shift = ps_scale - st->hb_scale, common_shift = (st_syn - ps_scale) - 8;
-    for (int l = 0; l < 32; l++)
+    for (int l = 0; l < NS; l++)
       for (int k = 0; k < 64; k++) {
         const int sh = k < lsb ? (l < 6 ? ov_lb_shift : lb_shift) : (k < usb ? hb_shift : 0);
         x(l, k) = adj_word(x(l, k), sh);
         x.im(l, k) = adj_word(x.im(l, k), sh);
       }
     int env = 0;
-    for (int l = 0; l < 32; l++) {
+    for (int l = 0; l < NS; l++) {
       int32_t right[128];
       XpHyb hy;
       memset(&hy, 0, sizeof(hy));
@@ -186,7 +235,7 @@ extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, 
         xp_init_rot_env(cx, &xaac_ps_tables, ps, pf, env, usb);
         env++;
       }
-      const int shiftdelay = l < 32 - 6 ? 0 : (int16_t)(st->lb_scale - ps_scale); /* thumb_ps_dec.c:77 */
+      const int shiftdelay = l < NS - XO_HYB_DELAY_SLOTS ? 0 : (int16_t)(st->lb_scale - ps_scale); /* thumb_ps_dec.c:77 */
       xp_hybrid_analysis(cx, &xaac_ps_tables, &x(l + 6, 0), &x.im(l + 6, 0), ps, &hy, shiftdelay);
       xp_decorrelation(cx, &xaac_ps_tables, ps, &hy, &x(l, 0), right, ratio, band_pw);
       xp_apply_rot(cx, &xaac_ps_tables, ps, &hy, &x(l, 0), right);
@@ -219,22 +268,33 @@ extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, 
     r.drc_offset = ps->syn_drc_offset_r;
     r.phase = ps->syn_phase_r;
     const int16_t sf_r[4] = {(int16_t)ps_scale, (int16_t)ps_scale, (int16_t)ps_scale, ps->st_syn_scale_r};
-    xo_qmf_synthesis_n(&x(0, 0), 128, sf_r, ps->syn_lsb_r, ps->syn_usb_r, 6, &r, 0, pcm_out + 1, out_stride, g_ds);
+    xo_qmf_synthesis_ns(&x(0, 0), 128, sf_r, ps->syn_lsb_r, ps->syn_usb_r, 6, &r, 0, pcm_out + 1, out_stride, g_ds, NS);
     memcpy(ps->syn_ring_r, r.ring, sizeof(r.ring));
     ps->syn_drc_offset_r = r.drc_offset;
     ps->syn_phase_r = r.phase;
   } else {
     const int16_t sf[4] = {st->lb_scale, st->ov_lb_scale, st->hb_scale, st->st_syn_scale};
-    xo_qmf_synthesis_n(&x(0, 0), 128, sf, st->syn_lsb, st->syn_usb, 6, &s, 0, pcm_out, out_stride, g_ds);
+    xo_qmf_synthesis_ns(&x(0, 0), 128, sf, st->syn_lsb, st->syn_usb, 6, &s, 0, pcm_out, out_stride, g_ds, NS);
   }
   memcpy(st->syn_ring, s.ring, sizeof(s.ring));
   st->syn_drc_offset = s.drc_offset;
   st->syn_phase = s.phase;
   /* sbr_dec.c:1283-1291 copies 6 * 64 words whatever the mode: in HQ that is the first three of the six
      complex overlap slots -- the other three keep what they held (kept as is: it is the reference's output) */
-  memcpy(st->overlap, &x(32, 0), sizeof(int32_t) * 6 * 64);
+  memcpy(st->overlap, &x(NS, 0), sizeof(int32_t) * 6 * 64);
   st->ov_lb_scale = (int16_t)save_lb_scale;
   return ps_clamped ? -1 : 0;
+}
+extern "C" int xo_sbr_dec_hq(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,
+                             const xaac_ps_frame *pf, xaac_ps_state *ps, const int16_t *pcm_in, int in_stride,
+                             int16_t *pcm_out, int out_stride) {
+  return sbr_dec_hq_t<32>(h, f, st, pf, ps, pcm_in, in_stride, pcm_out, out_stride);
+}
+/* the 960-sample cores: pcm_in 960 samples at in_stride, pcm_out 1920 samples (1920 L,R pairs with PS) */
+extern "C" int xo_sbr_dec_hq960(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,
+                                const xaac_ps_frame *pf, xaac_ps_state *ps, const int16_t *pcm_in, int in_stride,
+                                int16_t *pcm_out, int out_stride) {
+  return sbr_dec_hq_t<30>(h, f, st, pf, ps, pcm_in, in_stride, pcm_out, out_stride);
 }
 
 /* n independent channel-frames in a C loop (CPU baseline "port" when oracle/_ref did not travel) */

@@ -8,6 +8,8 @@
 #define XS_NO_ENV_PAIRS 1
 #define xo_sbr_dec_lp xo_sbr_dec_lp_seq
 #define xo_sbr_dec_hq xo_sbr_dec_hq_seq
+#define xo_sbr_dec_lp960 xo_sbr_dec_lp960_seq
+#define xo_sbr_dec_hq960 xo_sbr_dec_hq960_seq
 #define xo_sbr_dec_lp_batch xo_sbr_dec_lp_batch_seq
 #define xo_sbr_dec_hq_batch xo_sbr_dec_hq_batch_seq
 #define xo_sbr_dec_hq_phased xo_sbr_dec_hq_phased_seq

@@ -26,13 +26,14 @@ RAISE = [0, 9, 8, 12, 5]      # added to the carried State.st_syn_scale in front
 SEED, AMP = 5, 3000
 
 
-def _fuzz_ps(rng, pf):
-    """parser-like PS side info: tests/test_ps_frame_cpu.py's generator at wild = 0 (the same draws in the same order)"""
+def _fuzz_ps(rng, pf, nq=32):
+    """parser-like PS side info: tests/test_ps_frame_cpu.py's generator at wild = 0 (the same draws in the same order).
+    nq: the frame's QMF slots, 32 or -- the 960-sample cores -- 30"""
     pf.iid_quant = int(rng.integers(0, 2))
     nenv = int(rng.integers(1, 6))
-    borders = [0] + sorted(rng.choice(np.arange(1, 32), nenv - 1, replace=False).tolist()) + [32]
+    borders = [0] + sorted(rng.choice(np.arange(1, nq), nenv - 1, replace=False).tolist()) + [nq]
     for e in range(7):
-        pf.border_position[e] = int(borders[e]) if e < len(borders) else int(rng.integers(0, 33))
+        pf.border_position[e] = int(borders[e]) if e < len(borders) else int(rng.integers(0, nq + 1))
     lim = 15 if pf.iid_quant else 7
     for e in range(7):
         for b in range(34):
@@ -40,9 +41,9 @@ def _fuzz_ps(rng, pf):
             pf.icc_par_table[e][b] = int(rng.integers(0, 8))
 
 
-def _borders_off_zero(rng, pf):
+def _borders_off_zero(rng, pf, nq=32):
     nenv = int(rng.integers(1, 5))
-    borders = sorted(rng.choice(np.arange(1, 32), nenv, replace=False).tolist()) + [32]
+    borders = sorted(rng.choice(np.arange(1, nq), nenv, replace=False).tolist()) + [nq]
     for e in range(7):
         pf.border_position[e] = int(borders[e]) if e < len(borders) else 0
 

@@ -31,16 +31,17 @@ def set_grid(rng, h, f, n_env, borders):
         f.int_noise_floor[i] = int((int(rng.integers(0, 512)) << 6) | int(rng.integers(20, 50)))
 
 
-def legal_grid_frame(rng, h, f, kind):
+def legal_grid_frame(rng, h, f, kind, slots=16):
     """1..5 envelopes on a grid a parser can produce.  kind 0: a fixed frame's, 0 = b0 < .. < b_n = 16;  kind 1: a variable
-    frame's, first border 0..3, last border 13..19, strictly rising between"""
+    frame's, first border 0..3, last border 13..19, strictly rising between.  slots: the frame's time slots, 16 or -- the
+    960-sample cores -- 15, where the fixed grid ends at 15 and the variable one at 12..18 (the same draws in the same order)"""
     n_env = int(rng.integers(1, 6))
     if kind == 0:
-        inner = sorted(rng.choice(np.arange(1, 16), n_env - 1, replace=False).tolist())
-        borders = [0] + inner + [16]
+        inner = sorted(rng.choice(np.arange(1, slots), n_env - 1, replace=False).tolist())
+        borders = [0] + inner + [slots]
     else:
         assert kind == 1, kind
-        lo, hi = int(rng.integers(0, 4)), int(rng.integers(13, 20))
+        lo, hi = int(rng.integers(0, 4)), int(rng.integers(slots - 3, slots + 4))
         inner = sorted(rng.choice(np.arange(lo + 1, hi), n_env - 1, replace=False).tolist())
         borders = [lo] + inner + [hi]
     set_grid(rng, h, f, n_env, borders)
@@ -58,11 +59,12 @@ def grid_key(f):
     return int(f.num_env), int(f.border_vec[0]), int(f.border_vec[f.num_env]), transient_position(f)
 
 
-def grid_coverage_gaps(frames, headers=None, rets=None, min_late=20, early_end=True):
+def grid_coverage_gaps(frames, headers=None, rets=None, min_late=20, early_end=True, slots=16):
     """the coverage conditions of a grid fixture that the given frames (sbr_capture.Frame), their headers
     (sbr_capture.Header) and return codes do NOT meet: a list of plain words, empty when all are met.  Without headers the
     conditions on limiter gains, interpolation and smoothing are left out (the eSBR chains keep them elsewhere); early_end
-    False leaves out the last border below 16 (no bitstream says one, and the whole-frame eSBR boundary refuses it)."""
+    False leaves out the last border below 16 (no bitstream says one, and the whole-frame eSBR boundary refuses it).  slots: the
+    frame's time slots (16, or 15 for the 960-sample cores), which stand where 16 does in these words."""
     gaps = []
     need = lambda ok, what: None if ok else gaps.append(what)
     n_envs = {int(f.num_env) for f in frames}
@@ -75,8 +77,9 @@ def grid_coverage_gaps(frames, headers=None, rets=None, min_late=20, early_end=T
     first = [int(f.border_vec[0]) for f in frames]
     last = [int(f.border_vec[f.num_env]) for f in frames]
     need(any(b == 0 for b in first) and any(b > 0 for b in first), "first border 0 and > 0")
-    need(any(b == 16 for b in last) and (not early_end or any(b < 16 for b in last)), "last border = 16%s" % (" and < 16" if early_end else ""))
-    need(sum(b > 16 for b in last) >= min_late, "%d steps with the last border > 16 (has %d)" % (min_late, sum(b > 16 for b in last)))
+    need(any(b == slots for b in last) and (not early_end or any(b < slots for b in last)),
+         "last border = %d%s" % (slots, " and < %d" % slots if early_end else ""))
+    need(sum(b > slots for b in last) >= min_late, "%d steps with the last border > %d (has %d)" % (min_late, slots, sum(b > slots for b in last)))
     harm = [any(f.add_harmonics[i] for i in range(56)) for f in frames]
     need(any(harm) and not all(harm), "steps with and without add_harmonics")
     if headers is not None:

@@ -20,10 +20,11 @@ tests/ps_walk_cases.py; what they cover is asserted on the oracle's side (test_t
 Bin powers that saturate cannot be had through the whole chain (the tool's own scaling keeps a band's power below 2^29, see
 tests/test_ps_phases_gpu.py); they are in tests/test_ps_prep_cpu.py on the host build of the same function.
 
-30 slots (xaac_ps_kernel<30>): the host oracle has no 960-line chain, so these are five chains of three consecutive calls
-of the reference's own capture of a 960-line HE-AACv2 stream, states carried on the device, against the reference's PCM
-and PS states.  Their ring phases and band limits are the stream's; the case table above is forced at 32 slots only, and
-the host build of xp_ps_frame<30> runs the moving-limit chains in tests/test_ps_phases_cpu.py."""
+30 slots (xaac_ps_kernel<30>): here, five chains of three consecutive calls of the reference's own capture of a 960-line
+HE-AACv2 stream, states carried on the device, against the reference's PCM and PS states.  Their ring phases and band
+limits are the stream's.  The case table above forced at 30 slots, against the host oracle's 30-slot chain
+(xo_sbr_dec_hq960), is in tests/test_sbr960_fuzz_gpu.py; the host build of xp_ps_frame<30> runs the moving-limit chains in
+tests/test_ps_phases_cpu.py."""
 import numpy as np
 import pytest
 
