@@ -337,15 +337,21 @@ FX_HD int16_t xp_sin512(const XpTables *T, int32_t phi_by_4) {
 
 /* The reference's parser (ixheaacd_ps_bitdec.c:98-300) hands over IID indices within +-7 (+-15 fine), ICC indices
    0..7 and borders 0..32; the tool uses them as raw table indices.  A frame from anywhere else is brought into
-   those ranges before use (returns 1 if anything had to be changed: the caller reports status -1 for the stream). */
+   those ranges before use (returns 1 if anything had to be changed: the caller reports status -1 for the stream).
+   Only the rows of the frame's num_env envelopes and the 20 bins the groups read (group_to_bin) count for the report:
+   the parser leaves the other words as earlier frames wrote them (ixheaacd_ps_bitdec.c:79-282 writes num_env rows, and
+   maps 34 bands onto the first 20 in place), so a stream that goes from fine to coarse IID steps has fine indices there. */
+#define XP_BINS 20 /* NO_HI_RES_BINS */
 FX_HD int xp_frame_sanitize(const XsCx &cx, xaac_ps_frame *pf) {
-  int bad = 0;
+  const int rows = cx.uni(pf->num_env);
+  int bad = rows < 0 || rows > XAAC_PS_MAX_ENV + 2;
   const int steps = cx.uni(pf->iid_quant) ? 15 : 7;
   XS_PAR(i, 0, (XAAC_PS_MAX_ENV + 2) * XAAC_PS_BANDS_FINE) {
     int16_t *iid = &pf->iid_par_table[0][0] + i, *icc = &pf->icc_par_table[0][0] + i;
     const int a = *iid < -steps ? -steps : (*iid > steps ? steps : *iid);
     const int c = *icc < 0 ? 0 : (*icc > 7 ? 7 : *icc);
-    bad |= (a != *iid) | (c != *icc);
+    const int row = i / XAAC_PS_BANDS_FINE;
+    if (row < rows && i - row * XAAC_PS_BANDS_FINE < XP_BINS) bad |= (a != *iid) | (c != *icc);
     *iid = (int16_t)a;
     *icc = (int16_t)c;
   }

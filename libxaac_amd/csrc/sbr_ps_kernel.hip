@@ -162,14 +162,19 @@ __device__ __forceinline__ int xp_init_ps_scale_regs(const XsCx &cx, int32_t (&r
 
 /* xp_frame_sanitize (sbr_ps.h) the same way, on the side info's words in registers: borders into 0..NSL (32, or 30 for the
    960-sample cores, whose PS grids the parser ends at max_num_columns = 30: ps_bitdec.c:106, :243-249), IID indices into
-   +-7 (+-15 fine), ICC indices into 0..7; returns whether anything had to be changed */
+   +-7 (+-15 fine), ICC indices into 0..7; returns whether anything had to be changed in a border or in an index of the
+   frame's num_env rows and first XP_BINS bins */
 template <int NF, int NSL = 32>
 __device__ __forceinline__ int xp_frame_sanitize_regs(const XsCx &cx, int32_t (&rf)[NF]) {
   constexpr int E_BORDER = offsetof(xaac_ps_frame, border_position) / 2, E_IID = offsetof(xaac_ps_frame, iid_par_table) / 2;
   constexpr int E_ICC = offsetof(xaac_ps_frame, icc_par_table) / 2, E_END = sizeof(xaac_ps_frame) / 2;
   static_assert(offsetof(xaac_ps_frame, iid_quant) == 0 && E_BORDER + XAAC_PS_MAX_ENV + 2 < E_IID && E_IID % 2 == 0 && E_ICC % 2 == 0, "layout");
+  constexpr int E_NUM_ENV = offsetof(xaac_ps_frame, num_env) / 2;
+  static_assert(E_NUM_ENV / 2 < 64, "layout");
   const int steps = (int16_t)__builtin_amdgcn_readlane(rf[0], 0) ? 15 : 7;
-  int bad = 0;
+  const int32_t env_word = __builtin_amdgcn_readlane(rf[0], E_NUM_ENV / 2);
+  const int rows = (E_NUM_ENV & 1) ? env_word >> 16 : (int16_t)env_word;
+  int bad = rows < 0 || rows > XAAC_PS_MAX_ENV + 2;
 #pragma unroll
   for (int j = 0; j < NF; j++) {
     const int w = cx.lane + 64 * j;
@@ -181,7 +186,9 @@ __device__ __forceinline__ int xp_frame_sanitize_regs(const XsCx &cx, int32_t (&
       const bool border = e >= E_BORDER && e < E_BORDER + XAAC_PS_MAX_ENV + 2, iid = e >= E_IID && e < E_ICC, icc = e >= E_ICC && e < E_END;
       const int lo = border ? 0 : (iid ? -steps : (icc ? 0 : -32768)), hi = border ? NSL : (iid ? steps : (icc ? 7 : 32767));
       const int t = h[c] < lo ? lo : (h[c] > hi ? hi : h[c]);
-      bad |= t != h[c];
+      const int at = e - (iid ? E_IID : E_ICC), row = at / XAAC_PS_BANDS_FINE; /* an index: its envelope and bin */
+      const bool counts = border || ((iid || icc) && row < rows && at - row * XAAC_PS_BANDS_FINE < XP_BINS);
+      bad |= counts && t != h[c];
       h[c] = t;
     }
     rf[j] = (int32_t)xp_pack16((int16_t)h[0], (int16_t)h[1]);

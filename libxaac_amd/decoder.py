@@ -1123,6 +1123,9 @@ class _Pipeline:
             except ValueError:
                 bp.close()
                 raise
+        if bp.sbr and not bp.mc_sbr and 2 * bp.core_rate > 48000:   # the chains below write at twice the core's rate
+            bp.close()
+            raise ValueError("SBR with a down-sampled bank (an output rate above 48 kHz) is not supported")
         try:
             out_map = _pick_out_map(out_map, bp.n_ch, bool(bp.sbr), bp.channel_config)
             if drc is not None:

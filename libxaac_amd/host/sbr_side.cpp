@@ -1048,7 +1048,16 @@ int decode_envelope(XsHeader *h, XsFrameData *f, XsPrevData *p0, XsPrevData *p1,
   }
   if (enh) { /* usac_flag | enh_sbr: no concealment, no timing compensation, no range check, no dequantisation (:759-842) */
     delta_decode_env(h, f, p0);
-    for (int i = 0; i < f->num_env_sfac; i++) f->flt_env_sf[i] = (float)f->env_sf[i];
+    /* the float copy follows the decoded values -- but for the start value of an envelope coded along frequency, which the
+       reference steps over (env_dec.c:144-148): it stays what the payload reader wrote, and in a frame whose payload was not read
+       (a wrong CRC) what the frame before left there, its dequantised value */
+    float *flt = f->flt_env_sf;
+    const int16_t *sf = f->env_sf;
+    for (int i = 0; i < f->fi.num_env; i++) {
+      const int n = h->num_sf_bands[f->fi.freq_res[i]];
+      for (int b = f->dir_env[i] == DIR_FREQ ? 1 : 0; b < n; b++) flt[b] = (float)sf[b];
+      flt += n, sf += n;
+    }
     return 0;
   }
   if (h->err_flag) {

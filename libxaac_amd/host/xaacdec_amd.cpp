@@ -1470,6 +1470,10 @@ const char *fill_job(Job &J, const FirstFrame &f0, const Flags &F) {
     if (!F.esbr) die("-mcsbr:1 with -esbr:0 (the fixed-point SBR tools in a stream of more than two channels) is not supported");
     if (2 * f0.rate > 48000) die("-mcsbr:1 with a down-sampled bank (an output rate above 48 kHz) is not supported");
   }
+  /* above a 24 kHz core the reference goes over to the down-sampled synthesis bank and writes at the core's rate
+     (sbrdec_initfuncs.c:622); the chains of this decoder write at twice the core's rate, so such a stream is not taken */
+  if (sbr && !f0.channel_config && 2 * f0.rate > 48000)
+    return "SBR with a down-sampled bank (an output rate above 48 kHz) is not supported";
   const int downmix = F.downmix, dmix = F.dmix, tostereo = F.tostereo;
   if (downmix && dmix) return "-downmix:1 together with -dmix:1 is not supported";
   if (downmix && n_ch <= 2) return "-downmix:1 on a stream of one or two channels is not supported (there is nothing to mix down)";

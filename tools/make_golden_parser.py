@@ -30,10 +30,15 @@ def crc(b):
     return zlib.crc32(bytes(b)) & 0xffffffff
 
 
+def stream_path(name):
+    """a name of tests/golden/streams, or the path of any other stream"""
+    return name if os.path.isabs(name) else os.path.join(ROOT, "tests", "golden", "streams", name + ".aac")
+
+
 def capture(name, tmp):
     """-> (spec records [k, 1030] int32, sbr records or [])"""
     import sbr_capture as sc
-    src = os.path.join(ROOT, "tests", "golden", "streams", name + ".aac")
+    src = stream_path(name)
     spec, cap = os.path.join(tmp, "spec.bin"), os.path.join(tmp, "cap.bin")
     for f in (spec, cap):
         if os.path.exists(f):
@@ -51,7 +56,7 @@ def capture_esbr(name, tmp):
     import ctypes
     import sbr_capture as sc
     from esbr_structs import EsbrSide
-    src = os.path.join(ROOT, "tests", "golden", "streams", name + ".aac")
+    src = stream_path(name)
     cap = os.path.join(tmp, "esbr.bin")
     if os.path.exists(cap):
         os.remove(cap)

@@ -280,7 +280,8 @@ class Gen:
                         n = m.bit_length() - 5
                         b.put((1 << n) - 1, n), b.put(0, 1), b.put(m - (1 << (n + 4)), n + 4)
 
-    def frame(self, channels):
+    def frame(self, channels, behind=None):
+        """behind(b): called right behind the channel element (tools/make_synth_sbr_streams.py hangs the SBR fill element there)"""
         b = Bits()
         if self.r(0, 5) == 0:                       # a data stream element in front
             cnt, flag = self.r(0, 6), self.r(0, 1)
@@ -292,9 +293,13 @@ class Gen:
         if channels == 1:
             b.put(0, 3), b.put(0, 4)
             self.channel_with_gain(b, None, False, False, 0)
+            if behind:
+                behind(b)
             b.put(7, 3)
             return adts(b.bytes(), self.sr_index, 1)
         self.pair(b, 0)
+        if behind:
+            behind(b)
         if self.r(0, 3) == 0:                       # a fill element (not SBR)
             cnt = self.r(1, 10)
             b.put(6, 3), b.put(cnt, 4), b.put(0, 4), b.put(0, 4)
