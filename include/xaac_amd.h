@@ -286,7 +286,11 @@ typedef struct xaac_sbr_eld_batch {
   const xaac_sbr_frame *frame;     /* [n_ch] */
   xaac_sbr_eld_state *state;       /* [n_ch] in/out */
   int16_t *pcm_out;
-  int32_t *status;                 /* optional [n_ch]: 0, -1 where the reference returns an error or the side info is outside the tables */
+  int32_t *status;                 /* optional [n_ch]: 0, -1 where the reference returns an error, the side info is outside the tables
+                                      or the header's num_time_slots is not n_slots.  A refused channel does not disturb its
+                                      neighbours.  Its own state.ana has moved on by the frame's 32 n_slots samples (the analysis
+                                      bank runs in front of the refusal); every other member of its state, its pcm_out and its
+                                      qmf_handed_on rows are left as they were.  The oracle's xo_sbr_dec_eld_slots does the same. */
   void *workspace;                 /* device scratch, >= xaac_sbr_eld_workspace_bytes(n_ch) */
   uint64_t workspace_bytes;
   int32_t *qmf_handed_on;          /* optional [n_ch][n_slots][128]: the region-rescaled matrix the reference hands on through

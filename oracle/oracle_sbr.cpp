@@ -316,26 +316,40 @@ void xo_qmf_eld_region_scale(const int32_t *qmf, int slot_stride, const int16_t 
 void xo_qmf_synthesis_eld(const int32_t *qmf, int slot_stride, const int16_t *sf, int lsb, int usb, int split, int16_t *ring,
                           int16_t *state4, int n_slots, int16_t *pcm, int stride);
 }
-extern "C" int xo_sbr_dec_eld(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_eld_state *st, const int16_t *pcm_in,
-                              int in_stride, int16_t *pcm_out, int out_stride, int32_t *handed_on) {
+/* One channel of an xaac_sbr_eld_process_batch call of n_slots slots.  A channel whose side info is refused (status -1:
+   xs_side_info_bad, a header of another frame length than the batch's, or an error of the core) has had its n_slots slots
+   through the analysis bank -- in the chain the bank runs in front of the refusal -- so st->ana has moved on by the frame;
+   every other state member, pcm_out and handed_on are left as they were. */
+static int sbr_dec_eld(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_eld_state *st, const int16_t *pcm_in, int in_stride,
+                       int16_t *pcm_out, int out_stride, int32_t *handed_on, int n) {
   XO_MATRIX int32_t buf[(2 + 16) * 128];
   XsQmfT<1, 64, 1> x = {buf};
   const XsCx cx = {0, 1};
   XsWork w;
   memset(buf, 0, sizeof(buf));
-  if (xs_side_info_bad(cx, h, f, st, 1)) return -1;
-  const int n = h->num_time_slots;
-  st->lb_scale = 0;                                                   /* sbr_dec.c:767 */
-  if (f->apply_processing) xs_rescale_x_overlap(cx, h, f, st, x);     /* its two state words and scale bookkeeping: no rows */
+  const xaac_sbr_eld_state before = *st;
+  const int refused = xs_side_info_bad(cx, h, f, st, 1) || h->num_time_slots != n;
+  if (!refused) {
+    st->lb_scale = 0;                                                   /* sbr_dec.c:767 */
+    if (f->apply_processing) xs_rescale_x_overlap(cx, h, f, st, x);     /* its two state words and scale bookkeeping: no rows */
+  }
   {
     int16_t s4[4] = {st->ana.wr, st->ana.f1, st->ana.f2, st->ana.fp};
-    xo_qmf_analysis_eld(pcm_in, in_stride, st->ana.ring, s4, n, st->codec_usb, &x(0, 0), 128);
+    int usb = st->codec_usb; /* refused: what the chain's bank takes from the frame (the rows are not used: any limit inside the row) */
+    if (refused) usb = f->apply_processing ? f->max_qmf_subband_aac : st->codec_usb, usb = usb < 0 ? 0 : (usb > 32 ? 32 : usb);
+    xo_qmf_analysis_eld(pcm_in, in_stride, st->ana.ring, s4, n, usb, &x(0, 0), 128);
     st->ana.wr = s4[0], st->ana.f1 = s4[1], st->ana.f2 = s4[2], st->ana.fp = s4[3];
+    if (refused) return -1;
     st->st_lb_scale = 0;
     st->lb_scale = -9; /* generic:630-636 */
   }
   int save_lb_scale = 0;
-  if (xs_sbr_core(cx, h, f, f->int_env_sf_arr, f->int_noise_floor, st, x, &w, rand_hi_table(), &save_lb_scale)) return -1;
+  if (xs_sbr_core(cx, h, f, f->int_env_sf_arr, f->int_noise_floor, st, x, &w, rand_hi_table(), &save_lb_scale)) {
+    const xaac_qmf_ana_eld_state ana = st->ana;
+    *st = before;
+    st->ana = ana;
+    return -1;
+  }
   {
     const int16_t sf[4] = {st->lb_scale, st->ov_lb_scale, st->hb_scale, st->st_syn_scale};
     int16_t s4[4] = {st->syn.drc_offset, st->syn.phase, st->syn.fp, st->syn.sixty4};
@@ -345,6 +359,18 @@ extern "C" int xo_sbr_dec_eld(const xaac_sbr_header *h, const xaac_sbr_frame *f,
   }
   st->ov_lb_scale = (int16_t)save_lb_scale; /* sbr_dec.c:1304 */
   return 0;
+}
+/* a channel on its own: the frame length is its header's (another than 16 or 15 slots: refused with nothing touched) */
+extern "C" int xo_sbr_dec_eld(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_eld_state *st, const int16_t *pcm_in,
+                              int in_stride, int16_t *pcm_out, int out_stride, int32_t *handed_on) {
+  if (h->num_time_slots != 16 && h->num_time_slots != 15) return -1;
+  return sbr_dec_eld(h, f, st, pcm_in, in_stride, pcm_out, out_stride, handed_on, h->num_time_slots);
+}
+/* ... and as one of a batch of n_slots (16 or 15) slots a frame */
+extern "C" int xo_sbr_dec_eld_slots(const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_eld_state *st, const int16_t *pcm_in,
+                                    int in_stride, int16_t *pcm_out, int out_stride, int32_t *handed_on, int n_slots) {
+  if (n_slots != 16 && n_slots != 15) return -1;
+  return sbr_dec_eld(h, f, st, pcm_in, in_stride, pcm_out, out_stride, handed_on, n_slots);
 }
 
 extern "C" int xo_sbr_dec_hq_batch(int n, const xaac_sbr_header *h, const xaac_sbr_frame *f, xaac_sbr_state *st,

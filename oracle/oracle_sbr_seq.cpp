@@ -16,4 +16,5 @@
 #define xo_sbr_dec_lp_ds xo_sbr_dec_lp_ds_seq
 #define xo_sbr_dec_hq_ds xo_sbr_dec_hq_ds_seq
 #define xo_sbr_dec_eld xo_sbr_dec_eld_seq
+#define xo_sbr_dec_eld_slots xo_sbr_dec_eld_slots_seq
 #include "oracle_sbr.cpp"

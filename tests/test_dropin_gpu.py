@@ -110,11 +110,16 @@ def test_down_sampled_esbr_through_the_gpu(aac, tmp_path):
     assert len(a) > 50000 and a == b, (len(a), len(b))
 
 
+STREAMS_LD = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "streams_ld", "*.aac")))
+
+
 def test_streams_present():
     assert len(STREAMS) >= 3
-
-
-STREAMS_LD = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "streams_ld", "*.aac")))
+    # the other frame lengths, and the AAC-ELD streams with other SBR band layouts (tools/make_golden_streams.py:
+    # ELD_LAYOUT_STREAMS), each with its frame-size list
+    names = {os.path.basename(s)[:-4] for s in STREAMS_LD if os.path.exists(s[:-4] + ".txt")}
+    assert names >= {"lc960", "ld512", "ld480", "eld512", "eld480", "eld512_48k1_24", "eld512_48k2_96", "eld512_32k1_48",
+                     "eld512_44k2_24", "eld480_48k1_48", "eld480_32k1_24", "eld480_32k2_96", "eld480_48k2_48"}, names
 
 
 @pytest.mark.parametrize("aac", STREAMS_LD, ids=[os.path.basename(s) for s in STREAMS_LD])

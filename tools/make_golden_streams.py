@@ -16,6 +16,39 @@ ROOT = os.path.dirname(HERE)
 REF = os.path.join(ROOT, "oracle", "_ref")
 
 
+# AAC-ELD streams with other SBR band layouts than eld512 / eld480 (one layout: 48 kHz stereo at 64 kbit/s), for
+# tools/make_golden_sbr_eld_grid_chains.py and the drop-in test: name -> (sampling rate, channels, bit rate, frame length).
+# Together: 8 layouts, sub_band_start 11..29, sub_band_end 40..64, num_sf_bands (6, 12) / (7, 14) / (8, 16), 3..5 noise bands,
+# 2..4 patches, mono and stereo (with coupled frames at the low stereo rates); per frame length 6 channels.  Mono streams are
+# 2.3 s of signal, stereo ones 1.2 s: a frame is 1024 output samples, and the drop-in test wants more than 100 calls a stream.
+ELD_LAYOUT_STREAMS = {
+    "eld512_48k1_24": (48000, 1, 24000, 512), "eld512_48k2_96": (48000, 2, 96000, 512),
+    "eld512_32k1_48": (32000, 1, 48000, 512), "eld512_44k2_24": (44100, 2, 24000, 512),
+    "eld480_48k1_48": (48000, 1, 48000, 480), "eld480_32k1_24": (32000, 1, 24000, 480),
+    "eld480_32k2_96": (32000, 2, 96000, 480), "eld480_48k2_48": (48000, 2, 48000, 480),
+}
+
+
+def eld_layout_streams():
+    """the same mix as the other golden streams, played at the stream's rate (the encoder only sees numbers)"""
+    import wave
+    out_ld = os.path.join(ROOT, "tests", "golden", "streams_ld")
+    os.makedirs(out_ld, exist_ok=True)
+    sig = m.signals(seconds=2.3)
+    x = 0.5 * sig["clicks"] + 0.35 * sig["harmonic"] + 0.3 * sig["noise_sweep"]
+    for name, (fs, ch, br, flen) in ELD_LAYOUT_STREAMS.items():
+        n = x.shape[0] if ch == 1 else int(1.2 * m.FS)
+        wav = "/tmp/xaac_golden_%s.wav" % name
+        with wave.open(wav, "wb") as w:
+            w.setnchannels(ch), w.setsampwidth(2), w.setframerate(fs)
+            w.writeframes(np.clip(np.round(x[:n, :ch] * 32767.0), -32768, 32767).astype(np.int16).tobytes())
+        aac = os.path.join(out_ld, name + ".aac")
+        subprocess.run([os.path.join(REF, "xaacenc"), "-ifile:" + wav, "-ofile:" + aac, "-aot:39", "-br:%d" % br,
+                        "-framesize:%d" % flen], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+        os.remove(wav)
+        print(aac, os.path.getsize(aac))
+
+
 def main():
     out = os.path.join(ROOT, "tests", "golden", "streams")
     os.makedirs(out, exist_ok=True)
@@ -68,6 +101,7 @@ def main():
         subprocess.run([os.path.join(REF, "xaacenc"), "-ifile:" + wav, "-ofile:" + aac] + args, stdout=subprocess.DEVNULL,
                        stderr=subprocess.DEVNULL, check=True)
         print(aac, os.path.getsize(aac))
+    eld_layout_streams()
 
     # USAC (xHE-AAC, -aot:42) streams for the eSBR seam behind the reference's own USAC front end (tests/golden/streams_usac;
     # raw access units + frame-size list like the LD streams): stereo 2:1 eSBR without / with harmonic SBR (u21, u21harm),
@@ -114,4 +148,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ld"]:      # the low-delay layout streams alone
+        eld_layout_streams()
+    else:
+        main()
