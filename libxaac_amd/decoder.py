@@ -16,69 +16,19 @@ import time
 
 import numpy as np
 
-from . import (ESBR_PS_STATE_BYTES, ESBR_SIDE_BYTES, ESBR_STATE_BYTES, HANDOVER_PS_START, HBE_STATE_BYTES, LIMITER_STATE_BYTES,
-               PCM_LC, PCM_SBR, PS_FRAME_BYTES, PS_STATE_BYTES, SBR_FRAME_BYTES, SBR_HEADER_BYTES, SBR_STATE_BYTES, LimiterState,
-               XaacContext, out_map_channels, peak_limiter_init)
+from . import (CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES, DRC_SIDE_WORDS, ESBR_PS_STATE_BYTES, ESBR_SIDE_BYTES, ESBR_STATE_BYTES,
+               HANDOVER_PS_START, HBE_STATE_BYTES, LIMITER_STATE_BYTES, PCM_LC, PCM_SBR, PS_FRAME_BYTES, PS_STATE_BYTES,
+               SBR_FRAME_BYTES, SBR_HEADER_BYTES, SBR_STATE_BYTES, LimiterState, XaacContext, out_map_channels, peak_limiter_init)
 from . import out_map as make_out_map
+from .abi import (AdtsHeader, CoreFrame, CoreToolsChannel, CoreToolsSide, CoreToolsState, DrcConfig, SbrSide,  # noqa: F401
+                  TnsFilterSide)
+from .abi import ParseBatch as _ParseBatch   # the descriptor BatchParser fills
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _host = None
 torch = None    # imported by the first decode_streams call: the parser half of this module works without it
 
 TOOL_MS, TOOL_INTENSITY, TOOL_PNS, TOOL_TNS, TOOL_PULSE, TOOL_SHORT, TOOL_ESCAPE = 1, 2, 4, 8, 16, 32, 64
-
-
-class AdtsHeader(ctypes.Structure):
-    # struct xaac_adts_header
-    _fields_ = [(n, ctypes.c_int32) for n in ("id", "layer", "protection_absent", "profile", "sr_index", "sampling_rate",
-                                              "channel_config", "frame_bytes", "raw_blocks", "header_bytes")]
-
-
-class CoreFrame(ctypes.Structure):
-    # struct xaac_core_frame
-    _fields_ = [("n_ch", ctypes.c_int32), ("element_id", ctypes.c_int32), ("common_window", ctypes.c_int32),
-                ("sbr_ext_type", ctypes.c_int32), ("sbr_bytes", ctypes.c_int32), ("tools", ctypes.c_int32),
-                ("ics", (ctypes.c_int16 * 4) * 2), ("spec", (ctypes.c_int32 * 1024) * 2), ("sbr", ctypes.c_uint8 * 272)]
-
-
-class SbrSide(ctypes.Structure):
-    # struct xaac_sbr_side
-    _fields_ = [(n, ctypes.c_int32) for n in ("apply", "reset", "reset_channels", "upsampling", "stereo", "ps", "ps_start",
-                                              "frame_ok")] + \
-               [("header", ctypes.c_uint8 * SBR_HEADER_BYTES), ("frame", (ctypes.c_uint8 * SBR_FRAME_BYTES) * 2),
-                ("ps_frame", ctypes.c_uint8 * PS_FRAME_BYTES)]
-
-
-class TnsFilterSide(ctypes.Structure):
-    # struct xaac_tns_filter_side (include/xaac_tools.h)
-    _fields_ = [("start_band", ctypes.c_uint8), ("stop_band", ctypes.c_uint8), ("order", ctypes.c_int8),
-                ("direction", ctypes.c_int8), ("resolution", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3),
-                ("coef", ctypes.c_int8 * 12)]
-
-
-class CoreToolsChannel(ctypes.Structure):
-    # struct xaac_core_tools_channel
-    _fields_ = [("window_sequence", ctypes.c_uint8), ("max_sfb", ctypes.c_uint8), ("num_groups", ctypes.c_uint8),
-                ("pns_active", ctypes.c_uint8), ("tns_present", ctypes.c_uint8), ("wide", ctypes.c_uint8),
-                ("reserved", ctypes.c_uint8 * 2),
-                ("group_len", ctypes.c_uint8 * 8), ("n_filt", ctypes.c_uint8 * 8), ("cb", ctypes.c_uint8 * 128),
-                ("sf", ctypes.c_int16 * 128), ("pns_used", ctypes.c_uint8 * 128), ("tns", TnsFilterSide * 8)]
-
-
-class CoreToolsSide(ctypes.Structure):
-    # struct xaac_core_tools_side: what the M/S, intensity, PNS and TNS tools read of one channel element
-    _fields_ = [("element_id", ctypes.c_uint8), ("n_ch", ctypes.c_uint8), ("common_window", ctypes.c_uint8),
-                ("sr_index", ctypes.c_uint8), ("ms_used", ctypes.c_uint8 * 128), ("pns_correlated", ctypes.c_uint8 * 128),
-                ("ch", CoreToolsChannel * 2)]
-
-
-class CoreToolsState(ctypes.Structure):
-    # struct xaac_core_tools_state: the noise generator of one stream (a new one's: xaac_parse_core_tools_state)
-    _fields_ = [("pns_seed", ctypes.c_int32), ("pns_corr_seed", ctypes.c_int32 * 128)]
-
-
-from . import DRC_SIDE_WORDS, DrcConfig  # noqa: E402  (include/xaac_drc.h)
-from . import CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES  # noqa: E402  (tests/test_aac_tools_cpu.py pins them to the header)
 
 
 def host_library_path():
@@ -135,6 +85,11 @@ def load_host_library():
         lib.xaac_drc_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         for fn in ("xaac_parse_drc_config", "xaac_parse_drc_side", "xaac_drc_apply_host"):
             getattr(lib, fn).restype = ctypes.c_int32
+        lib.xaac_parse_batch_run.argtypes = [ctypes.c_void_p]       # (the original layout's symbols: no pos / frames / lines)
+        lib.xaac_parse_batch_start.argtypes = [ctypes.c_void_p]
+        lib.xaac_parse_batch_run_sized.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        lib.xaac_parse_batch_start_sized.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+        lib.xaac_parse_batch_wait.argtypes = [ctypes.c_void_p]
         _host = lib
     return _host
 
@@ -370,15 +325,6 @@ def parse_stream_mc(data, stage=2):
     return out
 
 
-class _ParseBatch(ctypes.Structure):
-    # struct xaac_parse_batch
-    _fields_ = [(n, ctypes.c_int32) for n in ("n_streams", "n_ch", "with_sbr", "ps_enable", "stage", "threads")] + \
-               [(n, ctypes.c_void_p) for n in ("parser", "data", "bytes", "spec", "ics", "header", "frame", "ps_frame", "flags",
-                                               "tools", "consumed", "status", "esbr_side", "reset_pitch", "pos")] + \
-               [("frames", ctypes.c_int32), ("lines", ctypes.c_void_p), ("tools_side", ctypes.c_void_p),
-                ("channel_config", ctypes.c_int32), ("mc_sbr", ctypes.c_int32), ("drc_side", ctypes.c_void_p)]
-
-
 F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(8)
 
 
@@ -476,11 +422,6 @@ class BatchParser:
 
     def __init__(self, streams, threads=0, stage=2, esbr=False, mc_sbr=False, drc=None):
         self.lib = load_host_library()
-        self.lib.xaac_parse_batch_run.argtypes = [ctypes.c_void_p]       # (the original layout's symbols: no pos / frames / lines)
-        self.lib.xaac_parse_batch_start.argtypes = [ctypes.c_void_p]
-        self.lib.xaac_parse_batch_run_sized.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-        self.lib.xaac_parse_batch_start_sized.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-        self.lib.xaac_parse_batch_wait.argtypes = [ctypes.c_void_p]
         self.esbr = bool(esbr)
         self.n = n = len(streams)
         self.length = np.array([len(d) for d in streams], np.uint64)

@@ -4,10 +4,13 @@ infrastructure only -- nothing in the product imports this."""
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)   # for runs with only tests/ and tools/ on it
+from libxaac_amd.abi import QmfAnaState, QmfSynState  # noqa: E402
 P32 = ctypes.POINTER(ctypes.c_int32)
 P16 = ctypes.POINTER(ctypes.c_int16)
 P8 = ctypes.POINTER(ctypes.c_int8)
@@ -67,14 +70,6 @@ class Oracle:
                                         ch_fac, int(pcm_mode), pcm[au * ch_fac:].ctypes.data_as(ctypes.c_void_p))
         return {"out32": np.ascontiguousarray(out32), "pcm16": np.ascontiguousarray(pcm), "qshift_adj": qadj,
                 "overlap": ovl, "state": np.stack([pseq, pshape], 1).astype(np.uint8)}
-
-
-class QmfAnaState(ctypes.Structure):
-    _fields_ = [("ring", ctypes.c_int16 * 320), ("wr", ctypes.c_int16), ("phase", ctypes.c_int16)]
-
-
-class QmfSynState(ctypes.Structure):
-    _fields_ = [("ring", ctypes.c_int16 * 1280), ("drc_offset", ctypes.c_int16), ("phase", ctypes.c_int16)]
 
 
 def qmf_analysis_batch(orc, pcm, state, low_pow, usb, slot_stride, ch_fac=1):

@@ -1,19 +1,13 @@
-"""ctypes mirrors of include/xaac_pvc.h and the seeded frame chains the PVC tests and tools/make_golden_pvc.py share."""
+"""The mirrors of include/xaac_pvc.h (libxaac_amd.abi) and the seeded frame chains the PVC tests and tools/make_golden_pvc.py share."""
 import ctypes
+import os
+import sys
 import zlib
 
 import numpy as np
 
-
-class PvcFrame(ctypes.Structure):
-    _fields_ = [("pvc_mode", ctypes.c_uint8), ("ns_mode", ctypes.c_uint8), ("pvc_rate", ctypes.c_uint8), ("low_power", ctypes.c_uint8),
-                ("first_bnd_idx", ctypes.c_int16), ("first_pvc_timeslot", ctypes.c_int16), ("pvc_id", ctypes.c_uint16 * 16)]
-
-
-class PvcState(ctypes.Structure):
-    _fields_ = [("esg", (ctypes.c_float * 3) * 15), ("prev_first_bnd_idx", ctypes.c_int16), ("prev_pvc_id", ctypes.c_uint16),
-                ("prev_pvc_flg", ctypes.c_uint8), ("prev_pvc_rate", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2)]
-
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # for runs with only tests/ and tools/ on it
+from libxaac_amd.abi import PvcFrame, PvcState  # noqa: E402
 
 PF = ctypes.POINTER(ctypes.c_float)
 

@@ -1,61 +1,15 @@
 """Reader for the records written by oracle/ref_capture.c (formats of include/xaac_sbr.h).
 Test infrastructure."""
 import ctypes
+import os
+import sys
 
 import numpy as np
 
-I16, I32, U8, I8 = ctypes.c_int16, ctypes.c_int32, ctypes.c_uint8, ctypes.c_int8
-
-
-class Patch(ctypes.Structure):
-    _fields_ = [(n, I16) for n in ("src_start_band", "src_end_band", "guard_start_band", "dst_start_band",
-                                   "dst_end_band", "num_bands_in_patch")]
-
-
-class Header(ctypes.Structure):
-    _fields_ = [("num_time_slots", I16), ("time_step", I16), ("channel_mode", I16), ("limiter_gains", I16),
-                ("interpol_freq", I16), ("smoothing_mode", I16), ("num_sf_bands", I16 * 2), ("num_nf_bands", I16),
-                ("sub_band_start", I16), ("sub_band_end", I16), ("num_lf_bands", I16), ("num_if_bands", I16),
-                ("freq_band_tbl_lim", I16 * 13), ("freq_band_tbl_lo", I16 * 29), ("freq_band_tbl_hi", I16 * 57),
-                ("freq_band_tbl_noise", I16 * 6), ("num_columns", I16), ("num_patches", I16), ("start_patch", I16),
-                ("stop_patch", I16), ("bw_borders", I16 * 10), ("patch", Patch * 6)]
-
-
-class Frame(ctypes.Structure):
-    _fields_ = [("num_env", I16), ("transient_env", I16), ("num_noise_env", I16), ("frame_class", I16),
-                ("border_vec", I16 * 9), ("freq_res", I16 * 8), ("noise_border_vec", I16 * 3), ("amp_res", I16),
-                ("apply_processing", I16), ("coupling_mode", I32), ("max_qmf_subband_aac", I32),
-                ("sbr_invf_mode", I32 * 10), ("add_harmonics", U8 * 56), ("int_env_sf_arr", I16 * 448),
-                ("int_noise_floor", I16 * 10)]
-
-
-class State(ctypes.Structure):
-    _fields_ = [("ana_ring", I16 * 320), ("ana_wr", I16), ("ana_phase", I16), ("syn_ring", I16 * 1280),
-                ("syn_drc_offset", I16), ("syn_phase", I16), ("codec_usb", I16), ("syn_lsb", I16), ("syn_usb", I16), ("pad2_", I16),
-                ("overlap", I32 * 768), ("lpc_real", (I32 * 32) * 2),
-                ("lpc_imag", (I32 * 32) * 2), ("bw_array_prev", I32 * 6), ("lb_scale", I16), ("st_lb_scale", I16),
-                ("ov_lb_scale", I16), ("hb_scale", I16), ("ov_hb_scale", I16), ("st_syn_scale", I16),
-                ("ps_scale", I16), ("pad0_", I16), ("prev_invf_mode", I32 * 10), ("prev_max_qmf_subband_aac", I32),
-                ("prev_coupling_mode", I32), ("prev_end_position", I16), ("prev_amp_res", I16),
-                ("filt_buf_me", I16 * 112), ("filt_buf_noise_m", I16 * 56), ("filt_buf_noise_e", I32),
-                ("start_up", I32), ("ph_index", I16), ("tansient_env_prev", I16), ("harm_index", I16), ("pad1_", I16),
-                ("harm_flags_prev", I8 * 56)]
-
-
-class PsFrame(ctypes.Structure):
-    _fields_ = [("iid_quant", I16), ("freq_res_ipd", I16), ("border_position", I16 * 7), ("num_env", I16),
-                ("iid_par_table", (I16 * 34) * 7), ("icc_par_table", (I16 * 34) * 7)]
-
-
-class PsState(ctypes.Structure):
-    _fields_ = [("ser", ((I16 * 64) * 3) * 5), ("ap", (I16 * 64) * 2), ("ld", (I16 * 24) * 14), ("sd", I16 * 64),
-                ("sub", (I16 * 32) * 2), ("sub_ser", ((I16 * 32) * 3) * 5), ("idx_ser", I16 * 3), ("sample_ser", I16 * 3),
-                ("idx", I16), ("idx_long", I16), ("peak_decay_diff", I32 * 20), ("energy_prev", I32 * 20),
-                ("peak_decay_diff_prev", I32 * 20), ("hyb_buf", ((I32 * 12) * 2) * 3), ("h11_h12_vec", I16 * 48),
-                ("h21_h22_vec", I16 * 48), ("H11_H12", I16 * 48), ("H21_H22", I16 * 48), ("delta_h11_h12", I16 * 48),
-                ("delta_h21_h22", I16 * 48), ("delay_buffer_scale", I16), ("usb", I16), ("syn_ring_r", I16 * 1280),
-                ("syn_drc_offset_r", I16), ("syn_phase_r", I16), ("syn_lsb_r", I16), ("syn_usb_r", I16),
-                ("st_syn_scale_r", I16), ("lb_scale_r", I16), ("ov_lb_scale_r", I16), ("hb_scale_r", I16)]
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # for runs with only tests/ and tools/ on it
+from libxaac_amd.abi import I8, I16, I32, U8, PsFrame, PsState  # noqa: E402,F401
+from libxaac_amd.abi import QmfAnaEldState as EldAna, QmfSynEldState as EldSyn, SbrEldState as EldState  # noqa: E402,F401
+from libxaac_amd.abi import SbrFrame as Frame, SbrHeader as Header, SbrPatch as Patch, SbrState as State  # noqa: E402,F401
 
 
 def diff_state(a, b):
@@ -100,20 +54,6 @@ def read_records(path, limit=None):
             if limit and len(recs) >= limit:
                 break
     return recs
-
-
-# ---- AAC-ELD channels (low-delay SBR): include/xaac_amd.h xaac_sbr_eld_state
-class EldAna(ctypes.Structure):
-    _fields_ = [("ring", I16 * 320), ("wr", I16), ("f1", I16), ("f2", I16), ("fp", I16)]
-
-
-class EldSyn(ctypes.Structure):
-    _fields_ = [("ring", I16 * 1280), ("drc_offset", I16), ("phase", I16), ("fp", I16), ("sixty4", I16)]
-
-
-class EldState(ctypes.Structure):
-    _fields_ = [("ana", EldAna), ("syn", EldSyn), ("codec_usb", I16), ("syn_lsb", I16), ("syn_usb", I16), ("pad2_", I16)] + \
-               State._fields_[State._fields_.index(("lpc_real", (I32 * 32) * 2)):]
 
 
 def eld_state_from(st):

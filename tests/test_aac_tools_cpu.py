@@ -101,7 +101,7 @@ def test_struct_layouts_match_the_header(tmp_path):
                    'sizeof(xaac_core_tools_state), sizeof(xaac_aac_tools_batch), offsetof(xaac_aac_tools_batch, status)); return 0; }\n')
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    B = libxaac_amd._AacToolsBatch
+    B = libxaac_amd.abi.AacToolsBatch
     assert got == [ctypes.sizeof(decoder.CoreToolsSide), decoder.CoreToolsSide.ch.offset, ctypes.sizeof(decoder.CoreToolsChannel),
                    decoder.CoreToolsChannel.sf.offset, decoder.CoreToolsChannel.tns.offset, ctypes.sizeof(decoder.CoreToolsState),
                    ctypes.sizeof(B), B.status.offset]

@@ -1,15 +1,17 @@
 """The C-ABI library loads on a GPU-less box and exports every symbol that
 include/xaac_amd.h declares; argument errors follow the reference's error-code
 convention.  No compute calls here."""
+import ast
 import ctypes
 import os
-import subprocess
-import sys
 import re
+import subprocess
 
+import numpy as np
 import pytest
 
 import libxaac_amd
+from libxaac_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,21 +63,6 @@ def test_host_library_exports_every_declared_symbol():
         assert hasattr(lib, n), n
 
 
-def test_host_struct_layouts_match_header(tmp_path):
-    """the ctypes mirrors of libxaac_amd/decoder.py against what a C compiler makes of include/xaac_parse.h"""
-    from libxaac_amd import decoder
-    src, exe = tmp_path / "h.c", tmp_path / "h"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_parse.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu\\n", '
-                   'sizeof(xaac_adts_header), sizeof(xaac_core_frame), offsetof(xaac_core_frame, spec), offsetof(xaac_core_frame, sbr), '
-                   'sizeof(xaac_sbr_side), offsetof(xaac_sbr_side, frame), offsetof(xaac_sbr_side, ps_frame)); return 0; }\n')
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    want = [ctypes.sizeof(decoder.AdtsHeader), ctypes.sizeof(decoder.CoreFrame), decoder.CoreFrame.spec.offset,
-            decoder.CoreFrame.sbr.offset, ctypes.sizeof(decoder.SbrSide), decoder.SbrSide.frame.offset,
-            decoder.SbrSide.ps_frame.offset]
-    assert got == want
-
-
 def test_version_string():
     assert b"gfx950" in libxaac_amd.load_library().xaac_version()
 
@@ -122,102 +109,6 @@ def test_null_and_bad_arguments_are_fatal_codes():
         assert fn(None, None) & 0x80000000, n
 
 
-def _eld_state():
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import sbr_capture
-    assert ctypes.sizeof(sbr_capture.EldState) == libxaac_amd.SBR_ELD_STATE_BYTES
-    return sbr_capture.EldState
-
-
-def test_struct_layout_matches_header(tmp_path):
-    """every batch descriptor's ctypes mirror against what a C compiler makes of include/xaac_amd.h"""
-    import subprocess
-    pairs = [("xaac_imdct_batch", libxaac_amd._ImdctBatch, "status"), ("xaac_qmf_ana_batch", libxaac_amd._QmfAnaBatch, "qmf"),
-             ("xaac_qmf_syn_batch", libxaac_amd._QmfSynBatch, "pcm"), ("xaac_sbr_lp_batch", libxaac_amd._SbrLpBatch, "workspace_bytes"),
-             ("xaac_sbr_hq_batch", libxaac_amd._SbrHqBatch, "max_band_hint"),
-             ("xaac_sbr_eld_batch", libxaac_amd._SbrEldBatch, "qmf_handed_on"), ("xaac_sbr_eld_state", _eld_state(), "harm_flags_prev")]
-    body = "".join('printf("%%zu %%zu\\n", sizeof(%s), offsetof(%s, %s));' % (c, c, last) for c, _, last in pairs)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_amd.h"\nint main(void) { %s return 0; }\n' % body)
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for _, cls, last in pairs:
-        want += [ctypes.sizeof(cls), getattr(cls, last).offset]
-    assert got == want
-    assert ctypes.sizeof(libxaac_amd._ImdctBatch) == 80   # 2 x int32 + 7 pointers + int32 (+ pad) + status pointer on LP64
-
-
-def test_round2_struct_layouts_match_headers(tmp_path):
-    """the round-2 descriptors and states (eSBR / Path A, float PS, USAC IMDCT, hand-over): ctypes mirrors of the binding
-    and of tests/esbr_structs.py against what a C compiler makes of include/xaac_amd.h and include/xaac_esbr.h"""
-    import subprocess
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import esbr_structs as es
-    pairs = [("xaac_esbr_ana_batch", libxaac_amd._EsbrAnaBatch, "qmf_im"), ("xaac_esbr_ana_nb_batch", libxaac_amd._EsbrAnaNbBatch, "qmf_im"),
-             ("xaac_esbr_syn_batch", libxaac_amd._EsbrSynBatch, "out"),
-             ("xaac_usac_imdct_batch", libxaac_amd._UsacImdctBatch, "fac_work"), ("xaac_sbr_handover_batch", libxaac_amd._HandoverBatch, "ps_state"),
-             ("xaac_sbr_apply_side_batch", libxaac_amd._ApplySideBatch, "ps_state"),
-             ("xaac_esbr_sbr_batch", libxaac_amd._EsbrSbrBatch, "down_sample"), ("xaac_esbr_side", es.EsbrSide, "pitch_in_bins"),
-             ("xaac_esbr_pvc_side", es.EsbrPvcSide, "pvc"), ("xaac_esbr_pvc_state", es.EsbrPvcState, "esbr_start_up_pvc"),
-             ("xaac_esbr_state", es.EsbrState, "ph_im"), ("xaac_esbr_ps_state", es.EsbrPsState, "syn_r"),
-             ("xaac_esbr_ana_state", es.EsbrAna, "win_off"), ("xaac_esbr_syn_state", es.EsbrSyn, "filt_off")]
-    body = "".join('printf("%%zu %%zu\\n", sizeof(%s), offsetof(%s, %s));' % (c, c, last) for c, _, last in pairs)
-    src = tmp_path / "layout2.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_esbr.h"\nint main(void) { %s return 0; }\n' % body)
-    exe = tmp_path / "layout2"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for _, cls, last in pairs:
-        want += [ctypes.sizeof(cls), getattr(cls, last).offset]
-    assert got == want
-    assert ctypes.sizeof(es.EsbrAna) == 4 * libxaac_amd.ESBR_ANA_STATE_WORDS and ctypes.sizeof(es.EsbrSyn) == 4 * libxaac_amd.ESBR_SYN_STATE_WORDS
-    assert (ctypes.sizeof(es.EsbrSide), ctypes.sizeof(es.EsbrState), ctypes.sizeof(es.EsbrPsState)) == \
-        (libxaac_amd.ESBR_SIDE_BYTES, libxaac_amd.ESBR_STATE_BYTES, libxaac_amd.ESBR_PS_STATE_BYTES)
-    assert (ctypes.sizeof(es.EsbrPvcSide), ctypes.sizeof(es.EsbrPvcState)) == (libxaac_amd.ESBR_PVC_SIDE_BYTES, libxaac_amd.ESBR_PVC_STATE_BYTES)
-
-
-def test_hbe_struct_layouts_match_header(tmp_path):
-    """the harmonic transposer's state and batch descriptors against include/xaac_hbe.h"""
-    import subprocess
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import hbe_structs as hs
-    pairs = [("xaac_hbe_state", hs.HbeState, "max_stretch"), ("xaac_hbe_synth_batch", libxaac_amd._HbeSynthBatch, "status"),
-             ("xaac_hbe_anal_batch", libxaac_amd._HbeAnalBatch, "status"),
-             ("xaac_hbe_apply_batch_desc", libxaac_amd._HbeApplyBatch, "status"),
-             ("xaac_hbe_dft_anal_batch", libxaac_amd._HbeDftAnalBatch, "status"), ("xaac_hbe_dft_anal_state", hs.HbeDftState, "a_start"),
-             ("xaac_hbe_dft_state", hs.HbeDftFullState, "last_status"), ("xaac_hbe_dft_cfg", hs.HbeDftCfg, "fd_win"),
-             ("xaac_hbe_dft_apply_batch", libxaac_amd._HbeDftApplyBatch, "rows32")]
-    body = "".join('printf("%%zu %%zu\\n", sizeof(%s), offsetof(%s, %s));' % (c, c, last) for c, _, last in pairs)
-    src = tmp_path / "layout3.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_hbe.h"\nint main(void) { %s return 0; }\n' % body)
-    exe = tmp_path / "layout3"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for _, cls, last in pairs:
-        want += [ctypes.sizeof(cls), getattr(cls, last).offset]
-    assert got == want
-    assert ctypes.sizeof(hs.HbeState) == libxaac_amd.HBE_STATE_BYTES
-    assert (ctypes.sizeof(hs.HbeDftFullState), ctypes.sizeof(hs.HbeDftCfg)) == (libxaac_amd.HBE_DFT_FULL_STATE_BYTES, libxaac_amd.HBE_DFT_CFG_BYTES)
-    src2 = tmp_path / "layout4.c"
-    src2.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_amd.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", '
-                    'sizeof(xaac_qmf_ana_eld_state), offsetof(xaac_qmf_ana_eld_state, fp), sizeof(xaac_qmf_ana_eld_batch), '
-                    'offsetof(xaac_qmf_ana_eld_batch, status), sizeof(xaac_qmf_syn_eld_state), offsetof(xaac_qmf_syn_eld_state, sixty4), '
-                    'sizeof(xaac_qmf_syn_eld_batch), offsetof(xaac_qmf_syn_eld_batch, status)); '
-                    'printf("%zu %zu %zu\\n", sizeof(xaac_imdct_ld_batch), offsetof(xaac_imdct_ld_batch, spec), offsetof(xaac_imdct_ld_batch, status)); return 0; }\n')
-    exe2 = tmp_path / "layout4"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src2), "-o", str(exe2)])
-    B = libxaac_amd._QmfAnaEldBatch
-    S = libxaac_amd._QmfSynEldBatch
-    assert [int(v) for v in subprocess.check_output([str(exe2)]).split()] == [
-        2 * libxaac_amd.QMF_ANA_ELD_STATE_WORDS, 646, ctypes.sizeof(B), B.status.offset,
-        2 * libxaac_amd.QMF_SYN_ELD_STATE_WORDS, 2566, ctypes.sizeof(S), S.status.offset,
-        ctypes.sizeof(libxaac_amd._ImdctLdBatch), libxaac_amd._ImdctLdBatch.spec.offset, libxaac_amd._ImdctLdBatch.status.offset]
-
-
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():
@@ -227,56 +118,124 @@ def test_no_cpu_fallback_without_device():
     assert e.value.code == 0xFFFF8002
 
 
-def test_limiter_structs_match_header(tmp_path):
-    """the ctypes mirrors of the limiter boundary against what a C compiler makes of include/xaac_amd.h"""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_amd.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(xaac_limiter_state), '
-                   'offsetof(xaac_limiter_state, pre_smoothed_gain), offsetof(xaac_limiter_state, max_buf), '
-                   'offsetof(xaac_limiter_state, delayed_input), sizeof(xaac_limiter_batch), '
-                   'offsetof(xaac_limiter_batch, stride), offsetof(xaac_limiter_batch, pcm16), '
-                   'offsetof(xaac_limiter_batch, workspace_bytes)); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    S, B = libxaac_amd.LimiterState, libxaac_amd._LimiterBatch
-    assert got == [ctypes.sizeof(S), S.pre_smoothed_gain.offset, S.max_buf.offset, S.delayed_input.offset,
-                   ctypes.sizeof(B), B.stride.offset, B.pcm16.offset, B.workspace_bytes.offset]
-    assert libxaac_amd.LIMITER_STATE_BYTES == got[0]
+def _header_text(h):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
 
 
-def test_pvc_struct_layouts_match_header(tmp_path):
-    """the PVC decoder's frame, state and batch descriptor against include/xaac_pvc.h"""
-    import subprocess
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import pvc_structs as ps
-    pairs = [("xaac_pvc_frame", ps.PvcFrame, "pvc_id"), ("xaac_pvc_state", ps.PvcState, "prev_pvc_rate"), ("xaac_pvc_batch", libxaac_amd._PvcBatch, "status")]
-    body = "".join('printf("%%zu %%zu\\n", sizeof(%s), offsetof(%s, %s));' % (c, c, last) for c, _, last in pairs)
-    src = tmp_path / "layout_pvc.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_pvc.h"\nint main(void) { %s return 0; }\n' % body)
-    exe = tmp_path / "layout_pvc"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    want = []
-    for _, cls, last in pairs:
-        want += [ctypes.sizeof(cls), getattr(cls, last).offset]
-    assert got == want
-    assert (ctypes.sizeof(ps.PvcFrame), ctypes.sizeof(ps.PvcState)) == (libxaac_amd.PVC_FRAME_BYTES, libxaac_amd.PVC_STATE_BYTES)
+def _header_groups():
+    """(device headers, host headers)"""
+    hs = sorted(os.listdir(os.path.join(ROOT, "include")))
+    return [h for h in hs if h not in HOST_HEADERS], [h for h in hs if h in HOST_HEADERS]
 
 
-def test_parse_batch_descriptor_matches_header(tmp_path):
-    """libxaac_amd/decoder.py's mirror of struct xaac_parse_batch (members appended in round 4: pos, frames, lines) against what
-    a C compiler makes of include/xaac_parse.h"""
-    import subprocess
+def test_registry_is_the_headers_struct_list():
+    declared = set()
+    for h in sum(_header_groups(), []):
+        declared |= set(re.findall(r"^\}\s*(xaac_\w+);", _header_text(h), flags=re.M))
+    assert len(declared) >= 73 and declared == set(abi.STRUCTS)
+    assert all(cls.c_name == name for name, cls in abi.STRUCTS.items())
+
+
+def test_struct_layouts_match_headers(tmp_path):
+    """every mirror of libxaac_amd.abi against what a C compiler makes of the headers: sizeof, and the offset and size of every
+    field the mirror names; one generated program per header group"""
+    got, want = {}, {}
+    for k, group in enumerate(_header_groups()):
+        names = [n for h in group for n in re.findall(r"^\}\s*(xaac_\w+);", _header_text(h), flags=re.M)]
+        body = []
+        for n in names:
+            body.append('printf("%s %%zu\\n", sizeof(%s));' % (n, n))
+            want[n] = ctypes.sizeof(abi.STRUCTS[n])
+            for f, _ in abi.STRUCTS[n]._fields_:
+                body.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (n, f, n, f, n, f))
+                want[n + "." + f] = (getattr(abi.STRUCTS[n], f).offset, getattr(abi.STRUCTS[n], f).size)
+        src, exe = tmp_path / ("layout%d.c" % k), tmp_path / ("layout%d" % k)
+        src.write_text("#include <stdio.h>\n#include <stddef.h>\n%s\nint main(void) {\n%s\nreturn 0; }\n"
+                       % ("\n".join('#include "%s"' % h for h in group), "\n".join(body)))
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+        for line in subprocess.check_output([str(exe)], text=True).splitlines():
+            key, *v = line.split()
+            got[key] = int(v[0]) if len(v) == 1 else (int(v[0]), int(v[1]))
+    assert len(want) > 700 and set(got) == set(want)
+    assert {k: (got[k], want[k]) for k in want if got[k] != want[k]} == {}
+
+
+# The sizes of the states and side-info rows are ABI facts like the workspace sizes (device tensors and golden files are cut to
+# them): the values libxaac_amd stated as literals before it read them off the mirrors.
+SIZES = {
+    "CORE_TOOLS_SIDE_BYTES": 1652, "CORE_TOOLS_STATE_BYTES": 516, "DRC_SIDE_WORDS": 33, "ESBR_ANA_STATE_WORDS": 322,
+    "ESBR_PS_STATE_BYTES": 23048, "ESBR_PVC_SIDE_BYTES": 84, "ESBR_PVC_STATE_BYTES": 12656, "ESBR_SIDE_BYTES": 2036,
+    "ESBR_STATE_BYTES": 38012, "ESBR_SYN_STATE_WORDS": 1282, "HBE_DFT_CFG_BYTES": 23648, "HBE_DFT_FULL_STATE_BYTES": 24120,
+    "HBE_DFT_STATE_BYTES": 2568, "HBE_STATE_BYTES": 61232, "LIMITER_STATE_BYTES": 17328, "PS_FRAME_BYTES": 972,
+    "PS_STATE_BYTES": 7764, "PVC_FRAME_BYTES": 40, "PVC_STATE_BYTES": 188, "QMF_ANA_ELD_STATE_WORDS": 324,
+    "QMF_ANA_STATE_WORDS": 322, "QMF_SYN_ELD_STATE_WORDS": 1284, "QMF_SYN_STATE_WORDS": 1282, "SBR_ELD_STATE_BYTES": 4236,
+    "SBR_FRAME_BYTES": 1072, "SBR_HEADER_BYTES": 336, "SBR_STATE_BYTES": 7300, "USAC_FAC_IN_WORDS": 402,
+}
+
+
+def test_sizes_are_the_published_ones():
     from libxaac_amd import decoder
-    src = tmp_path / "pb.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xaac_parse.h"\nint main(void) { printf("%zu %zu %zu %zu %zu\\n", '
-                   'sizeof(xaac_parse_batch), offsetof(xaac_parse_batch, parser), offsetof(xaac_parse_batch, pos), '
-                   'offsetof(xaac_parse_batch, frames), offsetof(xaac_parse_batch, lines)); return 0; }\n')
-    exe = tmp_path / "pb"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    P = decoder._ParseBatch
-    assert got == [ctypes.sizeof(P), P.parser.offset, P.pos.offset, P.frames.offset, P.lines.offset]
+    assert {k: v for k, v in vars(libxaac_amd).items() if k.endswith(("_BYTES", "_WORDS"))} == SIZES
+    for k, v in vars(decoder).items():
+        if k.endswith(("_BYTES", "_WORDS")):
+            assert v == SIZES[k], k
+
+
+def test_literal_layout_facts():
+    assert ctypes.sizeof(abi.ImdctBatch) == 80   # 2 x int32 + 7 pointers + int32 (+ pad) + status pointer on LP64
+    assert (abi.QmfAnaEldState.fp.offset, abi.QmfSynEldState.sixty4.offset) == (646, 2566)
+    S, B = abi.LimiterState, abi.LimiterBatch
+    assert (S.pre_smoothed_gain.offset, S.max_buf.offset, S.delayed_input.offset) == (32, 48, 1968)
+    assert (ctypes.sizeof(B), B.stride.offset, B.pcm16.offset, B.workspace_bytes.offset) == (80, 16, 48, 72)
+
+
+def test_entry_point_table_is_the_headers_prototype_list():
+    """every XAAC_API int32_t f(xaac_ctx *, const T *) of the device headers is in the table under T's mirror, every other device
+    function is listed with its own prototype, and bind() leaves POINTER(mirror) / c_int32 on the function objects"""
+    text = "".join(_header_text(h) for h in _header_groups()[0])
+    protos = dict(re.findall(r"XAAC_API int32_t (xaac_\w+)\(xaac_ctx \*\w+, const (\w+) \*\w+\);", text))
+    assert len(protos) >= 39 and set(protos) == set(abi.BATCH_ENTRY_POINTS)
+    assert sorted(set(abi.BATCH_ENTRY_POINTS) | set(abi.OTHER_ENTRY_POINTS)) == _declared_functions()
+    lib = abi.bind(ctypes.CDLL(libxaac_amd.library_path()))   # a handle of its own: other tests rebind the shared one's functions
+    for name, t in protos.items():
+        assert abi.BATCH_ENTRY_POINTS[name] is abi.STRUCTS[t], name
+        fn = getattr(lib, name)
+        assert fn.restype is ctypes.c_int32 and list(fn.argtypes) == [ctypes.c_void_p, ctypes.POINTER(abi.STRUCTS[t])], name
+    with pytest.raises(ctypes.ArgumentError):
+        lib.xaac_drc_apply_batch(None, ctypes.byref(abi.ImdctBatch()))   # a wrong descriptor type is caught
+
+
+def test_names_bench_and_entry_module_use_resolve():
+    """bench.py cannot run without a GPU: every libxaac_amd.NAME (and NAME of a submodule imported from it) that it and
+    __graft_entry__.py mention exists"""
+    import importlib
+    seen = set()
+    for f in ("bench.py", "__graft_entry__.py"):
+        tree = ast.parse(open(os.path.join(ROOT, f)).read())
+        alias = {"libxaac_amd": "libxaac_amd"}
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] == "libxaac_amd":
+                for a in node.names:
+                    seen.add((node.module, a.name))
+                    alias[a.asname or a.name] = node.module + "." + a.name
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Attribute) and ast.unparse(node.value) in alias:
+                seen.add((alias[ast.unparse(node.value)], node.attr))
+    assert len(seen) >= 12 and ("libxaac_amd", "PVC_FRAME_BYTES") in seen and ("libxaac_amd.decoder", "decode_streams") in seen
+    for mod, name in sorted(seen):
+        try:
+            m = importlib.import_module(mod)
+        except ImportError:
+            continue   # `from libxaac_amd import X` made an alias of a plain name, checked under ("libxaac_amd", X)
+        assert hasattr(m, name) or importlib.util.find_spec(mod + "." + name), (mod, name)
+
+
+def test_call_helper_raises_the_named_error():
+    """the check every XaacContext method shares, without a GPU: a context object whose handle is null"""
+    ctx = libxaac_amd.XaacContext.__new__(libxaac_amd.XaacContext)
+    ctx._lib, ctx._h = libxaac_amd.load_library(), None
+    n = 2
+    with pytest.raises(libxaac_amd.XaacError) as e:
+        ctx.imdct_process_batch_host(np.zeros((n, 1024), np.int32), np.zeros((n, 2), np.uint8), np.zeros((n, 512), np.int32),
+                                     np.zeros((n, 2), np.uint8), out32=np.zeros((n, 1024), np.int32))
+    assert e.value.code == 0xFFFF8000 and str(e.value) == "xaac_imdct_process_batch_host failed: 0xFFFF8000"   # XAAC_FATAL_NULL_ARG

@@ -226,7 +226,7 @@ def test_struct_layouts_match_the_header(tmp_path):
                    'offsetof(xaac_drc_batch, status), sizeof(xaac_parse_batch), offsetof(xaac_parse_batch, drc_side)); return 0; }\n')
     subprocess.check_call(["gcc", "-I", os.path.join(dc.ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    S, B, P = libxaac_amd.DrcSide, libxaac_amd._DrcBatch, decoder._ParseBatch
+    S, B, P = libxaac_amd.DrcSide, libxaac_amd.abi.DrcBatch, decoder._ParseBatch
     assert got == [ctypes.sizeof(S), S.fac.offset, ctypes.sizeof(libxaac_amd.DrcConfig), ctypes.sizeof(B), B.status.offset,
                    ctypes.sizeof(P), P.drc_side.offset]
     assert ctypes.sizeof(S) == 4 * libxaac_amd.DRC_SIDE_WORDS == 4 * dc.WORDS

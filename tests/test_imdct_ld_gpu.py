@@ -105,7 +105,7 @@ def test_refused_shape_bytes_and_bad_arguments():
     assert st[2] == st[3] == libxaac_amd.BAD_WINDOW_SEQ and (np.delete(st, [2, 3]) == 0).all()
     assert (pcm.cpu().numpy().reshape(n, 512)[[2, 3]] == 7).all() and (ov.cpu().numpy()[[2, 3]] == 5).all()
     assert sp.cpu().tolist() == [0, 1, 0, 3, 0, 0, 0, 1]
-    b = libxaac_amd._ImdctLdBatch()
+    b = libxaac_amd.abi.ImdctLdBatch()
     b.n_ch, b.ch_fac, b.frame_length, b.eld = n, 1, 500, 0
     b.spec, b.window_shape, b.overlap, b.shape_prev, b.pcm16 = spec.data_ptr(), shape.data_ptr(), ov.data_ptr(), sp.data_ptr(), pcm.data_ptr()
     assert libxaac_amd.load_library().xaac_imdct_ld_process_batch(ctx._h, ctypes.byref(b)) != 0   # neither 512 nor 480

@@ -214,7 +214,7 @@ def test_descriptor_layouts_match_the_headers(tmp_path):
                    'XAAC_OUT_MAP_DOWNMIX_STEREO, XAAC_OUT_MAP_MONO_MIX, XAAC_OUT_MAP_MONO_MIX_DUP, XAAC_OUT_MAP_DUP_STEREO); return 0; }\n')
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    M, L, S, P = libxaac_amd.OutMap, libxaac_amd._LimiterMapBatch, libxaac_amd._ScaleAdjustMapBatch, libxaac_amd._McPcmOutMapBatch
+    M, L, S, P = libxaac_amd.OutMap, libxaac_amd.abi.LimiterMapBatch, libxaac_amd.abi.ScaleAdjustMapBatch, libxaac_amd.abi.McPcmOutMapBatch
     assert got == [ctypes.sizeof(M), M.n_elements.offset, M.element_type.offset, M.element_slot.offset, ctypes.sizeof(L), L.map.offset,
                    ctypes.sizeof(S), S.samples.offset, S.stride.offset, S.pcm16.offset, S.map.offset, ctypes.sizeof(P), P.map.offset,
                    libxaac_amd.OUT_MAP_NONE, libxaac_amd.OUT_MAP_DOWNMIX_STEREO, libxaac_amd.OUT_MAP_MONO_MIX,
