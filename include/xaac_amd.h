@@ -325,8 +325,8 @@ typedef struct xaac_sbr_apply_side_batch {
   int32_t n_streams;
   int32_t ch_fac;                 /* channels per stream, 1 or 2: channel c of stream i is entry i * ch_fac + c */
   const xaac_sbr_header *header;  /* [n_streams * ch_fac] device: this frame's headers (sub_band_start / sub_band_end) */
-  const int32_t *flags;           /* [n_streams][8] device: the parser's flag rows (xaac_parse_batch: [1] reset, [2]
-                                     reset_channels, [3] upsampling); all zero for a stream without a frame */
+  const int32_t *flags;           /* [n_streams][XAAC_SBR_FLAG_WORDS] device: the parser's flag rows (enum xaac_sbr_flag, xaac_sbr.h:
+                                     _RESET, _RESET_CHANNELS and _UPSAMPLING are read); all zero for a stream without a frame */
   xaac_sbr_state *state;          /* [n_streams * ch_fac] device, in / out */
   xaac_ps_state *ps_state;        /* optional [n_streams] device (mono + PS streams: the right channel's bank), in / out */
 } xaac_sbr_apply_side_batch;

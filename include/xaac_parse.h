@@ -224,13 +224,13 @@ typedef struct xaac_parse_batch {
   xaac_sbr_header *header;    /* with_sbr: [n_streams][n_ch] (the channels of a pair get copies) */
   xaac_sbr_frame *frame;      /* with_sbr: [n_streams][n_ch] */
   xaac_ps_frame *ps_frame;    /* with_sbr, optional: [n_streams] */
-  int32_t *flags;             /* with_sbr: [n_streams][8] = apply, reset, reset_channels, upsampling, stereo, ps, ps_start,
-                                 frame_ok of xaac_sbr_side */
+  int32_t *flags;             /* with_sbr: [n_streams][XAAC_SBR_FLAG_WORDS]: the scalar members of xaac_sbr_side, indexed by enum
+                                 xaac_sbr_flag (xaac_sbr.h) */
   int32_t *tools;             /* optional [n_streams] */
   uint64_t *consumed;         /* [n_streams] frame length (0 where status != 0) */
   int32_t *status;            /* [n_streams] XAAC_PARSE_OK / _NEED_DATA / error: such a stream's rows are left as they were */
   xaac_esbr_side *esbr_side;  /* with_sbr, parsers in xaac_parser_set_esbr(1) mode, optional: [n_streams][n_ch] */
-  int32_t *reset_pitch;       /* ... optional: [n_streams], written for frames with flags[1] (reset): xaac_parse_reset_pitch */
+  int32_t *reset_pitch;       /* ... optional: [n_streams], written for frames with flags[XAAC_SBR_FLAG_RESET]: xaac_parse_reset_pitch */
   uint64_t *pos;              /* optional [n_streams], in / out: the library keeps the streams' read positions -- stream i's frame
                                  starts at data[i] + pos[i] with bytes[i] - pos[i] bytes available, and pos[i] moves on by the
                                  frame's length where status is XAAC_PARSE_OK.  A host that leaves data / bytes as the whole
@@ -239,7 +239,7 @@ typedef struct xaac_parse_batch {
   int32_t frames;             /* 0 or 1: one frame per stream and call.  T > 1 (needs pos): up to T consecutive frames of every
                                  stream per call -- a stream's parser state and bytes are fetched once for T frames -- with every
                                  output array T times as long, step t's rows behind step t - 1's (spec [T][n_streams][n_ch][1024],
-                                 status [T][n_streams], flags [T][n_streams][8], ...; consumed [n_streams] = the bytes of all its
+                                 status [T][n_streams], flags [T][n_streams][XAAC_SBR_FLAG_WORDS], ...; consumed [n_streams] = the bytes of all its
                                  frames).  A stream that runs out or fails at step t has that status word in steps t .. T - 1.
                                  The call then returns the number of frames parsed. */
   int32_t *lines;             /* optional [frames][n_streams], out: for a delivered frame the number of leading spectral lines
@@ -264,7 +264,7 @@ typedef struct xaac_parse_batch {
                                  is taken -- every channel element's SBR payload through the element's own front end
                                  (xaac_parse_sbr_side_mc; ps_enable is not looked at: no parametric stereo in such a frame).
                                  header / frame / esbr_side are [frames][n_streams][n_ch], one row per channel in bitstream order, the
-                                 channels of a pair with copies of the pair's header; flags is [frames][n_streams][n_elems][8] and
+                                 channels of a pair with copies of the pair's header; flags is [frames][n_streams][n_elems][XAAC_SBR_FLAG_WORDS] and
                                  reset_pitch [frames][n_streams][n_elems], one row per channel ELEMENT (n_elems = 2, 3, 3, 4); ps_frame
                                  is not written.  The LFE's rows say apply 0 (its SBR data is always missing) */
   xaac_drc_side *drc_side;    /* optional (appended with dynamic range control), out: [frames][n_streams][n_ch], one row beside every

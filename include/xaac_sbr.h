@@ -26,6 +26,21 @@
 #define XAAC_SBR_MAX_ENV_VALUES (XAAC_SBR_MAX_ENVELOPES * XAAC_SBR_MAX_FREQ_COEFFS)
 #define XAAC_SBR_MAX_NOISE_VALUES (XAAC_SBR_MAX_NOISE_ENVELOPES * XAAC_SBR_MAX_NOISE_COEFFS)
 
+/* The parser's flag row: XAAC_SBR_FLAG_WORDS int32 words per stream (per channel element of a multichannel stream) and step,
+ * the scalar members of xaac_sbr_side (xaac_parse.h) in their order.  xaac_parse_batch writes it (xaac_parse_batch.flags),
+ * xaac_sbr_state_apply_side_batch reads it on the device (xaac_amd.h: xaac_sbr_apply_side_batch.flags). */
+enum xaac_sbr_flag {
+  XAAC_SBR_FLAG_APPLY = 0,
+  XAAC_SBR_FLAG_RESET,
+  XAAC_SBR_FLAG_RESET_CHANNELS,
+  XAAC_SBR_FLAG_UPSAMPLING,
+  XAAC_SBR_FLAG_STEREO,
+  XAAC_SBR_FLAG_PS,
+  XAAC_SBR_FLAG_PS_START,
+  XAAC_SBR_FLAG_FRAME_OK,
+  XAAC_SBR_FLAG_WORDS
+};
+
 /* Header-derived tables; change only on an SBR header / reset.
  * = ia_sbr_header_data_struct scalars (decoder/ixheaacd_env_extr_part.h:51-100)
  * + ia_freq_band_data_struct (:33-49) + ia_transposer_settings_struct (decoder/ixheaacd_lpp_tran.h:42-56)

@@ -446,12 +446,12 @@ class XaacContext:
 
     def sbr_state_apply_side_batch(self, header, flags, state, ch_fac, ps_state=None):
         """ixheaacd_sbr_dec_reset / ixheaacd_prepare_upsamp (sbrdecoder.c:103-276) on the resident states of the streams whose
-        flag rows say so: header uint8[n * ch_fac, SBR_HEADER_BYTES] (this frame's), flags int32[n, 8] (the parser's rows;
+        flag rows say so: header uint8[n * ch_fac, SBR_HEADER_BYTES] (this frame's), flags int32[n, abi.SBR_FLAG_WORDS] (the parser's rows;
         zero for streams without a frame), state / ps_state the uint8 views of the xaac_sbr_state / xaac_ps_state arrays."""
         b = ApplySideBatch()
         b.n_streams, b.ch_fac = int(flags.shape[0]), int(ch_fac)
         b.header = _ptr(header, "uint8", b.n_streams * b.ch_fac * SBR_HEADER_BYTES, device_ok=True)
-        b.flags = _ptr(flags, "int32", b.n_streams * 8, device_ok=True)
+        b.flags = _ptr(flags, "int32", b.n_streams * abi.SBR_FLAG_WORDS, device_ok=True)
         b.state = _ptr(state, "uint8", b.n_streams * b.ch_fac * SBR_STATE_BYTES, device_ok=True)
         b.ps_state = _ptr(ps_state, "uint8", allow_none=True, device_ok=True)
         self._call("xaac_sbr_state_apply_side_batch", ctypes.byref(b))

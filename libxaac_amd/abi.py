@@ -1,6 +1,7 @@
 """libxaac_amd.abi -- the Python statement of the C boundary (include/*.h): one ctypes mirror per struct, registered under
-its C type name in STRUCTS, and the prototypes of the device library's entry points (BATCH_ENTRY_POINTS,
-OTHER_ENTRY_POINTS; bind() applies them).  Sizes are never restated beside it: callers take ctypes.sizeof of a mirror.
+its C type name in STRUCTS, the prototypes of the device library's entry points (BATCH_ENTRY_POINTS,
+OTHER_ENTRY_POINTS; bind() applies them) and of the host library's (HOST_ENTRY_POINTS; bind_host()), and the positions of the
+parser's flag row (F_*).  Sizes are never restated beside it: callers take ctypes.sizeof of a mirror.
 tests/test_abi.py holds every mirror's size and every field's offset and size against what a C compiler makes of the headers.
 """
 import ctypes
@@ -21,6 +22,13 @@ def _mirror(c_name):
 
 
 # ---- include/xaac_sbr.h
+# enum xaac_sbr_flag, the parser's flag row: XAAC_SBR_FLAG_<name> is the name's place here, XAAC_SBR_FLAG_WORDS their number
+# (tests/test_abi.py holds both against the header)
+SBR_FLAG_NAMES = ("APPLY", "RESET", "RESET_CHANNELS", "UPSAMPLING", "STEREO", "PS", "PS_START", "FRAME_OK")
+SBR_FLAG_WORDS = len(SBR_FLAG_NAMES)
+F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(SBR_FLAG_WORDS)
+
+
 @_mirror("xaac_sbr_patch")
 class SbrPatch(ctypes.Structure):
     _fields_ = [(n, I16) for n in ("src_start_band", "src_end_band", "guard_start_band", "dst_start_band",
@@ -473,7 +481,7 @@ class CoreFrame(ctypes.Structure):
 
 @_mirror("xaac_sbr_side")
 class SbrSide(ctypes.Structure):   # header / frame / ps_frame as the byte rows the GPU entry points take
-    _fields_ = [(n, I32) for n in ("apply", "reset", "reset_channels", "upsampling", "stereo", "ps", "ps_start", "frame_ok")] + \
+    _fields_ = [(n.lower(), I32) for n in SBR_FLAG_NAMES] + \
                [("header", U8 * ctypes.sizeof(SbrHeader)), ("frame", (U8 * ctypes.sizeof(SbrFrame)) * 2),
                 ("ps_frame", U8 * ctypes.sizeof(PsFrame))]
 
@@ -523,10 +531,46 @@ OTHER_ENTRY_POINTS = {
 }
 
 
+# ---- the host library's entry points (include/xaac_parse.h): name -> (restype, argtypes)
+_P32, _PSZ = ctypes.POINTER(I32), ctypes.POINTER(ctypes.c_size_t)
+HOST_ENTRY_POINTS = {
+    "xaac_parser_create": (I32, [ctypes.POINTER(PTR)]), "xaac_parser_destroy": (None, [PTR]),
+    "xaac_parser_set_esbr": (I32, [PTR, I32]),
+    "xaac_adts_parse_header": (I32, [PTR, ctypes.c_size_t, ctypes.POINTER(AdtsHeader)]),
+    "xaac_parse_adts_frame": (I32, [PTR, PTR, ctypes.c_size_t, I32, ctypes.POINTER(CoreFrame), _PSZ]),
+    "xaac_parse_adts_frame_mc": (I32, [PTR, PTR, ctypes.c_size_t, I32, PTR, I32, _P32, _PSZ]),
+    "xaac_parse_sbr_side": (I32, [PTR, I32, ctypes.POINTER(SbrSide)]),
+    "xaac_parse_esbr_side": (I32, [PTR, I32, PTR]), "xaac_parse_reset_pitch": (I32, [PTR, _P32]),
+    "xaac_parse_core_tools_side": (I32, [PTR, PTR]), "xaac_parse_core_tools_side_mc": (I32, [PTR, I32, PTR]),
+    "xaac_parse_core_tools_state": (I32, [PTR, PTR]), "xaac_parse_core_tools_state_mc": (I32, [PTR, I32, PTR]),
+    "xaac_core_tools_apply_host": (I32, [PTR, PTR, PTR]),
+    "xaac_parse_drc_config": (I32, [PTR, ctypes.POINTER(DrcConfig)]), "xaac_parse_drc_side": (I32, [PTR, PTR]),
+    "xaac_drc_apply_host": (I32, [PTR, PTR]),
+    "xaac_sbr_state_init": (None, [PTR]), "xaac_ps_state_init": (None, [PTR]), "xaac_esbr_state_init": (None, [PTR]),
+    "xaac_esbr_ps_state_init": (None, [PTR]), "xaac_hbe_state_init": (None, [PTR]),
+    "xaac_hbe_state_reinit": (I32, [PTR, PTR]), "xaac_hbe_state_reinit_tails": (I32, [PTR, PTR, I32]),
+    "xaac_sbr_state_apply_side": (None, [PTR, ctypes.POINTER(SbrSide), I32]),
+    "xaac_ps_state_apply_side": (None, [PTR, ctypes.POINTER(SbrSide)]),
+    "xaac_out_map_apply_host": (I32, [PTR, I32, PTR, I64, PTR]), "xaac_out_map_row_bound": (I32, [I32, ctypes.POINTER(I64)]),
+    # (_run / _start: the original layout's symbols, no pos / frames / lines)
+    "xaac_parse_batch_run": (I32, [PTR]), "xaac_parse_batch_start": (I32, [PTR]), "xaac_parse_batch_wait": (I32, [PTR]),
+    "xaac_parse_batch_run_sized": (I32, [PTR, U64]), "xaac_parse_batch_start_sized": (I32, [PTR, U64]),
+}
+
+
+def _apply(lib, table):
+    for name, (restype, argtypes) in table.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
+    return lib
+
+
+def bind_host(lib):
+    """the prototypes of HOST_ENTRY_POINTS onto a loaded libxaac_host.so"""
+    return _apply(lib, HOST_ENTRY_POINTS)
+
+
 def bind(lib):
     """the prototypes above onto a loaded libxaac_amd.so (this also resolves every function once, so that a call finds it cached)"""
     for name, desc in BATCH_ENTRY_POINTS.items():
         getattr(lib, name).restype, getattr(lib, name).argtypes = I32, [PTR, ctypes.POINTER(desc)]
-    for name, (restype, argtypes) in OTHER_ENTRY_POINTS.items():
-        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
-    return lib
+    return _apply(lib, OTHER_ENTRY_POINTS)

@@ -6,9 +6,8 @@
 #include <stdint.h>
 
 #include "../../include/xaac_amd.h"
+#include "sbr_chain.h"
 
-#define XAAC_SBR_X_ROWS 40                       /* 2 LPC history rows + 6 overlap slots + 32 new slots */
-#define XAAC_SBR_X_WORDS (XAAC_SBR_X_ROWS * 64)  /* int32 words of one channel's QMF matrix */
 #define XAAC_SBR_NARROW_BANDS 48                 /* bands per LDS row of the HQ core's narrow-row kernel */
 #ifndef XAAC_SBR_CORE_HQ_WAVES
 #define XAAC_SBR_CORE_HQ_WAVES 4                 /* its waves per workgroup (they share the lookup tables in LDS) */
@@ -20,7 +19,7 @@ typedef struct XaacSbrCoreParams {
   const xaac_sbr_frame *frame;
   xaac_sbr_state *state;
   int32_t *x;        /* [n_ch][XAAC_SBR_X_WORDS] */
-  int16_t *syn_par;  /* [n_ch][8]: lb, ov_lb, hb, st_syn scales, synthesis lsb, usb */
+  XaacSynPar *syn_par; /* [n_ch]: out, for the synthesis bank (sbr_chain.h) */
   int32_t *status;   /* optional [n_ch] */
   /* HQ only, optional (both or neither): [n_ch] stream numbers + one counter.  With them the launch runs the narrow-row
      kernel first and the streams it cannot take through the 64-band rows afterwards (sbr_core_kernel.hip) */
@@ -38,7 +37,7 @@ typedef struct XaacSbrCoreParams {
 extern "C" {
 #endif
 hipError_t xaac_launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t stream);
-/* qmf_slots 30 only: xs_side_info_bad of every channel up front, the verdict in syn_par[8 ch + 7] (1: refused) */
+/* qmf_slots 30 only: xs_side_info_bad of every channel up front, the verdict in syn_par[ch].refused */
 hipError_t xaac_launch_sbr_screen(const XaacSbrCoreParams *p, hipStream_t stream);
 /* HQ: x rows are 128 words (64 real | 64 imaginary): [n_ch][2 * XAAC_SBR_X_WORDS] */
 hipError_t xaac_launch_sbr_core_hq(const XaacSbrCoreParams *p, hipStream_t stream);

@@ -73,25 +73,10 @@ __device__ __forceinline__ void xs_wave_sync() { /* = XsCx::sync() */
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-/* LDS copy of the state members the core touches: the four bank-limit shorts + the struct tail */
-struct XsLdsState {
-  int16_t codec_usb, syn_lsb, syn_usb, pad2_;
-  XAAC_SBR_STATE_TAIL_FIELDS
-};
-constexpr int kHeadOff = offsetof(xaac_sbr_state, codec_usb);
-constexpr int kTailOff = offsetof(xaac_sbr_state, lpc_real);
-constexpr int kTailWords = (sizeof(xaac_sbr_state) - kTailOff) / 4;
-static_assert(kHeadOff % 4 == 0 && kTailOff % 4 == 0 && sizeof(xaac_sbr_state) % 4 == 0, "word copies");
-static_assert(offsetof(XsLdsState, lpc_real) == 8 && sizeof(XsLdsState) == 8 + kTailWords * 4, "mirror layout");
-static_assert(offsetof(xaac_sbr_state, overlap) % 16 == 0 || true, "");
-static_assert(sizeof(xaac_sbr_header) % 4 == 0 && sizeof(xaac_sbr_frame) % 4 == 0, "word copies");
-
-/* of the frame side info only the head lives in LDS: the envelope scale factors (896 B) are read once per envelope
-   and stay in global memory, the noise floor gets its own twenty bytes (sbr_core.h hands both in beside `f`) */
-constexpr int kFrameHeadBytes = offsetof(xaac_sbr_frame, int_env_sf_arr);
-static_assert(kFrameHeadBytes % 4 == 0 && offsetof(xaac_sbr_frame, int_noise_floor) % 4 == 0, "word copies");
-static_assert(offsetof(xaac_sbr_frame, int_noise_floor) == kFrameHeadBytes + sizeof(((xaac_sbr_frame *)0)->int_env_sf_arr),
-              "nothing but the two arrays behind the head");
+/* the LDS copy of the state members the core touches (XsLdsState) and of the frame's head: sbr_chain.h */
+typedef XsStateMirror<xaac_sbr_state> Mirror;
+constexpr int kHeadOff = Mirror::kHeadOff, kTailOff = Mirror::kTailOff, kTailWords = Mirror::kTailWords;
+constexpr int kSlot0 = XAAC_SBR_X_SLOT0_ROW, kNew = XAAC_SBR_X_NEW_ROW, kOv = XAAC_SBR_X_OV_SLOTS; /* rows of the matrix */
 
 /* NB: bands a matrix row holds in LDS ("narrow rows").  The reference's rows have 64 bands; an SBR range that ends at
    band 48 or below (sub_band_end, patches, tables, bank limits, nothing left above in the overlap slots) never touches
@@ -134,16 +119,16 @@ __device__ __forceinline__ void copy_words(int32_t *dst, const int32_t *src, int
 }
 
 /* one channel-frame; returns false when the stream has to go through the 64-band rows (nothing written then).
-   NS: QMF slots of the frame, 32 or 30 (960-sample cores): the matrix keeps its 40 rows, of which 2 + 6 + NS are in use. */
+   NS: QMF slots of the frame, 32 or 30 (960-sample cores): the matrix keeps its XAAC_SBR_X_ROWS rows, of which kNew + NS are in use. */
 template <int HQ, int NB, int NS = 32>
 __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int ch, XsLds<HQ, NB> &s, const int lane) {
   typedef XsQmfT<HQ, NB, 0, NS> Q;
-  constexpr int ROW = Q::ROW, ROWG = HQ ? 128 : 64, XWG = (HQ ? 2 : 1) * XAAC_SBR_X_WORDS;
-  if (NS != 32 && __builtin_amdgcn_readfirstlane((int)p.syn_par[8 * (size_t)ch + 7])) {
+  constexpr int ROW = Q::ROW, ROWG = HQ ? XAAC_SBR_ROW_WORDS_HQ : XAAC_SBR_ROW_WORDS_LP, XWG = (HQ ? 2 : 1) * XAAC_SBR_X_WORDS;
+  if (NS != 32 && __builtin_amdgcn_readfirstlane((int)p.syn_par[ch].refused)) {
     /* refused by the screen in front of the banks (xaac_launch_sbr_screen): status -1, the state left as it is, the synthesis
        bank told to leave the channel alone */
     if (lane == 0) {
-      p.syn_par[8 * (size_t)ch + 6] = 1;
+      p.syn_par[ch].skip = 1;
       if (p.status) p.status[ch] = -1;
     }
     return true;
@@ -161,10 +146,10 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
   /* ---- copy-in: every global load of the channel-frame is issued before the first LDS store, so the wave pays one
      memory latency here, not one per piece (the kernel is latency bound: a wave's lifetime is its cost) ---- */
   constexpr int NH = (sizeof(xaac_sbr_header) / 4 + 63) / 64, NF = (kFrameHeadBytes / 4 + 63) / 64;
-  constexpr int NT = (kTailWords + 63) / 64, NOV = 6 * ROWG / 64, NAS = NS * 32 * (HQ ? 2 : 1) / 64;
+  constexpr int NT = (kTailWords + 63) / 64, NOV = kOv * ROWG / 64, NAS = NS * 32 * (HQ ? 2 : 1) / 64;
   static_assert(NAS * 64 == NS * 32 * (HQ ? 2 : 1), "whole runs of lanes");
   constexpr int NNF = sizeof(s.noise_floor) / 4;
-  static_assert(NOV * 64 == 6 * ROWG && NF == 1, "whole rows of lanes");
+  static_assert(NOV * 64 == kOv * ROWG && NF == 1, "whole rows of lanes");
   constexpr int NSF = (sizeof(((xaac_sbr_frame *)0)->int_env_sf_arr) / 4 + 63) / 64; /* the envelopes' scale factors: 224 words */
   int32_t r_h[NH], r_f, r_nf = 0, r_hd = 0, r_t[NT], r_ov[NOV], r_an[NAS], r_sf[NSF];
   {
@@ -188,7 +173,7 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
     for (int j = 0; j < NAS; j++) { /* the analysed slots: bands 0..31 (re, im) */
       const int i = lane + 64 * j;
       const int row = HQ ? (i >> 6) : (i >> 5), col = HQ ? ((i & 31) + ((i & 32) ? 64 : 0)) : (i & 31);
-      r_an[j] = gx[(8 + row) * ROWG + col];
+      r_an[j] = gx[(kNew + row) * ROWG + col];
     }
   }
   const xaac_sbr_frame *f = reinterpret_cast<const xaac_sbr_frame *>(s.f_head); /* head members only */
@@ -204,9 +189,9 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
 #pragma unroll
     for (int j = 0; j < NT; j++)
       if (lane + 64 * j < kTailWords) m[2 + lane + 64 * j] = r_t[j];
-    for (int i = lane; i < 2 * ROW; i += 64) s.x[i] = 0;
+    for (int i = lane; i < XAAC_SBR_X_LPC_ROWS * ROW; i += 64) s.x[i] = 0;
     if (NS < 32) /* rows behind the frame's: the reference's buffers have them (MAX_ENV_COLS), the LP filter's edge writes reach them */
-      for (int i = lane; i < (32 - NS) * ROW; i += 64) s.x[(8 + NS) * ROW + i] = 0;
+      for (int i = lane; i < (32 - NS) * ROW; i += 64) s.x[(kNew + NS) * ROW + i] = 0;
     if (!HQ)
       for (int i = lane; i < 128; i += 64) s.x[XAAC_SBR_X_ROWS * ROW + i] = 0;
   }
@@ -221,19 +206,19 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
 #pragma unroll
       for (int j = 0; j < NOV; j++) {
         const int row = HQ ? j >> 1 : j, part = HQ ? j & 1 : 0;
-        s.x[(2 + row) * ROW + part * NB + lane] = r_ov[j];
+        s.x[(kSlot0 + row) * ROW + part * NB + lane] = r_ov[j];
       }
     }
 #pragma unroll
     for (int j = 0; j < NAS; j++) {
       const int i = lane + 64 * j;
       const int row = HQ ? (i >> 6) : (i >> 5), col = HQ ? ((i & 31) + ((i & 32) ? Q::IM : 0)) : (i & 31);
-      s.x[(8 + row) * ROW + col] = r_an[j];
+      s.x[(kNew + row) * ROW + col] = r_an[j];
     }
     /* what the analysis bank does not write is 0: bands 32 and up of the analysed slots (sbr_dec.c:1121) */
     for (int i = lane; i < NS * (HQ ? 2 : 1) * (NB - 32); i += 64) {
       const int row = i / ((HQ ? 2 : 1) * (NB - 32)), c = i % ((HQ ? 2 : 1) * (NB - 32));
-      s.x[(8 + row) * ROW + (c < NB - 32 ? 32 + c : Q::IM + 32 + (c - (NB - 32)))] = 0;
+      s.x[(kNew + row) * ROW + (c < NB - 32 ? 32 + c : Q::IM + 32 + (c - (NB - 32)))] = 0;
     }
   };
   xs_wave_sync();
@@ -328,24 +313,19 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
 
   /* ---- copy-out ---- */
   if (lane == 0) {
-    int16_t *par = p.syn_par + 8 * (size_t)ch;
-    par[0] = s.st.lb_scale;
-    par[1] = s.st.ov_lb_scale;
-    par[2] = s.st.hb_scale;
-    par[3] = s.st.st_syn_scale;
-    par[4] = s.st.syn_lsb;
-    par[5] = s.st.syn_usb;
-    par[6] = 0; /* channel active (the synthesis kernel skips channels flagged here) */
-    par[7] = 0;
+    XaacSynPar *par = p.syn_par + ch;
+    xaac_syn_par_fill(par, s.st);
+    par->skip = 0; /* channel active (the synthesis kernel skips channels flagged here) */
+    par->refused = 0;
     s.st.ov_lb_scale = (int16_t)save_lb_scale;  /* sbr_dec.c:1304 */
 #ifndef XS_PROFILE
     if (p.status) p.status[ch] = rc;
 #endif
   }
   xs_wave_sync();
-  /* slots 0..NS-1 for synthesis (+ NS..NS+5 for PS); bands the narrow rows do not hold are 0 */
+  /* slots 0..NS-1 for synthesis (+ the kOv behind them for PS); bands the narrow rows do not hold are 0 */
   {
-    constexpr int NW = (NS + 6) * ROWG / 64; /* runs of 64 words: (slot, part) with band = lane */
+    constexpr int NW = (NS + kOv) * ROWG / 64; /* runs of 64 words: (slot, part) with band = lane */
     const bool held = NB == 64 || lane < NB;
     const int lane_h = held ? lane : 0; /* every lane reads (a select, not a predicated region per word) */
     /* env_calc.c:975-1003 on the way: the adjusted bands' slots below 32 take the shift xs_calc_sbrenvelope left pending (a
@@ -366,7 +346,7 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
       for (int j = 0; j < 8; j++)
         if (j0 + j < NW) {
           const int row = HQ ? (j0 + j) >> 1 : j0 + j, part = HQ ? (j0 + j) & 1 : 0;
-          int32_t v = s.x[(2 + row) * ROW + part * NB + lane_h];
+          int32_t v = s.x[(kSlot0 + row) * ROW + part * NB + lane_h];
           if (row < NS) {
             const int sl = row < pend.first_start ? ov_l : mn_l, sr = row < pend.first_start ? ov_r : mn_r; /* (uniform) */
             const int32_t w = (int32_t)((uint32_t)v << sl) >> sr;
@@ -376,17 +356,17 @@ __device__ __forceinline__ bool core_one(const XaacSbrCoreParams &p, const int c
         }
 #pragma unroll
       for (int j = 0; j < 8; j++)
-        if (j0 + j < NW) gx[2 * ROWG + 64 * (j0 + j) + lane] = t[j];
+        if (j0 + j < NW) gx[kSlot0 * ROWG + 64 * (j0 + j) + lane] = t[j];
     }
   }
   {
     int32_t *gw = reinterpret_cast<int32_t *>(gst);
     /* sbr_dec.c:1283-1291 copies 6 * 64 words in either mode: in HQ the first three of the six slots */
 #pragma unroll
-    for (int j = 0; j < 6; j++) {
+    for (int j = 0; j < kOv; j++) {
       const int row = HQ ? j >> 1 : j, part = HQ ? j & 1 : 0;
       const bool held = NB == 64 || lane < NB;
-      int32_t v = s.x[(2 + NS + row) * ROW + part * NB + (held ? lane : 0)];
+      int32_t v = s.x[(kSlot0 + NS + row) * ROW + part * NB + (held ? lane : 0)];
       /* (a first border behind slot 32 -- no parser's grid has one -- leaves the pending overlap-side shift to these rows too:
          env_calc.c:975 adjusts slots 0 .. first border) */
       if (NS + row < pend.first_start && lane >= pend.b0 && lane < pend.b1) {
@@ -535,7 +515,7 @@ static hipError_t launch_sbr_core_lp(const XaacSbrCoreParams *p, hipStream_t str
   return hipGetLastError();
 }
 
-/* The side-info check of the core (xs_side_info_bad) for every channel, before the analysis bank runs: [7] of a channel's
+/* The side-info check of the core (xs_side_info_bad) for every channel, before the analysis bank runs: `refused` of a channel's
    synthesis parameter row becomes 1 where the channel is refused, else 0.  The banks, the core and the parametric-stereo tool
    then leave a refused channel's state and output alone (the 960-sample entries; the 1024-sample ones keep their own order).
    The check is the same in both modes. */
@@ -545,7 +525,7 @@ __global__ __launch_bounds__(256) void xaac_sbr_screen_kernel(XaacSbrCoreParams 
   if (ch >= p.n_ch) return;
   const XsCx cx = {lane, 64};
   const int bad = xs_side_info_bad(cx, p.header + ch, p.frame + ch, p.state + ch, 0, NS);
-  if (lane == 0) p.syn_par[8 * (size_t)ch + 7] = (int16_t)(bad ? 1 : 0);
+  if (lane == 0) p.syn_par[ch].refused = (int16_t)(bad ? 1 : 0);
 }
 
 extern "C" hipError_t xaac_launch_sbr_screen(const XaacSbrCoreParams *p, hipStream_t stream) {

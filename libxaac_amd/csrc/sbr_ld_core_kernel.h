@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/xaac_amd.h"
+#include "sbr_chain.h"
 
 #define XAAC_SBR_LD_CORE_BLOCK 64 /* one wave per channel, no dynamic LDS: what xaac_sbr_eld_process_batch reports of its chain */
 
@@ -14,8 +15,8 @@ typedef struct XaacSbrLdCoreParams {
   const xaac_sbr_header *header;
   const xaac_sbr_frame *frame;
   xaac_sbr_eld_state *state;
-  int32_t *x;        /* [n_ch][n_slots][128]: the analysed slots in, the synthesis bank's rows out */
-  int16_t *syn_par;  /* [n_ch][8]: lb, ov_lb, hb, st_syn scales, synthesis lsb, usb, 1 = not synthesised, 0 */
+  int32_t *x;        /* [n_ch][n_slots][XAAC_SBR_ROW_WORDS_HQ]: the analysed slots in, the synthesis bank's rows out */
+  XaacSynPar *syn_par; /* [n_ch]: out, for the synthesis bank (sbr_chain.h); skip = 1 where the frame is not synthesised */
   int32_t *status;   /* optional [n_ch] */
 } XaacSbrLdCoreParams;
 

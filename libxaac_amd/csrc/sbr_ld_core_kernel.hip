@@ -19,21 +19,15 @@
 #include "sbr_ld_core_kernel.h"
 
 namespace {
-struct XlLdsState { /* the state members the core touches: the three bank limits + the struct tail */
-  int16_t codec_usb, syn_lsb, syn_usb, pad2_;
-  XAAC_SBR_STATE_TAIL_FIELDS
-};
-constexpr int kHeadOff = offsetof(xaac_sbr_eld_state, codec_usb);
-constexpr int kTailOff = offsetof(xaac_sbr_eld_state, lpc_real);
-constexpr int kTailWords = (sizeof(xaac_sbr_eld_state) - kTailOff) / 4;
-static_assert(kHeadOff % 4 == 0 && kTailOff % 4 == 0 && sizeof(xaac_sbr_eld_state) % 4 == 0 && kTailOff == kHeadOff + 8, "word copies");
-static_assert(offsetof(XlLdsState, lpc_real) == 8 && sizeof(XlLdsState) == 8 + kTailWords * 4, "mirror layout");
-constexpr int kFrameHeadBytes = offsetof(xaac_sbr_frame, int_env_sf_arr);
-static_assert(kFrameHeadBytes % 4 == 0 && offsetof(xaac_sbr_frame, int_noise_floor) % 4 == 0 && sizeof(xaac_sbr_header) % 4 == 0, "word copies");
+/* the LDS copy of the state members the core touches (XsLdsState) and of the frame's head: sbr_chain.h */
+typedef XsStateMirror<xaac_sbr_eld_state> Mirror;
+constexpr int kHeadOff = Mirror::kHeadOff, kTailOff = Mirror::kTailOff, kTailWords = Mirror::kTailWords;
+static_assert(kTailOff == kHeadOff + 8, "head and tail are neighbours in this state: one run of words");
+constexpr int kSlot0 = XAAC_SBR_X_SLOT0_ROW, kRow = XAAC_SBR_ROW_WORDS_HQ; /* the matrix: first slot's row in LDS, words per row */
 
 struct XlLds {
-  int32_t x[(2 + 16) * 128];
-  XlLdsState st;
+  int32_t x[XAAC_SBR_LD_X_ROWS * kRow];
+  XsLdsState st;
   xaac_sbr_header h;
   int32_t f_head[kFrameHeadBytes / 4];
   int32_t noise_floor[sizeof(((xaac_sbr_frame *)0)->int_noise_floor) / 4];
@@ -46,7 +40,7 @@ __global__ __launch_bounds__(XAAC_SBR_LD_CORE_BLOCK) void xaac_sbr_ld_core_kerne
   const int ch = blockIdx.x, lane = threadIdx.x, n = p.n_slots;
   xaac_sbr_eld_state *gst = p.state + ch;
   int32_t *gw = reinterpret_cast<int32_t *>(gst);
-  int32_t *gx = p.x + (size_t)ch * n * 128; /* the banks' layout: [n_ch][n_slots][128] */
+  int32_t *gx = p.x + (size_t)ch * n * kRow; /* the banks' layout: [n_ch][n_slots][kRow] */
   /* ---- copy-in: side info, state, the analysed slots (bands 0..31 real | imaginary; the rest of a row is cleared below) */
   {
     const int32_t *gh = reinterpret_cast<const int32_t *>(p.header + ch), *gf = reinterpret_cast<const int32_t *>(p.frame + ch);
@@ -56,10 +50,10 @@ __global__ __launch_bounds__(XAAC_SBR_LD_CORE_BLOCK) void xaac_sbr_ld_core_kerne
       s.noise_floor[i] = reinterpret_cast<const int32_t *>(p.frame[ch].int_noise_floor)[i];
     int32_t *m = reinterpret_cast<int32_t *>(&s.st);
     for (int i = lane; i < 2 + kTailWords; i += 64) m[i] = gw[kHeadOff / 4 + i];
-    for (int i = lane; i < 2 * 128; i += 64) s.x[i] = 0;
+    for (int i = lane; i < XAAC_SBR_X_LPC_ROWS * kRow; i += 64) s.x[i] = 0;
     for (int r = 0; r < n; r++) {
-      s.x[(2 + r) * 128 + lane] = (lane < 32) ? gx[r * 128 + lane] : 0;
-      s.x[(2 + r) * 128 + 64 + lane] = (lane < 32) ? gx[r * 128 + 64 + lane] : 0;
+      s.x[(kSlot0 + r) * kRow + lane] = (lane < 32) ? gx[r * kRow + lane] : 0;
+      s.x[(kSlot0 + r) * kRow + 64 + lane] = (lane < 32) ? gx[r * kRow + 64 + lane] : 0;
     }
   }
   __syncthreads();
@@ -85,23 +79,18 @@ __global__ __launch_bounds__(XAAC_SBR_LD_CORE_BLOCK) void xaac_sbr_ld_core_kerne
   cx.sync();
   /* ---- copy-out: the synthesis bank's parameters, the matrix, the state */
   if (lane == 0) {
-    int16_t *par = p.syn_par + 8 * (size_t)ch;
-    par[0] = s.st.lb_scale;
-    par[1] = s.st.ov_lb_scale;
-    par[2] = s.st.hb_scale;
-    par[3] = s.st.st_syn_scale;
-    par[4] = s.st.syn_lsb;
-    par[5] = s.st.syn_usb;
-    par[6] = (int16_t)(rc != 0); /* a refused / failed frame is not synthesised (the reference returns in front of its bank) */
-    par[7] = 0;
+    XaacSynPar *par = p.syn_par + ch;
+    xaac_syn_par_fill(par, s.st);
+    par->skip = (int16_t)(rc != 0); /* a refused / failed frame is not synthesised (the reference returns in front of its bank) */
+    par->refused = 0;
     if (rc == 0) s.st.ov_lb_scale = (int16_t)save_lb_scale; /* sbr_dec.c:1304 */
     if (p.status) p.status[ch] = rc;
   }
   cx.sync();
   if (rc == 0) {
     for (int r = 0; r < n; r++) {
-      gx[r * 128 + lane] = s.x[(2 + r) * 128 + lane];
-      gx[r * 128 + 64 + lane] = s.x[(2 + r) * 128 + 64 + lane];
+      gx[r * kRow + lane] = s.x[(kSlot0 + r) * kRow + lane];
+      gx[r * kRow + 64 + lane] = s.x[(kSlot0 + r) * kRow + 64 + lane];
     }
     const int32_t *m = reinterpret_cast<const int32_t *>(&s.st);
     for (int i = lane; i < 2 + kTailWords; i += 64) gw[kHeadOff / 4 + i] = m[i];

@@ -45,6 +45,7 @@ __shared__ long long xp_prof_acc[16];
 #define XS_SYNC_WAVE_LDS 1
 #include "sbr_ps_frame.h"
 #include "sbr_ps_kernel.h"
+#include "sbr_apply_side.h"
 
 namespace {
 
@@ -199,7 +200,7 @@ __device__ __forceinline__ int xp_frame_sanitize_regs(const XsCx &cx, int32_t (&
 }  // namespace
 
 /* NSL: QMF slots of a frame, 32 or 30 (the 960-sample cores: xaac_sbr_hq960_process_batch).  At 30 a stream the screen in front
-   of the banks refused (its synthesis parameter row's [7], sbr_core_kernel.hip: xaac_sbr_screen_kernel) is left alone: PS state,
+   of the banks refused (its synthesis parameter row's `refused`, sbr_core_kernel.hip: xaac_sbr_screen_kernel) is left alone: PS state,
    parameter rows (the core has flagged the left bank already) and status as they are, the right bank told to skip it. */
 template <int NSL = 32>
 __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel(XaacPsParams p) {
@@ -222,9 +223,9 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
 #endif
   for (int n = blockIdx.x * kPsWaves + wave; n < p.n; n += gridDim.x * kPsWaves) {
     xaac_ps_state *gps = p.state + n;
-    int32_t *gx = p.x + (size_t)n * (40 * 128) + 2 * 128; /* slot 0 */
-    int32_t *gr = p.xr + (size_t)n * (32 * 128); /* (30-slot frames use the first 30 rows) */
-    int16_t *par = p.par_l + 8 * (size_t)n;
+    int32_t *gx = p.x + (size_t)n * (2 * XAAC_SBR_X_WORDS) + XAAC_SBR_X_SLOT0_ROW * XAAC_SBR_ROW_WORDS_HQ; /* slot 0 */
+    int32_t *gr = p.xr + (size_t)n * XAAC_SBR_XR_WORDS; /* (30-slot frames use the first 30 rows) */
+    XaacSynPar *par = XAAC_SYN_PAR_ROW(p.par_l, n);
     /* Everything the stream's set-up reads from global memory in flight together: the two words that say whether this is a PS
        frame at all, state, side info and the six scale parameters the core left (as a chain -- flags, then state, then
        parameters -- a stream paid three memory latencies before its first instruction of work) */
@@ -232,7 +233,10 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     int32_t rs[NS], rf[NF];
     const int32_t *gs = reinterpret_cast<const int32_t *>(gps), *gf = reinterpret_cast<const int32_t *>(p.frame + n);
     const int apply_v = p.sbr_frame[n].apply_processing, mode_v = p.header[n].channel_mode;
-    const int par_v = lane < (NSL != 32 ? 8 : 6) ? par[lane] : 0;
+    /* the row, one member per lane: lane XAAC_SYN_PAR_AT(m) holds member m.  What the core left ends with usb; the screen's
+       verdict, which only the 30-slot chains have, is the last member */
+    static_assert(XAAC_SYN_PAR_AT(usb) == 5 && XAAC_SYN_PAR_AT(refused) == XAAC_SYN_PAR_WORDS - 1, "the lanes that load");
+    const int par_v = lane < (NSL != 32 ? XAAC_SYN_PAR_WORDS : XAAC_SYN_PAR_AT(usb) + 1) ? reinterpret_cast<const int16_t *>(par)[lane] : 0;
     /* the right bank's scale and band limits, for the parameter row written at the end: read here with the rest -- read there,
        by one lane, they came back behind every store of the stream (a wave's memory operations retire in order) and the row,
        and the next stream's loads behind it, waited for that */
@@ -242,20 +246,21 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
     for (int j = 0; j < NS; j++) rs[j] = lane + 64 * j < kHeadWords ? gs[lane + 64 * j] : 0;
 #pragma unroll
     for (int j = 0; j < NF; j++) rf[j] = lane + 64 * j < (int)(sizeof(xaac_ps_frame) / 4) ? gf[lane + 64 * j] : 0;
-    if (NSL != 32 && __builtin_amdgcn_readlane(par_v, 7)) { /* refused up front */
-      if (lane == 0) p.par_r[8 * (size_t)n + 6] = 1;
+    if (NSL != 32 && __builtin_amdgcn_readlane(par_v, XAAC_SYN_PAR_AT(refused))) { /* refused up front */
+      if (lane == 0) XAAC_SYN_PAR_ROW(p.par_r, n)->skip = 1;
       continue;
     }
     if (!(__builtin_amdgcn_readfirstlane(apply_v) && __builtin_amdgcn_readfirstlane(mode_v) == 3)) { /* sbr_dec.c:1246: mono this frame */
       if (lane == 0) {
-        p.par_l[8 * (size_t)n + 6] = 0;
-        p.par_r[8 * (size_t)n + 6] = 1;
+        XAAC_SYN_PAR_ROW(p.par_l, n)->skip = 0;
+        XAAC_SYN_PAR_ROW(p.par_r, n)->skip = 1;
       }
       continue;
     }
-    const int lb_scale = __builtin_amdgcn_readlane(par_v, 0), ov_lb_scale = __builtin_amdgcn_readlane(par_v, 1);
-    const int hb_scale = __builtin_amdgcn_readlane(par_v, 2), st_syn = __builtin_amdgcn_readlane(par_v, 3);
-    const int lsb = __builtin_amdgcn_readlane(par_v, 4), usb = __builtin_amdgcn_readlane(par_v, 5);
+#define XP_PAR(m) __builtin_amdgcn_readlane(par_v, XAAC_SYN_PAR_AT(m))
+    const int lb_scale = XP_PAR(lb_scale), ov_lb_scale = XP_PAR(ov_lb_scale), hb_scale = XP_PAR(hb_scale), st_syn = XP_PAR(st_syn_scale);
+    const int lsb = XP_PAR(lsb), usb = XP_PAR(usb);
+#undef XP_PAR
     const int ps_scale_done = xp_init_ps_scale_regs<NS>(cx, rs, lb_scale, ov_lb_scale, hb_scale);
     const int ps_clamped = xp_frame_sanitize_regs<NF, NSL>(cx, rf); /* indices a parser cannot produce: contained, reported */
     xp_wave_sync(); /* the previous stream's state has left the LDS copy */
@@ -281,15 +286,15 @@ __global__ __launch_bounds__(64 * kPsWaves, XP_WAVES_PER_EU) void xaac_ps_kernel
       for (int i = lane; i < kHeadWords; i += 64) dst[i] = src[i];
     }
     if (lane == 0) {
-      int16_t *pr = p.par_r + 8 * (size_t)n;
+      XaacSynPar *pr = XAAC_SYN_PAR_ROW(p.par_r, n);
       const int16_t ready = (int16_t)(st_syn - 8); /* makes the bank's own rescale a no-op: data is in place */
-      par[0] = par[1] = par[2] = ready;
-      pr[0] = pr[1] = pr[2] = (int16_t)ps_scale;
-      pr[3] = (int16_t)__builtin_amdgcn_readlane(tail_v, 0);
-      pr[4] = (int16_t)__builtin_amdgcn_readlane(tail_v, 1);
-      pr[5] = (int16_t)__builtin_amdgcn_readlane(tail_v, 2);
-      pr[6] = 0;
-      par[6] = 0;
+      par->lb_scale = par->ov_lb_scale = par->hb_scale = ready;
+      pr->lb_scale = pr->ov_lb_scale = pr->hb_scale = (int16_t)ps_scale;
+      pr->st_syn_scale = (int16_t)__builtin_amdgcn_readlane(tail_v, 0);
+      pr->lsb = (int16_t)__builtin_amdgcn_readlane(tail_v, 1);
+      pr->usb = (int16_t)__builtin_amdgcn_readlane(tail_v, 2);
+      pr->skip = 0;
+      par->skip = 0;
       gps->lb_scale_r = gps->ov_lb_scale_r = gps->hb_scale_r = (int16_t)ps_scale; /* sbr_dec.c:1261-1264 */
       p.sbr_state[n].ps_scale = (int16_t)ps_scale;
 #ifndef XS_PROFILE
@@ -328,40 +333,19 @@ __global__ __launch_bounds__(64) void xaac_sbr_handover_kernel(xaac_sbr_handover
 }
 
 /* sbrdecoder.c:103-252 (ixheaacd_sbr_dec_reset) and :254-276 (ixheaacd_prepare_upsamp): the state words a frame with the
-   reset / up-sampling flag rewrites -- the same as libxaac_amd/host/xaac_parse.cpp: xaac_sbr_state_apply_side and
-   xaac_ps_state_apply_side.  One thread per channel. */
+   reset / up-sampling flag rewrites -- sbr_apply_side.h, the statement the host's xaac_sbr_state_apply_side and
+   xaac_ps_state_apply_side (libxaac_amd/host/xaac_parse.cpp) compile too.  One thread per channel. */
 __global__ __launch_bounds__(256) void xaac_sbr_apply_side_kernel(xaac_sbr_apply_side_batch b) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= b.n_streams * b.ch_fac) return;
   const int i = e / b.ch_fac, c = e % b.ch_fac;
-  const int32_t *f = b.flags + 8 * (size_t)i;
-  const int reset = f[1], reset_channels = f[2], upsampling = f[3];
+  const int32_t *f = b.flags + XAAC_SBR_FLAG_WORDS * (size_t)i;
+  const int reset = f[XAAC_SBR_FLAG_RESET], reset_channels = f[XAAC_SBR_FLAG_RESET_CHANNELS], upsampling = f[XAAC_SBR_FLAG_UPSAMPLING];
   if (!reset && !upsampling) return;
-  xaac_sbr_state *s = b.state + e;
   const xaac_sbr_header *h = b.header + (size_t)i * b.ch_fac; /* the stream's header (channel 0's copy, as the host one reads) */
-  if (reset && c < reset_channels) {
-    s->ph_index = 0;
-    s->filt_buf_noise_e = 0;
-    s->start_up = 1;
-    s->syn_lsb = s->codec_usb = h->sub_band_start;
-    s->syn_usb = h->sub_band_end;
-    for (int k = 0; k < XAAC_SBR_MAX_PATCHES; k++) s->bw_array_prev[k] = 0;
-  }
-  if (upsampling) {
-    s->syn_lsb = s->codec_usb = 32;
-    s->syn_usb = 64;
-  }
-  if (b.ps_state && c == 0) {
-    xaac_ps_state *ps = b.ps_state + i;
-    if (reset && reset_channels > 1) {
-      ps->syn_lsb_r = h->sub_band_start;
-      ps->syn_usb_r = h->sub_band_end;
-    }
-    if (upsampling) {
-      ps->syn_lsb_r = 32;
-      ps->syn_usb_r = 64;
-    }
-  }
+  const int start = h->sub_band_start, end = h->sub_band_end;
+  xs_apply_side_channel(b.state + e, start, end, reset, reset_channels, upsampling, c);
+  if (b.ps_state && c == 0) xs_apply_side_ps(b.ps_state + i, start, end, reset, reset_channels, upsampling);
 }
 
 extern "C" hipError_t xaac_launch_sbr_apply_side(const xaac_sbr_apply_side_batch *b, hipStream_t stream) {

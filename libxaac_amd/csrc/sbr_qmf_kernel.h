@@ -7,6 +7,7 @@
 
 #include "../../include/xaac_amd.h"
 #include "../../include/xaac_sbr.h"
+#include "sbr_chain.h"
 
 /* waves per workgroup of the generic banks; each wave owns two channel-frames.  One: seven workgroups of 21 KB fit a CU
    where three pairs did, and with a host that keeps two HIP streams busy (bench.py) single-wave workgroups find room
@@ -27,7 +28,7 @@
 
 /* state / qmf / scale are addressed with explicit per-channel strides so that the same kernels serve the
    stand-alone QMF entry points (tight arrays) and the fused SBR path (fields inside xaac_sbr_state, rows
-   inside the per-channel 40 x 64 QMF matrix). */
+   inside the per-channel QMF matrix, sbr_chain.h). */
 typedef struct XaacQmfAnaParams {
   int32_t n_ch, ch_fac, low_pow, usb, slot_stride;
   int32_t state_stride;   /* bytes between consecutive channels' xaac_qmf_ana_state */
@@ -42,14 +43,15 @@ typedef struct XaacQmfAnaParams {
   const xaac_sbr_frame *frame;
   int32_t *zero_words; /* optional: two words the HQ kernel clears for the launch behind it (the SBR core's counters) */
   int32_t n_slots;     /* 0 / 32, or 30: 960 samples in per channel */
-  const int16_t *refused; /* optional [n_ch][8], [7] != 0: the channel's state is left alone (xaac_launch_sbr_screen) */
+  const XaacSynPar *refused; /* optional [n_ch], .refused != 0: the channel's state is left alone (xaac_launch_sbr_screen) */
 } XaacQmfAnaParams;
 
 typedef struct XaacQmfSynParams {
   int32_t n_ch, ch_fac, low_pow, lsb, usb, split, slot_stride;
   int32_t state_stride, qmf_ch_stride;
-  int32_t scale_stride;   /* int16 words between channels' {lb, ov_lb, hb, st_syn[, lsb, usb]} */
-  int32_t per_ch_bands;   /* 1: lsb/usb come from scale[4], scale[5] of each channel */
+  int32_t scale_stride;   /* int16 words between channels' rows of `scale`: XAAC_SYN_PAR_WORDS, the rows are XaacSynPar (the chains'
+                             workspaces); XAAC_SYN_PAR_PUBLIC_WORDS, they are its first four members alone (xaac_qmf_syn_batch.scale) */
+  int32_t per_ch_bands;   /* 1 (whole rows only): lsb / usb and the skip flag come from each channel's row */
   int32_t down_sample;    /* 1: the 32-channel bank (sbrdec_initfuncs.c:1165): 1024 samples out, 640-sample ring */
   const int32_t *qmf;
   const int16_t *scale;
@@ -63,8 +65,8 @@ typedef struct XaacQmfSynParams {
 } XaacQmfSynParams;
 
 /* HE-AACv2: both complex synthesis banks of a stream in one wave (channel 0 = left, state in xaac_sbr_state; channel
-   1 = right, state in xaac_ps_state), output as interleaved L,R pairs.  scale[c] + 8 i: lb, ov_lb, hb, st_syn scales,
-   lsb, usb, and [6] != 0 where the channel is not synthesised this frame (bank and output samples left alone). */
+   1 = right, state in xaac_ps_state), output as interleaved L,R pairs.  scale[c][i]: the stream's parameter row of that
+   channel (sbr_chain.h); skip != 0 where the channel is not synthesised this frame (bank and output samples left alone). */
 #define XAAC_QMF_SYN_PAIR_BLOCK 128 /* a wave per half of the bands, one workgroup per stream */
 #define XAAC_QMF_SYN_PAIR_LDS (2 * 42 * 65 * 4) /* the 2 x 42 x 65 pair rows; the two 32 x 65-word half-row tiles (one per wave, one channel at a time) alias them */
 typedef struct XaacQmfSynPairParams {
@@ -72,7 +74,7 @@ typedef struct XaacQmfSynPairParams {
   int32_t split;   /* first slot of the current frame's low band (op_delay = 6) */
   const int32_t *qmf[2];
   int32_t qmf_stride[2];    /* words between consecutive streams' slot 0 (rows of 64 re | 64 im) */
-  const int16_t *scale[2];
+  const XaacSynPar *scale[2];
   xaac_qmf_syn_state *state[2];
   int32_t state_stride[2];  /* bytes */
   int16_t *pcm;             /* [n][32 n_slots][2] */
@@ -96,7 +98,7 @@ typedef struct XaacQmfEldChain {
                                    leaves in str_codec_qmf_bank.usb in front of the bank: the frame's max_qmf_subband_aac when it is
                                    processed, else codec_usb */
   const int16_t *codec_usb;     /* ... of channel 0, the others state_stride bytes apart */
-  const int16_t *syn_par;       /* synthesis, [n_ch][8]: lb, ov_lb, hb, st_syn scales, lsb, usb, [6] != 0: channel left alone */
+  const XaacSynPar *syn_par;    /* synthesis, [n_ch]: the core's parameter rows (sbr_chain.h); skip != 0: channel left alone */
 } XaacQmfEldChain;
 hipError_t xaac_launch_qmf_analysis_eld(const xaac_qmf_ana_eld_batch *p, hipStream_t stream);
 hipError_t xaac_launch_qmf_analysis_eld_chain(const xaac_qmf_ana_eld_batch *p, const XaacQmfEldChain *c, hipStream_t stream);

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_analysis_kernel(XaacQ
     for (int c = 0; c < 2; c++) {
       const int ch = 2 * pair + c;
       if (ch >= p.n_ch) break;
-      if (NS != 32 && p.refused && __builtin_amdgcn_readfirstlane((int)p.refused[8 * (size_t)ch + 7])) continue;
+      if (NS != 32 && p.refused && __builtin_amdgcn_readfirstlane((int)XAAC_SYN_PAR_ROW(p.refused, ch)->refused)) continue;
       xaac_qmf_ana_state *st =
           reinterpret_cast<xaac_qmf_ana_state *>(reinterpret_cast<char *>(p.state) + (size_t)ch * p.state_stride);
       const int wr_new = (__builtin_amdgcn_readfirstlane(wr_v[c]) + 320 - (32 * NS) % 320) % 320;
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(128) void xaac_qmf_analysis_hq_kernel(XaacQmfAnaPar
 #pragma unroll 8
     for (int r = 0; r < NS; r++) row[(size_t)r * p.slot_stride] = src[33 * r];
   }
-  if (NS != 32 && p.refused && __builtin_amdgcn_readfirstlane((int)p.refused[8 * (size_t)chw + 7])) return;
+  if (NS != 32 && p.refused && __builtin_amdgcn_readfirstlane((int)XAAC_SYN_PAR_ROW(p.refused, chw)->refused)) return;
   /* ---- state: the ring as the reference leaves it after NS slots (32 NS samples further on) ---- */
   {
     const int wr_new = (wr + 320 - (32 * NS) % 320) % 320;
@@ -429,23 +429,25 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(Xaac
     constexpr int G = LP ? XQ_SYN_GROUP_LP : 8;
     /* the lane's channel's scale row, the two ring offsets and the two inactive flags: asked for here, in front of the rows, and
        looked at behind the transform -- read where they are used they were three more memory round trips per pair */
-    int16_t sfv[6] = {0, 0, 0, 0, 0, 0};
+    XaacSynPar sfv = {0, 0, 0, 0, 0, 0, 0, 0};
     int d_v[2] = {0, 0}, off_v[2] = {0, 0};
+    const auto row_of = [&](int ch) { /* a public row is the first four members alone (scale_stride) */
+      return reinterpret_cast<const XaacSynPar *>(p.scale + (size_t)p.scale_stride * ch);
+    };
     {
       const int ch = 2 * pair + (lane >> 5);
-      const int16_t *sf = p.scale + (size_t)p.scale_stride * (ch < p.n_ch ? ch : p.n_ch - 1);
-#pragma unroll
-      for (int k = 0; k < 4; k++) sfv[k] = sf[k];
+      const XaacSynPar *sf = row_of(ch < p.n_ch ? ch : p.n_ch - 1);
+      sfv.lb_scale = sf->lb_scale, sfv.ov_lb_scale = sf->ov_lb_scale, sfv.hb_scale = sf->hb_scale, sfv.st_syn_scale = sf->st_syn_scale;
       if (p.per_ch_bands) {
-        sfv[4] = sf[4];
-        sfv[5] = sf[5];
+        sfv.lsb = sf->lsb;
+        sfv.usb = sf->usb;
       }
 #pragma unroll
       for (int c = 0; c < 2; c++) {
         const int chc = 2 * pair + c;
         if (chc < p.n_ch) {
           d_v[c] = reinterpret_cast<const xaac_qmf_syn_state *>(reinterpret_cast<const char *>(p.state) + (size_t)chc * p.state_stride)->drc_offset;
-          if (p.per_ch_bands) off_v[c] = p.scale[(size_t)p.scale_stride * chc + 6];
+          if (p.per_ch_bands) off_v[c] = row_of(chc)->skip;
         }
       }
     }
@@ -498,13 +500,13 @@ __global__ __launch_bounds__(XAAC_QMF_BLOCK) void xaac_qmf_synthesis_kernel(Xaac
     /* ---- per-slot: region rescale (qmf_dec.c:937-953) + inverse modulation; lane = slot ----------- */
     int16_t b[BLK];
     {
-      const int16_t *sf = sfv; /* lb_scale, ov_lb_scale, hb_scale, st_syn_scale (+ lsb, usb) of the lane's channel */
-      const int st_syn = sf[3];
-      const int lsb = p.per_ch_bands ? sf[4] : p.lsb, usb = p.per_ch_bands ? sf[5] : p.usb;
+      const XaacSynPar &sf = sfv; /* the scales (+ lsb, usb) of the lane's channel */
+      const int st_syn = sf.st_syn_scale;
+      const int lsb = p.per_ch_bands ? sf.lsb : p.lsb, usb = p.per_ch_bands ? sf.usb : p.usb;
       const int bias = LP ? 4 : 8;
       const int s = lane & 31;
-      const int lo_shift = (st_syn - (s < p.split ? sf[1] : sf[0])) - bias;
-      const int hb_shift = (st_syn - sf[2]) - bias;
+      const int lo_shift = (st_syn - (s < p.split ? sf.ov_lb_scale : sf.lb_scale)) - bias;
+      const int hb_shift = (st_syn - sf.hb_scale) - bias;
       int32_t x[ROW], t[ROW];
 #pragma unroll
       for (int k = 0; k < ROW; k++) {
@@ -690,24 +692,24 @@ __global__ __launch_bounds__(XAAC_QMF_SYN_PAIR_BLOCK) void xaac_qmf_synthesis_pa
   typedef int xq_int4 __attribute__((ext_vector_type(4)));
   xaac_qmf_syn_state *st_w = reinterpret_cast<xaac_qmf_syn_state *>(reinterpret_cast<char *>(p.state[w]) + (size_t)i * p.state_stride[w]);
   const xaac_qmf_syn_state *st_o = reinterpret_cast<const xaac_qmf_syn_state *>(reinterpret_cast<const char *>(p.state[1 - w]) + (size_t)i * p.state_stride[1 - w]);
-  const xq_int4 par0 = *reinterpret_cast<const xq_int4 *>(p.scale[0] + 8 * (size_t)i);
-  const xq_int4 par1 = *reinterpret_cast<const xq_int4 *>(p.scale[1] + 8 * (size_t)i);
+  static_assert(sizeof(XaacSynPar) == sizeof(xq_int4), "a row is the one 16-byte load");
+  const xq_int4 par0 = *reinterpret_cast<const xq_int4 *>(p.scale[0] + i);
+  const xq_int4 par1 = *reinterpret_cast<const xq_int4 *>(p.scale[1] + i);
   const int d_old_v = st_w->drc_offset, d_oth_v = st_o->drc_offset;
   int32_t x[64];
   int32_t tmp[64]; /* (behind the small loads: memory operations return in order, so what follows waits for those four only) */
 #pragma unroll
   for (int r = 0; r < 64; r++) {
     const int c = r >> 5;
-    tmp[r] = (r & 31) < NS ? (p.qmf[c] + (size_t)i * p.qmf_stride[c] + (size_t)(r & 31) * 128 + 64 * w)[lane] : 0;
+    tmp[r] = (r & 31) < NS ? (p.qmf[c] + (size_t)i * p.qmf_stride[c] + (size_t)(r & 31) * XAAC_SBR_ROW_WORDS_HQ + 64 * w)[lane] : 0;
   }
-  const auto lo16 = [](int v) { return (int)(int16_t)v; };
-  const auto hi16 = [](int v) { return v >> 16; };
-  const int u0 = __builtin_amdgcn_readfirstlane(par0.x), u1 = __builtin_amdgcn_readfirstlane(par0.y);
-  const int u2 = __builtin_amdgcn_readfirstlane(par0.z), u3 = __builtin_amdgcn_readfirstlane(par0.w);
-  const int v0 = __builtin_amdgcn_readfirstlane(par1.x), v1 = __builtin_amdgcn_readfirstlane(par1.y);
-  const int v2 = __builtin_amdgcn_readfirstlane(par1.z), v3 = __builtin_amdgcn_readfirstlane(par1.w);
-  const int inactive0 = lo16(u3), inactive1 = lo16(v3);
-  const int st_syn0 = hi16(u1), st_syn1 = hi16(v1);
+  /* the rows' four words, uniform; a member is a half of one of them (sbr_chain.h: XAAC_SYN_PAR_OF_WORDS) */
+  const int u[4] = {__builtin_amdgcn_readfirstlane(par0.x), __builtin_amdgcn_readfirstlane(par0.y),
+                    __builtin_amdgcn_readfirstlane(par0.z), __builtin_amdgcn_readfirstlane(par0.w)};
+  const int v[4] = {__builtin_amdgcn_readfirstlane(par1.x), __builtin_amdgcn_readfirstlane(par1.y),
+                    __builtin_amdgcn_readfirstlane(par1.z), __builtin_amdgcn_readfirstlane(par1.w)};
+  const int inactive0 = XAAC_SYN_PAR_OF_WORDS(u, skip), inactive1 = XAAC_SYN_PAR_OF_WORDS(v, skip);
+  const int st_syn0 = XAAC_SYN_PAR_OF_WORDS(u, st_syn_scale), st_syn1 = XAAC_SYN_PAR_OF_WORDS(v, st_syn_scale);
   /* this wave's channel for history / state: channel w */
   const int d_old = __builtin_amdgcn_readfirstlane(d_old_v);
   {
@@ -721,11 +723,12 @@ __global__ __launch_bounds__(XAAC_QMF_SYN_PAIR_BLOCK) void xaac_qmf_synthesis_pa
     int shl[2][2], shr[2][2]; /* [channel][slot < split] for band = 64 w' + lane -> the band is lane (both halves: re | im of band lane) */
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-      const int w0 = c ? v0 : u0, w1 = c ? v1 : u1, w2 = c ? v2 : u2;
-      const int st_syn = hi16(w1), lsb = lo16(w2), usb = hi16(w2), hb = lo16(w1);
+      const int(&wd)[4] = c ? v : u;
+      const int st_syn = XAAC_SYN_PAR_OF_WORDS(wd, st_syn_scale), lsb = XAAC_SYN_PAR_OF_WORDS(wd, lsb), usb = XAAC_SYN_PAR_OF_WORDS(wd, usb);
+      const int hb = XAAC_SYN_PAR_OF_WORDS(wd, hb_scale);
 #pragma unroll
       for (int ov = 0; ov < 2; ov++) {
-        const int lo_sf = ov ? hi16(w0) : lo16(w0); /* sf[ov]: lb_scale, ov_lb_scale */
+        const int lo_sf = ov ? XAAC_SYN_PAR_OF_WORDS(wd, ov_lb_scale) : XAAC_SYN_PAR_OF_WORDS(wd, lb_scale);
         int sh = lane < lsb ? (st_syn - lo_sf) - 8 : (lane < usb ? (st_syn - hb) - 8 : 0);
         sh = sh > 31 ? 31 : (sh < -31 ? -31 : sh); /* env_calc.c:1099 */
         shl[c][ov] = sh > 0 ? sh : 0;
@@ -1022,7 +1025,7 @@ __global__ __launch_bounds__(XAAC_QMF_ELD_BLOCK) void xaac_qmf_synthesis_eld_ker
   for (int c = 0; c < 4; c++) {
     const int ch = 4 * quad + c;
     phase[c] = ch < p.n_ch ? eld_syn_phase(state_of(ch)) : -1;
-    const bool skipped = ch < p.n_ch && cn.syn_par && cn.syn_par[8 * (size_t)ch + 6] != 0; /* the chain's core refused the frame */
+    const bool skipped = ch < p.n_ch && cn.syn_par && cn.syn_par[ch].skip != 0; /* the chain's core refused the frame */
     if (lane == 0 && p.status && ch < p.n_ch && !skipped && (!cn.syn_par || phase[c] < 0)) p.status[ch] = phase[c] >= 0 ? 0 : -1;
     if (skipped) phase[c] = -1;
     int16_t *vc = v + c * VS * VR;
@@ -1040,10 +1043,11 @@ __global__ __launch_bounds__(XAAC_QMF_ELD_BLOCK) void xaac_qmf_synthesis_eld_ker
   {
     const int c = lane >> 4, s = lane & 15, ch = 4 * quad + c;
     if (phase[c] >= 0 && s < ns) {
-      const int16_t *sf = cn.syn_par ? cn.syn_par + 8 * (size_t)ch : p.scale + 4 * (size_t)ch;
-      const int lsb = cn.syn_par ? sf[4] : p.lsb, usb = cn.syn_par ? sf[5] : p.usb;
-      const int st_syn = sf[3];
-      const int ov_lb_shift = (st_syn - sf[1]) - 7, lb_shift = (st_syn - sf[0]) - 7, hb_shift = (st_syn - sf[2]) - 7;
+      /* the chain's row, or the public one: its first four members alone */
+      const XaacSynPar *sf = cn.syn_par ? cn.syn_par + ch : reinterpret_cast<const XaacSynPar *>(p.scale + XAAC_SYN_PAR_PUBLIC_WORDS * (size_t)ch);
+      const int lsb = cn.syn_par ? sf->lsb : p.lsb, usb = cn.syn_par ? sf->usb : p.usb;
+      const int st_syn = sf->st_syn_scale;
+      const int ov_lb_shift = (st_syn - sf->ov_lb_scale) - 7, lb_shift = (st_syn - sf->lb_scale) - 7, hb_shift = (st_syn - sf->hb_scale) - 7;
       const int32_t *row = p.qmf + ((size_t)ch * ns + s) * p.slot_stride;
       int32_t x[128], t[128];
       int16_t b[128];

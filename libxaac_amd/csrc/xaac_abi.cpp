@@ -128,12 +128,12 @@ struct Cursor {
 
 struct SbrLpWs {
   int32_t *x;        /* [n][XAAC_SBR_X_WORDS]: the channels' QMF matrices */
-  int16_t *par;      /* [n][8]: the synthesis parameters */
+  XaacSynPar *par;   /* [n]: the synthesis parameters */
   int32_t *counters; /* the core's work counter and its neighbour */
   uint64_t end;
   SbrLpWs(void *base, size_t n) {
     Cursor k(base, 256);
-    x = k.take<int32_t>(n * XAAC_SBR_X_WORDS), par = k.take<int16_t>(n * 8);
+    x = k.take<int32_t>(n * XAAC_SBR_X_WORDS), par = k.take<XaacSynPar>(n);
     counters = k.align(64).take<int32_t>(2);
     end = k.at;
   }
@@ -141,15 +141,15 @@ struct SbrLpWs {
 constexpr uint64_t kSbrLpWsSurplus = 58; /* the size was written as the parts + 256 + 128: the two pads and the counters take 326 */
 
 struct SbrHqWs {
-  int32_t *x, *xr;        /* [n][2 * XAAC_SBR_X_WORDS]: 40 rows of 64 real | 64 imaginary; PS: [n][32][128], the right channel */
-  int16_t *par_l, *par_r; /* [n][8]: the synthesis parameters (par_r: PS) */
+  int32_t *x, *xr;           /* [n][2 * XAAC_SBR_X_WORDS]: rows of 64 real | 64 imaginary; PS: [n][XAAC_SBR_XR_WORDS], the right channel */
+  XaacSynPar *par_l, *par_r; /* [n]: the synthesis parameters (par_r: PS) */
   int32_t *counters;      /* streams deferred to the 64-band rows, next stream of the persistent waves */
   int32_t *defer_list;    /* [n]: the deferred streams */
   uint64_t end;
   SbrHqWs(void *base, size_t n, bool with_ps) {
     Cursor k(base, 256);
-    x = k.take<int32_t>(n * 2 * XAAC_SBR_X_WORDS), xr = k.take<int32_t>(with_ps ? n * 32 * 128 : 0);
-    par_l = k.take<int16_t>(n * 8), par_r = k.take<int16_t>(with_ps ? n * 8 : 0);
+    x = k.take<int32_t>(n * 2 * XAAC_SBR_X_WORDS), xr = k.take<int32_t>(with_ps ? n * XAAC_SBR_XR_WORDS : 0);
+    par_l = k.take<XaacSynPar>(n), par_r = k.take<XaacSynPar>(with_ps ? n : 0);
     counters = k.align(64).take<int32_t>(2), defer_list = k.take<int32_t>(n);
     end = k.at;
   }
@@ -157,12 +157,12 @@ struct SbrHqWs {
 constexpr uint64_t kSbrHqWsSurplus = 314; /* ... as the parts + 512 + 128: the two pads and the counters take 326 */
 
 struct SbrEldWs {
-  int32_t *x;   /* [n][16][128]: the matrices */
-  int16_t *par; /* [n][8]: the synthesis parameters */
+  int32_t *x;      /* [n][XAAC_SBR_LD_X_SLOTS][XAAC_SBR_ROW_WORDS_HQ]: the matrices */
+  XaacSynPar *par; /* [n]: the synthesis parameters */
   uint64_t end;
   SbrEldWs(void *base, size_t n) {
     Cursor k(base, 256);
-    x = k.take<int32_t>(n * 16 * 128), par = k.take<int16_t>(n * 8);
+    x = k.take<int32_t>(n * XAAC_SBR_LD_X_SLOTS * XAAC_SBR_ROW_WORDS_HQ), par = k.take<XaacSynPar>(n);
     end = k.at;
   }
 };
@@ -274,19 +274,19 @@ int32_t esbr_qmf_synthesis(xaac_ctx *c, const xaac_esbr_syn_batch *b, bool ds) {
 }
 
 /* The two SBR chains (B: xaac_sbr_lp_batch | xaac_sbr_hq_batch; ns: QMF slots of the frames -- 32, or 30: 960 samples in, 1920
-   out) around their cores.  w: words of a slot, 64 real (| 64 imaginary). */
+   out) around their cores.  w: words of a slot, 64 real (| 64 imaginary).  The matrix' rows and the parameter row: sbr_chain.h. */
 
 /* 0. 30 slots: the side-info check up front -- a refused channel's SBR state, PS state and output are left as they are
       (xaac_sbr_lp960_process_batch, xaac_sbr_hq960_process_batch)
-   1. the analysis bank: ns new slots into rows 8..7 + ns of each channel's matrix; it clears the core's counters on its way */
+   1. the analysis bank: ns new slots into the rows from XAAC_SBR_X_NEW_ROW on of each channel's matrix; it clears the core's counters on its way */
 template <class B>
-hipError_t sbr_front(xaac_ctx *c, const B *b, bool hq, int ns, int32_t *x, int16_t *par, int32_t *counters) {
-  const int w = hq ? 128 : 64;
+hipError_t sbr_front(xaac_ctx *c, const B *b, bool hq, int ns, int32_t *x, XaacSynPar *par, int32_t *counters) {
+  const int w = hq ? XAAC_SBR_ROW_WORDS_HQ : XAAC_SBR_ROW_WORDS_LP;
   XaacQmfAnaParams pa = {};
   pa.n_ch = b->n_ch; pa.ch_fac = b->in_ch_fac; pa.low_pow = hq ? 0 : 1; pa.usb = 32; pa.slot_stride = w; pa.n_slots = ns;
   pa.state_stride = (int32_t)sizeof(xaac_sbr_state); pa.qmf_ch_stride = XAAC_SBR_X_ROWS * w; pa.pcm = b->pcm_in;
   pa.state = reinterpret_cast<xaac_qmf_ana_state *>(reinterpret_cast<char *>(b->state) + offsetof(xaac_sbr_state, ana_ring));
-  pa.qmf = x + (2 + 6) * w; pa.zero_words = counters;
+  pa.qmf = x + XAAC_SBR_X_NEW_ROW * w; pa.zero_words = counters;
   if (hq) pa.frame = b->frame;
   if (ns == 30) {
     XaacSbrCoreParams sc = {};
@@ -300,7 +300,7 @@ hipError_t sbr_front(xaac_ctx *c, const B *b, bool hq, int ns, int32_t *x, int16
 
 /* 2. what both cores take: everything between the banks */
 template <class B>
-XaacSbrCoreParams sbr_core_params(const xaac_ctx *c, const B *b, int ns, int32_t *x, int16_t *par, int32_t *counters) {
+XaacSbrCoreParams sbr_core_params(const xaac_ctx *c, const B *b, int ns, int32_t *x, XaacSynPar *par, int32_t *counters) {
   XaacSbrCoreParams pc = {};
   pc.n_ch = b->n_ch; pc.header = b->header; pc.frame = b->frame; pc.state = b->state; pc.x = x; pc.syn_par = par;
   pc.status = b->status; pc.qmf_slots = ns;
@@ -308,15 +308,16 @@ XaacSbrCoreParams sbr_core_params(const xaac_ctx *c, const B *b, int ns, int32_t
   return pc;
 }
 
-/* 3. the synthesis bank over rows 2..1 + ns (the 6 delayed + first ns - 6 new slots), and the chain's report */
+/* 3. the synthesis bank over the ns rows from XAAC_SBR_X_SLOT0_ROW on (the delayed slots + the first ns - XAAC_SBR_X_OV_SLOTS new
+      ones), and the chain's report */
 template <class B>
-int32_t sbr_back(xaac_ctx *c, const B *b, bool hq, int ns, const int32_t *x, const int16_t *par) {
-  const int w = hq ? 128 : 64;
+int32_t sbr_back(xaac_ctx *c, const B *b, bool hq, int ns, const int32_t *x, const XaacSynPar *par) {
+  const int w = hq ? XAAC_SBR_ROW_WORDS_HQ : XAAC_SBR_ROW_WORDS_LP;
   XaacQmfSynParams ps = {};
-  ps.n_ch = b->n_ch; ps.ch_fac = b->out_ch_fac; ps.low_pow = hq ? 0 : 1; ps.split = 6; ps.n_slots = ns; ps.down_sample = b->down_sample ? 1 : 0;
+  ps.n_ch = b->n_ch; ps.ch_fac = b->out_ch_fac; ps.low_pow = hq ? 0 : 1; ps.split = XAAC_SBR_X_OV_SLOTS; ps.n_slots = ns; ps.down_sample = b->down_sample ? 1 : 0;
   ps.slot_stride = w; ps.state_stride = (int32_t)sizeof(xaac_sbr_state); ps.qmf_ch_stride = XAAC_SBR_X_ROWS * w;
-  ps.scale_stride = 8; ps.per_ch_bands = 1;
-  ps.qmf = x + 2 * w; ps.scale = par; ps.pcm = b->pcm_out; ps.dbg = XAAC_DBG_BUF(b->status, b->n_ch);
+  ps.scale_stride = XAAC_SYN_PAR_WORDS; ps.per_ch_bands = 1;
+  ps.qmf = x + XAAC_SBR_X_SLOT0_ROW * w; ps.scale = &par->lb_scale; ps.pcm = b->pcm_out; ps.dbg = XAAC_DBG_BUF(b->status, b->n_ch);
   ps.state = reinterpret_cast<xaac_qmf_syn_state *>(reinterpret_cast<char *>(b->state) + offsetof(xaac_sbr_state, syn_ring));
   const int grid = qmf_grid(c, b->n_ch, hq ? 3 : 2);
   XAAC_TRY(xaac_launch_qmf_synthesis(&ps, grid, c->stream));
@@ -361,18 +362,18 @@ int32_t sbr_hq_run(xaac_ctx *c, const xaac_sbr_hq_batch *b, int ns) {
   pc.narrow_only = b->max_band_hint == XAAC_SBR_NARROW_BANDS ? 1 : 0;
   XAAC_TRY(xaac_launch_sbr_core_hq(&pc, c->stream));
   if (!with_ps) return sbr_back(c, b, true, ns, w.x, w.par_l);
-  /* parametric stereo: rows 2..1 + ns become the left channel, xr the right one */
+  /* parametric stereo: the ns rows from XAAC_SBR_X_SLOT0_ROW on become the left channel, xr the right one */
   XaacPsParams pp = {};
   pp.n_slots = ns; pp.n = b->n_ch; pp.x = w.x; pp.xr = w.xr; pp.header = b->header; pp.sbr_frame = b->frame; pp.frame = b->ps_frame;
   pp.state = b->ps_state; pp.sbr_state = b->state; pp.par_l = w.par_l; pp.par_r = w.par_r; pp.status = b->status; pp.dbg = XAAC_DBG_BUF(b->status, b->n_ch);
   XAAC_TRY(xaac_launch_ps(&pp, c->stream));
   /* both synthesis banks of a stream in one workgroup, interleaved L,R out */
   XaacQmfSynPairParams pq = {};
-  pq.n = b->n_ch; pq.split = 6; pq.n_slots = ns;
-  pq.qmf[0] = w.x + 2 * 128; pq.qmf_stride[0] = 2 * XAAC_SBR_X_WORDS; pq.scale[0] = w.par_l;
+  pq.n = b->n_ch; pq.split = XAAC_SBR_X_OV_SLOTS; pq.n_slots = ns;
+  pq.qmf[0] = w.x + XAAC_SBR_X_SLOT0_ROW * XAAC_SBR_ROW_WORDS_HQ; pq.qmf_stride[0] = 2 * XAAC_SBR_X_WORDS; pq.scale[0] = w.par_l;
   pq.state[0] = reinterpret_cast<xaac_qmf_syn_state *>(reinterpret_cast<char *>(b->state) + offsetof(xaac_sbr_state, syn_ring));
   pq.state_stride[0] = (int32_t)sizeof(xaac_sbr_state);
-  pq.qmf[1] = w.xr; pq.qmf_stride[1] = 32 * 128; pq.scale[1] = w.par_r;
+  pq.qmf[1] = w.xr; pq.qmf_stride[1] = XAAC_SBR_XR_WORDS; pq.scale[1] = w.par_r;
   pq.state[1] = reinterpret_cast<xaac_qmf_syn_state *>(reinterpret_cast<char *>(b->ps_state) + offsetof(xaac_ps_state, syn_ring_r));
   pq.state_stride[1] = (int32_t)sizeof(xaac_ps_state);
   pq.pcm = b->pcm_out; pq.status = b->status;
@@ -623,7 +624,7 @@ int32_t xaac_qmf_synthesis_batch(xaac_ctx *c, const xaac_qmf_syn_batch *b) {
   p.split = b->split; p.slot_stride = b->slot_stride; p.qmf = b->qmf; p.scale = b->scale; p.state = b->state;
   p.pcm = b->pcm;
   p.state_stride = (int32_t)sizeof(xaac_qmf_syn_state); p.qmf_ch_stride = 32 * b->slot_stride;
-  p.scale_stride = 4; p.per_ch_bands = 0;
+  p.scale_stride = XAAC_SYN_PAR_PUBLIC_WORDS; p.per_ch_bands = 0; /* the caller's rows: the first four members of XaacSynPar */
   const int grid = qmf_grid(c, b->n_ch, p.low_pow ? 2 : 3);
   return run(c, grid, XAAC_QMF_BLOCK, p.low_pow ? XAAC_QMF_SYN_LDS_LP : XAAC_QMF_SYN_LDS_HQ,
              [&] { return xaac_launch_qmf_synthesis(&p, grid, c->stream); });
@@ -957,7 +958,7 @@ int32_t xaac_sbr_eld_process_batch(xaac_ctx *c, const xaac_sbr_eld_batch *b) {
   cn.state_stride = (int32_t)sizeof(xaac_sbr_eld_state);
   /* 1. analysis: n_slots slots of 32 real | 32 imaginary bands into each channel's matrix */
   xaac_qmf_ana_eld_batch a = {};
-  a.n_ch = b->n_ch; a.n_slots = b->n_slots; a.usb = 32; a.slot_stride = 128; a.pcm = b->pcm_in;
+  a.n_ch = b->n_ch; a.n_slots = b->n_slots; a.usb = 32; a.slot_stride = XAAC_SBR_ROW_WORDS_HQ; a.pcm = b->pcm_in;
   a.state = reinterpret_cast<xaac_qmf_ana_eld_state *>(st + offsetof(xaac_sbr_eld_state, ana));
   a.qmf = w.x; a.status = nullptr;
   cn.pcm_ch_fac = b->in_ch_fac; cn.frame = b->frame;
@@ -970,7 +971,7 @@ int32_t xaac_sbr_eld_process_batch(xaac_ctx *c, const xaac_sbr_eld_batch *b) {
   XAAC_TRY(xaac_launch_sbr_ld_core(&pc, c->stream));
   /* 3. synthesis */
   xaac_qmf_syn_eld_batch sy = {};
-  sy.n_ch = b->n_ch; sy.n_slots = b->n_slots; sy.split = 0; sy.slot_stride = 128; sy.qmf = w.x; sy.scale = w.par;
+  sy.n_ch = b->n_ch; sy.n_slots = b->n_slots; sy.split = 0; sy.slot_stride = XAAC_SBR_ROW_WORDS_HQ; sy.qmf = w.x; sy.scale = &w.par->lb_scale;
   sy.state = reinterpret_cast<xaac_qmf_syn_eld_state *>(st + offsetof(xaac_sbr_eld_state, syn));
   sy.pcm = b->pcm_out; sy.status = nullptr; sy.qmf_scaled = b->qmf_handed_on;
   cn.pcm_ch_fac = b->out_ch_fac; cn.syn_par = w.par;

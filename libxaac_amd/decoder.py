@@ -20,8 +20,11 @@ from . import (CORE_TOOLS_SIDE_BYTES, CORE_TOOLS_STATE_BYTES, DRC_SIDE_WORDS, ES
                HANDOVER_PS_START, HBE_STATE_BYTES, LIMITER_STATE_BYTES, PCM_LC, PCM_SBR, PS_FRAME_BYTES, PS_STATE_BYTES,
                SBR_FRAME_BYTES, SBR_HEADER_BYTES, SBR_STATE_BYTES, LimiterState, XaacContext, out_map_channels, peak_limiter_init)
 from . import out_map as make_out_map
+from . import abi
 from .abi import (AdtsHeader, CoreFrame, CoreToolsChannel, CoreToolsSide, CoreToolsState, DrcConfig, SbrSide,  # noqa: F401
                   TnsFilterSide)
+from .abi import (F_APPLY, F_FRAME_OK, F_PS, F_PS_START, F_RESET, F_RESET_CHANNELS, F_STEREO,  # noqa: F401  (the flag row's positions)
+                  F_UPSAMPLING)
 from .abi import ParseBatch as _ParseBatch   # the descriptor BatchParser fills
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,55 +45,7 @@ def load_host_library():
         path = host_library_path()
         if not os.path.exists(path):
             raise RuntimeError("libxaac_host.so is not built: make -C libxaac_amd/host")
-        lib = ctypes.CDLL(path)
-        lib.xaac_parser_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
-        lib.xaac_parser_destroy.argtypes = [ctypes.c_void_p]
-        lib.xaac_parser_destroy.restype = None
-        lib.xaac_adts_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(AdtsHeader)]
-        lib.xaac_parse_adts_frame.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32,
-                                              ctypes.POINTER(CoreFrame), ctypes.POINTER(ctypes.c_size_t)]
-        lib.xaac_parse_sbr_side.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(SbrSide)]
-        lib.xaac_parse_adts_frame_mc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_void_p,
-                                                 ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_size_t)]
-        lib.xaac_parse_core_tools_side_mc.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-        lib.xaac_parse_core_tools_side_mc.restype = ctypes.c_int32
-        for fn in ("xaac_sbr_state_init", "xaac_ps_state_init", "xaac_esbr_state_init", "xaac_esbr_ps_state_init",
-                   "xaac_hbe_state_init"):
-            getattr(lib, fn).argtypes = [ctypes.c_void_p]
-            getattr(lib, fn).restype = None
-        lib.xaac_parser_set_esbr.argtypes = [ctypes.c_void_p, ctypes.c_int32]
-        lib.xaac_parse_core_tools_side.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        lib.xaac_parse_core_tools_side.restype = ctypes.c_int32
-        lib.xaac_parse_core_tools_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        lib.xaac_parse_core_tools_state.restype = ctypes.c_int32
-        lib.xaac_parse_core_tools_state_mc.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-        lib.xaac_parse_core_tools_state_mc.restype = ctypes.c_int32
-        lib.xaac_core_tools_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.xaac_core_tools_apply_host.restype = ctypes.c_int32
-        lib.xaac_parse_esbr_side.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-        lib.xaac_hbe_state_reinit.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        lib.xaac_hbe_state_reinit_tails.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
-        lib.xaac_hbe_state_reinit_tails.restype = ctypes.c_int32
-        lib.xaac_parse_reset_pitch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
-        lib.xaac_sbr_state_apply_side.argtypes = [ctypes.c_void_p, ctypes.POINTER(SbrSide), ctypes.c_int32]
-        lib.xaac_sbr_state_apply_side.restype = None
-        lib.xaac_ps_state_apply_side.argtypes = [ctypes.c_void_p, ctypes.POINTER(SbrSide)]
-        lib.xaac_ps_state_apply_side.restype = None
-        lib.xaac_out_map_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-        lib.xaac_out_map_apply_host.restype = ctypes.c_int32
-        lib.xaac_out_map_row_bound.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-        lib.xaac_out_map_row_bound.restype = ctypes.c_int32
-        lib.xaac_parse_drc_config.argtypes = [ctypes.c_void_p, ctypes.POINTER(DrcConfig)]
-        lib.xaac_parse_drc_side.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        lib.xaac_drc_apply_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        for fn in ("xaac_parse_drc_config", "xaac_parse_drc_side", "xaac_drc_apply_host"):
-            getattr(lib, fn).restype = ctypes.c_int32
-        lib.xaac_parse_batch_run.argtypes = [ctypes.c_void_p]       # (the original layout's symbols: no pos / frames / lines)
-        lib.xaac_parse_batch_start.argtypes = [ctypes.c_void_p]
-        lib.xaac_parse_batch_run_sized.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-        lib.xaac_parse_batch_start_sized.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-        lib.xaac_parse_batch_wait.argtypes = [ctypes.c_void_p]
-        _host = lib
+        _host = abi.bind_host(ctypes.CDLL(path))
     return _host
 
 
@@ -325,9 +280,6 @@ def parse_stream_mc(data, stage=2):
     return out
 
 
-F_APPLY, F_RESET, F_RESET_CHANNELS, F_UPSAMPLING, F_STEREO, F_PS, F_PS_START, F_FRAME_OK = range(8)
-
-
 def usable_cores():
     """host cores this process may really use: the scheduler affinity mask cut by the cgroup CPU quota (v2 cpu.max or v1
     cfs_quota_us / cfs_period_us) when there is one"""
@@ -451,7 +403,7 @@ class BatchParser:
         channels, n_elems, sbr, config = probe_first_frame(streams[0])
         self.sbr = bool(sbr)
         # several channel elements (channel_config 3 .. 6): the multichannel form of the batch call; with SBR payloads only when
-        # the caller asked for per-element SBR (mc_sbr: flags int32[n, n_elems, 8] and reset_pitch int32[n, n_elems], a row per
+        # the caller asked for per-element SBR (mc_sbr: flags int32[n, n_elems, abi.SBR_FLAG_WORDS] and reset_pitch int32[n, n_elems], a row per
         # channel element; header / frame / eside rows per channel in bitstream order)
         self.channel_config, self.n_elems = (config, n_elems) if n_elems > 1 else (0, 1)
         for d in streams[1:]:   # a multichannel stream only beside streams of its own channel_config, whichever comes first
@@ -612,8 +564,8 @@ class Staging:
         self.psf, self.eside = want("psf", n, PS_FRAME_BYTES), want("eside", nc, ESBR_SIDE_BYTES)
         self.flags = self.flags_pin = None
         if "flags" in arrays:
-            self.flags = np.zeros((T, n, bp.n_elems, 8) if bp.mc_sbr else (T, n, 8), np.int32)   # (mc_sbr: a row per channel element)
-            self.flags_pin = pinned(T, n, 8, dtype=torch.int32)   # the rows as they go up for xaac_sbr_state_apply_side_batch
+            self.flags = np.zeros((T, n, bp.n_elems, abi.SBR_FLAG_WORDS) if bp.mc_sbr else (T, n, abi.SBR_FLAG_WORDS), np.int32)   # (mc_sbr: a row per channel element)
+            self.flags_pin = pinned(T, n, abi.SBR_FLAG_WORDS, dtype=torch.int32)   # the rows as they go up for xaac_sbr_state_apply_side_batch
         self.seconds = 0.0
         self.sent = [torch.cuda.Event() for _ in range(T)]   # step t's copies up are over (sent[T - 1]: the parser may write the set again)
         self.sent_once = False
@@ -814,7 +766,7 @@ class _SbrChain(_SbrBase):
         _SbrBase.allocate(self, dz, pinned)
         ctx, lib, n, n_ch = self.ctx, self.lib, self.n, self.n_ch
         self.state = self._states(lib.xaac_sbr_state_init, SBR_STATE_BYTES, self.nc)
-        self.flags_d2 = [dz(n, 8, dtype=torch.int32) for _ in range(2)]
+        self.flags_d2 = [dz(n, abi.SBR_FLAG_WORDS, dtype=torch.int32) for _ in range(2)]
         self.side_words = False
         if n_ch == 2:
             self.ws = dz(ctx.sbr_lp_workspace_bytes(self.nc))
@@ -864,9 +816,12 @@ class _SbrChain(_SbrBase):
         return (n, 2048, 2), 0, False
 
 
-# float offsets of members of struct xaac_esbr_state (include/xaac_esbr.h; tests/test_parser_esbr.py checks them against the
-# ctypes mirror of the header): qmf_re / qmf_im rows, and the transposer's last rows ph_re / ph_im
-_ES_QMF_RE, _ES_QMF_IM, _ES_PH_RE, _ES_PH_IM = 1604, 4164, 8479, 8991
+# float offsets of members of struct xaac_esbr_state, from its mirror (tests/test_parser_esbr.py pins the values): qmf_re / qmf_im
+# rows, and the transposer's last rows ph_re / ph_im
+_ES_QMF_RE, _ES_QMF_IM, _ES_PH_RE, _ES_PH_IM = (getattr(abi.EsbrState, m).offset // 4 for m in ("qmf_re", "qmf_im", "ph_re", "ph_im"))
+# struct xaac_hbe_state: the floats of its two delay lines (synth_buf and analy_buf, neighbours), and where its integers begin
+_HBE_DELAY_LINES = slice(abi.HbeState.synth_buf.offset // 4, (abi.HbeState.analy_buf.offset + abi.HbeState.analy_buf.size) // 4)
+_HBE_TAIL_AT = abi.HbeState.synth_size.offset
 
 
 class _EsbrChain(_SbrBase):
@@ -890,7 +845,8 @@ class _EsbrChain(_SbrBase):
         else:
             self.plain = (self.out_l[1:], 4096)          # a pair's channels are neighbouring rows
         self.older = dz(nc, 2, 24 * 64, dtype=torch.float32)   # rows 8..31 of the QMF history as the frame before found them
-        self.hbe_tail = np.zeros((nc, 48), np.uint8)            # the transposers' integers (struct xaac_hbe_state from synth_size on)
+        # the transposers' integers (struct xaac_hbe_state from synth_size on)
+        self.hbe_tail = np.zeros((nc, HBE_STATE_BYTES - _HBE_TAIL_AT), np.uint8)
 
     def hbe_hint(self):   # the largest transposer bank of the batch, as the ABI's LDS hint takes it (8, or 0 = any)
         return 8 if int(self.hbe_tail.view(np.int32)[:, 0].max()) <= 8 else 0
@@ -914,16 +870,15 @@ class _EsbrChain(_SbrBase):
         k = len(rows_h)
         rows = torch.from_numpy(rows_h).to(dev)
         hb = self.hbe.index_select(0, rows)
-        tail_off = HBE_STATE_BYTES - 48
         tails = np.ascontiguousarray(self.hbe_tail[rows_h])            # (one call for all of them: every stream's first
         heads = np.ascontiguousarray(step.hdr.numpy()[rows_h])         #  frame is a reset frame)
         bad = self.lib.xaac_hbe_state_reinit_tails(tails.ctypes.data, heads.ctypes.data, len(rows_h))
         if bad >= 0:
             raise RuntimeError("the QMF transposer refused the SBR band tables of stream %d" % (rows_h[bad] // n_ch))
         self.hbe_tail[rows_h] = tails
-        hb[:, tail_off:] = torch.from_numpy(tails).to(dev)
+        hb[:, _HBE_TAIL_AT:] = torch.from_numpy(tails).to(dev)
         hb32 = hb.view(torch.float32)
-        hb32[:, 1088:1088 + 1280 + 640] = 0.0          # synth_buf, analy_buf (behind input_buf[1024 + 64])
+        hb32[:, _HBE_DELAY_LINES] = 0.0                # synth_buf, analy_buf
         pitch = torch.from_numpy(np.ascontiguousarray(pitch_h, np.int32)).to(dev)
         st32 = self.state.view(torch.float32)
         hist, old = st32.index_select(0, rows), self.older.index_select(0, rows)
@@ -945,6 +900,12 @@ class _EsbrChain(_SbrBase):
         st32.index_copy_(0, rows, hist)
         self.hbe.index_copy_(0, rows, hb)
 
+    def keep_older(self):
+        """rows 8..31 of the QMF history as this frame finds them: for the reset a later frame may bring"""
+        st32 = self.state.view(torch.float32)
+        self.older[:, 0] = st32[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 32 * 64]
+        self.older[:, 1] = st32[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 32 * 64]
+
     def run(self, step, slot, got, first, spec_d, ics_d):
         ctx, n_ch, flags, state, out_l = self.ctx, self.n_ch, step.flags, self.state, self.out_l
         hdr_d, frm_d, eside_d = self.hdr_d2[slot], self.frm_d2[slot], self.eside_d2[slot]
@@ -954,9 +915,7 @@ class _EsbrChain(_SbrBase):
         touched = np.nonzero(got & (flags[:, F_RESET] != 0))[0]
         if touched.size:
             self.reset_transposers(step, touched)
-        st32 = state.view(torch.float32)
-        self.older[:, 0] = st32[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 32 * 64]   # for the reset a later frame may bring
-        self.older[:, 1] = st32[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 32 * 64]
+        self.keep_older()
         ctx.esbr_core_from_pcm16(self.core16, self.core, ch_fac=n_ch)
         if self.trace is not None:   # debugging: the device states in front of the chain call
             self.trace(dict(state=state, hbe=self.hbe, ps_state=self.ps_state, core=self.core, side=eside_d, header=hdr_d, frame=frm_d))
@@ -1006,9 +965,7 @@ class _McEsbrChain(_EsbrChain):
         rows_h = np.nonzero(reset.ravel())[0]
         if rows_h.size:
             self.reset_rows(step, rows_h, step.reset_pitch[:, self.el_of_ch].ravel()[rows_h])
-        st32 = state.view(torch.float32)
-        self.older[:, 0] = st32[:, _ES_QMF_RE + 8 * 64:_ES_QMF_RE + 32 * 64]
-        self.older[:, 1] = st32[:, _ES_QMF_IM + 8 * 64:_ES_QMF_IM + 32 * 64]
+        self.keep_older()
         ctx.mc_core_from_out32(self.out32, self.qadj, self.core, n_ch)
         if self.trace is not None:
             self.trace(dict(state=state, hbe=self.hbe, ps_state=None, core=self.core, side=eside_d, header=hdr_d, frame=frm_d))

@@ -26,6 +26,7 @@
 
 #include "../csrc/aac_tools.h"
 #include "../csrc/drc.h"
+#include "../csrc/sbr_apply_side.h"
 #include "aac_core.h"
 #include "sbr_side.h"
 
@@ -666,9 +667,11 @@ int32_t parse_one(const xaac_parse_batch *b, int i, int t, std::atomic<int> *ok)
         b->frame[row] = side.frame[c];
         if (b->esbr_side && p->esbr) xs_export_esbr_side(&s->sbr, c, b->esbr_side + row);
       }
-      int32_t *f = b->flags + e_row * 8;
-      f[0] = side.apply, f[1] = side.reset, f[2] = side.reset_channels, f[3] = side.upsampling;
-      f[4] = side.stereo, f[5] = side.ps, f[6] = side.ps_start, f[7] = side.frame_ok;
+      int32_t *f = b->flags + e_row * XAAC_SBR_FLAG_WORDS;
+      f[XAAC_SBR_FLAG_APPLY] = side.apply, f[XAAC_SBR_FLAG_RESET] = side.reset;
+      f[XAAC_SBR_FLAG_RESET_CHANNELS] = side.reset_channels, f[XAAC_SBR_FLAG_UPSAMPLING] = side.upsampling;
+      f[XAAC_SBR_FLAG_STEREO] = side.stereo, f[XAAC_SBR_FLAG_PS] = side.ps;
+      f[XAAC_SBR_FLAG_PS_START] = side.ps_start, f[XAAC_SBR_FLAG_FRAME_OK] = side.frame_ok;
       if (b->reset_pitch && side.reset) b->reset_pitch[e_row] = s->sbr.reset_pitch;
       if (ps && b->ps_frame) b->ps_frame[S + i] = side.ps_frame;
     }
@@ -1014,30 +1017,14 @@ int32_t xaac_hbe_state_reinit_tails(uint8_t *tails, const xaac_sbr_header *heade
   return -1;
 }
 
+/* (the words themselves: ../csrc/sbr_apply_side.h, which the device's xaac_sbr_apply_side_kernel compiles too) */
 void xaac_sbr_state_apply_side(xaac_sbr_state *s, const xaac_sbr_side *side, int32_t channel) {
-  if (side->reset && channel < side->reset_channels) {
-    s->ph_index = 0;
-    s->filt_buf_noise_e = 0;
-    s->start_up = 1;
-    s->syn_lsb = s->codec_usb = side->header.sub_band_start;
-    s->syn_usb = side->header.sub_band_end;
-    memset(s->bw_array_prev, 0, sizeof(s->bw_array_prev));
-  }
-  if (side->upsampling) {
-    s->syn_lsb = s->codec_usb = 32;
-    s->syn_usb = 64;
-  }
+  xs_apply_side_channel(s, side->header.sub_band_start, side->header.sub_band_end, side->reset, side->reset_channels, side->upsampling,
+                        channel);
 }
 
 void xaac_ps_state_apply_side(xaac_ps_state *s, const xaac_sbr_side *side) {
-  if (side->reset && side->reset_channels > 1) {
-    s->syn_lsb_r = side->header.sub_band_start;
-    s->syn_usb_r = side->header.sub_band_end;
-  }
-  if (side->upsampling) {
-    s->syn_lsb_r = 32;
-    s->syn_usb_r = 64;
-  }
+  xs_apply_side_ps(s, side->header.sub_band_start, side->header.sub_band_end, side->reset, side->reset_channels, side->upsampling);
 }
 
 }  // extern "C"

@@ -247,7 +247,7 @@ struct Staging { /* what one step's parse leaves for the GPU */
   xaac_esbr_side *eside;
   xaac_core_tools_side *tside; /* -gputools:1: the side info of the M/S, intensity, PNS and TNS tools */
   xaac_drc_side *dside;        /* -drc_*: a row of band ends and gain factors beside every row of spec */
-  const int32_t *flags, *status, *reset_pitch; /* the step's rows of its group's vectors: [N][8], [N], [N] */
+  const int32_t *flags, *status, *reset_pitch; /* the step's rows of its group's vectors: [N][XAAC_SBR_FLAG_WORDS], [N], [N] */
   int delivered;
   int lines; /* leading spectral lines that may be non-zero in a delivered row (xaac_parse_batch::lines, rounded up to 64) */
 };
@@ -369,7 +369,7 @@ class ParseSide {
       xaac_drc_side *dside = J.drc ? mem.pinned<xaac_drc_side>((size_t)T * NC) : nullptr;
       StagingGroup &G = grp_[g];
       const int NF = J.channel_config && J.sbr ? NE : 1; /* flag rows of a stream: one, or one per channel element (mc_sbr) */
-      G.flags.assign((size_t)T * N * NF * 8, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N * NF, 0);
+      G.flags.assign((size_t)T * N * NF * XAAC_SBR_FLAG_WORDS, 0), G.status.assign((size_t)T * N, 0), G.reset_pitch.assign((size_t)T * N * NF, 0);
       G.lines.assign((size_t)T * N, 0), G.consumed.assign((size_t)N, 0);
       for (int t = 0; t < T; t++) {
         Staging &s = st_[g * T + t];
@@ -378,7 +378,7 @@ class ParseSide {
         s.ps = psf ? psf + (size_t)t * N : nullptr, s.eside = eside ? eside + (size_t)t * NC : nullptr;
         s.tside = tside ? tside + (size_t)t * N * NE : nullptr;
         s.dside = dside ? dside + (size_t)t * NC : nullptr;
-        s.flags = &G.flags[(size_t)t * N * NF * 8], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N * NF];
+        s.flags = &G.flags[(size_t)t * N * NF * XAAC_SBR_FLAG_WORDS], s.status = &G.status[(size_t)t * N], s.reset_pitch = &G.reset_pitch[(size_t)t * N * NF];
         s.delivered = 0, s.lines = 1024;
       }
     }
@@ -696,7 +696,7 @@ class SbrChain : public Chain {
       std::vector<xaac_sbr_state> all((size_t)NC, s0);
       HIP(hipMemcpy(d_state_, all.data(), all.size() * sizeof(s0), hipMemcpyHostToDevice));
     }
-    d_flags_ = E.mem.dev<int32_t>((size_t)N * 8), h_flags_ = E.mem.pinned<int32_t>((size_t)N * 8);
+    d_flags_ = E.mem.dev<int32_t>((size_t)N * XAAC_SBR_FLAG_WORDS), h_flags_ = E.mem.pinned<int32_t>((size_t)N * XAAC_SBR_FLAG_WORDS);
     if (mono_) {
       d_psf_ = E.mem.dev<xaac_ps_frame>((size_t)N);
       d_ps_state_ = E.mem.dev<xaac_ps_state>((size_t)N);
@@ -732,19 +732,19 @@ class SbrChain : public Chain {
     const int N = E_.N;
     bool any = false;
     for (int i = 0; i < N; i++) {
-      const int32_t *f = &s.flags[(size_t)i * 8];
-      any = any || (s.status[(size_t)i] == 0 && (f[1] || f[3]));
+      const int32_t *f = &s.flags[(size_t)i * XAAC_SBR_FLAG_WORDS];
+      any = any || (s.status[(size_t)i] == 0 && (f[XAAC_SBR_FLAG_RESET] || f[XAAC_SBR_FLAG_UPSAMPLING]));
     }
     if (!any) return;
     /* h_flags is one pinned buffer: an earlier step's copy up may still be reading it, so the stream is drained BEFORE the
        rows are rewritten (rewriting first and draining behind, as this did, could hand that copy the new rows) */
     HIP(hipStreamSynchronize(E_.stream));
     for (int i = 0; i < N; i++) {
-      const int32_t *f = &s.flags[(size_t)i * 8];
+      const int32_t *f = &s.flags[(size_t)i * XAAC_SBR_FLAG_WORDS];
       const bool live = s.status[(size_t)i] == 0;
-      for (int k = 0; k < 8; k++) h_flags_[(size_t)i * 8 + k] = live ? f[k] : 0;
+      for (int k = 0; k < XAAC_SBR_FLAG_WORDS; k++) h_flags_[(size_t)i * XAAC_SBR_FLAG_WORDS + k] = live ? f[k] : 0;
     }
-    HIP(hipMemcpyAsync(d_flags_, h_flags_, (size_t)N * 8 * 4, hipMemcpyHostToDevice, E_.stream));
+    HIP(hipMemcpyAsync(d_flags_, h_flags_, (size_t)N * XAAC_SBR_FLAG_WORDS * sizeof(int32_t), hipMemcpyHostToDevice, E_.stream));
     xaac_sbr_apply_side_batch ab;
     memset(&ab, 0, sizeof(ab));
     ab.n_streams = N, ab.ch_fac = E_.J.n_ch, ab.header = d_header_, ab.flags = d_flags_, ab.state = d_state_;
@@ -764,8 +764,8 @@ class SbrChain : public Chain {
     int with_ps = 0, starts = 0;
     std::vector<int32_t> idx;
     for (int i = 0; i < N; i++) {
-      with_ps += s.status[(size_t)i] == 0 && s.flags[(size_t)i * 8 + 5] != 0;
-      if (s.status[(size_t)i] == 0 && s.flags[(size_t)i * 8 + 6]) idx.push_back(i), starts++;
+      with_ps += s.status[(size_t)i] == 0 && s.flags[(size_t)i * XAAC_SBR_FLAG_WORDS + XAAC_SBR_FLAG_PS] != 0;
+      if (s.status[(size_t)i] == 0 && s.flags[(size_t)i * XAAC_SBR_FLAG_WORDS + XAAC_SBR_FLAG_PS_START]) idx.push_back(i), starts++;
     }
     /* streams with and without parametric stereo in one step (independent HE-AAC / HE-AACv2 streams, or streams whose PS
        starts at different frames): the batch runs with the PS launch, which passes a stream without PS through as the mono
@@ -1044,9 +1044,9 @@ class EsbrChain : public Chain {
     XA(xaac_imdct_process_batch(E_.ctx, &ib));
     int resets = 0, with_ps = 0; /* channel rows that reset; streams with PS (never with more than two channels) */
     for (int i = 0; i < NC; i++)
-      if (s.status[(size_t)(i / E_.J.n_ch)] == 0) resets += s.flags[E_.J.flag_row(i) * 8 + 1] != 0;
+      if (s.status[(size_t)(i / E_.J.n_ch)] == 0) resets += s.flags[E_.J.flag_row(i) * XAAC_SBR_FLAG_WORDS + XAAC_SBR_FLAG_RESET] != 0;
     for (int i = 0; i < N && !mc_; i++)
-      if (s.status[(size_t)i] == 0) with_ps += s.flags[(size_t)i * 8 + 5] != 0;
+      if (s.status[(size_t)i] == 0) with_ps += s.flags[(size_t)i * XAAC_SBR_FLAG_WORDS + XAAC_SBR_FLAG_PS] != 0;
     if (resets) reset_runs(s, slot, resets == s.delivered * E_.J.n_ch);
     /* what this frame finds as rows 8..31 of its history: the frame behind it may need them at a reset */
     float *older_re = d_older_, *older_im = d_older_ + (size_t)NC * 24 * 64;
@@ -1134,7 +1134,7 @@ class EsbrChain : public Chain {
     R.gathered = tr_->always_gathers() || !every;
     if (R.gathered)
       for (int i = 0; i < NC; i++)
-        if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[E_.J.flag_row(i) * 8 + 1] != 0) R.chs.push_back(i);
+        if (s.status[(size_t)(i / n_ch)] == 0 && s.flags[E_.J.flag_row(i) * XAAC_SBR_FLAG_WORDS + XAAC_SBR_FLAG_RESET] != 0) R.chs.push_back(i);
     R.n = R.gathered ? (int)R.chs.size() : NC;
     if (!sc_.q_re) {
       sc_.q_re = E_.mem.dev<float>((size_t)NC * 2 * 2048), sc_.pv_re = E_.mem.dev<float>((size_t)NC * 2 * 2048);
@@ -1353,7 +1353,7 @@ class ShardDriver {
                                      samples into the interleaved rows and left the right ones alone */
       const int32_t *fl = pending_.s->flags;
       for (int i = 0; i < N; i++)
-        if (alive[i] == 0 && fl[(size_t)i * 8 + 5] == 0)
+        if (alive[i] == 0 && fl[(size_t)i * XAAC_SBR_FLAG_WORDS + XAAC_SBR_FLAG_PS] == 0)
           for (int k = 0; k < 2048; k++) h_pcm[(size_t)i * 4096 + 2 * k + 1] = h_pcm[(size_t)i * 4096 + 2 * k];
     }
     lap(2);

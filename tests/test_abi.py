@@ -160,6 +160,25 @@ def test_struct_layouts_match_headers(tmp_path):
     assert {k: (got[k], want[k]) for k in want if got[k] != want[k]} == {}
 
 
+def test_flag_row_names_match_the_headers_enum(tmp_path):
+    """abi.SBR_FLAG_NAMES / abi.F_* / abi.SBR_FLAG_WORDS against enum xaac_sbr_flag of include/xaac_sbr.h, through both headers
+    that hand the row on, and against the members xaac_sbr_side starts with"""
+    from libxaac_amd import decoder
+    enum = re.search(r"enum xaac_sbr_flag \{(.*?)\}", _header_text("xaac_sbr.h"), flags=re.S).group(1)
+    declared = re.findall(r"XAAC_SBR_FLAG_(\w+)", enum)
+    assert declared == list(abi.SBR_FLAG_NAMES) + ["WORDS"]           # every enumerator has its name here, in the enum's order
+    body = "\n".join('printf("%%d\\n", (int)XAAC_SBR_FLAG_%s);' % n for n in declared)
+    for k, h in enumerate(("xaac_parse.h", "xaac_amd.h")):
+        src, exe = tmp_path / ("flags%d.c" % k), tmp_path / ("flags%d" % k)
+        src.write_text('#include <stdio.h>\n#include "%s"\nint main(void) {\n%s\nreturn 0; }\n' % (h, body))
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+        got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+        assert got == [getattr(abi, "F_" + n) for n in abi.SBR_FLAG_NAMES] + [abi.SBR_FLAG_WORDS]
+    assert got == list(range(8)) + [8]                                # the published row
+    assert [f for f, _ in abi.SbrSide._fields_[:abi.SBR_FLAG_WORDS]] == [n.lower() for n in abi.SBR_FLAG_NAMES]
+    assert all(getattr(decoder, "F_" + n) == getattr(abi, "F_" + n) for n in abi.SBR_FLAG_NAMES)
+
+
 # The sizes of the states and side-info rows are ABI facts like the workspace sizes (device tensors and golden files are cut to
 # them): the values libxaac_amd stated as literals before it read them off the mirrors.
 SIZES = {

@@ -85,6 +85,11 @@ def test_new_stream_states():
     lib = decoder.load_host_library()
     es, ps, hb = EsbrState(), EsbrPsState(), HbeState()
     assert (ctypes.sizeof(es), ctypes.sizeof(ps), ctypes.sizeof(hb)) == (ESBR_STATE_BYTES, ESBR_PS_STATE_BYTES, HBE_STATE_BYTES)
+    # what the decoder reads off the mirrors to reach into these states on the device: the values it held as literals
+    assert (decoder._ES_QMF_RE, decoder._ES_QMF_IM, decoder._ES_PH_RE, decoder._ES_PH_IM) == (1604, 4164, 8479, 8991)
+    assert (decoder._ES_QMF_RE, decoder._ES_PH_IM) == (EsbrState.qmf_re.offset // 4, EsbrState.ph_im.offset // 4)
+    assert decoder._HBE_DELAY_LINES == slice(1088, 1088 + 1280 + 640) and HBE_STATE_BYTES - decoder._HBE_TAIL_AT == 48
+    assert (HbeState.synth_buf.offset // 4, HbeState.synth_size.offset) == (decoder._HBE_DELAY_LINES.start, decoder._HBE_TAIL_AT)
     for st in (es, ps, hb):
         ctypes.memset(ctypes.byref(st), 0xa5, ctypes.sizeof(st))
     lib.xaac_esbr_state_init(ctypes.byref(es))
